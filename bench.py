@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: images/s of the multi_pose hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--dtype bf16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--dtype bf16] [--dump-outputs DIR] [--full]
 
 One "step" = one batch of synthetic 512x512 images (already resident in HBM) through
 DLA-34+DCNv2 (+pose/shape heads) -> sigmoid+NMS+top-k decode -> per-detection SMPL/LBS meshes,
@@ -12,7 +12,11 @@ and for N>1 the single all-gather of the decoded detections (RCCL).  One process
 `python -m torch.distributed.run --nproc-per-node N bench.py ...`, spawned before anything touches the GPU) and relays
 rank 0's JSON line; under torchrun it is a rank.
 
-Rank 0 prints ONE JSON line with the driver's contract fields plus
+Rank 0 prints ONE JSON line with the driver's contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = one
+timed step's milliseconds, ...).  A plain run does nothing else: set-up, warm-up, the K timed steps, the outputs of the last
+one when --dump-outputs DIR is given (DIR/<name>.npy), the line.  With --full the line also carries "value_long" (200 more
+steps), "shader_clock_mhz", the records measured after the timed region (shard_sweep, parity_mode, fp16_plan,
+offset_robustness, other_archs: see --no-extras) and
   "roofline"     -- dominant kernel family (by device time) timed live with HIP events on the
                     launch stream: algorithmic FLOP per launch / mean launch duration vs the dense
                     bf16 MFMA peak of MI355X;
@@ -23,6 +27,7 @@ Rank 0 prints ONE JSON line with the driver's contract fields plus
                     (oracle/index_match.py; the oracle is the checker here, never the thing measured).
 """
 import argparse
+import contextlib
 import ctypes
 import json
 import os
@@ -602,14 +607,15 @@ def steps_in_flight_default(arch_name, batch):
     return 4 if batch <= 16 else 3
 
 
-def make_step(det, images, nslot, world, n_global, dev, graph=False, rehearse=False):
+def make_step(det, images, nslot, world, n_global, dev, graph=False, rehearse=False, keep_last=False):
     """-> (step(), per-image dets shape).  step() issues one batch: consecutive calls alternate between `nslot` HIP streams, each
     with its own copy of the plan's buffers; for world > 1 the single collective (all-gather of dets) follows on the
-    default stream, in step order."""
+    default stream, in step order.  keep_last: step.last["res"] holds the whole result dict of the latest step (--dump-outputs)."""
     slot_streams = _streams(nslot, dev) if nslot > 1 else [None]
     counter = [0]
     dets_shape = (det.opt.K, 6 if det.opt.task == "ctdet" else 40)
     collective = world > 1 or rehearse          # rehearse: the N > 1 code path with a group of one rank (RCCL on a one-GPU box)
+    last = {}
 
     def step():
         k = counter[0] % nslot
@@ -617,9 +623,13 @@ def make_step(det, images, nslot, world, n_global, dev, graph=False, rehearse=Fa
         kw = {"graph": True} if graph else {}
         if slot_streams[k] is None:
             res = det.run(images, slot=0, **kw)
+            if keep_last:
+                last["res"] = res
             return gather_detections(res["dets"], n_images=n_global, force=rehearse) if collective else res["dets"]
         with torch.cuda.stream(slot_streams[k]):
             res = det.run(images, slot=k, **kw)
+            if keep_last:
+                last["res"] = res
             if not collective:
                 return res["dets"]
             done = torch.cuda.Event()
@@ -630,6 +640,7 @@ def make_step(det, images, nslot, world, n_global, dev, graph=False, rehearse=Fa
         res["dets"].record_stream(cur)
         return gather_detections(res["dets"], n_images=n_global, force=rehearse)
 
+    step.last = last
     return step, dets_shape
 
 
@@ -644,6 +655,38 @@ def time_steps(step, steps, warmup, issued=None):
         issued.append(time.perf_counter() - t0)
     torch.cuda.synchronize()
     return time.perf_counter() - t0
+
+
+DUMP_BUDGET_BYTES = 64_000_000     # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir, dets, res):
+    """--dump-outputs: what the last timed step handed its caller -> out_dir/<name>.npy.  `dets` as the step returned it (after
+    the all-gather when there is one), then every other tensor of the detector's result dict (inds, verts, joints) and every
+    head (heads_<name>).  Floating arrays are written as float32, integer ones as float64 (exact).  An array larger than its
+    share of DUMP_BUDGET_BYTES is written flat, as the elements at a fixed set of positions (numpy default_rng(0), sorted):
+    the same arguments give the same positions, so two builds can be compared array for array.  -> {name: description}."""
+    arrays = {"dets": dets}
+    for k, v in res.items():
+        if k == "heads":
+            arrays.update({"heads_" + h: t for h, t in v.items()})
+        elif k != "dets" and torch.is_tensor(v):
+            arrays[k] = v
+    cap = min(1 << 20, DUMP_BUDGET_BYTES // (8 * len(arrays)))      # elements per array: within budget even as float64
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, t in sorted(arrays.items()):
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        sampled = n > cap
+        if sampled:
+            pos = np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+            flat = flat[torch.from_numpy(pos).to(flat.device)]
+        a = flat.cpu()
+        a = (a.double() if not a.is_floating_point() else a.float() if a.dtype != torch.float64 else a).numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if sampled else a.reshape(tuple(t.shape)))
+        written[name] = "%s %s%s" % (tuple(t.shape), str(t.dtype).replace("torch.", ""), (" -> %d sampled" % cap) if sampled else "")
+    return written
 
 
 def shard_sweep(det, images, nslot, dev, batches, steps=200):
@@ -814,8 +857,16 @@ def main():
                     help="one GPU only: run the step exactly as a multi-GPU rank does -- RCCL process group (of one rank), the per-step "
                          "all_gather_into_tensor of dets issued from the default stream behind an event of the slot stream, barrier + "
                          "max-over-ranks timing -- so that the N > 1 code path meets the device before the driver's 8-GPU run does")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the shader clock, the 200-step value_long, roofline and per-kernel "
+                         "times, the CPU baseline with index_match, and the records measured after the timed region (shard_sweep, "
+                         "parity_mode, fp16_plan, offset_robustness, other_archs).  Off by default: a plain run sets up, warms up, "
+                         "times the K steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (dets, inds, SMPL verts / joints, every head) as "
+                         "DIR/<name>.npy, float32 (integer arrays float64), at most 64 MB in all: larger arrays as a fixed sample")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the records measured after the timed region (shard_sweep, parity_mode, other_archs)")
+                    help="with --full: skip the records measured after the timed region (shard_sweep, parity_mode, other_archs)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32", "f16x3"])
     ap.add_argument("--people", type=int, default=100, help="SMPL meshes per image (<= K)")
     ap.add_argument("--streams", type=int, default=1, help="sub-batches run concurrently on their own HIP streams")
@@ -836,8 +887,8 @@ def main():
                          "8-GPU batch, network + decode, no SMPL stage, no CPU baseline")
     ap.add_argument("--size", type=int, default=0, help="input height = width (default 512; 768 for resdcn_101)")
     ap.add_argument("--engine-flag", action="append", default=[], help="engine lowering flag NAME=INT (engine.Plan.FLAGS), repeatable")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline / index_match")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no roofline / kernels records")
     ap.add_argument("--dry-run", action="store_true", help="launcher + collective plumbing only, gloo on CPU (tests)")
     args = ap.parse_args()
     if args.dtype == "f16x3":          # the roofline record reads the f16x3 plan's own committed profile
@@ -901,7 +952,8 @@ def main():
     if args.streams > 1 and args.pipeline is None:
         nslot = 1              # sub-batch streams and plan slots are two uses of the same idea: combined only on request
     use_graph = dla and args.graph == 1 and args.streams <= 1
-    step, dets_shape = make_step(det, images, nslot, world, n_global, dev, graph=use_graph, rehearse=args.rehearse_collective and world == 1)
+    step, dets_shape = make_step(det, images, nslot, world, n_global, dev, graph=use_graph, rehearse=args.rehearse_collective and world == 1,
+                                 keep_last=args.dump_outputs is not None)
 
     # one-time setup outside both warm-up and the timed region: weight packing + plan lowering (host work and uploads,
     # no network launches) and the SMPL model upload.  The first launch of every kernel still pays its code-object
@@ -925,8 +977,8 @@ def main():
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
-    clock = ClockSampler(local)
-    with clock:
+    clock = ClockSampler(local) if args.full else None
+    with clock or contextlib.nullcontext():
         t0 = time.perf_counter()
         for _ in range(args.steps):
             out = step()
@@ -944,9 +996,12 @@ def main():
     if rank == 0:
         print("[bench] %d GPU(s): %.1f images/s, %.3f ms/step" % (world, n_global * args.steps / dt,
                                                                  1e3 * dt / args.steps), file=sys.stderr, flush=True)
+        if args.dump_outputs is not None:       # before anything else runs the step again (the result buffers are the plan's)
+            written = dump_outputs(args.dump_outputs, out, step.last["res"])
+            print("[bench] outputs of the last timed step -> %s: %s" % (args.dump_outputs, json.dumps(written)), file=sys.stderr, flush=True)
     # a second, longer measurement of the same step (the driver fixes --steps: 20 steps are 0.15 s, boxes of the pool differ by a few
     # percent over such a window).  Never `value`.
-    long_steps = max(200, args.steps) if (dla and not args.no_extras) else 0
+    long_steps = max(200, args.steps) if (args.full and dla and not args.no_extras) else 0
     value_long = None
     if long_steps:
         clock_long = ClockSampler(local)
@@ -970,7 +1025,6 @@ def main():
             "n_gpus": world, "rccl_ranks": dist.get_world_size() if dist is not None else 1,
             "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(1e3 * dt / args.steps, 3), "host_issue_ms_per_step": round(1e3 * t_issued / args.steps, 3),
-            "value_long": value_long, "shader_clock_mhz": clock.summary(),
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
             "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
@@ -991,7 +1045,9 @@ def main():
                            "reported with set overlap / agreement (index_match)" % (args.dtype, args.dtype),
         }
         line["model_tflops"] = round(gflop_img * line["value"] / 1e3 / world, 1)      # per GPU
-        if not args.no_roofline:
+        if args.full:
+            line["value_long"], line["shader_clock_mhz"] = value_long, clock.summary()
+        if args.full and not args.no_roofline:
             plan = eng.plan(batch, size, size)
             groups = per_kernel_profile(plan, iters=5)
             total_ms = sum(g["ms"] for g in groups.values())
@@ -1049,12 +1105,12 @@ def main():
             if world == 1 and dla:
                 line["boundary_op"] = boundary_op_times(min(batch, 16), dev)
                 print("[bench] boundary_op %s" % json.dumps(line["boundary_op"]), file=sys.stderr, flush=True)
-        extras = world == 1 and dla and not args.no_extras and not strong and args.dtype == "bf16"
+        extras = args.full and world == 1 and dla and not args.no_extras and not strong and args.dtype == "bf16"
         if extras:
             # the per-GPU shards a STRONG-scaling run of the headline batch would see (64 over 8 GPUs = 8 per GPU)
             line["shard_sweep"] = shard_sweep(det, images, nslot, dev, (8, 16, 32))
             print("[bench] shard_sweep %s" % json.dumps(line["shard_sweep"]), file=sys.stderr, flush=True)
-        if not args.no_cpu_baseline and world == 1 and dla:
+        if args.full and not args.no_cpu_baseline and world == 1 and dla:
             keep = {}
             line["cpu_baseline"] = cpu_baseline(opt, sd, keep=keep)
             # the checker's second use: the same 2 images through the GPU path, indices compared with the oracle's

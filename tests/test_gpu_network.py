@@ -730,12 +730,12 @@ def test_flip_test_on_a_mirror_symmetric_input_keeps_symmetry_and_runs_both_pass
 
 @pytest.mark.parametrize("arch_args", [[], ["--arch", "resdcn_101"], ["--arch", "hourglass"], ["--dtype", "f16x3"]])
 def test_bench_cli_prints_one_contract_line(arch_args):
-    """bench.py end to end as the driver starts it (a child process; small batch and image): ONE JSON line with the contract's
+    """bench.py --full end to end as the driver starts it (a child process; small batch and image): ONE JSON line with the contract's
     keys, `roofline` with a live per-launch figure, and a value that is a rate of the K timed steps."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4", "--size", "128",
-           "--no-cpu-baseline"] + arch_args
+           "--full", "--no-cpu-baseline"] + arch_args
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -754,6 +754,50 @@ def test_bench_cli_prints_one_contract_line(arch_args):
               "peak_assumes_mhz"):
         assert k in rf, k
     assert rf["avg_launch_ms"] > 0 and 0 < rf["frac"] < 1
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """bench.py without --full: the line holds the headline fields and none of the --full records, `--steps` sets the timed steps,
+    and --dump-outputs writes the last timed step's result as float32 / float64 .npy files within 64 MB: dets and inds whole,
+    the SMPL vertices as the seeded sample, all equal to what the same detector computes on the same inputs in this process."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = str(tmp_path / "outputs")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "4",
+                        "--size", "128", "--dump-outputs", out], cwd=root, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["dtype"] == "bf16" and d["unit"] == "images/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) <= 0.01 * d["value"]
+    for k in ("roofline", "kernels", "cpu_baseline", "index_match", "value_long", "shader_clock_mhz", "shard_sweep", "parity_mode"):
+        assert k not in d, k
+    files = sorted(os.listdir(out))
+    assert {"dets.npy", "inds.npy", "verts.npy", "joints.npy", "heads_hm.npy", "heads_pose.npy"} <= set(files), files
+    assert sum(os.path.getsize(os.path.join(out, f)) for f in files) <= 64e6
+    got = {f[:-4]: np.load(os.path.join(out, f)) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    # the same detector and images as bench.py's defaults, in this process
+    opt = Opt(input_h=128, input_w=128, smpl=True, smpl_people=100, dtype="bf16", K=100)
+    sd = synth.synth_state_dict(arch.state_dict_shapes(opt.heads, True), seed=0, offset_scale=0.5, gain=1.25)
+    det = MultiPoseDetector(opt, {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, device=DEV)
+    x = torch.from_numpy(synth.synth_image_batch(4, 128, 128, seed=317)).to(DEV)
+    det.model.engine(DEV).calibrate_dcn_margins(x)
+    res = det.run(x)
+    torch.cuda.synchronize()
+    assert got["inds"].dtype == np.float64 and np.array_equal(got["inds"], res["inds"].cpu().numpy().astype(np.float64))
+    assert got["dets"].shape == (4, 100, 40)
+    np.testing.assert_allclose(got["dets"], res["dets"].cpu().numpy(), rtol=0, atol=1e-5)
+    verts = res["verts"].cpu().numpy().reshape(-1)
+    n = got["verts"].size
+    assert got["verts"].ndim == 1 and n < verts.size
+    pos = np.sort(np.random.default_rng(0).choice(verts.size, n, replace=False))
+    np.testing.assert_allclose(got["verts"], verts[pos], rtol=0, atol=1e-5)
 
 
 @pytest.mark.parametrize("scale", [0.5, 2.0])
