@@ -7,7 +7,8 @@ fallback: using a compute entry point without the built library raises.
 
 Reference-named entry points (same names / argument meaning as the reference's src/lib):
     models.model.dla_net                      -> h3d_amd.model.dla_net
-    models.DCNv2.dcn_v2.{dcn_v2_conv,DCNv2,DCN}, _ext.dcn_v2_forward -> h3d_amd.dcn_v2.*
+    models.DCNv2.dcn_v2.{dcn_v2_conv,DCNv2,DCN,dcn_v2_pooling,DCNv2Pooling,DCNPooling},
+        _ext.{dcn_v2_forward,dcn_v2_psroi_pooling_forward} -> h3d_amd.dcn_v2.*
     models.decode.{_nms,_topk,_topk_channel,multi_pose_decode,ctdet_decode} -> h3d_amd.decode.*
     models.utils.{_sigmoid,_gather_feat,_transpose_and_gather_feat} -> h3d_amd.utils.*
     utils.post_process.multi_pose_post_process -> h3d_amd.detector.multi_pose_post_process

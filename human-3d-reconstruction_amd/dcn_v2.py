@@ -1,8 +1,11 @@
 """Host mirror of the reference's models/DCNv2/dcn_v2.py (forward path): `dcn_v2_forward`
 (the `_ext` entry point, DCNv2/src/dcn_v2.h:9-39), `dcn_v2_conv`, `DCNv2`, `DCN` with the same
-constructor arguments and state_dict keys (weight, bias, conv_offset_mask.{weight,bias}).
+constructor arguments and state_dict keys (weight, bias, conv_offset_mask.{weight,bias}); and the
+deformable PS-ROI pooling forward: `dcn_v2_psroi_pooling_forward` (the `_ext` entry point,
+DCNv2/src/dcn_v2.h:76-107), `dcn_v2_pooling`, `DCNv2Pooling`, `DCNPooling` (state_dict keys
+offset_mask_fc.{0,2,4}.{weight,bias}).
 
-Backward (dcn_v2_backward) and PS-ROI pooling are out of scope:
+The backward passes (dcn_v2_backward, dcn_v2_psroi_pooling_backward) are out of scope:
 inference only -- an INPUT that requires grad (with autograd enabled) raises; parameters may require grad (the
 nn.Parameter default), results are computed without a graph and returned detached."""
 import math
@@ -298,3 +301,173 @@ class DCN(DCNv2):
                                                       self.deformable_groups, _lib.stream_ptr()), "DCN: conv_offset_mask")
         return dcn_v2_conv(x, offset, mask, self.weight, self.bias, self.stride, self.padding,
                            self.dilation, self.deformable_groups)
+
+
+# ---- deformable PS-ROI pooling, forward (dcn_v2.py:130-303 of the reference; kernel: csrc/psroi.hip) ----------------------------
+
+def _pool_common(what, input, bbox, output_dim, group_size, pooled_size, part_size, sample_per_part):
+    """Argument checks shared by the two pooling entry points; returns contiguous (input, bbox) and (B, C, H, W, R)."""
+    _lib.require_cuda(input, bbox)
+    for t in (input, bbox):
+        if t.dtype != torch.float32:
+            raise RuntimeError("%s: expected float32 tensors (reference uses .data<float>())" % what)
+    if input.dim() != 4:
+        raise RuntimeError("%s: input must be [B,C,H,W], got %s" % (what, tuple(input.shape)))
+    if bbox.dim() != 2 or bbox.shape[1] != 5:
+        raise RuntimeError("%s: rois must be [R,5] (batch, x1, y1, x2, y2), got %s" % (what, tuple(bbox.shape)))
+    if bbox.device != input.device:
+        raise RuntimeError("%s: rois are on %s, input on %s" % (what, bbox.device, input.device))
+    B, C, H, W = input.shape
+    if C != output_dim:
+        raise RuntimeError("input channels and output channels must equal")
+    if group_size != 1:
+        raise RuntimeError("%s: only group_size == 1 is supported (the reference reads channel (ctop*gs+gh)*gs+gw past the input "
+                           "for group_size %d)" % (what, group_size))
+    if pooled_size < 1 or part_size < 1 or sample_per_part < 1:
+        raise RuntimeError("%s: pooled_size, part_size and sample_per_part must be positive" % what)
+    if B == 0 or H == 0 or W == 0:
+        raise RuntimeError("%s: empty input %s" % (what, tuple(input.shape)))
+    return input.contiguous(), bbox.contiguous(), (B, C, H, W, bbox.shape[0])
+
+
+def dcn_v2_psroi_pooling_forward(input, bbox, trans, no_trans, spatial_scale, output_dim, group_size, pooled_size, part_size,
+                                 sample_per_part, trans_std):
+    """Positional twin of `_ext.dcn_v2_psroi_pooling_forward` (DCNv2/src/dcn_v2.h:76-107): returns (output, output_count), both
+    [R, output_dim, P, P] fp32, P = pooled_size; output_count holds the number of valid samples per bin.  Launches on the current
+    stream of input's device; no host synchronisation.  fp32 only, group_size == 1 only, output_dim == C; without no_trans, trans
+    is [>= R, 2*num_classes, part_size, part_size] (include/h3d.h lists what this library decides where the reference does not)."""
+    what = "dcn_v2_psroi_pooling_forward"
+    input, bbox, (B, C, H, W, R) = _pool_common(what, input, bbox, output_dim, group_size, pooled_size, part_size, sample_per_part)
+    no_trans = int(bool(no_trans))
+    ct = 0
+    if not no_trans:
+        _lib.require_cuda(trans)
+        if trans.dtype != torch.float32:
+            raise RuntimeError("%s: expected float32 tensors (reference uses .data<float>())" % what)
+        if trans.device != input.device:
+            raise RuntimeError("%s: trans is on %s, input on %s" % (what, trans.device, input.device))
+        if trans.dim() != 4 or tuple(trans.shape[2:]) != (part_size, part_size) or trans.shape[0] < R:
+            raise RuntimeError("%s: trans %s does not match [>= %d, 2*num_classes, %d, %d]"
+                               % (what, tuple(trans.shape), R, part_size, part_size))
+        ct = trans.shape[1]
+        if ct < 2 or ct % 2:
+            raise RuntimeError("%s: trans has %d channels, expected 2 * num_classes" % (what, ct))
+        if output_dim % (ct // 2):
+            raise RuntimeError("%s: output_dim %d is not a multiple of num_classes %d" % (what, output_dim, ct // 2))
+        trans = trans.contiguous()
+    out = torch.empty(R, output_dim, pooled_size, pooled_size, dtype=torch.float32, device=input.device)
+    count = torch.empty_like(out)
+    if R == 0:
+        return out, count
+    with torch.cuda.device(input.device):
+        rc = _lib.lib().h3d_dcn_v2_psroi_pooling_forward(
+            _lib.ptr(input), _lib.ptr(bbox), _lib.ptr(None if no_trans else trans), _lib.ptr(out), _lib.ptr(count),
+            B, C, H, W, R, ct, no_trans, float(spatial_scale), output_dim, group_size, pooled_size, part_size, sample_per_part,
+            float(trans_std), _lib.stream_ptr())
+    _lib.check(rc, what)
+    return out, count
+
+
+def _dcn_pooling_modulated(input, rois, offset_mask, spatial_scale, pooled_size, output_dim, group_size, part_size,
+                           sample_per_part, trans_std):
+    """DCNPooling's second pass (dcn_v2.py:281-292): offset = channels 0/1 of offset_mask [R,3,P,P], result x sigmoid(channel 2),
+    in one launch (`h3d_dcn_pooling_modulated`)."""
+    what = "DCNPooling"
+    input, rois, (B, C, H, W, R) = _pool_common(what, input, rois, output_dim, group_size, pooled_size, part_size, sample_per_part)
+    if part_size != pooled_size:
+        raise RuntimeError("%s: part_size %d != pooled_size %d: the reference indexes its [R,2,P,P] offsets with part_size"
+                           % (what, part_size, pooled_size))
+    offset_mask = offset_mask.contiguous()
+    if offset_mask.dtype != torch.float32 or tuple(offset_mask.shape) != (R, 3, pooled_size, pooled_size):
+        raise RuntimeError("%s: offset/mask %s is not float32 [%d, 3, %d, %d]" % (what, tuple(offset_mask.shape), R, pooled_size,
+                                                                                 pooled_size))
+    out = torch.empty(R, output_dim, pooled_size, pooled_size, dtype=torch.float32, device=input.device)
+    if R == 0:
+        return out
+    with torch.cuda.device(input.device):
+        rc = _lib.lib().h3d_dcn_pooling_modulated(
+            _lib.ptr(input), _lib.ptr(rois), _lib.ptr(offset_mask), _lib.ptr(out), B, C, H, W, R, float(spatial_scale), output_dim,
+            group_size, pooled_size, part_size, sample_per_part, float(trans_std), _lib.stream_ptr())
+    _lib.check(rc, what)
+    return out
+
+
+def dcn_v2_pooling(input, rois, offset, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None,
+                   sample_per_part=4, trans_std=.0):
+    """`_DCNv2Pooling.apply` argument order and defaults (dcn_v2.py:132-161), forward only: returns `output`."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, offset)):
+        raise RuntimeError("h3d_amd DCNv2 pooling is inference-only (dcn_v2_psroi_pooling_backward is out of scope): "
+                           "an input tensor requires grad")
+    part_size = pooled_size if part_size is None else part_size
+    with torch.no_grad():
+        out, _ = dcn_v2_psroi_pooling_forward(input, rois, offset, int(no_trans), spatial_scale, output_dim, group_size, pooled_size,
+                                              part_size, sample_per_part, trans_std)
+    return out
+
+
+class DCNv2Pooling(nn.Module):
+    """Pooling parameters + forward(input, rois, offset) (dcn_v2.py:190-226)."""
+
+    def __init__(self, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None, sample_per_part=4,
+                 trans_std=.0):
+        super().__init__()
+        self.spatial_scale = spatial_scale
+        self.pooled_size = pooled_size
+        self.output_dim = output_dim
+        self.no_trans = no_trans
+        self.group_size = group_size
+        self.part_size = pooled_size if part_size is None else part_size
+        self.sample_per_part = sample_per_part
+        self.trans_std = trans_std
+
+    def forward(self, input, rois, offset):
+        assert input.shape[1] == self.output_dim
+        if self.no_trans:
+            offset = input.new()
+        return dcn_v2_pooling(input, rois, offset, self.spatial_scale, self.pooled_size, self.output_dim, self.no_trans,
+                              self.group_size, self.part_size, self.sample_per_part, self.trans_std)
+
+
+class DCNPooling(DCNv2Pooling):
+    """DCNv2Pooling + its own offset/mask predictor (dcn_v2.py:229-303): `offset_mask_fc` = Linear / ReLU / Linear / ReLU / Linear,
+    the last layer zero-initialised.  forward(input, rois): pool without translation, run the MLP (torch nn.Linear: plumbing), then
+    ONE launch pools with the predicted offsets and multiplies by sigmoid(mask)."""
+
+    def __init__(self, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None, sample_per_part=4,
+                 trans_std=.0, deform_fc_dim=1024):
+        super().__init__(spatial_scale, pooled_size, output_dim, no_trans, group_size, part_size, sample_per_part, trans_std)
+        self.deform_fc_dim = deform_fc_dim
+        if not no_trans:
+            self.offset_mask_fc = nn.Sequential(
+                nn.Linear(self.pooled_size * self.pooled_size * self.output_dim, self.deform_fc_dim),
+                nn.ReLU(inplace=True),
+                nn.Linear(self.deform_fc_dim, self.deform_fc_dim),
+                nn.ReLU(inplace=True),
+                nn.Linear(self.deform_fc_dim, self.pooled_size * self.pooled_size * 3))
+            with torch.no_grad():
+                self.offset_mask_fc[4].weight.zero_()
+                self.offset_mask_fc[4].bias.zero_()
+
+    def forward(self, input, rois):
+        if torch.is_grad_enabled() and input.requires_grad:
+            raise RuntimeError("h3d_amd DCNv2 pooling is inference-only (dcn_v2_psroi_pooling_backward is out of scope): "
+                               "the input requires grad")
+        with torch.no_grad():
+            out = self._forward(input, rois)
+        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return _InferenceOnly.apply(out, *[p for p in self.parameters() if p.requires_grad])    # forward works, backward raises
+        return out
+
+    def _forward(self, input, rois):
+        if self.no_trans:
+            return dcn_v2_pooling(input, rois, input.new(), self.spatial_scale, self.pooled_size, self.output_dim, self.no_trans,
+                                  self.group_size, self.part_size, self.sample_per_part, self.trans_std)
+        if self.part_size != self.pooled_size:
+            raise RuntimeError("DCNPooling: part_size %d != pooled_size %d: the reference indexes its [R,2,P,P] offsets with "
+                               "part_size" % (self.part_size, self.pooled_size))
+        n = rois.shape[0]
+        roi = dcn_v2_pooling(input, rois, input.new(), self.spatial_scale, self.pooled_size, self.output_dim, True,
+                             self.group_size, self.part_size, self.sample_per_part, self.trans_std)
+        offset_mask = self.offset_mask_fc(roi.reshape(n, self.output_dim * self.pooled_size ** 2)).view(n, 3, self.pooled_size, self.pooled_size)
+        return _dcn_pooling_modulated(input, rois, offset_mask, self.spatial_scale, self.pooled_size, self.output_dim,
+                                      self.group_size, self.part_size, self.sample_per_part, self.trans_std)

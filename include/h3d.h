@@ -127,6 +127,34 @@ int h3d_dcn_v2_forward_packed(const void *input, const void *packed, const float
                               int B, int C, int H, int W, int Cout, int dtype, int flags,
                               void *workspace, size_t workspace_bytes, void *stream);
 
+/* Deformable PS-ROI pooling, forward: `_ext.dcn_v2_psroi_pooling_forward` (DCNv2/src/dcn_v2.h:76-107 ->
+ * dcn_v2_psroi_pooling_cuda.cu:58-146, 271-341), positional twin plus outputs, shapes and stream (csrc/psroi.hip).
+ *   input  [B,C,H,W] fp32 NCHW contiguous     bbox [num_bbox,5] rows (batch, x1, y1, x2, y2) in input-image px
+ *   trans  [>= num_bbox, channels_trans, part_size, part_size]; may be NULL when no_trans (channels_trans is then ignored)
+ *   output, output_count [num_bbox, output_dim, P, P], P = pooled_size; output_count = number of valid samples (as float)
+ * Arithmetic: the reference's, op for op in fp32 (roundf = half away from zero, fmaxf / fminf clamps, corners floor / ceil).
+ * Where this library decides (the reference is undefined or wider):
+ *   1. fp32 only (the reference also dispatches double).
+ *   2. group_size == 1 only (H3D_ERR_UNSUPPORTED): the reference asserts channels == output_dim yet reads channel
+ *      (ctop*gs+gh)*gs+gw, past the input for any group_size > 1.
+ *   3. output_dim == C (H3D_ERR_SHAPE, "input channels and output channels must equal").
+ *   4. without no_trans: channels_trans even >= 2, num_classes = channels_trans / 2 divides output_dim (H3D_ERR_SHAPE); trans may
+ *      have more rows than rois.
+ *   5. no read out of bounds on any input: a roi whose batch index is not finite or truncates outside [0,B) gives 0 with count 0
+ *      (the reference reads out of bounds); non-finite coordinates / translations follow the reference's arithmetic (infinite
+ *      samples fail the gate, NaN ones clamp to 0), so outputs stay finite.
+ *   num_bbox == 0: nothing is launched.  pooled_size <= 45.  NULL pointers: H3D_ERR_ARG. */
+int h3d_dcn_v2_psroi_pooling_forward(const float *input, const float *bbox, const float *trans, float *output, float *output_count,
+                                     int B, int C, int H, int W, int num_bbox, int channels_trans, int no_trans, float spatial_scale,
+                                     int output_dim, int group_size, int pooled_size, int part_size, int sample_per_part,
+                                     float trans_std, void *stream);
+/* The second pooling pass of the `DCNPooling` module (dcn_v2.py:266-292) in one launch: offset_mask is the fully-connected output
+ * [num_bbox,3,P,P]; channels 0/1 are the translations (no_trans = 0, one class) and the pooled result is multiplied by
+ * sigmoid(channel 2) -- chunk + cat + sigmoid + pool + mul.  part_size == pooled_size; no count output; otherwise as above. */
+int h3d_dcn_pooling_modulated(const float *input, const float *bbox, const float *offset_mask, float *output, int B, int C, int H,
+                              int W, int num_bbox, float spatial_scale, int output_dim, int group_size, int pooled_size, int part_size,
+                              int sample_per_part, float trans_std, void *stream);
+
 /* =====================================================================================
  * 2. Network ops (DLA-34 + DLAUp/IDAUp + heads, model.py:32-61,148-222,286-292,346-415,475-489)
  *    on the internal layout: activations NHWC (channels-last) of element type f32 or bf16,
