@@ -17,7 +17,7 @@ OP_IM2COL, OP_MAXPOOL3, OP_DEPTH2SPACE = 15, 16, 17
 HEADS_MAX = 16
 OUT_NHWC, OUT_NCHW_F32, OUT_NHWC_F32, OUT_NHWC_F16 = 0, 1, 2, 3
 DCN_INPUT_NHWC, DCN_OUTPUT_NHWC, DCN_F32_MFMA = 1, 2, 4
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 c_vp, c_i, c_fp = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
 
@@ -59,6 +59,7 @@ SIGNATURES = {
     "h3d_dcn_v2_pack_weights_cached": [c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp, c_vp],
     "h3d_dcn_fused_pack_f32_cached": [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp],
     "h3d_dcn_v2_forward_packed": [c_vp] * 5 + [c_i] * 7 + [c_vp, ctypes.c_size_t, c_vp],
+    "h3d_dcn_nchw_to_nhwc_scaled": [c_vp, c_vp] + [c_i] * 4 + [c_vp, c_vp],
     "h3d_dcn_offset_mask": [c_vp] * 5 + [c_i] * 11 + [c_vp],
     "h3d_dcn_v2_psroi_pooling_forward": [c_vp] * 5 + [c_i] * 7 + [ctypes.c_float] + [c_i] * 5 + [ctypes.c_float, c_vp],
     "h3d_dcn_pooling_modulated": [c_vp] * 4 + [c_i] * 5 + [ctypes.c_float] + [c_i] * 5 + [ctypes.c_float, c_vp],

@@ -172,8 +172,9 @@ template <> struct ET<f16_t> {
 // survives fp32-level head errors.  A fragment is the SAME 32 bytes per lane as ET<float>'s (8 K elements), holding the 8 hi halves
 // in the first 16 bytes and the 8 lo halves in the second: the LDS geometry of every kernel is the f32 one, filters are pre-split
 // by the host (engine.PackedWeights), activations are split by the thread that stages them into LDS.
-// CONTRACT: |activation| <= 65504 (fp16's range; larger values saturate, finite) -- three orders of magnitude above anything a
-// DLA-34 / Hourglass / ResNet feature map holds.
+// CONTRACT (network plans): |activation| <= 65504 (fp16's range; larger values and NaN saturate, finite) -- three orders of magnitude
+// above anything a DLA-34 / Hourglass / ResNet feature map holds.  The fp32 OPERATOR (csrc/dcn2.hip behind 0x200000, csrc/dcn3.hip's
+// `DCN` module launch) scales its activations by a device-derived power of two first (dcn_act_exp) and does not clamp its samples.
 struct x3_t { float v; };          // element type tag: 4 bytes of fp32 in memory
 // 4 fp32 (16 raw bytes) -> their 4 hi and 4 lo fp16 terms
 // (CLAMP = false: the caller knows |x| <= 65504 already -- a DeformConv sample blended from clamped apron values)
@@ -192,10 +193,11 @@ __device__ __forceinline__ void x3_split4(const u32x4 raw, u32x2 &hi, u32x2 &lo)
 }
 // the staging store of one 16-byte vector (4 fp32) of a 32-byte K group at LDS address `grp`: sub = 0 | 1 = which half of the group's
 // 8 elements the vector holds.  hi terms land in bytes [8 sub, 8 sub + 8), lo terms 16 bytes further on.
+template <bool CLAMP = true>
 __device__ __forceinline__ void x3_store4(char *grp, int sub, const u32x4 raw)
 {
     u32x2 hi, lo;
-    x3_split4(raw, hi, lo);
+    x3_split4<CLAMP>(raw, hi, lo);
     *reinterpret_cast<u32x2 *>(grp + 8 * sub) = hi;
     *reinterpret_cast<u32x2 *>(grp + 16 + 8 * sub) = lo;
 }

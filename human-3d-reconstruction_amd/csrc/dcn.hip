@@ -14,6 +14,7 @@
 #include "common.h"
 #include "epilogue.h"
 #include "dcn_sample.h"
+#include "dcn_traits.h"
 #include <algorithm>
 
 // ================================================================================================
@@ -73,6 +74,8 @@ __global__ __launch_bounds__(256) void dcn_nchw_kernel(DcnNchwArgs a)
                     const float v3 = s.off[2] >= 0 ? im[s.off[2]] : 0.f;
                     const float v4 = s.off[3] >= 0 ? im[s.off[3]] : 0.f;
                     val = (s.w[0] * v1 + s.w[1] * v2 + s.w[2] * v3 + s.w[3] * v4) * s.mask;
+                } else {
+                    val = 0.f * m;      // the reference's `val * mask` with val = 0 (im2col.cu:178): NaN for a NaN / inf mask
                 }
             }
             s_col[kl][p] = val;
@@ -171,22 +174,101 @@ extern "C" int h3d_dcn_v2_forward(const float *input, const float *weight, const
 // (LDS apron gather, sampling geometry once per pixel instead of once per pixel AND channel as
 // dcn_v2_im2col_cuda.cu:170-172 does, exact fmaf chains on v_mfma_f32_32x32x2_f32), which writes the NCHW output itself.
 int h3d_launch_dcn2(const h3d_op &op, hipStream_t st);
+static size_t ws_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
-__global__ void dcn_om_pack_kernel(const float *__restrict__ off, const float *__restrict__ mask, float *__restrict__ om, int HW, size_t total)
+// max |v| over the FINITE values a wave holds, as the bit pattern of the float (monotonic for non-negative values), into *out with one
+// atomicMax per wave -- skipped when the word already holds as much (it only grows: thousands of waves contending for one address cost
+// more than the reads they reduce); *out was zeroed in front (stream ordered).  Every lane of the wave must call it.
+__device__ __forceinline__ void dcn_absmax_commit(unsigned *out, unsigned m)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, d));
+    if ((threadIdx.x & 63) == 0 && m && m > __atomic_load_n(out, __ATOMIC_RELAXED)) atomicMax(out, m);
+}
+__device__ __forceinline__ unsigned dcn_finite_abs_bits(float v)
+{
+    const unsigned u = __float_as_uint(v) & 0x7fffffffu;
+    return u < 0x7f800000u ? u : 0u;                    // NaN / inf do not take part (a NaN must not disable the scale)
+}
+
+// max |x| over the finite elements of a tensor (any layout: the maximum is over all of it) -- the source of the operator's activation
+// scale on the fp16 matrix cores (dcn_act_exp, csrc/dcn_traits.h).  VEC: 16-byte aligned and n % 4 == 0.
+template <bool VEC>
+__global__ __launch_bounds__(256) void dcn_absmax_kernel(const float *__restrict__ p, size_t n, unsigned *__restrict__ out)
+{
+    unsigned m = 0;
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    if constexpr (VEC) {
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n / 4; i += step) {
+            const f32x4 v = reinterpret_cast<const f32x4 *>(p)[i];
+            m = max(max(m, dcn_finite_abs_bits(v[0])), max(dcn_finite_abs_bits(v[1]), max(dcn_finite_abs_bits(v[2]), dcn_finite_abs_bits(v[3]))));
+        }
+    } else {
+        for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += step) m = max(m, dcn_finite_abs_bits(p[i]));
+    }
+    // one atomic per workgroup: the workgroups finish together, and a word thousands of waves update at once costs more than the read
+    __shared__ unsigned s_m[4];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, d));
+    if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = max(max(s_m[0], s_m[1]), max(s_m[2], s_m[3]));
+        if (m) atomicMax(out, m);
+    }
+}
+
+static int dcn_absmax(const float *p, size_t n, unsigned *out, hipStream_t st)
+{
+    const bool vec = ((uintptr_t)p & 15) == 0 && n % 4 == 0;
+    const size_t items = vec ? n / 4 : n;
+    const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((items + 4 * 256 - 1) / (4 * 256), 1), 512);
+    if (vec) hipLaunchKernelGGL(dcn_absmax_kernel<true>, dim3(blocks), dim3(256), 0, st, p, n, out);
+    else hipLaunchKernelGGL(dcn_absmax_kernel<false>, dim3(blocks), dim3(256), 0, st, p, n, out);
+    H3D_CHECK_LAUNCH("dcn_absmax_kernel");
+    return H3D_OK;
+}
+
+// mmax != nullptr: max |mask| over the finite mask values as well (the activation scale's headroom for a caller's mask outside [0, 1])
+__global__ void dcn_om_pack_kernel(const float *__restrict__ off, const float *__restrict__ mask, float *__restrict__ om, int HW, size_t total,
+                                   unsigned *__restrict__ mmax)
 {
     // thread = pixel: 27 coalesced channel reads (consecutive threads = consecutive pixels), one 128-byte row written
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const size_t b = i / HW, n = i - b * HW;
-    f32x4 row[8];
+    unsigned mx = 0;
+    if (i < total) {
+        const size_t b = i / HW, n = i - b * HW;
+        f32x4 row[8];
 #pragma unroll
-    for (int c = 0; c < 18; ++c) row[c >> 2][c & 3] = off[(b * 18 + c) * HW + n];
+        for (int c = 0; c < 18; ++c) row[c >> 2][c & 3] = off[(b * 18 + c) * HW + n];
 #pragma unroll
-    for (int c = 0; c < 9; ++c) row[(18 + c) >> 2][(18 + c) & 3] = mask[(b * 9 + c) * HW + n];
+        for (int c = 0; c < 9; ++c) {
+            const float v = mask[(b * 9 + c) * HW + n];
+            row[(18 + c) >> 2][(18 + c) & 3] = v;
+            mx = max(mx, dcn_finite_abs_bits(v));
+        }
 #pragma unroll
-    for (int c = 27; c < 32; ++c) row[c >> 2][c & 3] = 0.f;
+        for (int c = 27; c < 32; ++c) row[c >> 2][c & 3] = 0.f;
 #pragma unroll
-    for (int q = 0; q < 8; ++q) reinterpret_cast<f32x4 *>(om + i * 32)[q] = row[q];
+        for (int q = 0; q < 8; ++q) reinterpret_cast<f32x4 *>(om + i * 32)[q] = row[q];
+    }
+    if (mmax) dcn_absmax_commit(mmax, mx);
+}
+
+// The offset / mask rows of the fp32 fast path, followed by the two activation maxima (max |x|, max |mask|) the f16x3 kernel scales by
+// (h3d_op.reserved 0x200000 in csrc/dcn2.hip): zeroed, then filled by dcn_absmax and the om pack kernel -- all on the caller's stream.
+static size_t dcn_om_bytes(size_t px) { return ws_align(px * 32 * 4 + 16); }
+static int dcn_om_pack(const float *x, size_t nx, const float *offset, const float *mask, float *om, int HW, size_t px, bool f16x3, hipStream_t st)
+{
+    unsigned *amax = f16x3 ? (unsigned *)(om + px * 32) : nullptr;
+    if (amax) {
+        if (hipMemsetAsync(amax, 0, 16, st) != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "dcn_v2_forward: memset");
+        int rc = dcn_absmax(x, nx, amax, st);
+        if (rc != H3D_OK) return rc;
+    }
+    hipLaunchKernelGGL(dcn_om_pack_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, offset, mask, om, HW, px, amax ? amax + 1 : nullptr);
+    H3D_CHECK_LAUNCH("dcn_om_pack_kernel");
+    return H3D_OK;
 }
 
 // max |filter| of an fp32 pack, as the bit pattern of the float (monotonic for non-negative values; a NaN sorts above everything and
@@ -219,8 +301,6 @@ __global__ void dcn_w_pack_kernel(const float *__restrict__ w, const float *__re
     dcn_wmax_accumulate(wmax, v);          // (every lane of the wave takes part in the shuffles)
 }
 
-static size_t ws_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // fp16 twin of dcn_w_pack_kernel: the filter format of the bf16 DeformConv kernels (csrc/dcn2.hip)
 __global__ void dcn_w_pack_f16_kernel(const float *__restrict__ w, const float *__restrict__ bias, _Float16 *__restrict__ wp, float *__restrict__ bp,
                                       int Cout, int C, int rows)
@@ -239,7 +319,7 @@ extern "C" size_t h3d_dcn_v2_workspace_bytes(int B, int C, int H, int W, int Cou
 {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
     const size_t rows = ((size_t)Cout + 127) / 128 * 128, px = (size_t)B * H * W;
-    return ws_align(px * C * 4) + ws_align(px * 32 * 4) + ws_align(rows * 9 * C * 4) + ws_align(rows * 4) + H3D_DCN_AUX_BYTES;
+    return ws_align(px * C * 4) + dcn_om_bytes(px) + ws_align(rows * 9 * C * 4) + ws_align(rows * 4) + H3D_DCN_AUX_BYTES;
 }
 
 // The arithmetic of the operator's fp32 fast path: three fp16 MFMAs on split operands per fp32 product (H3D_F16X3: 2^-22 relative per
@@ -268,24 +348,25 @@ extern "C" int h3d_dcn_v2_forward_ws(const float *input, const float *weight, co
     const size_t px = (size_t)B * H * W;
     char *ws = (char *)workspace;
     float *x_nhwc = (float *)ws;                ws += ws_align(px * C * 4);
-    float *om = (float *)ws;                    ws += ws_align(px * 32 * 4);
+    float *om = (float *)ws;                    ws += dcn_om_bytes(px);
     float *wp = (float *)ws;                    ws += ws_align((size_t)rows * 9 * C * 4);
     float *bp = (float *)ws;                    // [rows] + H3D_DCN_AUX_BYTES (rows is a multiple of 128: no padding in between)
     unsigned *wmax = (unsigned *)(bp + rows);
     if (hipMemsetAsync(wmax, 0, H3D_DCN_AUX_BYTES, st) != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "dcn_v2_forward: memset");
     int rc = h3d_nchw_f32_to_nhwc(input, x_nhwc, H3D_F32, B, C, H, W, C, stream);
     if (rc != H3D_OK) return rc;
-    hipLaunchKernelGGL(dcn_om_pack_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, offset, mask, om, H * W, px);
-    H3D_CHECK_LAUNCH("dcn_om_pack_kernel");
+    const bool f16x3 = !dcn_op_f32_mfma();
+    rc = dcn_om_pack(input, px * C, offset, mask, om, H * W, px, f16x3, st);
+    if (rc != H3D_OK) return rc;
     const size_t wtotal = (size_t)rows * 9 * C;
     hipLaunchKernelGGL(dcn_w_pack_kernel, dim3((unsigned)((wtotal + 255) / 256)), dim3(256), 0, st, weight, bias, wp, bp, Cout, C, rows, wmax);
     H3D_CHECK_LAUNCH("dcn_w_pack_kernel");
     h3d_op op = {};
-    op.kind = H3D_OP_DCN; op.dtype = dcn_op_f32_mfma() ? H3D_F32 : H3D_F16X3;
+    op.kind = H3D_OP_DCN; op.dtype = f16x3 ? H3D_F16X3 : H3D_F32;
     op.in = x_nhwc; op.in2 = om; op.w = wp; op.bias = bp; op.out = output;
     op.B = B; op.H = H; op.W = W; op.Cin = C; op.in_cs = C; op.in2_cs = 32; op.Ho = H; op.Wo = W; op.Cout = Cout; op.out_cs = Cout;
     op.ksize = 3; op.stride = 1; op.relu = 0; op.out_mode = H3D_OUT_NCHW_F32; op.wrows = rows;
-    op.reserved = 0x800 | (op.dtype == H3D_F16X3 ? 0x100000 : 0);      // the mask operand is final (the reference applies the sigmoid in DCN.forward, dcn_v2.py:124); fp32 pack + max |w|
+    op.reserved = 0x800 | (f16x3 ? 0x300000 : 0);      // the mask operand is final (the reference applies the sigmoid in DCN.forward, dcn_v2.py:124); fp32 pack + max |w|; activation maxima
     return h3d_launch_dcn2(op, st);
 }
 
@@ -495,7 +576,7 @@ extern "C" size_t h3d_dcn_v2_packed_workspace_bytes(int B, int C, int H, int W, 
 {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
     const size_t px = (size_t)B * H * W;
-    return ws_align(px * 32 * 4) + ((flags & H3D_DCN_INPUT_NHWC) ? 0 : ws_align(px * C * 4));
+    return dcn_om_bytes(px) + ((flags & H3D_DCN_INPUT_NHWC) ? 0 : ws_align(px * C * 4));
 }
 
 extern "C" int h3d_dcn_v2_forward_packed(const void *input, const void *packed, const float *offset, const float *mask, void *output, int B,
@@ -514,23 +595,58 @@ extern "C" int h3d_dcn_v2_forward_packed(const void *input, const void *packed, 
     const int rows = (Cout + 127) / 128 * 128;
     const size_t px = (size_t)B * H * W;
     char *ws = (char *)workspace;
-    float *om = (float *)ws;                    ws += ws_align(px * 32 * 4);
+    float *om = (float *)ws;                    ws += dcn_om_bytes(px);
     const void *x = input;
     if (!(flags & H3D_DCN_INPUT_NHWC)) {
         int rc = h3d_nchw_f32_to_nhwc((const float *)input, ws, H3D_F32, B, C, H, W, C, stream);
         if (rc != H3D_OK) return rc;
         x = ws;
     }
-    hipLaunchKernelGGL(dcn_om_pack_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, offset, mask, om, H * W, px);
-    H3D_CHECK_LAUNCH("dcn_om_pack_kernel");
+    const bool f16x3 = dtype == H3D_F32 && !(flags & H3D_DCN_F32_MFMA) && !dcn_op_f32_mfma();
+    int rc = dcn_om_pack((const float *)input, px * C, offset, mask, om, H * W, px, f16x3, st);      // (max |x| from the caller's tensor, either layout)
+    if (rc != H3D_OK) return rc;
     h3d_op op = {};
     op.kind = H3D_OP_DCN;
-    op.dtype = dtype == H3D_F32 && !(flags & H3D_DCN_F32_MFMA) && !dcn_op_f32_mfma() ? H3D_F16X3 : dtype;
+    op.dtype = f16x3 ? H3D_F16X3 : dtype;
     op.in = x; op.in2 = om; op.w = packed;
     op.bias = (const float *)((const char *)packed + ws_align((size_t)rows * 9 * C * (dtype == H3D_F32 ? 4 : 2)));
     op.out = output;
     op.B = B; op.H = H; op.W = W; op.Cin = C; op.in_cs = C; op.in2_cs = 32; op.Ho = H; op.Wo = W; op.Cout = Cout; op.out_cs = Cout;
     op.ksize = 3; op.stride = 1; op.relu = 0; op.out_mode = (flags & H3D_DCN_OUTPUT_NHWC) ? H3D_OUT_NHWC : H3D_OUT_NCHW_F32; op.wrows = rows;
-    op.reserved = 0x800 | (op.dtype == H3D_F16X3 ? 0x100000 : 0);      // the mask operand is final; fp32 pack + max |w| behind the bias
+    op.reserved = 0x800 | (f16x3 ? 0x300000 : 0);      // the mask operand is final; fp32 pack + max |w| behind the bias; activation maxima behind om
     return h3d_launch_dcn2(op, st);
+}
+
+// The stand-alone `DCN` module's input for its f16x3 fused launch (H3D_OP_DCN_FUSED, dtype H3D_F16X3, reserved 0x300000): max |x| over the
+// finite elements into amax[0], then NCHW -> NHWC with x multiplied by 2^dcn_act_exp(max |x|, 0) (exact: a power of two), so that the
+// kernel's fp16 operand split sees values below 2^14 whatever the caller's magnitude; the kernel multiplies both of its accumulations
+// (offset convolution, DeformConv) by the inverse.  amax: one word of device memory (h3d_dcn_fused_pack_f32_cached's bias_out[rows + 34]).
+__global__ void dcn_nchw_to_nhwc_scaled_kernel(const float *__restrict__ src, float *__restrict__ dst, int C, int HW, const unsigned *__restrict__ amax)
+{
+    __shared__ float tile[32][33];
+    const float sc = ldexpf(1.f, dcn_act_exp(*amax, 0u));
+    const int b = blockIdx.z, p0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    for (int k = ty; k < 32; k += 8) {
+        const int c = c0 + k, p = p0 + tx;
+        tile[k][tx] = (c < C && p < HW) ? src[((size_t)b * C + c) * HW + p] : 0.f;
+    }
+    __syncthreads();
+    for (int k = ty; k < 32; k += 8) {
+        const int p = p0 + k, c = c0 + tx;
+        if (p < HW && c < C) dst[((size_t)b * HW + p) * C + c] = tile[tx][k] * sc;
+    }
+}
+
+extern "C" int h3d_dcn_nchw_to_nhwc_scaled(const float *src, float *dst, int B, int C, int H, int W, unsigned *amax, void *stream)
+{
+    if (!src || !dst || !amax) H3D_FAIL(H3D_ERR_ARG, "dcn_nchw_to_nhwc_scaled: null pointer");
+    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) H3D_FAIL(H3D_ERR_SHAPE, "dcn_nchw_to_nhwc_scaled: bad shape");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(amax, 0, 4, st) != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "dcn_nchw_to_nhwc_scaled: memset");
+    int rc = dcn_absmax(src, (size_t)B * C * H * W, amax, st);
+    if (rc != H3D_OK) return rc;
+    hipLaunchKernelGGL(dcn_nchw_to_nhwc_scaled_kernel, dim3(cdiv(H * W, 32), cdiv(C, 32), B), dim3(256), 0, st, src, dst, C, H * W, amax);
+    H3D_CHECK_LAUNCH("dcn_nchw_to_nhwc_scaled_kernel");
+    return H3D_OK;
 }

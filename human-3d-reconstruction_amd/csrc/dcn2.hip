@@ -32,6 +32,7 @@ struct Dcn2Args {
     int dbg;   // ablation switches for profiling (h3d_op.reserved): 1 = stage only chunk 0, 2 = no gather/blend, 4 = no MFMA
     int mask_final;   // om[18..26] is the mask itself, not its logit (operator boundary h3d_dcn_v2_forward_ws; op.reserved & 0x800)
     const unsigned *wmax;   // H3D_F16X3 (the operator's fp32 fast path): bit pattern of max |filter|, written by the pack kernels (csrc/dcn.hip)
+    const unsigned *amax;   // H3D_F16X3 behind 0x200000: [0] max |x|, [1] max |mask| over finite elements (csrc/dcn.hip), the activation scale's source
 };
 
 template <typename T, int MT, int CK, int MARGIN, int NT_>
@@ -96,6 +97,17 @@ __global__ __launch_bounds__(512 / NT_) void dcn2_kernel(Dcn2Args a)
         wsc = ldexpf(1.f, e);
         wun = ldexpf(1.f, -e);
     }
+    // ... and the activations by a second power of two (dcn_act_exp), folded into the mask of every sample: the blend runs in fp32 on the
+    // unconverted apron, so the blended sample comes out scaled and is split without a clamp (a NaN or an infinity stays non-finite);
+    // the accumulators are multiplied by the inverse after wun (two exact steps)
+    [[maybe_unused]] float xsc = 1.f, xun = 1.f;
+    if constexpr (std::is_same_v<T, x3_t>) {
+        if (a.amax) {
+            const int e = dcn_act_exp(a.amax[0], a.amax[1]);
+            xsc = ldexpf(1.f, e);
+            xun = ldexpf(1.f, -e);
+        }
+    }
     [[maybe_unused]] auto store_w = [&](char *dst_row_tap, int v, u32x4 raw) {      // one 16-byte vector of a staged filter row -> LDS
         if constexpr (std::is_same_v<T, x3_t>) {
 #pragma unroll
@@ -134,7 +146,13 @@ __global__ __launch_bounds__(512 / NT_) void dcn2_kernel(Dcn2Args a)
             const float w_im = (float)(ox - 1 + tj) + omv[2 * tap + 1];
             const bool inside = live && (h_im > -1.f && w_im > -1.f && h_im < (float)a.H && w_im < (float)a.W);
             typename X::geo g = X::zero_geo();
-            int off = 8 * h * SS;
+            // a sample with zero coefficients still reads its four corners: point it at the undeformed tap, inside the apron and inside
+            // this pixel's own 4x4 neighbourhood, so that a non-finite pixel elsewhere in the tile cannot reach this output through 0 * v
+            int off = 8 * h * SS + (oy - 1 + ti - hy0) * C::RBH + (ox - 1 + tj - hx0) * C::SBH;
+            if (!inside && live && a.mask_final) {
+                const float w0[4] = {0.f, 0.f, 0.f, 0.f};
+                g = X::make_geo(w0, omv[18 + tap]);        // the reference's `val * mask` with val = 0 (im2col.cu:178): NaN for a NaN / inf mask
+            }
             if (inside) {
                 const int hl = (int)floorf(h_im), wl = (int)floorf(w_im);
                 const int ry = hl - hy0, rx = wl - hx0;
@@ -142,8 +160,8 @@ __global__ __launch_bounds__(512 / NT_) void dcn2_kernel(Dcn2Args a)
                     const float lh = h_im - (float)hl, lw = w_im - (float)wl;
                     const float hh = 1.f - lh, hw = 1.f - lw;
                     const float w4[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
-                    g = X::make_geo(w4, a.mask_final ? omv[18 + tap] : dcn2_sigmoid(omv[18 + tap]));
-                    off += ry * C::RBH + rx * C::SBH;
+                    g = X::make_geo(w4, (a.mask_final ? omv[18 + tap] : dcn2_sigmoid(omv[18 + tap])) * xsc);
+                    off = 8 * h * SS + ry * C::RBH + rx * C::SBH;
                 } else {
                     slow = true;
                 }
@@ -187,7 +205,9 @@ __global__ __launch_bounds__(512 / NT_) void dcn2_kernel(Dcn2Args a)
             if (i < NH) {
                 const int v = i % C::VPP, pix = i / C::VPP;
                 const int iy = pix / C::HH, ix = pix - iy * C::HH;
-                *reinterpret_cast<u32x4 *>(s_h + iy * C::RBH + ix * C::SBH + v * 16) = X::convert16(stg[j]);
+                // (f16x3 with an activation scale: the apron stays unconverted fp32 -- the scale is applied in the blend -- and unclamped)
+                *reinterpret_cast<u32x4 *>(s_h + iy * C::RBH + ix * C::SBH + v * 16) =
+                    (std::is_same_v<T, x3_t> && a.amax) ? stg[j] : X::convert16(stg[j]);
             } else if (i < NH + NW) {
                 const int q0 = i - NH;
                 const int row = q0 / WV, q = q0 - row * WV;
@@ -328,7 +348,7 @@ __global__ __launch_bounds__(512 / NT_) void dcn2_kernel(Dcn2Args a)
                     const float lh = h_im - (float)hl, lw = w_im - (float)wl;
                     const float hh = 1.f - lh, hw = 1.f - lw;
                     const float w4[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
-                    const typename X::geo g = X::make_geo(w4, a.mask_final ? omp[18 + tap] : dcn2_sigmoid(omp[18 + tap]));
+                    const typename X::geo g = X::make_geo(w4, (a.mask_final ? omp[18 + tap] : dcn2_sigmoid(omp[18 + tap])) * xsc);
                     const bool okh0 = hl >= 0, okh1 = hl + 1 <= a.H - 1, okw0 = wl >= 0, okw1 = wl + 1 <= a.W - 1;
                     const bool ok[4] = {okh0 && okw0, okh0 && okw1, okh1 && okw0, okh1 && okw1};
                     const int pix[4] = {hl * a.W + wl, hl * a.W + wl + 1, (hl + 1) * a.W + wl, (hl + 1) * a.W + wl + 1};
@@ -349,7 +369,8 @@ __global__ __launch_bounds__(512 / NT_) void dcn2_kernel(Dcn2Args a)
                     for (int m = 0; m < MT; ++m) fa[m] = X::lds_w(s_w + aoff + m * 32 * C::WB + (tap * CK + kk * 16) * SS);
 #pragma unroll
                     for (int n = 0; n < NT; ++n) {
-                        const typename X::bfrag pb = X::prep_raw(fb[n][kk]);      // (corners straight from memory: the split clamps)
+                        // (corners straight from memory: the split clamps -- unless the activations are scaled, which bounds the sample)
+                        const typename X::bfrag pb = (std::is_same_v<T, x3_t> && a.amax) ? X::prep(fb[n][kk]) : X::prep_raw(fb[n][kk]);
 #pragma unroll
                         for (int m = 0; m < MT; ++m) X::mma(acc[m][n], fa[m], pb);
                     }
@@ -363,7 +384,7 @@ __global__ __launch_bounds__(512 / NT_) void dcn2_kernel(Dcn2Args a)
 #pragma unroll
             for (int n = 0; n < NT; ++n)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) acc[m][n][i] *= wun;
+                for (int i = 0; i < 16; ++i) acc[m][n][i] = acc[m][n][i] * wun * xun;
     }
     EpiArgs e;
     e.bias = a.bias; e.res = nullptr; e.out = a.out; e.Ho = a.H; e.Wo = a.W; e.Cout = a.Cout;
@@ -410,6 +431,7 @@ int h3d_launch_dcn2(const h3d_op &op, hipStream_t st)
     a.dbg = op.reserved;
     a.mask_final = (op.reserved >> 11) & 1;
     a.wmax = nullptr;
+    a.amax = nullptr;
     if (op.dtype == H3D_BF16) {
         if (op.Cin % 32 == 0 && op.Cout <= 64) {
             if (op.Cout <= 32) return launch_dcn2_cfg<bf16_t, 1, 32, 2, 2>(a, st);
@@ -429,6 +451,8 @@ int h3d_launch_dcn2(const h3d_op &op, hipStream_t st)
         // the operator's fp32 fast path on the fp16 matrix cores: fp32 tensors and the plain fp32 filter pack of H3D_F32, every product as
         // three fp16 MFMAs on split operands (csrc/common.h ET<x3_t>).  bias[wrows] holds the bit pattern of max |filter| (see Dcn2Args)
         a.wmax = (const unsigned *)(op.bias + op.wrows);
+        // 0x200000: the two activation maxima follow the [B,H,W,in2_cs] offset / mask rows (csrc/dcn.hip)
+        if (op.reserved & 0x200000) a.amax = (const unsigned *)((const float *)op.in2 + (size_t)op.B * op.H * op.W * op.in2_cs);
         if (op.Cout <= 32) return launch_dcn2_cfg<x3_t, 1, 16, 2, 1>(a, st);
         return launch_dcn2_cfg<x3_t, 2, 16, 2, 1>(a, st);
     }

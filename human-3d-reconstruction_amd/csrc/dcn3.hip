@@ -41,6 +41,7 @@ struct Dcn3Args {
     const unsigned *wmax;   // f16x3, register-staged filters only (the stand-alone `DCN` module): the filters are PLAIN fp32 packs and [0] / [1] hold the
                             // bit patterns of max |main filter| / max |offset filter| (csrc/dcn.hip dcn_fused_pack_f32_if_kernel): scaled by a power of
                             // two and split while they are staged, as csrc/dcn2.hip does for the operator; nullptr = pre-split filters (network plans)
+    int xscaled;   // with wmax: the input was scaled by 2^dcn_act_exp(wmax[2]) (reserved 0x200000, the `DCN` module's f16x3 launch)
     int xcd;   // h3d_tile_id mode
     unsigned long long *stamps;   // profiling builds: in-kernel phase stamps (common.h H3D_STAMP)
 };
@@ -170,8 +171,22 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
                 wsc[q] = ldexpf(1.f, e);
                 (q ? oun : wun) = ldexpf(1.f, -e);
             }
+            if (a.xscaled) {            // the input was multiplied by 2^e in its relayout (h3d_dcn_nchw_to_nhwc_scaled): unscale both contractions
+                const float xun = ldexpf(1.f, -dcn_act_exp(a.wmax[2], 0u));
+                wun *= xun;
+                oun *= xun;
+            }
         }
     }
+    // the `DCN` module's launch (0x200000): x arrives scaled below 2^14 (h3d_dcn_nchw_to_nhwc_scaled), so staging and splitting need no
+    // clamp -- and take none, so that a NaN / inf activation stays non-finite through both contractions as it does in the reference
+    [[maybe_unused]] const bool xraw = std::is_same_v<T, x3_t> && !WDMA && a.xscaled;
+    [[maybe_unused]] auto prep_mem = [&](const typename X::frag &f) {      // a sample blended from values read straight from memory
+        if constexpr (std::is_same_v<T, x3_t> && !WDMA) {
+            if (xraw) return X::prep(f);
+        }
+        return X::prep_raw(f);
+    };
     [[maybe_unused]] auto store_w = [&](char *dst_row_tap, int v, u32x4 raw, int which) {      // one 16-byte vector of a staged filter row -> LDS
         if constexpr (std::is_same_v<T, x3_t> && !WDMA) {
             if (rawf) {
@@ -239,11 +254,12 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
                 const int iy = pix / C::HH, ix = pix - iy * C::HH;
                 if constexpr (X::SPLIT_A) {
                     if (s < nchunks) {                              // (f16x3, phase A: operand fragments; phase B: the fp32 values the blend reads)
-                        x3_store4(s_h + iy * C::RBH + ix * C::SBH + (v >> 1) * 32, v & 1, stg[j]);
+                        if (xraw) x3_store4<false>(s_h + iy * C::RBH + ix * C::SBH + (v >> 1) * 32, v & 1, stg[j]);
+                        else x3_store4(s_h + iy * C::RBH + ix * C::SBH + (v >> 1) * 32, v & 1, stg[j]);
                         continue;
                     }
                 }
-                *reinterpret_cast<u32x4 *>(s_h + iy * C::RBH + ix * C::SBH + ((PK ? (v ^ (iy & 1)) : v) * 16)) = X::convert16(stg[j]);
+                *reinterpret_cast<u32x4 *>(s_h + iy * C::RBH + ix * C::SBH + ((PK ? (v ^ (iy & 1)) : v) * 16)) = xraw ? stg[j] : X::convert16(stg[j]);
             } else if (i < NH + NW) {
                 const int q0 = i - NH;
                 const int row = q0 / WV, q = q0 - row * WV;
@@ -414,9 +430,15 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
             const float lh = h_im - fh, lw = w_im - fw;
             const float hh = 1.f - lh, hw = 1.f - lw;
             const float w4[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
-            typename X::geo g = X::select_geo(inside, X::make_geo(w4, dcn2_sigmoid(aoffs[3 * u + 2])));
+            // a gated sample keeps zero weights times its mask: the reference's `val * mask` with val = 0 (im2col.cu:178), NaN for a NaN mask
+            const float w4g[4] = {inside ? w4[0] : 0.f, inside ? w4[1] : 0.f, inside ? w4[2] : 0.f, inside ? w4[3] : 0.f};
+            typename X::geo g = X::make_geo(w4g, dcn2_sigmoid(aoffs[3 * u + 2]));
             const bool inap = (unsigned)ry < (unsigned)(C::HH - 1) && (unsigned)rx < (unsigned)(C::HH - 1);   // all four corners in the apron
-            const int off = (inside && inap) ? ry * C::RBH + rx * C::SBH + (PK ? ((ry & 1) << 4) : 0) : 0;    // (PK: half 0's bytes; half 1 reads off ^ 16)
+            // (a sample with zero weights still reads four corners: those of its undeformed tap, inside the apron and inside this pixel's
+            //  4 x 4 neighbourhood, so a non-finite pixel elsewhere in the tile cannot reach this output through 0 * v)
+            const int ry0 = py + ti + MARGIN, rx0 = px + tj + MARGIN;
+            const int off = (inside && inap) ? ry * C::RBH + rx * C::SBH + (PK ? ((ry & 1) << 4) : 0)
+                                             : ry0 * C::RBH + rx0 * C::SBH + (PK ? ((ry0 & 1) << 4) : 0);    // (PK: half 0's bytes; half 1 reads off ^ 16)
             const bool want = inside && !inap;               // inside the image, corners outside the apron
             my_want[u] = want;
             my_hw[u] = ((uint32_t)hl << 16) | ((uint32_t)wl & 0xffffu);
@@ -889,7 +911,7 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
 #pragma unroll
                             for (int k = 0; k < 4; ++k) v[k].v = __builtin_bit_cast(half8_t, X::convert16(pv[j][k][0]));
                         }
-                        fbs[j] = X::prep_raw(X::blend(v, qg[t0 + j]));
+                        fbs[j] = prep_mem(X::blend(v, qg[t0 + j]));
                     }
                     if (t0 + TB < 9) fetch(t0 + TB);                               // the next taps fly while these are multiplied
 #pragma unroll
@@ -959,7 +981,7 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
                     typename X::wfrag fa[MT];
 #pragma unroll
                     for (int m = 0; m < MT; ++m) fa[m] = X::lds_w(s_w + aoff + m * 32 * C::WB + (tap * CK + kk * 16) * SS);
-                    const typename X::bfrag pb = X::prep_raw(fb[kk]);
+                    const typename X::bfrag pb = prep_mem(fb[kk]);
 #pragma unroll
                     for (int m = 0; m < MT; ++m) X::mma(acc[m][0], fa[m], pb);
                 }
@@ -1138,6 +1160,7 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
     a.wscale = ldexpf(1.f, -op.wexp);
     a.oscale = ldexpf(1.f, -op.wexp2);
     a.wmax = nullptr;
+    a.xscaled = 0;
     if (wdma && (size_t)op.H * op.W * op.in_cs * es >= 0x7ffffff0ull) H3D_FAIL(H3D_ERR_SHAPE, "dcn_fused_stream: image of 2 GiB or more");
     if (op.dtype == H3D_BF16 && (op.reserved & 0x40000)) return launch_dcn3_lowp<bf16_t, true>(op, a, wdma, st);
     if (op.dtype == H3D_BF16) return launch_dcn3_lowp<bf16_t>(op, a, wdma, st);
@@ -1187,6 +1210,7 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
         if (op.reserved & 0x100000) {
             if (op.wexp || op.wexp2) H3D_FAIL(H3D_ERR_ARG, "dcn_fused (f16x3, raw filters): wexp must be 0 (the scale comes from the pack's maxima)");
             a.wmax = (const unsigned *)(op.bias + op.wrows + 32);
+            a.xscaled = (op.reserved >> 21) & 1;
         }
         if (op.reserved & 0x2000) {         // tuning override (tools/ab_flag.py): the f32 plan's margin-2 double-buffered tile
             if (op.Cout <= 32) return launch_dcn3_cfg<x3_t, 1, 16, 2>(a, st);

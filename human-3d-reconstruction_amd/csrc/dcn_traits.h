@@ -265,4 +265,19 @@ template <> struct SE<x3_t> : SE<float> {
     static __device__ __forceinline__ void mma(f32x16 &acc, const wfrag &a, const bfrag &b) { ET<x3_t>::mma(acc, a, b); }
 };
 
+// The fp32 operator's ACTIVATION scale on the fp16 matrix cores (H3D_F16X3 behind 0x200000, csrc/dcn2.hip / dcn3.hip): the power of two
+// 2^e that puts max |x| * max(1, max |mask|) -- both maxima over FINITE elements only, left on the device by csrc/dcn.hip as float bit
+// patterns -- below 2^14, so that a blended sample (a convex combination of x times the mask) stays far inside fp16's range and the
+// lo terms of its split stay normal fp16 numbers down to 2^-17 of max |x|.  0 when nothing finite is nonzero; e <= 100 - log2 max(1,
+// max |mask|) keeps the scaled mask finite.
+__device__ __forceinline__ int dcn_act_exp(unsigned xmax_bits, unsigned mmax_bits)
+{
+    const float xm = __uint_as_float(xmax_bits), mm = __uint_as_float(mmax_bits);
+    if (!(xm > 0.f)) return 0;
+    int kx, km = 1;
+    (void)frexpf(xm, &kx);
+    if (mm > 1.f) (void)frexpf(mm, &km);
+    return min(100 - km, max(-126, 14 - kx - km));
+}
+
 __device__ __forceinline__ float dcn2_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }   // v_exp + v_rcp (1 ulp each)

@@ -43,9 +43,10 @@ extern "C" {
 const char *h3d_last_error(void);
 /* ABI version of this header; the loader checks it. */
 int h3d_abi_version(void);
-#define H3D_ABI_VERSION 3      /* 2: h3d_op.wexp / wexp2 (120-byte descriptor); 3: fp32 DeformConv packs carry their filter maxima (the sizes
+#define H3D_ABI_VERSION 4      /* 2: h3d_op.wexp / wexp2 (120-byte descriptor); 3: fp32 DeformConv packs carry their filter maxima (the sizes
                                   h3d_dcn_v2_packed_weight_bytes / _workspace_bytes return grew by 256 B; bias_out of h3d_dcn_fused_pack_f32_cached
-                                  is [rows | 32 | 64] floats) */
+                                  is [rows | 32 | 64] floats); 4: the fp32 operator scales its activations too (h3d_dcn_v2_workspace_bytes and
+                                  h3d_dcn_v2_packed_workspace_bytes grew by at most 256 B; h3d_dcn_nchw_to_nhwc_scaled) */
 /* How this library was built: H3D_BUILD_EXTRA = `make EXTRA=1` (the superseded kernel generations kept as A/B references are in:
  * H3D_OP_DCN_V1, H3D_OP_DCN_FUSED_F16, H3D_OP_UPDCN_F16, the 0x4000 DeformConv variant, h3d_smpl_verts2 -- without it they return
  * H3D_ERR_UNSUPPORTED); H3D_BUILD_ABLATE = `make ABLATE=1` (profiling switches and in-kernel stamps compiled in). */
@@ -123,6 +124,21 @@ int h3d_dcn_v2_pack_weights_cached(const float *weight, const float *bias, int C
 int h3d_dcn_fused_pack_f32_cached(const float *weight, const float *bias, const float *off_weight, const float *off_bias, int Cout, int C,
                                   float *wp, float *wo, float *bias_out, void *state, void *stream);
 size_t h3d_dcn_v2_packed_workspace_bytes(int B, int C, int H, int W, int flags);
+/* Numerics of the fp32 fast path (h3d_dcn_v2_forward_ws, h3d_dcn_v2_forward_packed with H3D_F32) in its default arithmetic (split
+ * operands on the fp16 matrix cores): the filters AND the activations are scaled by powers of two the device derives on the caller's
+ * stream -- from max |w|, and from S = max |x| * max(1, max |mask|) over the finite elements of this call -- so every output meets
+ * |y - y64| <= 2e-6 (A + |b|), A = sum |w| |column| (the fp64 value on |x|, |w|, |mask|), when its SAMPLES (bilinear blend times mask,
+ * |blend| * |mask|) lie within 2^-17 of S; below that window -- small inputs, or small masks such as the sigmoid of a strongly negative
+ * logit -- the error stays under 4e-7 S sum |w| of the output row.  Any fp32 mask (values outside [0, 1] included).  Non-finite
+ * values follow the reference (dcn_v2_im2col_cuda.cu:37-48, 178): a NaN / inf offset gates its tap out, a NaN / inf mask makes its
+ * output NaN even when the tap is gated, a NaN / inf pixel makes every output non-finite whose samples read it.
+ * DECIDED HERE: a pixel read with bilinear weight zero counts as read, as in the reference; in addition an output (oy, ox) MAY come out
+ * non-finite when a non-finite pixel lies in rows oy-1 .. oy+2, columns ox-1 .. ox+2 (a gated or far sample still reads its undeformed
+ * tap's 2x2 corners with weight zero).  No NaN becomes a finite number.  H3D_DCN_F32_MFMA follows the same rules with exact fmaf chains.
+ * The stand-alone `DCN` module's launch (H3D_OP_DCN_FUSED; f16x3: h3d_dcn_nchw_to_nhwc_scaled -- max |x|, then x scaled by 2^e in the
+ * relayout -- and reserved 0x300000, under which the kernel stages and splits without a clamp) keeps the same rules, its own offset
+ * convolution included: a NaN pixel gives NaN offsets and a sigmoid(NaN) mask, and 0 * NaN is NaN. */
+int h3d_dcn_nchw_to_nhwc_scaled(const float *src, float *dst, int B, int C, int H, int W, unsigned *amax, void *stream);
 int h3d_dcn_v2_forward_packed(const void *input, const void *packed, const float *offset, const float *mask, void *output,
                               int B, int C, int H, int W, int Cout, int dtype, int flags,
                               void *workspace, size_t workspace_bytes, void *stream);

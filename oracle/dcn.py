@@ -66,7 +66,7 @@ def dcn_v2_forward(input, weight, bias, offset, mask, kh, kw, sh, sw, ph, pw, dh
                     ok = ok & inside
                     idx = (hi.clamp(0, H - 1) * W + wi.clamp(0, W - 1)).view(B, 1, Ho * Wo)
                     v = torch.gather(src, 2, idx.expand(B, cpg, Ho * Wo))
-                    return v * ok.view(B, 1, Ho * Wo).to(dt)
+                    return torch.where(ok.view(B, 1, Ho * Wo), v, torch.zeros((), dtype=dt))   # conditional read (a NaN outside stays out)
 
                 v1 = corner(h_low, w_low, (h_low >= 0) & (w_low >= 0))
                 v2 = corner(h_low, w_high, (h_low >= 0) & (w_high <= W - 1))
@@ -85,7 +85,7 @@ def dcn_v2_forward(input, weight, bias, offset, mask, kh, kw, sh, sw, ph, pw, dh
                     cols[:, g * cpg:(g + 1) * cpg, t] = xv.to(dt)
                     continue
                 val = w1 * v1 + w2 * v2 + w3 * v3 + w4 * v4
-                val = val * inside.view(B, 1, -1).to(dt)
+                val = torch.where(inside.view(B, 1, -1), val, torch.zeros((), dtype=dt))     # im2col.cu:178: val = 0, then val * mask
                 cols[:, g * cpg:(g + 1) * cpg, t] = val * m.reshape(B, 1, -1)
     a = weight.reshape(Co, C * kh * kw)
     c = cols.reshape(B, C * kh * kw, Ho * Wo)
@@ -95,6 +95,18 @@ def dcn_v2_forward(input, weight, bias, offset, mask, kh, kw, sh, sw, ph, pw, dh
     else:
         out = torch.matmul(a, c) + bias.view(1, Co, 1)
     return out.view(B, Co, Ho, Wo)
+
+
+def dcn_v2_forward_absbound(input, weight, offset, mask, kh, kw, sh, sw, ph, pw, dh, dw, dg, finite_only=False):
+    """A = sum |w| |column| per output element, in fp64: the same sampling on |x|, |w| and |mask| with bias 0 (a bilinear blend of |x|
+    is at least |blend of x|, so A bounds the magnitude of every term the contraction adds).  finite_only: non-finite x and mask values
+    count as 0 (the bound over the finite terms)."""
+    x, m = input.double().abs(), mask.double().abs()
+    if finite_only:
+        x = torch.where(torch.isfinite(x), x, torch.zeros((), dtype=x.dtype))
+        m = torch.where(torch.isfinite(m), m, torch.zeros((), dtype=m.dtype))
+    w = weight.double().abs()
+    return dcn_v2_forward(x, w, torch.zeros(w.shape[0], dtype=torch.float64), offset.double(), m, kh, kw, sh, sw, ph, pw, dh, dw, dg)
 
 
 def dcn_module_forward(x, weight, bias, om_weight, om_bias, stride=1, padding=1, dilation=1, dg=1,

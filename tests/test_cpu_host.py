@@ -32,6 +32,18 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert L.h3d_abi_version() == _lib.ABI_VERSION
 
 
+def test_abi4_operator_workspaces_hold_the_activation_maxima():
+    # ABI 4: behind the [B*H*W, 32] offset / mask rows both operator workspaces keep 16 bytes for max |x| and max |mask|
+    L = _lib.lib()
+    B, C, H, W, Co = 2, 64, 10, 12, 64
+    px = B * H * W
+    om = (px * 32 * 4 + 16 + 255) // 256 * 256
+    assert L.h3d_dcn_v2_packed_workspace_bytes(B, C, H, W, _lib.DCN_INPUT_NHWC) == om
+    assert L.h3d_dcn_v2_packed_workspace_bytes(B, C, H, W, 0) == om + px * C * 4
+    assert L.h3d_dcn_v2_workspace_bytes(B, C, H, W, Co) == px * C * 4 + om + 128 * 9 * C * 4 + 128 * 4 + 256
+    assert L.h3d_dcn_nchw_to_nhwc_scaled(None, None, 1, 16, 4, 4, None, None) == -5 and b"null pointer" in L.h3d_last_error()
+
+
 def test_op_struct_matches_header_layout():
     # 2 int32, 5 pointers, 18 int32 (ABI 2: + wexp, wexp2) -> 8 + 40 + 72 = 120 bytes on LP64
     assert ctypes.sizeof(_lib.H3dOp) == 120 and _lib.H3dOp.wexp.offset == 112

@@ -2,6 +2,7 @@
 reference's own known-answer test (DCNv2/test.py:32-67: zero offset + mask 0.5 + identity
 kernel => input == 2*output) and derived identities."""
 import numpy as np
+import pytest
 import torch
 import torch.nn.functional as F
 
@@ -181,3 +182,82 @@ def test_f16_blend_mode_models_four_fp16_roundings():
     scale = float(a.abs().max())
     err = float((a - f).abs().max())
     assert 0 < err < 6 * 2.0 ** -11 * scale, (err, scale)
+
+
+# ---- non-finite values: the reference's conditional reads (im2col.cu:37-48 corners, :178 `val * mask` with val = 0 when gated) --------
+_NF_CFGS = [(3, 3, 1, 1, 1, 1, 1, 1, 1), (3, 3, 2, 2, 1, 1, 1, 1, 1), (3, 3, 1, 1, 2, 2, 2, 2, 2), (2, 3, 1, 2, 0, 1, 1, 1, 2)]
+
+
+def _nf_case(cfg, where, val, seed):
+    kh, kw, sh, sw, ph, pw, dh, dw, dg = cfg
+    B, C, Co, H, W = 2, 4, 3, 7, 9
+    Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) // sh + 1
+    Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) // sw + 1
+    g = np.random.default_rng(seed)
+    x = g.uniform(-2, 2, (B, C, H, W)).astype(np.float32)
+    w = g.uniform(-1, 1, (Co, C, kh, kw)).astype(np.float32)
+    b = g.uniform(-1, 1, (Co,)).astype(np.float32)
+    off = g.uniform(-2.5, 2.5, (B, 2 * dg * kh * kw, Ho, Wo)).astype(np.float32)
+    m = g.uniform(-1.5, 1.5, (B, dg * kh * kw, Ho, Wo)).astype(np.float32)
+    t = {"x": x, "off": off, "mask": m}[where]
+    idx = tuple(g.integers(0, s, 5) for s in t.shape)
+    t[idx] = val
+    return [torch.from_numpy(a) for a in (x, w, b, off, m)], cfg
+
+
+@pytest.mark.parametrize("cfg", _NF_CFGS)
+@pytest.mark.parametrize("where", ["x", "off", "mask"])
+@pytest.mark.parametrize("val", [float("nan"), float("inf"), float("-inf")])
+def test_non_finite_values_follow_the_reference_conditional_reads(cfg, where, val):
+    # oracle/dcn.py against the plain-C restatement (literal `if` reads): the same outputs are non-finite, the finite ones agree
+    for seed in range(3):
+        (x, w, b, off, m), a = _nf_case(cfg, where, val, seed)
+        y = odcn.dcn_v2_forward(x, w, b, off, m, *a).numpy()
+        yc = odcn.dcn_v2_forward_c(x.numpy(), w.numpy(), b.numpy(), off.numpy(), m.numpy(), *a)
+        assert np.array_equal(np.isfinite(y), np.isfinite(yc)), (cfg, where, val, seed)
+        f = np.isfinite(y)
+        scale = max(float(np.abs(yc[f]).max()) if f.any() else 1.0, 1.0)
+        assert np.abs(y[f] - yc[f]).max(initial=0.0) <= 1e-5 * scale, (cfg, where, val, seed)
+        if where == "off":
+            assert f.all(), "a non-finite offset gates its tap out (the reference reads nothing)"
+
+
+def test_nan_offset_tap_is_gated_out_not_propagated():
+    x = torch.ones(1, 1, 4, 4)
+    off = torch.zeros(1, 18, 4, 4)
+    off[0, 8, 1, 1] = float("nan")           # tap 4 (centre), dh of output (1, 1)
+    m = torch.ones(1, 9, 4, 4)
+    y = odcn.dcn_v2_forward(x, torch.ones(1, 1, 3, 3), torch.zeros(1), off, m, 3, 3, 1, 1, 1, 1, 1, 1, 1)
+    assert torch.isfinite(y).all() and float(y[0, 0, 1, 1]) == 8.0
+
+
+def test_absbound_bounds_every_output_and_is_tight_for_positive_data():
+    (x, w, b, off, m), a = _nf_case(_NF_CFGS[1], "x", 0.5, 0)
+    y64 = odcn.dcn_v2_forward(x, w, torch.zeros_like(b), off, m, *a, acc_dtype=torch.float64).double()
+    A = odcn.dcn_v2_forward_absbound(x, w, off, m, *a)
+    assert (y64.abs() <= A * (1 + 1e-6) + 1e-12).all()
+    Ap = odcn.dcn_v2_forward_absbound(x.abs(), w.abs(), off, m.abs(), *a)
+    yp = odcn.dcn_v2_forward(x.abs().double(), w.abs().double(), torch.zeros(3, dtype=torch.float64), off.double(), m.abs().double(), *a)
+    assert torch.allclose(Ap, yp, rtol=1e-12, atol=0)
+
+
+TAU = 2e-6      # the element-wise criterion of tests/test_gpu_dcn_domain.py: |y - y64| <= TAU (A + |b|)
+
+
+@pytest.mark.parametrize("g", [1e-7, 1e-5, 1e-3, 1.0, 1e3, 1e5, 1e7])
+def test_tau_is_calibrated_on_the_references_fp32_arithmetic(g):
+    # the fp32 oracle (the reference's arithmetic: fp32 sampling, fp32 GEMM) meets the criterion the GPU tests apply, at every input scale
+    B, C, Co, H, W = 2, 64, 24, 12, 14
+    gen = np.random.default_rng(11)
+    x = torch.from_numpy(gen.uniform(-2, 2, (B, C, H, W)).astype(np.float32)) * g
+    w = torch.from_numpy((gen.uniform(-1, 1, (Co, C, 3, 3)) / np.sqrt(C * 9)).astype(np.float32))
+    b = torch.from_numpy(gen.uniform(-1, 1, (Co,)).astype(np.float32)) * g
+    off = torch.from_numpy(gen.uniform(-3, 3, (B, 18, H, W)).astype(np.float32))
+    m = torch.from_numpy(gen.uniform(0, 1, (B, 9, H, W)).astype(np.float32))
+    a = (3, 3, 1, 1, 1, 1, 1, 1, 1)
+    y = odcn.dcn_v2_forward(x, w, b, off, m, *a).double()
+    y64 = odcn.dcn_v2_forward(x, w, b, off, m, *a, acc_dtype=torch.float64).double()
+    A = odcn.dcn_v2_forward_absbound(x, w, off, m, *a)
+    ratio = float(((y - y64).abs() / (TAU * (A + b.double().abs().view(1, -1, 1, 1)))).max())
+    print("g %g: fp32 oracle worst |y - y64| / (tau (A + |b|)) = %.3g" % (g, ratio))
+    assert ratio <= 1.0
