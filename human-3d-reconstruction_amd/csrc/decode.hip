@@ -5,8 +5,9 @@
 //
 //   nms_topk_kernel      _sigmoid (utils.py:8-10, optional) + _nms (decode.py:6-13) +
 //                        per-map top-K (decode.py:18/29) -- one workgroup per (b, c) map;
-//                        map keys live in LDS, 4x8-bit radix select for the K-th key, ordered
-//                        compaction of ties (lowest index first), bitonic sort of the K survivors.
+//                        the map lives in LDS; the 3x3 maxima go to a list and an 8-bit radix select finds
+//                        the K-th (key, index) word of the list (full-map select with ordered compaction of
+//                        ties when the list does not apply), bitonic sort of the K selected.
 //   topk_merge_kernel    stage 2 of _topk (decode.py:34-39)
 //   gather_feat_kernel   _transpose_and_gather_feat (utils.py:23-27) without the NHWC transpose
 //   pose_assemble_kernel multi_pose_decode body (decode.py:86-161)
@@ -94,8 +95,17 @@ struct NmsJob {
 // are cut into `nbands` bands of `band_rows` rows: workgroup (map, band) loads its rows plus one halo row on either side (the
 // 3x3 max needs them), only the band's own rows are candidates, and the band's top K go to a [maps][nbands][K] scratch that
 // topk_merge_kernel reduces (same order: score descending, lowest flat index first).  nbands = 1 is the plain case.
+//
+// The select itself runs over the SURVIVORS only.  Just the pixels whose masked value is above +0 can be among the K largest as long
+// as there are K of them, and after the 3x3 max that is about one pixel in nine: the max pass appends their local indices to a
+// list of `cap` 16-bit entries (unordered: one LDS atomic per wave and step), and the 8-bit radix select then runs on the 48-bit
+// words (key << 16 | 0xffff - index) of the list, which are all different -- so the K-th word is exact, equal scores fall lowest
+// index first with no separate tie pass, and the select stops at the first digit whose bin holds exactly the elements still
+// wanted (two or three digits on a map without ties).  A map with fewer than K survivors (zeros get selected), with more than
+// `cap` (a constant map: every pixel is a maximum) or with a NaN among its masked values takes the full-map path below
+// unchanged: the same results, at the old speed.
 __global__ __launch_bounds__(NMS_THREADS) void nms_topk_kernel(NmsJob j0, NmsJob j1, int H_img, int W, int K, int ncand, int flags,
-                                                               int band_rows, int nbands)
+                                                               int band_rows, int nbands, int cap)
 {
     int blk = blockIdx.x / nbands;
     const int band = blockIdx.x - blk * nbands;
@@ -113,13 +123,16 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_topk_kernel(NmsJob j0, NmsJob
     extern __shared__ __attribute__((aligned(16))) uint32_t s_key[];  // [HW] keys, then candidates, then keep bits
     __shared__ uint32_t s_hist[256];
     __shared__ uint32_t s_wave[NMS_WAVES];
-    __shared__ uint32_t s_sel[2];  // [0] = chosen bin, [1] = remaining need
+    __shared__ uint32_t s_sel[3];  // [0] = chosen bin, [1] = remaining need, [2] = elements in the chosen bin (survivor select)
     __shared__ uint32_t s_cnt;
+    __shared__ uint32_t s_nlist, s_bad;   // survivors found (may exceed cap: the list then is incomplete); a masked value was NaN
     const int tid = threadIdx.x;
     const int HW = H * W;
     const float *map = heat + (size_t)blk * H_img * W + (size_t)ly0 * W;
     u64 *s_cand = reinterpret_cast<u64 *>(s_key + ((HW + 1) & ~1));
     u64 *s_mask = s_cand + ncand;             // keep bits, one word per 64 pixels
+    uint16_t *s_list = reinterpret_cast<uint16_t *>(s_mask + ((HW + 63) >> 6));      // [cap] local indices of the survivors
+    if (tid == 0) { s_cnt = 0; s_nlist = 0; s_bad = 0; }
 
     // ---- sigmoid + 3x3 NMS -> order-preserving keys ----------------------------------------------
     // pass 1: (optional) sigmoid of every pixel ONCE, straight into LDS; 8 independent loads per
@@ -140,107 +153,211 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_topk_kernel(NmsJob j0, NmsJob
         }
     }
     __syncthreads();
-    // pass 2: keep = (3x3 max == centre) on the LDS map (the reference pools the sigmoid outputs,
-    //         decode.py:6-13); one ballot word per 64 consecutive pixels
-    for (int base = 0; base < HW; base += NMS_THREADS) {
-        const int i = base + tid;
-        bool keep = false;
-        if (i < HW) {
-            const int y = wshift >= 0 ? (i >> wshift) : i / W, x = i - y * W;     // (a division costs ~25 instructions per pixel)
-            const float v = s_val[i];
-            float m = v;
-            if (!(flags & 2)) {
-                const int y0 = max(y - 1, 0), y1 = min(y + 1, H - 1), x0 = max(x - 1, 0), x1 = min(x + 1, W - 1);
-                // clamped taps repeat an in-range neighbour (or the centre): the max is unchanged
-                const float *r0 = s_val + y0 * W, *r1 = s_val + y * W, *r2 = s_val + y1 * W;
-                const float a0 = r0[x0], a1 = r0[x], a2 = r0[x1], b0 = r1[x0], b2 = r1[x1], c0 = r2[x0], c1 = r2[x],
-                            c2 = r2[x1];
-                m = fmaxf(fmaxf(fmaxf(fmaxf(a0, a1), fmaxf(a2, b0)), fmaxf(fmaxf(b2, c0), fmaxf(c1, c2))), v);
+    // pass 2: the survivors.  val = heat * (3x3 max == centre) as in the full-map path below (the max is over the same nine
+    //         values, in another order: the largest of a set does not depend on it, and -0 == +0 in the comparison); the
+    //         pixels with fkey(val) > fkey(+0) go to the list.  Rows of a multiple of 4 pixels: 4 pixels per thread, 3 x (one
+    //         16-byte + 2 scalar) LDS reads for their 36 taps.
+    const uint32_t ZKEY = 0x80000000u;        // fkey(+0.0f)
+    const bool quads = (W & 3) == 0;
+    const int nitem = quads ? HW >> 2 : HW;
+    for (int base = 0; base < nitem; base += NMS_THREADS) {
+        const int it = base + tid;
+        bool put[4] = {false, false, false, false};
+        if (it < nitem) {
+            const int i = quads ? it << 2 : it;
+            const int y = wshift >= 0 ? (i >> wshift) : i / W, x = i - y * W;
+            const int y0 = max(y - 1, 0), y1 = min(y + 1, H - 1);
+            const float *r0 = s_val + y0 * W, *r1 = s_val + y * W, *r2 = s_val + y1 * W;
+            float v[4], m[4];
+            if (quads) {
+                const int xl = max(x - 1, 0), xr = min(x + 4, W - 1);
+                const f32x4 a = *reinterpret_cast<const f32x4 *>(r0 + x), b = *reinterpret_cast<const f32x4 *>(r1 + x),
+                            c = *reinterpret_cast<const f32x4 *>(r2 + x);
+                float cm[6];
+                cm[0] = fmaxf(fmaxf(r0[xl], r1[xl]), r2[xl]);
+                cm[5] = fmaxf(fmaxf(r0[xr], r1[xr]), r2[xr]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    v[j] = b[j];
+                    cm[j + 1] = fmaxf(fmaxf(a[j], b[j]), c[j]);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) m[j] = fmaxf(fmaxf(cm[j], cm[j + 1]), cm[j + 2]);
+            } else {
+                const int x0 = max(x - 1, 0), x1 = min(x + 1, W - 1);
+                v[0] = r1[x];
+                m[0] = fmaxf(fmaxf(fmaxf(fmaxf(r0[x0], r0[x]), fmaxf(r0[x1], r1[x0])), fmaxf(fmaxf(r1[x1], r2[x0]), fmaxf(r2[x], r2[x1]))), v[0]);
             }
-            keep = (m == v);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j && !quads) break;
+                const bool keep = ((flags & 2) ? v[j] : m[j]) == v[j];
+                const float val = (keep ? v[j] : v[j] * 0.0f) + 0.0f;
+                if (val != val) s_bad = 1u;
+                put[j] = fkey(val) > ZKEY && i + j >= c_lo && i + j < c_hi;
+            }
         }
-        const u64 word = __ballot(keep);
-        if ((tid & 63) == 0 && i < HW) s_mask[i >> 6] = word;        // i is a multiple of 64 in lane 0
+        // append: one atomic per wave, the lanes' slots by ballot + prefix count
+        u64 bal[4];
+        uint32_t tot = 0, mine[4];
+        const u64 below = (1ull << (tid & 63)) - 1ull;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            bal[j] = __ballot(put[j]);
+            mine[j] = tot + (uint32_t)__popcll(bal[j] & below);
+            tot += (uint32_t)__popcll(bal[j]);
+        }
+        uint32_t wbase = 0;
+        if ((tid & 63) == 0 && tot) wbase = atomicAdd(&s_nlist, tot);
+        wbase = __shfl(wbase, 0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (put[j] && wbase + mine[j] < (uint32_t)cap) s_list[wbase + mine[j]] = (uint16_t)((quads ? it << 2 : it) + j);
     }
     __syncthreads();
-    // pass 3: heat * keep -> key, in place (+0.0f folds -0 into +0 so equal values share one key)
-    for (int base = 0; base < HW; base += NMS_THREADS) {
-        const int i = base + tid;
-        if (i < HW) {
-            const float sv = s_val[i];
-            const bool keep = (s_mask[i >> 6] >> (i & 63)) & 1ull;
-            const float val = (keep ? sv : sv * 0.0f) + 0.0f;
-            s_key[i] = (i >= c_lo && i < c_hi) ? fkey(val) : 0u;     // halo rows of a band: below every real key, never selected
+    const uint32_t nlist = s_nlist;
+    const bool fast = !s_bad && nlist >= (uint32_t)K && nlist <= (uint32_t)cap;       // (workgroup-uniform)
+    if (fast) {
+        // ---- radix select of the K-th largest 48-bit word (key << 16 | 0xffff - index) of the list -----------------------------
+        // a listed pixel is a maximum (a pixel that is not has val = +0, or NaN: not on this path), so its val is heat + 0.0f
+        u64 prefix = 0, pmask = 0;
+        uint32_t need = (uint32_t)K;
+        for (int pass = 5; pass >= 0; --pass) {
+            if (tid < 256) s_hist[tid] = 0;
+            __syncthreads();
+            const int sh = pass * 8;
+            for (uint32_t j = tid; j < nlist; j += NMS_THREADS) {
+                const uint32_t i = s_list[j];
+                const u64 cw = ((u64)fkey(s_val[i] + 0.0f) << 16) | (u64)(0xffffu - i);
+                if ((cw & pmask) == prefix) atomicAdd(&s_hist[(uint32_t)(cw >> sh) & 255u], 1u);
+            }
+            __syncthreads();
+            const uint32_t hv = (tid < 256) ? s_hist[tid] : 0u;
+            uint32_t total;
+            const uint32_t excl = block_excl_scan(hv, s_wave, tid, &total);
+            const uint32_t above = total - excl - hv;
+            if (tid < 256 && above + hv >= need && above < need) { s_sel[0] = (uint32_t)tid; s_sel[1] = need - above; s_sel[2] = hv; }
+            __syncthreads();
+            prefix |= (u64)s_sel[0] << sh;
+            pmask |= (u64)0xffu << sh;
+            need = s_sel[1];
+            const bool whole_bin = s_sel[2] == need;        // every element of the bin is wanted: nothing left to split
+            __syncthreads();
+            if (whole_bin) break;
         }
-    }
-    __syncthreads();
+        // exactly K words have (word & pmask) >= prefix
+        for (uint32_t j = tid; j < nlist; j += NMS_THREADS) {
+            const uint32_t i = s_list[j];
+            const uint32_t k = fkey(s_val[i] + 0.0f);
+            const u64 cw = ((u64)k << 16) | (u64)(0xffffu - i);
+            if ((cw & pmask) >= prefix) {
+                const uint32_t pos = atomicAdd(&s_cnt, 1u);
+                s_cand[pos] = ((u64)k << 32) | (u64)(0xffffffffu - i);
+            }
+        }
+    } else {
+        // pass 2: keep = (3x3 max == centre) on the LDS map (the reference pools the sigmoid outputs,
+        //         decode.py:6-13); one ballot word per 64 consecutive pixels
+        for (int base = 0; base < HW; base += NMS_THREADS) {
+            const int i = base + tid;
+            bool keep = false;
+            if (i < HW) {
+                const int y = wshift >= 0 ? (i >> wshift) : i / W, x = i - y * W;     // (a division costs ~25 instructions per pixel)
+                const float v = s_val[i];
+                float m = v;
+                if (!(flags & 2)) {
+                    const int y0 = max(y - 1, 0), y1 = min(y + 1, H - 1), x0 = max(x - 1, 0), x1 = min(x + 1, W - 1);
+                    // clamped taps repeat an in-range neighbour (or the centre): the max is unchanged
+                    const float *r0 = s_val + y0 * W, *r1 = s_val + y * W, *r2 = s_val + y1 * W;
+                    const float a0 = r0[x0], a1 = r0[x], a2 = r0[x1], b0 = r1[x0], b2 = r1[x1], c0 = r2[x0], c1 = r2[x],
+                                c2 = r2[x1];
+                    m = fmaxf(fmaxf(fmaxf(fmaxf(a0, a1), fmaxf(a2, b0)), fmaxf(fmaxf(b2, c0), fmaxf(c1, c2))), v);
+                }
+                keep = (m == v);
+            }
+            const u64 word = __ballot(keep);
+            if ((tid & 63) == 0 && i < HW) s_mask[i >> 6] = word;        // i is a multiple of 64 in lane 0
+        }
+        __syncthreads();
+        // pass 3: heat * keep -> key, in place (+0.0f folds -0 into +0 so equal values share one key)
+        for (int base = 0; base < HW; base += NMS_THREADS) {
+            const int i = base + tid;
+            if (i < HW) {
+                const float sv = s_val[i];
+                const bool keep = (s_mask[i >> 6] >> (i & 63)) & 1ull;
+                const float val = (keep ? sv : sv * 0.0f) + 0.0f;
+                s_key[i] = (i >= c_lo && i < c_hi) ? fkey(val) : 0u;     // halo rows of a band: below every real key, never selected
+            }
+        }
+        __syncthreads();
 
 #ifdef H3D_ABLATE
-    if (flags & 0x100) return;
+        if (flags & 0x100) return;
 #endif
-    // ---- radix select: key of the K-th largest element ------------------------------------------
-    uint32_t prefix = 0, pmask = 0, need = (uint32_t)K;
-    for (int pass = 3; pass >= 0; --pass) {
-        if (tid < 256) s_hist[tid] = 0;
-        __syncthreads();
-        const int sh = pass * 8;
-        // run-length aggregation: NMS leaves most of a heat map at exactly 0 (one hot bin), so a plain
-        // atomic per element would serialise ~HW LDS atomics on one address
-        uint32_t run_bin = 0xffffffffu, run_cnt = 0;
-        for (int i = tid; i < HW; i += NMS_THREADS) {
-            const uint32_t k = s_key[i];
-            if ((k & pmask) == prefix) {
-                const uint32_t bin = (k >> sh) & 255u;
-                if (bin == run_bin) {
-                    ++run_cnt;
-                } else {
-                    if (run_cnt) atomicAdd(&s_hist[run_bin], run_cnt);
-                    run_bin = bin;
-                    run_cnt = 1;
+        // ---- radix select: key of the K-th largest element ------------------------------------------
+        uint32_t prefix = 0, pmask = 0, need = (uint32_t)K;
+        for (int pass = 3; pass >= 0; --pass) {
+            if (tid < 256) s_hist[tid] = 0;
+            __syncthreads();
+            const int sh = pass * 8;
+            // run-length aggregation: NMS leaves most of a heat map at exactly 0 (one hot bin), so a plain
+            // atomic per element would serialise ~HW LDS atomics on one address
+            uint32_t run_bin = 0xffffffffu, run_cnt = 0;
+            for (int i = tid; i < HW; i += NMS_THREADS) {
+                const uint32_t k = s_key[i];
+                if ((k & pmask) == prefix) {
+                    const uint32_t bin = (k >> sh) & 255u;
+                    if (bin == run_bin) {
+                        ++run_cnt;
+                    } else {
+                        if (run_cnt) atomicAdd(&s_hist[run_bin], run_cnt);
+                        run_bin = bin;
+                        run_cnt = 1;
+                    }
                 }
             }
+            if (run_cnt) atomicAdd(&s_hist[run_bin], run_cnt);
+            __syncthreads();
+            // thread t < 256 owns bin t: elements in bins > t = total - inclusive prefix
+            const uint32_t hv = (tid < 256) ? s_hist[tid] : 0u;
+            uint32_t total;
+            const uint32_t excl = block_excl_scan(hv, s_wave, tid, &total);
+            const uint32_t above = total - excl - hv;
+            if (tid < 256 && above + hv >= need && above < need) { s_sel[0] = (uint32_t)tid; s_sel[1] = need - above; }
+            __syncthreads();
+            prefix |= s_sel[0] << sh;
+            pmask |= 0xffu << sh;
+            need = s_sel[1];
+            __syncthreads();
         }
-        if (run_cnt) atomicAdd(&s_hist[run_bin], run_cnt);
-        __syncthreads();
-        // thread t < 256 owns bin t: elements in bins > t = total - inclusive prefix
-        const uint32_t hv = (tid < 256) ? s_hist[tid] : 0u;
-        uint32_t total;
-        const uint32_t excl = block_excl_scan(hv, s_wave, tid, &total);
-        const uint32_t above = total - excl - hv;
-        if (tid < 256 && above + hv >= need && above < need) { s_sel[0] = (uint32_t)tid; s_sel[1] = need - above; }
-        __syncthreads();
-        prefix |= s_sel[0] << sh;
-        pmask |= 0xffu << sh;
-        need = s_sel[1];
-        __syncthreads();
-    }
-    const uint32_t kth = prefix;            // exact key of the K-th largest
-    const uint32_t n_gt = (uint32_t)K - need;  // elements strictly greater; take `need` equal ones
+        const uint32_t kth = prefix;            // exact key of the K-th largest
+        const uint32_t n_gt = (uint32_t)K - need;  // elements strictly greater; take `need` equal ones
 
 #ifdef H3D_ABLATE
-    if (flags & 0x200) return;
+        if (flags & 0x200) return;
 #endif
-    // ---- compaction: all keys > kth (any order), then `need` keys == kth in index order ----------
-    if (tid == 0) s_cnt = 0;
-    __syncthreads();
-    for (int i = tid; i < HW; i += NMS_THREADS) {
-        const uint32_t k = s_key[i];
-        if (k > kth) {
-            const uint32_t pos = atomicAdd(&s_cnt, 1u);
-            s_cand[pos] = ((u64)k << 32) | (u64)(0xffffffffu - (uint32_t)i);
+        // ---- compaction: all keys > kth (any order), then `need` keys == kth in index order ----------
+        if (tid == 0) s_cnt = 0;
+        __syncthreads();
+        for (int i = tid; i < HW; i += NMS_THREADS) {
+            const uint32_t k = s_key[i];
+            if (k > kth) {
+                const uint32_t pos = atomicAdd(&s_cnt, 1u);
+                s_cand[pos] = ((u64)k << 32) | (u64)(0xffffffffu - (uint32_t)i);
+            }
         }
+        const int chunk = (HW + NMS_THREADS - 1) / NMS_THREADS;
+        const int lo = tid * chunk, hi = min(lo + chunk, HW);
+        uint32_t eq = 0;
+        for (int i = lo; i < hi; ++i) eq += (s_key[i] == kth);
+        uint32_t total_eq;
+        uint32_t rank = block_excl_scan(eq, s_wave, tid, &total_eq);
+        for (int i = lo; i < hi && rank < need; ++i)
+            if (s_key[i] == kth) {
+                s_cand[n_gt + rank] = ((u64)kth << 32) | (u64)(0xffffffffu - (uint32_t)i);
+                ++rank;
+            }
     }
-    const int chunk = (HW + NMS_THREADS - 1) / NMS_THREADS;
-    const int lo = tid * chunk, hi = min(lo + chunk, HW);
-    uint32_t eq = 0;
-    for (int i = lo; i < hi; ++i) eq += (s_key[i] == kth);
-    uint32_t total_eq;
-    uint32_t rank = block_excl_scan(eq, s_wave, tid, &total_eq);
-    for (int i = lo; i < hi && rank < need; ++i)
-        if (s_key[i] == kth) {
-            s_cand[n_gt + rank] = ((u64)kth << 32) | (u64)(0xffffffffu - (uint32_t)i);
-            ++rank;
-        }
     int N = 1;
     while (N < K) N <<= 1;
     for (int i = K + tid; i < N; i += NMS_THREADS) s_cand[i] = 0ull;
@@ -274,7 +391,12 @@ static int nms_topk_launch(const NmsJob &j0, const NmsJob &j1, int H_img, int W,
         H3D_FAIL(H3D_ERR_UNSUPPORTED, "nms_topk: K=%d (max %d), H*W=%ld (max %ld: larger maps through h3d_nms_topk_large)", K, NMS_MAXK, HW, NMS_MAXHW);
     int N = 1;
     while (N < K) N <<= 1;
-    const size_t lds = (size_t)((HW + 1) & ~1L) * 4 + (size_t)N * 8 + (size_t)((HW + 63) / 64) * 8;
+    size_t lds = (size_t)((HW + 1) & ~1L) * 4 + (size_t)N * 8 + (size_t)((HW + 63) / 64) * 8;
+    // survivor list (16-bit local indices): 4096 entries where two workgroups still share a CU's 160 KiB (a 128 x 128 map: 75 KiB
+    // + 1.3 KiB static), what is left of the 160 KiB on a larger map, none (cap 0: full-map select) if that is below K
+    long cap = min(4096L, (160L * 1024 - 2048 - (long)lds) / 2);
+    if (cap < K) cap = 0;
+    lds += (size_t)cap * 2;
     static thread_local size_t max_set = 0;
     if (lds > 64 * 1024 && lds > max_set) {
         if (hipFuncSetAttribute((const void *)nms_topk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -282,7 +404,7 @@ static int nms_topk_launch(const NmsJob &j0, const NmsJob &j1, int H_img, int W,
         max_set = lds;
     }
     hipLaunchKernelGGL(nms_topk_kernel, dim3((j0.nblk + j1.nblk) * nbands), dim3(NMS_THREADS), lds, (hipStream_t)stream, j0, j1, H_img, W, K, N, flags,
-                       band_rows, nbands);
+                       band_rows, nbands, (int)cap);
     H3D_CHECK_LAUNCH("nms_topk_kernel");
     return H3D_OK;
 }
