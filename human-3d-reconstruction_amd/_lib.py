@@ -60,6 +60,9 @@ SIGNATURES = {
     "h3d_dcn_fused_pack_f32_cached": [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp],
     "h3d_dcn_v2_forward_packed": [c_vp] * 5 + [c_i] * 7 + [c_vp, ctypes.c_size_t, c_vp],
     "h3d_dcn_nchw_to_nhwc_scaled": [c_vp, c_vp] + [c_i] * 4 + [c_vp, c_vp],
+    "h3d_dcn_v2_backward_workspace_bytes": [c_i] * 14 + [ctypes.POINTER(ctypes.c_size_t)],
+    "h3d_dcn_v2_backward": [c_vp] * 11 + [c_i] * 14 + [c_vp, ctypes.c_size_t, c_vp],
+    "h3d_dcn_v2_backward_general": [c_vp] * 11 + [c_i] * 14 + [c_vp, ctypes.c_size_t, c_vp],
     "h3d_dcn_offset_mask": [c_vp] * 5 + [c_i] * 11 + [c_vp],
     "h3d_dcn_v2_psroi_pooling_forward": [c_vp] * 5 + [c_i] * 7 + [ctypes.c_float] + [c_i] * 5 + [ctypes.c_float, c_vp],
     "h3d_dcn_pooling_modulated": [c_vp] * 4 + [c_i] * 5 + [ctypes.c_float] + [c_i] * 5 + [ctypes.c_float, c_vp],

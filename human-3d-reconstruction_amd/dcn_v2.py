@@ -5,15 +5,20 @@ deformable PS-ROI pooling forward: `dcn_v2_psroi_pooling_forward` (the `_ext` en
 DCNv2/src/dcn_v2.h:76-107), `dcn_v2_pooling`, `DCNv2Pooling`, `DCNPooling` (state_dict keys
 offset_mask_fc.{0,2,4}.{weight,bias}).
 
-The backward passes (dcn_v2_backward, dcn_v2_psroi_pooling_backward) are out of scope:
-inference only -- an INPUT that requires grad (with autograd enabled) raises; parameters may require grad (the
-nn.Parameter default), results are computed without a graph and returned detached."""
+`dcn_v2_conv`, `DCNv2`, `DCN` and the pooling classes are inference only -- an INPUT that requires grad (with autograd enabled)
+raises; parameters may require grad (the nn.Parameter default), results are computed without a graph and returned detached.
+
+Training is opt-in: `dcn_v2_backward` (the `_ext` entry point, DCNv2/src/dcn_v2.h:41-74; kernels: csrc/dcn_bwd.hip), the autograd
+function `_DCNv2` / `dcn_v2_conv_autograd` (dcn_v2.py:16-51) and the modules `TrainableDCNv2` / `TrainableDCN` (same constructors and
+state_dict keys as `DCNv2` / `DCN`; their forward builds a graph).  dcn_v2_psroi_pooling_backward is not implemented."""
+import ctypes
 import math
 
 import os
 
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 from torch.nn.modules.utils import _pair
 
 from . import _lib
@@ -138,7 +143,7 @@ def dcn_v2_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride
 def dcn_v2_conv(input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups):
     """`_DCNv2.apply` argument order (dcn_v2.py:18-33), forward only."""
     if torch.is_grad_enabled() and any(t.requires_grad for t in (input, offset, mask)):
-        raise RuntimeError("h3d_amd DCNv2 is inference-only (dcn_v2_backward is out of scope): "
+        raise RuntimeError("h3d_amd DCNv2 is inference-only (use dcn_v2_conv_autograd / TrainableDCNv2 to train): "
                            "an input tensor requires grad")
     sh, sw = _pair(stride)
     ph, pw = _pair(padding)
@@ -159,7 +164,7 @@ class _InferenceOnly(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad):
-        raise RuntimeError("h3d_amd DCNv2 is inference-only (dcn_v2_backward is out of scope): call .eval() or run under torch.no_grad()")
+        raise RuntimeError("h3d_amd DCNv2 is inference-only (use TrainableDCNv2 / TrainableDCN to train): call .eval() or run under torch.no_grad()")
 
 
 class DCNv2(nn.Module):
@@ -243,7 +248,7 @@ class DCN(DCNv2):
         reach memory); other configurations run conv_offset_mask + chunk / cat / sigmoid as one launch of the library's general
         kernel (`h3d_dcn_offset_mask`) and then the operator: no nn.Conv2d / vendor library call on any path."""
         if torch.is_grad_enabled() and input.requires_grad:
-            raise RuntimeError("h3d_amd DCNv2 is inference-only (dcn_v2_backward is out of scope): the input requires grad")
+            raise RuntimeError("h3d_amd DCNv2 is inference-only (use TrainableDCN to train): the input requires grad")
         if not input.is_cuda:
             raise RuntimeError("Not implemented on the CPU")
         # (parameters require grad by default: `dcn(x)` outside no_grad must return the forward result as it does in the reference,
@@ -307,6 +312,122 @@ class DCN(DCNv2):
                                                       self.deformable_groups, _lib.stream_ptr()), "DCN: conv_offset_mask")
         return dcn_v2_conv(x, offset, mask, self.weight, self.bias, self.stride, self.padding,
                            self.dilation, self.deformable_groups)
+
+
+# ---- training: dcn_v2_backward, the autograd function and the trainable modules (kernels: csrc/dcn_bwd.hip) ----------------------
+
+def _dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
+                     dilation_h, dilation_w, deformable_group, need=(True,) * 5, general=False):
+    """`dcn_v2_backward` with a choice of outputs (`need`: input, offset, mask, weight, bias -- autograd's needs_input_grad; an output that is
+    not needed is None) and of kernels (`general`: the general kernels on the model's configuration too)."""
+    _lib.require_cuda(input, weight, bias, offset, mask, grad_output)
+    for t in (input, weight, bias, offset, mask, grad_output):
+        if t.dtype != torch.float32:
+            raise RuntimeError("dcn_v2_backward: expected float32 tensors (reference uses .data<float>())")
+    input, weight, bias, offset, mask, grad_output = [t.contiguous() for t in (input, weight, bias, offset, mask, grad_output)]
+    if input.dim() != 4 or weight.dim() != 4:
+        raise RuntimeError("dcn_v2_backward: input must be [B,C,H,W] and weight [Cout,C,kh,kw]")
+    B, C, H, W = input.shape
+    Cout, Ck, kh_, kw_ = weight.shape
+    if kh_ != kernel_h or kw_ != kernel_w:
+        raise RuntimeError("Input shape and kernel shape wont match: (%d x %d vs %d x %d)."
+                           % (kernel_h, kernel_w, kh_, kw_))
+    if C != Ck:
+        raise RuntimeError("Input shape and kernel channels wont match: (%d vs %d)." % (C, Ck))
+    Ho = (H + 2 * pad_h - (dilation_h * (kernel_h - 1) + 1)) // stride_h + 1
+    Wo = (W + 2 * pad_w - (dilation_w * (kernel_w - 1) + 1)) // stride_w + 1
+    if tuple(offset.shape) != (B, 2 * deformable_group * kernel_h * kernel_w, Ho, Wo):
+        raise RuntimeError("offset shape %s does not match [B, 2*dg*kh*kw, Ho, Wo] = %s"
+                           % (tuple(offset.shape), (B, 2 * deformable_group * kernel_h * kernel_w, Ho, Wo)))
+    if tuple(mask.shape) != (B, deformable_group * kernel_h * kernel_w, Ho, Wo):
+        raise RuntimeError("mask shape %s does not match [B, dg*kh*kw, Ho, Wo]" % (tuple(mask.shape),))
+    if bias.numel() != Cout:
+        raise RuntimeError("bias has %d elements, expected %d" % (bias.numel(), Cout))
+    if tuple(grad_output.shape) != (B, Cout, Ho, Wo):
+        raise RuntimeError("grad_output shape %s does not match [B, Cout, Ho, Wo] = %s" % (tuple(grad_output.shape), (B, Cout, Ho, Wo)))
+    geo = (B, C, H, W, Cout, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group)
+    L = _lib.lib()
+    with torch.cuda.device(input.device):
+        nws = ctypes.c_size_t(0)
+        _lib.check(L.h3d_dcn_v2_backward_workspace_bytes(*geo, ctypes.byref(nws)), "dcn_v2_backward")
+        ws = torch.empty(max(int(nws.value), 1), dtype=torch.uint8, device=input.device)
+        outs = [torch.empty_like(t) if n else None for t, n in zip((input, offset, mask, weight, bias), need)]
+        fn = L.h3d_dcn_v2_backward_general if general else L.h3d_dcn_v2_backward
+        rc = fn(*[_lib.ptr(t) for t in (input, weight, bias, offset, mask, grad_output)], *[_lib.ptr(t) for t in outs], *geo,
+                _lib.ptr(ws), int(nws.value), _lib.stream_ptr())
+    _lib.check(rc, "dcn_v2_backward")
+    return tuple(outs)
+
+
+def dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, kernel_w, stride_h, stride_w,
+                    pad_h, pad_w, dilation_h, dilation_w, deformable_group):
+    """Positional twin of `_ext.dcn_v2_backward` (dcn_v2.py:39-48 call site): fp32 CUDA tensors in, new tensors
+    (grad_input, grad_offset, grad_mask, grad_weight, grad_bias) out.  Current stream, no host synchronisation."""
+    return _dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w,
+                            dilation_h, dilation_w, deformable_group)
+
+
+class _DCNv2(torch.autograd.Function):
+    """The reference's autograd function (dcn_v2.py:16-51), argument order included."""
+
+    @staticmethod
+    def forward(ctx, input, offset, mask, weight, bias, stride, padding, dilation, deformable_groups):
+        ctx.stride, ctx.padding, ctx.dilation = _pair(stride), _pair(padding), _pair(dilation)
+        ctx.kernel_size = _pair(weight.shape[2:4])
+        ctx.deformable_groups = deformable_groups
+        output = dcn_v2_forward(input, weight, bias, offset, mask, ctx.kernel_size[0], ctx.kernel_size[1], ctx.stride[0], ctx.stride[1],
+                                ctx.padding[0], ctx.padding[1], ctx.dilation[0], ctx.dilation[1], ctx.deformable_groups)
+        ctx.save_for_backward(input, offset, mask, weight, bias)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        input, offset, mask, weight, bias = ctx.saved_tensors
+        ni, no, nm, nw, nb = ctx.needs_input_grad[:5]
+        gi, go, gm, gw, gb = _dcn_v2_backward(input, weight, bias, offset, mask, grad_output, ctx.kernel_size[0], ctx.kernel_size[1],
+                                              ctx.stride[0], ctx.stride[1], ctx.padding[0], ctx.padding[1], ctx.dilation[0],
+                                              ctx.dilation[1], ctx.deformable_groups, need=(ni, no, nm, nw, nb))
+        return gi, go, gm, gw, gb, None, None, None, None
+
+
+dcn_v2_conv_autograd = _DCNv2.apply
+
+
+class TrainableDCNv2(DCNv2):
+    """`DCNv2` whose forward builds a graph (the reference's behaviour): same constructor, same state_dict keys."""
+
+    def forward(self, input, offset, mask):
+        k = self.deformable_groups * self.kernel_size[0] * self.kernel_size[1]
+        assert 2 * k == offset.shape[1]
+        assert k == mask.shape[1]
+        return dcn_v2_conv_autograd(input, offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation,
+                                    self.deformable_groups)
+
+
+class TrainableDCN(DCN):
+    """`DCN` whose forward builds a graph: same constructor, same state_dict keys.  conv_offset_mask runs as the operator itself with zero
+    offsets and a unit mask (what `h3d_dcn_offset_mask` does for the inference module), so its gradients come from the same kernels and
+    no vendor convolution enters the module; chunk / cat / sigmoid are torch ops (dcn_v2.py:118-128)."""
+
+    def forward(self, input):
+        if not input.is_cuda:
+            raise RuntimeError("Not implemented on the CPU")
+        if input.dtype != torch.float32 or input.dim() != 4:
+            raise RuntimeError("DCN: expected a float32 [B,C,H,W] input (reference uses .data<float>())")
+        B, C, H, W = input.shape
+        kh, kw = self.kernel_size
+        Ho = (H + 2 * self.padding[0] - kh) // self.stride[0] + 1
+        Wo = (W + 2 * self.padding[1] - kw) // self.stride[1] + 1
+        zero = torch.zeros(B, 2 * kh * kw, Ho, Wo, dtype=torch.float32, device=input.device)
+        one = torch.ones(B, kh * kw, Ho, Wo, dtype=torch.float32, device=input.device)
+        out = dcn_v2_conv_autograd(input, zero, one, self.conv_offset_mask.weight, self.conv_offset_mask.bias, self.stride, self.padding,
+                                   (1, 1), 1)             # (nn.Conv2d of dcn_v2.py:107-111: no dilation, no groups)
+        o1, o2, mask = torch.chunk(out, 3, dim=1)
+        offset = torch.cat((o1, o2), dim=1)
+        mask = torch.sigmoid(mask)
+        return dcn_v2_conv_autograd(input, offset, mask, self.weight, self.bias, self.stride, self.padding, self.dilation,
+                                    self.deformable_groups)
 
 
 # ---- deformable PS-ROI pooling, forward (dcn_v2.py:130-303 of the reference; kernel: csrc/psroi.hip) ----------------------------

@@ -46,7 +46,9 @@ int h3d_abi_version(void);
 #define H3D_ABI_VERSION 4      /* 2: h3d_op.wexp / wexp2 (120-byte descriptor); 3: fp32 DeformConv packs carry their filter maxima (the sizes
                                   h3d_dcn_v2_packed_weight_bytes / _workspace_bytes return grew by 256 B; bias_out of h3d_dcn_fused_pack_f32_cached
                                   is [rows | 32 | 64] floats); 4: the fp32 operator scales its activations too (h3d_dcn_v2_workspace_bytes and
-                                  h3d_dcn_v2_packed_workspace_bytes grew by at most 256 B; h3d_dcn_nchw_to_nhwc_scaled) */
+                                  h3d_dcn_v2_packed_workspace_bytes grew by at most 256 B; h3d_dcn_nchw_to_nhwc_scaled).
+                                  Still 4 with dcn_v2_backward: three new entry points, nothing existing changed (additive), so a library built
+                                  before them still serves every older caller and tools/ab_lib.py can load it as a baseline */
 /* How this library was built: H3D_BUILD_EXTRA = `make EXTRA=1` (the superseded kernel generations kept as A/B references are in:
  * H3D_OP_DCN_V1, H3D_OP_DCN_FUSED_F16, H3D_OP_UPDCN_F16, the 0x4000 DeformConv variant, h3d_smpl_verts2 -- without it they return
  * H3D_ERR_UNSUPPORTED); H3D_BUILD_ABLATE = `make ABLATE=1` (profiling switches and in-kernel stamps compiled in). */
@@ -72,6 +74,42 @@ int h3d_dcn_v2_forward(const float *input, const float *weight, const float *bia
                        int kernel_h, int kernel_w, int stride_h, int stride_w,
                        int pad_h, int pad_w, int dilation_h, int dilation_w,
                        int deformable_group, void *stream);
+
+/* =====================================================================================
+ * 1b. dcn_v2_backward (DCNv2/src/dcn_v2.h:41-74, cuda/dcn_v2_cuda.cu:175-336): the gradients of the operator above, fp32 contiguous
+ *    NCHW.  Operand order of the reference (input, weight, bias, offset, mask, grad_output [B,Cout,Ho,Wo]), then the five outputs,
+ *    shaped like input / offset / mask / weight / bias.  ANY of the five output pointers may be NULL: that gradient is not computed and
+ *    nothing is written for it.  `bias` is not read (may be NULL).  The callee zeroes what it accumulates into (grad_input, on `stream`);
+ *    every other requested output is overwritten.  Asynchronous on `stream`, no allocation, no global state.
+ *    Kernels (csrc/dcn_bwd.hip): general fp32 kernels for every configuration; for the model's configuration (3x3, stride 1, pad 1,
+ *    dilation 1, deformable_group 1, C % 16 == 0, Cout <= 1024) both contractions run on v_mfma_f32_32x32x2_f32 (exact fmaf chains) with the
+ *    sampling in the same kernel.  The _general entry point runs the general kernels on every configuration, the model's included.
+ *    Reproducibility: grad_offset, grad_mask, grad_weight and grad_bias are sums in a fixed order -- bit-identical from run to run and
+ *    whichever other outputs are requested; grad_input is scattered with float atomic adds (the order of the adds varies: last bits differ).
+ *    Workspace (device memory, 256-byte aligned), with NPX = B*Ho*Wo, K = C*kh*kw, a256(x) = x rounded up to 256:
+ *      general  = a256(4 * Sg * Cout * K), Sg = splits of the pixels for grad_weight: min(max(ceil(512 / (ceil(K/64) ceil(Cout/64))), 1),
+ *                 max(NPX/256, 1), 64), then re-derived from the split length rounded up to 16 pixels
+ *      model    = a256(4*B*H*W*C) [input in NHWC] + a256(4 * 9 * ceil(C/32) * ceil(Cout/8) * 256) [filters in MFMA operand order]
+ *                 + a256(4 * B*SP * 9*Cout*C) [grad_weight partials], SP = splits per image: min(max(ceil(1024 / (ceil(C/32) ceil(Cout/64) B)), 1),
+ *                 max(H*W/512, 1)), then re-derived from the split length rounded up to 8 pixels
+ *      bytes    = max(general, model) in the model's configuration, general otherwise -- never a [B, 9C, Ho*Wo] column buffer.
+ *    The workspace is needed for grad_weight (and, in the model's configuration, for the data gradients); a NULL or short one is
+ *    H3D_ERR_ARG.  The size query returns a status like every other entry and hands the size back through `bytes`. */
+int h3d_dcn_v2_backward_workspace_bytes(int B, int C, int H, int W, int Cout, int kernel_h, int kernel_w,
+                                        int stride_h, int stride_w, int pad_h, int pad_w, int dilation_h, int dilation_w,
+                                        int deformable_group, size_t *bytes);
+int h3d_dcn_v2_backward(const float *input, const float *weight, const float *bias, const float *offset, const float *mask,
+                        const float *grad_output,
+                        float *grad_input, float *grad_offset, float *grad_mask, float *grad_weight, float *grad_bias,
+                        int B, int C, int H, int W, int Cout, int kernel_h, int kernel_w, int stride_h, int stride_w,
+                        int pad_h, int pad_w, int dilation_h, int dilation_w, int deformable_group,
+                        void *workspace, size_t workspace_bytes, void *stream);
+int h3d_dcn_v2_backward_general(const float *input, const float *weight, const float *bias, const float *offset, const float *mask,
+                                const float *grad_output,
+                                float *grad_input, float *grad_offset, float *grad_mask, float *grad_weight, float *grad_bias,
+                                int B, int C, int H, int W, int Cout, int kernel_h, int kernel_w, int stride_h, int stride_w,
+                                int pad_h, int pad_w, int dilation_h, int dilation_w, int deformable_group,
+                                void *workspace, size_t workspace_bytes, void *stream);
 
 /* The convolution in front of the operator inside the `DCN` module (dcn_v2.py:107-111, 119-124), for ANY module configuration:
  *   out = Conv2d(C, 3*dg*kh*kw, (kh,kw), stride, padding)(input);  o1, o2, m = chunk(out, 3, dim=1)
