@@ -19,6 +19,65 @@ OUT_NHWC, OUT_NCHW_F32, OUT_NHWC_F32, OUT_NHWC_F16 = 0, 1, 2, 3
 DCN_INPUT_NHWC, DCN_OUTPUT_NHWC, DCN_F32_MFMA = 1, 2, 4
 ABI_VERSION = 4
 
+# h3d_op.reserved: the flag catalogue of include/h3d.h under the same names minus the H3D_ prefix (what each flag requires of the
+# buffers is stated there).  OPF_* = operand / plan flags, TUNE_* = tuning overrides of tests and tools.
+DCN_AUX_BYTES = 256
+DCN_FUSED_BIAS_WMAX, DCN_FUSED_BIAS_AMAX = 32, 34       # float offsets behind `rows` in h3d_dcn_fused_pack_f32_cached's bias_out
+OPF_DCN_MASK_FINAL, OPF_DCN_RAW_PACK, OPF_DCN_ACT_MAXIMA, TUNE_DCN_ABLATE_MASK = 0x800, 0x100000, 0x200000, 0x1f
+OPF_DCN_FUSED_RAW_PACK, OPF_DCN_FUSED_SCALED_INPUT = 0x100000, 0x200000
+TUNE_DCN_FUSED_X3_MARGIN2, TUNE_DCN_FUSED_X3_MARGIN6, TUNE_DCN_FUSED_X3_MARGIN4, TUNE_DCN_FUSED_X3_ABLATE_MASK = 0x2000, 0x4000, 0x8000, 0x1f
+OPF_DCN_STREAM_NO_SLOTS, OPF_DCN_STREAM_WIDE_MARGIN, OPF_DCN_STREAM_SLOTS512, OPF_DCN_STREAM_F16_INPUT = 0x1000, 0x8000, 0x10000, 0x40000
+OPF_DCN_STREAM_STATS, OPF_DCN_STREAM_VARIANT_MASK = 0x20000, 0x58600
+TUNE_DCN_STREAM_FORCE_NARROW_WG, TUNE_DCN_STREAM_FORCE_WIDE_WG = 0x200, 0x400
+TUNE_DCN_STREAM_F16_DCN5, TUNE_DCN_STREAM_F16_KEEP_DCN3, TUNE_DCN_STREAM_ABLATE_MASK = 0x4000, 0x2000, 0x1f
+TUNE_DCN_STREAM_X3_MARGIN2, TUNE_DCN_STREAM_X3_MARGIN3, TUNE_DCN_STREAM_X3_MARGIN4, TUNE_DCN_STREAM_X3_ABLATE_MASK = 0x4000, 0x8000, 0x10000, 0x1f
+TUNE_DCN_F16_ONE_WG_PER_CU, TUNE_DCN_F16_ABLATE_MASK = 0x100, 0xff
+TUNE_CONV_STREAM_TILE_MASK, TUNE_CONV_STREAM_AUTO, TUNE_CONV_STREAM_ROUND4_RULE, TUNE_CONV_STREAM_ABLATE_MASK = 0xffff, 1, 0x10000000, 0x1f0000
+TUNE_CONV_TILE, TUNE_CONV_HALO_TILE, TUNE_CONV_FORCE_GEMM, TUNE_CONV_GEMM_TILE_MASK = 0x1000, 0x2000, 0x4000, 0xf00
+TUNE_CONV_X3_TILED, TUNE_CONV_X3_TILE_MASK, TUNE_CONV_X3_CK16, TUNE_CONV_X3_MT2 = 0x1000, 0x1fff, 0x2000, 0x4000
+TUNE_UPADD_TAPS_GLOBAL, TUNE_UPADD_TAPS_LDS = 1, 2
+TUNE_HEADS_SEPARATE_BIAS, TUNE_HEADS_ABLATE_MASK = 0x200, 0xff
+
+
+def TUNE_DCN_STREAM_DCN5_XP(xp):
+    return xp << 16
+
+
+def TUNE_DCN_STREAM_DCN5_XP_OF(reserved):
+    return (reserved >> 16) & 0xff
+
+
+def TUNE_CONV_STREAM_TILE(variant, mt, waves):
+    return variant << 12 | mt << 8 | waves
+
+
+def TUNE_CONV_STREAM_ABLATE(bits):
+    return bits << 16
+
+
+def TUNE_CONV_STREAM_ABLATE_OF(reserved):
+    return (reserved & TUNE_CONV_STREAM_ABLATE_MASK) >> 16
+
+
+def TUNE_CONV_1X1_TILE(mt, th):
+    return TUNE_CONV_TILE | mt << 4 | th >> 3
+
+
+def TUNE_CONV_1X1_TILE_MT(reserved):
+    return (reserved >> 4) & 15
+
+
+def TUNE_CONV_1X1_TILE_TH(reserved):
+    return (reserved & 15) * 8
+
+
+def TUNE_CONV_GEMM_TILE(n):
+    return n << 8
+
+
+def TUNE_CONV_X3_TILE(mt, waves, th):
+    return TUNE_CONV_X3_TILED | mt << 8 | waves << 4 | th >> 3
+
 c_vp, c_i, c_fp = ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p
 
 

@@ -283,8 +283,8 @@ template <typename T> static int launch_conv_t(const h3d_op &op, const ConvArgs 
     }
     if (op.ksize == 1 && op.stride == 1) {
         if (cin % 64 == 0) {
-            if (co > 32 && (op.reserved & 0x1000)) {           // tuning override (tools/ab_conv1x1.py): 0x1000 | MT << 4 | TH >> 3
-                const int mt = (op.reserved >> 4) & 15, th = (op.reserved & 15) * 8;
+            if (co > 32 && (op.reserved & H3D_TUNE_CONV_TILE)) {           // tuning override (tools/ab_conv1x1.py): H3D_TUNE_CONV_1X1_TILE(MT, TH)
+                const int mt = H3D_TUNE_CONV_1X1_TILE_MT(op.reserved), th = H3D_TUNE_CONV_1X1_TILE_TH(op.reserved);
                 if (mt == 4 && th == 16) return launch_conv_cfg<T, 1, 1, 4, 64, 16>(a, st);
                 if (mt == 4 && th == 8) return launch_conv_cfg<T, 1, 1, 4, 64, 8>(a, st);
                 if (mt == 2 && th == 16) return launch_conv_cfg<T, 1, 1, 2, 64, 16>(a, st);
@@ -333,22 +333,22 @@ template <> int launch_conv_t<float>(const h3d_op &op, const ConvArgs &a, hipStr
 }
 
 // f16x3 plans: the f32 plan's layouts (4-byte elements, 16-channel chunks) on 3 fp16 MFMAs per step instead of 8 fp32 ones.
-// (tuning override, tools/ab_conv.py --dtype f16x3: reserved = 0x1000 | MT << 8 | WAVES << 4 | TH >> 3)
+// (tuning override, tools/ab_conv.py --dtype f16x3: reserved = H3D_TUNE_CONV_X3_TILE(MT, WAVES, TH))
 template <> int launch_conv_t<x3_t>(const h3d_op &op, const ConvArgs &a, hipStream_t st)
 {
     const int co = op.Cout;
     if (op.ksize == 3 && op.stride == 1) {
-        if (op.reserved & 0x1000) {
-            switch (op.reserved & 0xfff) {
-            case 0x142: return launch_conv_cfg<x3_t, 3, 1, 1, 16, 16>(a, st);
-            case 0x182: return launch_conv_cfg<x3_t, 3, 1, 1, 16, 16, 8>(a, st);
-            case 0x242: return launch_conv_cfg<x3_t, 3, 1, 2, 16, 16>(a, st);
-            case 0x282: return launch_conv_cfg<x3_t, 3, 1, 2, 16, 16, 8>(a, st);
-            case 0x482: return launch_conv_cfg<x3_t, 3, 1, 4, 16, 16, 8>(a, st);
-            case 0x441: return launch_conv_cfg<x3_t, 3, 1, 4, 16, 8>(a, st);
-            case 0x241: return launch_conv_cfg<x3_t, 3, 1, 2, 16, 8>(a, st);
-            case 0x484: return launch_conv_cfg<x3_t, 3, 1, 4, 16, 32, 8>(a, st);      // two N-tiles per wave: a filter fragment feeds 6 MFMAs
-            case 0x284: return launch_conv_cfg<x3_t, 3, 1, 2, 16, 32, 8>(a, st);
+        if (op.reserved & H3D_TUNE_CONV_X3_TILED) {
+            switch (op.reserved & H3D_TUNE_CONV_X3_TILE_MASK) {
+            case H3D_TUNE_CONV_X3_TILE(1, 4, 16): return launch_conv_cfg<x3_t, 3, 1, 1, 16, 16>(a, st);
+            case H3D_TUNE_CONV_X3_TILE(1, 8, 16): return launch_conv_cfg<x3_t, 3, 1, 1, 16, 16, 8>(a, st);
+            case H3D_TUNE_CONV_X3_TILE(2, 4, 16): return launch_conv_cfg<x3_t, 3, 1, 2, 16, 16>(a, st);
+            case H3D_TUNE_CONV_X3_TILE(2, 8, 16): return launch_conv_cfg<x3_t, 3, 1, 2, 16, 16, 8>(a, st);
+            case H3D_TUNE_CONV_X3_TILE(4, 8, 16): return launch_conv_cfg<x3_t, 3, 1, 4, 16, 16, 8>(a, st);
+            case H3D_TUNE_CONV_X3_TILE(4, 4, 8): return launch_conv_cfg<x3_t, 3, 1, 4, 16, 8>(a, st);
+            case H3D_TUNE_CONV_X3_TILE(2, 4, 8): return launch_conv_cfg<x3_t, 3, 1, 2, 16, 8>(a, st);
+            case H3D_TUNE_CONV_X3_TILE(4, 8, 32): return launch_conv_cfg<x3_t, 3, 1, 4, 16, 32, 8>(a, st);      // two N-tiles per wave: a filter fragment feeds 6 MFMAs
+            case H3D_TUNE_CONV_X3_TILE(2, 8, 32): return launch_conv_cfg<x3_t, 3, 1, 2, 16, 32, 8>(a, st);
             default: H3D_FAIL(H3D_ERR_ARG, "conv (f16x3): unknown tuning override %#x", op.reserved);
             }
         }
@@ -362,12 +362,12 @@ template <> int launch_conv_t<x3_t>(const h3d_op &op, const ConvArgs &a, hipStre
         return launch_conv_cfg<x3_t, 3, 1, 4, 16, 16, 8>(a, st);
     }
     if (op.ksize == 3 && op.stride == 2) {
-        if (op.reserved & 0x1000) {         // tuning override (tools/ab_conv_x3.py --stride 2)
-            switch (op.reserved & 0xfff) {
-            case 0x282: return launch_conv_cfg<x3_t, 3, 2, 2, 16, 16, 8>(a, st);
-            case 0x182: return launch_conv_cfg<x3_t, 3, 2, 1, 16, 16, 8>(a, st);
-            case 0x141: return launch_conv_cfg<x3_t, 3, 2, 1, 16, 8>(a, st);
-            case 0x241: return launch_conv_cfg<x3_t, 3, 2, 2, 16, 8>(a, st);
+        if (op.reserved & H3D_TUNE_CONV_X3_TILED) {         // tuning override (tools/ab_conv_x3.py --stride 2)
+            switch (op.reserved & H3D_TUNE_CONV_X3_TILE_MASK) {
+            case H3D_TUNE_CONV_X3_TILE(2, 8, 16): return launch_conv_cfg<x3_t, 3, 2, 2, 16, 16, 8>(a, st);
+            case H3D_TUNE_CONV_X3_TILE(1, 8, 16): return launch_conv_cfg<x3_t, 3, 2, 1, 16, 16, 8>(a, st);
+            case H3D_TUNE_CONV_X3_TILE(1, 4, 8): return launch_conv_cfg<x3_t, 3, 2, 1, 16, 8>(a, st);
+            case H3D_TUNE_CONV_X3_TILE(2, 4, 8): return launch_conv_cfg<x3_t, 3, 2, 2, 16, 8>(a, st);
             default: H3D_FAIL(H3D_ERR_ARG, "conv (f16x3, stride 2): unknown tuning override %#x", op.reserved);
             }
         }
@@ -378,11 +378,11 @@ template <> int launch_conv_t<x3_t>(const h3d_op &op, const ConvArgs &a, hipStre
     }
     if (op.ksize == 1 && op.stride == 1) {
         // 64-channel chunks where the layer allows (Root convs over a concat: 128 ... 1280 input channels): a 16-channel chunk of a
-        // 1x1 conv is two barriers and a global round trip for 2 * MT * NT * 3 MFMAs per wave (0x2000: tuning override, 16-channel chunks)
+        // 1x1 conv is two barriers and a global round trip for 2 * MT * NT * 3 MFMAs per wave (H3D_TUNE_CONV_X3_CK16: tuning override, 16-channel chunks)
         // ... and 128-channel tiles above 64 output channels: a 64-channel tile walks the whole input once per channel block (tools/ab_conv_x3.py
         // --ksize 1, batch 64: 448 -> 128 @64x64 0.218 -> 0.156 ms, 256 -> 128 0.144 -> 0.108, 896 -> 256 0.149 -> 0.126, 1280 -> 512 0.102 -> 0.080)
-        if (op.Cin % 64 == 0 && co > 64 && !(op.reserved & 0x6000)) return launch_conv_cfg<x3_t, 1, 1, 4, 64, 8>(a, st);
-        if (op.Cin % 64 == 0 && co > 32 && !(op.reserved & 0x2000)) return launch_conv_cfg<x3_t, 1, 1, 2, 64, 8>(a, st);      // (0x4000: force these for > 64 channels)      // (8-row tiles: 52 KB of LDS, three workgroups per CU)
+        if (op.Cin % 64 == 0 && co > 64 && !(op.reserved & (H3D_TUNE_CONV_X3_CK16 | H3D_TUNE_CONV_X3_MT2))) return launch_conv_cfg<x3_t, 1, 1, 4, 64, 8>(a, st);
+        if (op.Cin % 64 == 0 && co > 32 && !(op.reserved & H3D_TUNE_CONV_X3_CK16)) return launch_conv_cfg<x3_t, 1, 1, 2, 64, 8>(a, st);      // (H3D_TUNE_CONV_X3_MT2: force these for > 64 channels)      // (8-row tiles: 52 KB of LDS, three workgroups per CU)
         if (co <= 32) return launch_conv_cfg<x3_t, 1, 1, 1, 16, 16>(a, st);
         return launch_conv_cfg<x3_t, 1, 1, 2, 16, 16>(a, st);
     }
@@ -800,9 +800,9 @@ int h3d_launch_elementwise(const h3d_op &op, hipStream_t st)
     // tap table in LDS only while staging it is cheap next to the workgroup's 8 rows x (256 / vectors per pixel) pixels.
     // With the skewed rows (no bank conflicts, see upadd_kernel), same box, batch 64: 4 KiB (64 ch, f = 2) 0.070 -> 0.063 ms;
     // 8 KiB (128 ch) 0.057 -> 0.043; 16 KiB with 64 channels (f = 4) 0.102 -> 0.075; 16 KiB with 256 channels (8-pixel
-    // segments) 0.029 -> 0.041: stays in global memory.  Tuning override: reserved 1 = never, 2 = whenever it fits 64 KiB
+    // segments) 0.029 -> 0.041: stays in global memory.  Tuning override: H3D_TUNE_UPADD_TAPS_GLOBAL = never, H3D_TUNE_UPADD_TAPS_LDS = whenever it fits 64 KiB
     const size_t up_wbytes = (size_t)op.ksize * op.ksize * op.Cin * sizeof(float);
-    const bool up_wlds = op.reserved == 1 ? false : op.reserved == 2 ? up_wbytes <= 64 * 1024 : (up_wbytes <= 8192 || (up_wbytes <= 16384 && op.Cin <= 64));
+    const bool up_wlds = op.reserved == H3D_TUNE_UPADD_TAPS_GLOBAL ? false : op.reserved == H3D_TUNE_UPADD_TAPS_LDS ? up_wbytes <= 64 * 1024 : (up_wbytes <= 8192 || (up_wbytes <= 16384 && op.Cin <= 64));
     // (measured and dropped in round 3: f = 2 tap weights in registers, rows in pairs with ten loads in flight -- 0.341 vs 0.325 ms
     //  over the six f = 2 launches of the batch-64 plan: the kernel sits at the 4.4-4.9 TB/s these mixed read / write streams reach)
     if (h3d_note_kernel("%s<%s%s%s>", op.kind == H3D_OP_MAXPOOL ? "maxpool_kernel" : op.kind == H3D_OP_UPADD ? "upadd_kernel" : "copy_kernel",
@@ -829,7 +829,7 @@ int h3d_launch_elementwise(const h3d_op &op, hipStream_t st)
         const int vpc = op.Cin / n;
         if (vpc > 256) H3D_FAIL(H3D_ERR_UNSUPPORTED, "upadd: C=%d", op.Cin);
         const size_t wfl = (size_t)op.ksize * op.ksize * op.Cin;
-        // tap table in LDS when it fits the default 64 KiB (tuning override: reserved 1 = never, 2 = always)
+        // tap table in LDS when it fits the default 64 KiB (tuning override: H3D_TUNE_UPADD_TAPS_GLOBAL / _LDS)
         const bool wlds = up_wlds;
         const size_t lds = wlds ? (wfl + 4 * (size_t)op.ksize * op.ksize) * sizeof(float) : 0;     // rows of C + 4 floats
         const dim3 ugrid(cdiv(op.Wo, 256 / vpc), op.B * cdiv(op.Ho, UP_ROWS));

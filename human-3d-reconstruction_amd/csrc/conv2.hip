@@ -27,7 +27,7 @@ struct Conv2Args {
     int B, H, W, Cin, in_cs;
     int Ho, Wo, Cout, out_cs, res_cs, relu, out_mode;
     int G, tiles_x, tiles_y;
-    int dbg;   // ABLATE builds only (op.reserved >> 16): 1 = no DMA after stage 0, 2 = no fragment reads / MFMA
+    int dbg;   // ABLATE builds only (H3D_TUNE_CONV_STREAM_ABLATE_OF(op.reserved)): 1 = no DMA after stage 0, 2 = no fragment reads / MFMA
     int xcd;   // h3d_tile_id mode
     int f16;   // host side only: fp16 plan (the launcher picks the f16_t instantiation)
     unsigned long long *stamps;   // profiling builds: per workgroup and wave (0-7) the cycles spent at the stage barrier; slot 7: wave 0's {DMA issue} (tools/stamp_conv2.py)
@@ -302,45 +302,46 @@ int h3d_launch_conv_stream(const h3d_op &op, hipStream_t st)
     a.Ho = op.Ho; a.Wo = op.Wo; a.Cout = op.Cout; a.out_cs = op.out_cs; a.res_cs = op.in2_cs; a.relu = op.relu; a.out_mode = op.out_mode;
     a.G = op.wrows / 32; a.tiles_x = a.tiles_y = 0;
     a.f16 = op.dtype == H3D_F16;
-    a.dbg = op.reserved >> 16;
+    a.dbg = H3D_TUNE_CONV_STREAM_ABLATE_OF(op.reserved);
+    const int tile = op.reserved & H3D_TUNE_CONV_STREAM_TILE_MASK;       // tuning override: H3D_TUNE_CONV_STREAM_TILE(variant, MT, WAVES)
     // workgroups a (th rows x 16 px) x (32*mt channels) tiling produces
     const int gq = cdiv(op.Cout, 32);
     auto nblk = [&](int th, int mt) { return (long)op.B * cdiv(op.Wo, 16) * cdiv(op.Ho, th) * cdiv(gq, mt); };
     if (op.stride == 2) {          // the stride-2 halo is (2 TH + 1) x 33 pixels: 4-wave tiles are what fits twice in the LDS
-        switch (op.reserved & 0xffff) {           // tuning override (tools/ab_conv.py)
-        case 0x4404: return launch_conv2_cfg<4, 4, 2, 1>(a, st);    // 0x4...: ONE ring slot (more workgroups per CU)
-        case 0x4408: return launch_conv2_cfg<4, 8, 2, 1>(a, st);
-        case 0x4204: return launch_conv2_cfg<2, 4, 2, 1>(a, st);
+        switch (tile) {                           // (tools/ab_conv.py)
+        case H3D_TUNE_CONV_STREAM_TILE(4, 4, 4): return launch_conv2_cfg<4, 4, 2, 1>(a, st);    // variant 4: ONE ring slot (more workgroups per CU)
+        case H3D_TUNE_CONV_STREAM_TILE(4, 4, 8): return launch_conv2_cfg<4, 8, 2, 1>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(4, 2, 4): return launch_conv2_cfg<2, 4, 2, 1>(a, st);
         default: break;
         }
         // one ring slot (73 KB): two workgroups per CU instead of one 4-wave workgroup with a two-slot ring
         // (tools/ab_conv_s2.py, batch 64: 64->128 0.093 -> 0.073 ms, 128->256 0.081 -> 0.082, 256->512 0.064 -> 0.051)
-        if (gq >= 4) return (op.reserved & 0xffff) == 0x2404 ? launch_conv2_cfg<4, 4, 2>(a, st) : launch_conv2_cfg<4, 4, 2, 1>(a, st);
+        if (gq >= 4) return tile == H3D_TUNE_CONV_STREAM_TILE(2, 4, 4) ? launch_conv2_cfg<4, 4, 2>(a, st) : launch_conv2_cfg<4, 4, 2, 1>(a, st);
         if (gq >= 2) return launch_conv2_cfg<2, 4, 2>(a, st);
         return launch_conv2_cfg<1, 4, 2>(a, st);
     }
-    if (op.reserved & 0xffff) {   // tuning override (profiling): reserved = MT << 8 | WAVES
-        switch (op.reserved & 0xffff) {
-        case 0x410: return launch_conv2_cfg<4, 16>(a, st);
-        case 0x408: return launch_conv2_cfg<4, 8>(a, st);
-        case 0x404: return launch_conv2_cfg<4, 4>(a, st);
-        case 0x208: return launch_conv2_cfg<2, 8>(a, st);
-        case 0x204: return launch_conv2_cfg<2, 4>(a, st);
-        case 0x108: return launch_conv2_cfg<1, 8>(a, st);
-        case 0x104: return launch_conv2_cfg<1, 4>(a, st);
-        case 0x2408: return launch_conv2_cfg<4, 8, 1, 2, 2>(a, st);   // 0x2...: two N-tiles per wave (32 x 16 px tile, 8 waves)
-        case 0x2208: return launch_conv2_cfg<2, 8, 1, 2, 2>(a, st);
-        case 0x3208: return launch_conv2_cfg<2, 8, 1, 3>(a, st);      // 0x3...: three ring slots
-        case 0x3108: return launch_conv2_cfg<1, 8, 1, 3>(a, st);
-        case 0x3404: return launch_conv2_cfg<4, 4, 1, 3>(a, st);
-        case 0x5408: return launch_conv2_cfg<4, 8, 1, 1>(a, st);      // 0x5...: ONE ring slot
-        case 0x5208: return launch_conv2_cfg<2, 8, 1, 1>(a, st);
-        case 0x5108: return launch_conv2_cfg<1, 8, 1, 1>(a, st);
-        case 0x6410: return launch_conv2_cfg<4, 16, 1, 2, 1, true>(a, st);   // 0x6...: fragment reads one tap ahead (PIPE)
-        case 0x6408: return launch_conv2_cfg<4, 8, 1, 2, 1, true>(a, st);
-        case 0x6208: return launch_conv2_cfg<2, 8, 1, 2, 1, true>(a, st);
-        case 0x6404: return launch_conv2_cfg<4, 4, 1, 2, 1, true>(a, st);
-        case 0x1: break;           // 1 = auto configuration (used with the ablation bits)
+    if (tile) {
+        switch (tile) {
+        case H3D_TUNE_CONV_STREAM_TILE(0, 4, 16): return launch_conv2_cfg<4, 16>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(0, 4, 8): return launch_conv2_cfg<4, 8>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(0, 4, 4): return launch_conv2_cfg<4, 4>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(0, 2, 8): return launch_conv2_cfg<2, 8>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(0, 2, 4): return launch_conv2_cfg<2, 4>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(0, 1, 8): return launch_conv2_cfg<1, 8>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(0, 1, 4): return launch_conv2_cfg<1, 4>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(2, 4, 8): return launch_conv2_cfg<4, 8, 1, 2, 2>(a, st);   // variant 2: two N-tiles per wave (32 x 16 px tile, 8 waves)
+        case H3D_TUNE_CONV_STREAM_TILE(2, 2, 8): return launch_conv2_cfg<2, 8, 1, 2, 2>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(3, 2, 8): return launch_conv2_cfg<2, 8, 1, 3>(a, st);      // variant 3: three ring slots
+        case H3D_TUNE_CONV_STREAM_TILE(3, 1, 8): return launch_conv2_cfg<1, 8, 1, 3>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(3, 4, 4): return launch_conv2_cfg<4, 4, 1, 3>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(5, 4, 8): return launch_conv2_cfg<4, 8, 1, 1>(a, st);      // variant 5: ONE ring slot
+        case H3D_TUNE_CONV_STREAM_TILE(5, 2, 8): return launch_conv2_cfg<2, 8, 1, 1>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(5, 1, 8): return launch_conv2_cfg<1, 8, 1, 1>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(6, 4, 16): return launch_conv2_cfg<4, 16, 1, 2, 1, true>(a, st);   // variant 6: fragment reads one tap ahead (PIPE)
+        case H3D_TUNE_CONV_STREAM_TILE(6, 4, 8): return launch_conv2_cfg<4, 8, 1, 2, 1, true>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(6, 2, 8): return launch_conv2_cfg<2, 8, 1, 2, 1, true>(a, st);
+        case H3D_TUNE_CONV_STREAM_TILE(6, 4, 4): return launch_conv2_cfg<4, 4, 1, 2, 1, true>(a, st);
+        case H3D_TUNE_CONV_STREAM_AUTO: break;           // auto configuration (used with the ablation bits)
         default: H3D_FAIL(H3D_ERR_ARG, "conv_stream: unknown tuning override %#x", op.reserved);
         }
     }
@@ -354,7 +355,7 @@ int h3d_launch_conv_stream(const h3d_op &op, hipStream_t st)
         // width, so more, smaller workgroups per CU is what hides them (tools/arch_kernels.py hourglass --codes ..., batch 16, same process:
         // 384 -> 384 @32x32 1.166 -> 0.846 ms for the 18 launches on <2,8>; @16x16 0.708 -> 0.421, @8x8 0.685 -> 0.337 on <1,4>;
         // 512 -> 512 @4x4 1.041 -> 0.559 for the 26 launches)
-        if (!(op.reserved & 0x10000000)) {          // (0x10000000: round 4's rule, 128-channel 8-row tiles, for A/B runs)
+        if (!(op.reserved & H3D_TUNE_CONV_STREAM_ROUND4_RULE)) {          // (H3D_TUNE_CONV_STREAM_ROUND4_RULE: round 4's rule, 128-channel 8-row tiles, for A/B runs)
             if (nblk(16, 2) >= 256) return launch_conv2_cfg<2, 8, 1, 2, 1, true>(a, st);
             if (nblk(16, 1) >= 256) return launch_conv2_cfg<1, 8>(a, st);
             return launch_conv2_cfg<1, 4>(a, st);

@@ -256,7 +256,7 @@ __global__ void dcn_om_pack_kernel(const float *__restrict__ off, const float *_
 }
 
 // The offset / mask rows of the fp32 fast path, followed by the two activation maxima (max |x|, max |mask|) the f16x3 kernel scales by
-// (h3d_op.reserved 0x200000 in csrc/dcn2.hip): zeroed, then filled by dcn_absmax and the om pack kernel -- all on the caller's stream.
+// (H3D_OPF_DCN_ACT_MAXIMA in csrc/dcn2.hip): zeroed, then filled by dcn_absmax and the om pack kernel -- all on the caller's stream.
 static size_t dcn_om_bytes(size_t px) { return ws_align(px * 32 * 4 + 16); }
 static int dcn_om_pack(const float *x, size_t nx, const float *offset, const float *mask, float *om, int HW, size_t px, bool f16x3, hipStream_t st)
 {
@@ -274,7 +274,7 @@ static int dcn_om_pack(const float *x, size_t nx, const float *offset, const flo
 // max |filter| of an fp32 pack, as the bit pattern of the float (monotonic for non-negative values; a NaN sorts above everything and
 // is recognised by the consumer): one atomicMax per wave into `wmax`, which the caller zeroed in front of the pack kernel.  The f16x3
 // operator kernel (csrc/dcn2.hip, H3D_F16X3) derives its power-of-two filter scale from it -- on the device, no host round trip.
-#define H3D_DCN_AUX_BYTES 256      // behind the bias of an fp32 pack: [0] = max |filter| bits
+// (H3D_DCN_AUX_BYTES behind the bias of an fp32 pack, word 0 = max |filter| bits: include/h3d.h)
 __device__ __forceinline__ void dcn_wmax_accumulate(unsigned *wmax, float v)
 {
     unsigned m = __float_as_uint(fabsf(v));
@@ -315,11 +315,45 @@ __global__ void dcn_w_pack_f16_kernel(const float *__restrict__ w, const float *
     wp[i] = (_Float16)(o < Cout ? __builtin_amdgcn_fmed3f(w[((size_t)o * C + c) * 9 + tap], -65504.f, 65504.f) : 0.f);
 }
 
+// Layout of a DeformConv filter pack (h3d_dcn_v2_pack_weights[_cached]; the tail of h3d_dcn_v2_forward_ws's workspace), in bytes:
+// [rows = Cout padded to 128][9][C] filters (fp32, or fp16 for H3D_BF16) | at `bias`: fp32 [rows] | at `aux`, fp32 packs only:
+// H3D_DCN_AUX_BYTES, word 0 = max |filter| bits (rows is a multiple of 128: no padding between the biases and the maxima)
+struct DcnPackLayout {
+    int rows;
+    size_t wtotal;                  // filter elements
+    size_t bias, aux, bytes;
+};
+static DcnPackLayout dcn_pack_layout(int Cout, int C, int dtype)
+{
+    DcnPackLayout L;
+    L.rows = (Cout + 127) / 128 * 128;
+    L.wtotal = (size_t)L.rows * 9 * C;
+    L.bias = ws_align(L.wtotal * (dtype == H3D_F32 ? 4 : 2));
+    L.aux = L.bias + (size_t)L.rows * 4;
+    L.bytes = L.aux + (dtype == H3D_F32 ? H3D_DCN_AUX_BYTES : 0);
+    return L;
+}
+
+// The H3D_OP_DCN launch of the operator's fast path: x = the NHWC input, om = the [B,H,W,32] offset / mask rows of dcn_om_pack, w / bias = a
+// filter pack.  The mask operand is final (the reference applies the sigmoid in DCN.forward, dcn_v2.py:124); f16x3: the fp32 pack with
+// max |w| behind the bias, the activation maxima behind om.
+static int dcn_launch_boundary_op(int dtype, bool f16x3, const void *x, const float *om, const void *packed, const DcnPackLayout &L, void *out,
+                                  int out_mode, int B, int C, int H, int W, int Cout, hipStream_t st)
+{
+    h3d_op op = {};
+    op.kind = H3D_OP_DCN; op.dtype = f16x3 ? H3D_F16X3 : dtype;
+    op.in = x; op.in2 = om; op.w = packed; op.bias = (const float *)((const char *)packed + L.bias); op.out = out;
+    op.B = B; op.H = H; op.W = W; op.Cin = C; op.in_cs = C; op.in2_cs = 32; op.Ho = H; op.Wo = W; op.Cout = Cout; op.out_cs = Cout;
+    op.ksize = 3; op.stride = 1; op.relu = 0; op.out_mode = out_mode; op.wrows = L.rows;
+    op.reserved = H3D_OPF_DCN_MASK_FINAL | (f16x3 ? H3D_OPF_DCN_RAW_PACK | H3D_OPF_DCN_ACT_MAXIMA : 0);
+    return h3d_launch_dcn2(op, st);
+}
+
 extern "C" size_t h3d_dcn_v2_workspace_bytes(int B, int C, int H, int W, int Cout)
 {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-    const size_t rows = ((size_t)Cout + 127) / 128 * 128, px = (size_t)B * H * W;
-    return ws_align(px * C * 4) + dcn_om_bytes(px) + ws_align(rows * 9 * C * 4) + ws_align(rows * 4) + H3D_DCN_AUX_BYTES;
+    const size_t px = (size_t)B * H * W;
+    return ws_align(px * C * 4) + dcn_om_bytes(px) + dcn_pack_layout(Cout, C, H3D_F32).bytes;
 }
 
 // The arithmetic of the operator's fp32 fast path: three fp16 MFMAs on split operands per fp32 product (H3D_F16X3: 2^-22 relative per
@@ -344,30 +378,23 @@ extern "C" int h3d_dcn_v2_forward_ws(const float *input, const float *weight, co
     if (!input || !weight || !bias || !offset || !mask || !output) H3D_FAIL(H3D_ERR_ARG, "dcn_v2_forward: null pointer");
     if (B <= 0 || H <= 0 || W <= 0 || Cout <= 0) H3D_FAIL(H3D_ERR_SHAPE, "dcn_v2_forward: non-positive dimension");
     hipStream_t st = (hipStream_t)stream;
-    const int rows = (Cout + 127) / 128 * 128;
+    const DcnPackLayout L = dcn_pack_layout(Cout, C, H3D_F32);
     const size_t px = (size_t)B * H * W;
     char *ws = (char *)workspace;
     float *x_nhwc = (float *)ws;                ws += ws_align(px * C * 4);
     float *om = (float *)ws;                    ws += dcn_om_bytes(px);
-    float *wp = (float *)ws;                    ws += ws_align((size_t)rows * 9 * C * 4);
-    float *bp = (float *)ws;                    // [rows] + H3D_DCN_AUX_BYTES (rows is a multiple of 128: no padding in between)
-    unsigned *wmax = (unsigned *)(bp + rows);
+    float *wp = (float *)ws;                    // the filter pack
+    float *bp = (float *)(ws + L.bias);
+    unsigned *wmax = (unsigned *)(ws + L.aux);
     if (hipMemsetAsync(wmax, 0, H3D_DCN_AUX_BYTES, st) != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "dcn_v2_forward: memset");
     int rc = h3d_nchw_f32_to_nhwc(input, x_nhwc, H3D_F32, B, C, H, W, C, stream);
     if (rc != H3D_OK) return rc;
     const bool f16x3 = !dcn_op_f32_mfma();
     rc = dcn_om_pack(input, px * C, offset, mask, om, H * W, px, f16x3, st);
     if (rc != H3D_OK) return rc;
-    const size_t wtotal = (size_t)rows * 9 * C;
-    hipLaunchKernelGGL(dcn_w_pack_kernel, dim3((unsigned)((wtotal + 255) / 256)), dim3(256), 0, st, weight, bias, wp, bp, Cout, C, rows, wmax);
+    hipLaunchKernelGGL(dcn_w_pack_kernel, dim3((unsigned)((L.wtotal + 255) / 256)), dim3(256), 0, st, weight, bias, wp, bp, Cout, C, L.rows, wmax);
     H3D_CHECK_LAUNCH("dcn_w_pack_kernel");
-    h3d_op op = {};
-    op.kind = H3D_OP_DCN; op.dtype = f16x3 ? H3D_F16X3 : H3D_F32;
-    op.in = x_nhwc; op.in2 = om; op.w = wp; op.bias = bp; op.out = output;
-    op.B = B; op.H = H; op.W = W; op.Cin = C; op.in_cs = C; op.in2_cs = 32; op.Ho = H; op.Wo = W; op.Cout = Cout; op.out_cs = Cout;
-    op.ksize = 3; op.stride = 1; op.relu = 0; op.out_mode = H3D_OUT_NCHW_F32; op.wrows = rows;
-    op.reserved = 0x800 | (f16x3 ? 0x300000 : 0);      // the mask operand is final (the reference applies the sigmoid in DCN.forward, dcn_v2.py:124); fp32 pack + max |w|; activation maxima
-    return h3d_launch_dcn2(op, st);
+    return dcn_launch_boundary_op(H3D_F32, f16x3, x_nhwc, om, wp, L, output, H3D_OUT_NCHW_F32, B, C, H, W, Cout, st);
 }
 
 // ---- the operator's THROUGHPUT form (round 3): what a caller that runs the same layer on every batch wants ----------------------
@@ -380,8 +407,7 @@ extern "C" int h3d_dcn_v2_forward_ws(const float *input, const float *weight, co
 extern "C" size_t h3d_dcn_v2_packed_weight_bytes(int Cout, int C, int dtype)
 {
     if (Cout <= 0 || C <= 0 || (dtype != H3D_F32 && dtype != H3D_BF16)) return 0;
-    const size_t rows = ((size_t)Cout + 127) / 128 * 128;
-    return ws_align(rows * 9 * C * (dtype == H3D_F32 ? 4 : 2)) + ws_align(rows * 4) + (dtype == H3D_F32 ? H3D_DCN_AUX_BYTES : 0);
+    return dcn_pack_layout(Cout, C, dtype).bytes;
 }
 
 extern "C" int h3d_dcn_v2_pack_weights(const float *weight, const float *bias, int Cout, int C, int dtype, void *packed, void *stream)
@@ -389,15 +415,15 @@ extern "C" int h3d_dcn_v2_pack_weights(const float *weight, const float *bias, i
     if (!weight || !bias || !packed) H3D_FAIL(H3D_ERR_ARG, "dcn_v2_pack_weights: null pointer");
     if (Cout <= 0 || C <= 0 || C % 16) H3D_FAIL(H3D_ERR_SHAPE, "dcn_v2_pack_weights: C=%d must be a positive multiple of 16", C);
     if (dtype != H3D_F32 && dtype != H3D_BF16) H3D_FAIL(H3D_ERR_DTYPE, "dcn_v2_pack_weights: dtype %d (f32 | bf16)", dtype);
-    const int rows = (Cout + 127) / 128 * 128;
-    const size_t wtotal = (size_t)rows * 9 * C;
-    float *bp = (float *)((char *)packed + ws_align(wtotal * (dtype == H3D_F32 ? 4 : 2)));
+    const DcnPackLayout L = dcn_pack_layout(Cout, C, dtype);
+    float *bp = (float *)((char *)packed + L.bias);
+    unsigned *wmax = (unsigned *)((char *)packed + L.aux);
     if (dtype == H3D_F32) {
-        if (hipMemsetAsync(bp + rows, 0, H3D_DCN_AUX_BYTES, (hipStream_t)stream) != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "dcn_v2_pack_weights: memset");
-        hipLaunchKernelGGL(dcn_w_pack_kernel, dim3((unsigned)((wtotal + 255) / 256)), dim3(256), 0, (hipStream_t)stream, weight, bias, (float *)packed, bp, Cout, C, rows,
-                           (unsigned *)(bp + rows));
+        if (hipMemsetAsync(wmax, 0, H3D_DCN_AUX_BYTES, (hipStream_t)stream) != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "dcn_v2_pack_weights: memset");
+        hipLaunchKernelGGL(dcn_w_pack_kernel, dim3((unsigned)((L.wtotal + 255) / 256)), dim3(256), 0, (hipStream_t)stream, weight, bias, (float *)packed, bp, Cout, C, L.rows,
+                           wmax);
     } else
-        hipLaunchKernelGGL(dcn_w_pack_f16_kernel, dim3((unsigned)((wtotal + 255) / 256)), dim3(256), 0, (hipStream_t)stream, weight, bias, (_Float16 *)packed, bp, Cout, C, rows);
+        hipLaunchKernelGGL(dcn_w_pack_f16_kernel, dim3((unsigned)((L.wtotal + 255) / 256)), dim3(256), 0, (hipStream_t)stream, weight, bias, (_Float16 *)packed, bp, Cout, C, L.rows);
     H3D_CHECK_LAUNCH("dcn_w_pack_kernel");
     return H3D_OK;
 }
@@ -492,15 +518,14 @@ extern "C" int h3d_dcn_v2_pack_weights_cached(const float *weight, const float *
     const size_t nb[2] = {(size_t)Cout * C * 9 * 4, (size_t)Cout * 4};
     int rc = sig_begin(state, bufs, nb, 2, st);
     if (rc != H3D_OK) return rc;
-    const int rows = (Cout + 127) / 128 * 128;
-    const size_t wtotal = (size_t)rows * 9 * C;
-    float *bp = (float *)((char *)packed + ws_align(wtotal * (dtype == H3D_F32 ? 4 : 2)));
-    unsigned *wmax = dtype == H3D_F32 ? (unsigned *)(bp + rows) : nullptr;
+    const DcnPackLayout L = dcn_pack_layout(Cout, C, dtype);
+    float *bp = (float *)((char *)packed + L.bias);
+    unsigned *wmax = dtype == H3D_F32 ? (unsigned *)((char *)packed + L.aux) : nullptr;
     if (wmax) {
         hipLaunchKernelGGL(dcn_wmax_reset_if_kernel, dim3(1), dim3(1), 0, st, state, wmax);
         H3D_CHECK_LAUNCH("dcn_wmax_reset_if_kernel");
     }
-    hipLaunchKernelGGL(dcn_w_pack_if_kernel, dim3((unsigned)((wtotal + 255) / 256)), dim3(256), 0, st, weight, bias, packed, bp, Cout, C, rows,
+    hipLaunchKernelGGL(dcn_w_pack_if_kernel, dim3((unsigned)((L.wtotal + 255) / 256)), dim3(256), 0, st, weight, bias, packed, bp, Cout, C, L.rows,
                        dtype == H3D_F32 ? 0 : 1, state, wmax);
     H3D_CHECK_LAUNCH("dcn_w_pack_if_kernel");
     hipLaunchKernelGGL(sig_commit_kernel, dim3(1), dim3(1), 0, st, state);
@@ -517,7 +542,7 @@ __global__ void dcn_fused_pack_f32_if_kernel(const float *__restrict__ w, const 
                                              int Cout, int C, int rows, const unsigned long long *__restrict__ state)
 {
     if (state[0] == state[1]) return;
-    unsigned *wmax = (unsigned *)(bo + rows + 32);         // [0] max |main filter|, [1] max |offset / mask filter| (reset by dcn_wmax_reset_if_kernel)
+    unsigned *wmax = (unsigned *)(bo + rows + H3D_DCN_FUSED_BIAS_WMAX);         // [0] max |main filter|, [1] max |offset / mask filter| (reset by dcn_wmax_reset_if_kernel)
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t main_total = (size_t)rows * 9 * C, total = main_total + (size_t)128 * 9 * C;
     auto src_channel = [](int row) {                       // MFMA row of the permuted offset conv -> conv_offset_mask channel (-1: unused)
@@ -562,7 +587,7 @@ extern "C" int h3d_dcn_fused_pack_f32_cached(const float *weight, const float *b
     if (rc != H3D_OK) return rc;
     const int rows = (Cout + 127) / 128 * 128;
     const size_t total = ((size_t)rows + 128) * 9 * C;
-    hipLaunchKernelGGL(dcn_wmax_reset_if_kernel, dim3(1), dim3(1), 0, st, state, (unsigned *)(bias_out + rows + 32));
+    hipLaunchKernelGGL(dcn_wmax_reset_if_kernel, dim3(1), dim3(1), 0, st, state, (unsigned *)(bias_out + rows + H3D_DCN_FUSED_BIAS_WMAX));
     H3D_CHECK_LAUNCH("dcn_wmax_reset_if_kernel");
     hipLaunchKernelGGL(dcn_fused_pack_f32_if_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, weight, bias, off_weight, off_bias, wp, wo,
                        bias_out, Cout, C, rows, state);
@@ -592,7 +617,6 @@ extern "C" int h3d_dcn_v2_forward_packed(const void *input, const void *packed, 
     if (workspace_bytes < h3d_dcn_v2_packed_workspace_bytes(B, C, H, W, flags))
         H3D_FAIL(H3D_ERR_ARG, "dcn_v2_forward_packed: workspace of %zu bytes, %zu needed", workspace_bytes, h3d_dcn_v2_packed_workspace_bytes(B, C, H, W, flags));
     hipStream_t st = (hipStream_t)stream;
-    const int rows = (Cout + 127) / 128 * 128;
     const size_t px = (size_t)B * H * W;
     char *ws = (char *)workspace;
     float *om = (float *)ws;                    ws += dcn_om_bytes(px);
@@ -605,22 +629,14 @@ extern "C" int h3d_dcn_v2_forward_packed(const void *input, const void *packed, 
     const bool f16x3 = dtype == H3D_F32 && !(flags & H3D_DCN_F32_MFMA) && !dcn_op_f32_mfma();
     int rc = dcn_om_pack((const float *)input, px * C, offset, mask, om, H * W, px, f16x3, st);      // (max |x| from the caller's tensor, either layout)
     if (rc != H3D_OK) return rc;
-    h3d_op op = {};
-    op.kind = H3D_OP_DCN;
-    op.dtype = f16x3 ? H3D_F16X3 : dtype;
-    op.in = x; op.in2 = om; op.w = packed;
-    op.bias = (const float *)((const char *)packed + ws_align((size_t)rows * 9 * C * (dtype == H3D_F32 ? 4 : 2)));
-    op.out = output;
-    op.B = B; op.H = H; op.W = W; op.Cin = C; op.in_cs = C; op.in2_cs = 32; op.Ho = H; op.Wo = W; op.Cout = Cout; op.out_cs = Cout;
-    op.ksize = 3; op.stride = 1; op.relu = 0; op.out_mode = (flags & H3D_DCN_OUTPUT_NHWC) ? H3D_OUT_NHWC : H3D_OUT_NCHW_F32; op.wrows = rows;
-    op.reserved = 0x800 | (f16x3 ? 0x300000 : 0);      // the mask operand is final; fp32 pack + max |w| behind the bias; activation maxima behind om
-    return h3d_launch_dcn2(op, st);
+    return dcn_launch_boundary_op(dtype, f16x3, x, om, packed, dcn_pack_layout(Cout, C, dtype), output,
+                                  (flags & H3D_DCN_OUTPUT_NHWC) ? H3D_OUT_NHWC : H3D_OUT_NCHW_F32, B, C, H, W, Cout, st);
 }
 
-// The stand-alone `DCN` module's input for its f16x3 fused launch (H3D_OP_DCN_FUSED, dtype H3D_F16X3, reserved 0x300000): max |x| over the
+// The stand-alone `DCN` module's input for its f16x3 fused launch (H3D_OP_DCN_FUSED, dtype H3D_F16X3, H3D_OPF_DCN_FUSED_RAW_PACK | _SCALED_INPUT): max |x| over the
 // finite elements into amax[0], then NCHW -> NHWC with x multiplied by 2^dcn_act_exp(max |x|, 0) (exact: a power of two), so that the
 // kernel's fp16 operand split sees values below 2^14 whatever the caller's magnitude; the kernel multiplies both of its accumulations
-// (offset convolution, DeformConv) by the inverse.  amax: one word of device memory (h3d_dcn_fused_pack_f32_cached's bias_out[rows + 34]).
+// (offset convolution, DeformConv) by the inverse.  amax: one word of device memory (h3d_dcn_fused_pack_f32_cached's bias_out[rows + H3D_DCN_FUSED_BIAS_AMAX]).
 __global__ void dcn_nchw_to_nhwc_scaled_kernel(const float *__restrict__ src, float *__restrict__ dst, int C, int HW, const unsigned *__restrict__ amax)
 {
     __shared__ float tile[32][33];

@@ -29,10 +29,10 @@ struct Dcn2Args {
     int B, H, W, Cin, in_cs, om_cs;
     int Cout, out_cs, relu, out_mode;
     int tiles_x, tiles_y;
-    int dbg;   // ablation switches for profiling (h3d_op.reserved): 1 = stage only chunk 0, 2 = no gather/blend, 4 = no MFMA
-    int mask_final;   // om[18..26] is the mask itself, not its logit (operator boundary h3d_dcn_v2_forward_ws; op.reserved & 0x800)
+    int dbg;   // ablation switches for profiling (h3d_op.reserved & H3D_TUNE_DCN_ABLATE_MASK): 1 = stage only chunk 0, 2 = no gather/blend, 4 = no MFMA
+    int mask_final;   // om[18..26] is the mask itself, not its logit (operator boundary h3d_dcn_v2_forward_ws; H3D_OPF_DCN_MASK_FINAL)
     const unsigned *wmax;   // H3D_F16X3 (the operator's fp32 fast path): bit pattern of max |filter|, written by the pack kernels (csrc/dcn.hip)
-    const unsigned *amax;   // H3D_F16X3 behind 0x200000: [0] max |x|, [1] max |mask| over finite elements (csrc/dcn.hip), the activation scale's source
+    const unsigned *amax;   // H3D_F16X3 behind H3D_OPF_DCN_ACT_MAXIMA: [0] max |x|, [1] max |mask| over finite elements (csrc/dcn.hip), the activation scale's source
 };
 
 template <typename T, int MT, int CK, int MARGIN, int NT_>
@@ -428,8 +428,8 @@ int h3d_launch_dcn2(const h3d_op &op, hipStream_t st)
     a.out = (char *)op.out; a.B = op.B; a.H = op.H; a.W = op.W; a.Cin = op.Cin; a.in_cs = op.in_cs;
     a.om_cs = op.in2_cs; a.Cout = op.Cout; a.out_cs = op.out_cs; a.relu = op.relu; a.out_mode = op.out_mode;
     a.tiles_x = a.tiles_y = 0;
-    a.dbg = op.reserved;
-    a.mask_final = (op.reserved >> 11) & 1;
+    a.dbg = op.reserved & H3D_TUNE_DCN_ABLATE_MASK;
+    a.mask_final = (op.reserved & H3D_OPF_DCN_MASK_FINAL) ? 1 : 0;
     a.wmax = nullptr;
     a.amax = nullptr;
     if (op.dtype == H3D_BF16) {
@@ -445,14 +445,14 @@ int h3d_launch_dcn2(const h3d_op &op, hipStream_t st)
         if (op.Cout <= 32) return launch_dcn2_cfg<float, 1, 16, 2, 1>(a, st);
         return launch_dcn2_cfg<float, 2, 16, 2, 1>(a, st);
     }
-    if (op.dtype == H3D_F16X3 && (op.reserved & 0x100000)) {
-        // (0x100000: set by the operator entry points of csrc/dcn.hip -- a network plan's f16x3 DeformConvs are H3D_OP_DCN_FUSED[_STREAM]
+    if (op.dtype == H3D_F16X3 && (op.reserved & H3D_OPF_DCN_RAW_PACK)) {
+        // (H3D_OPF_DCN_RAW_PACK: set by the operator entry points of csrc/dcn.hip -- a network plan's f16x3 DeformConvs are H3D_OP_DCN_FUSED[_STREAM]
         //  with pre-split filters and h3d_op.wexp; an H3D_OP_DCN of that kind has no kernel and fails below as before)
         // the operator's fp32 fast path on the fp16 matrix cores: fp32 tensors and the plain fp32 filter pack of H3D_F32, every product as
         // three fp16 MFMAs on split operands (csrc/common.h ET<x3_t>).  bias[wrows] holds the bit pattern of max |filter| (see Dcn2Args)
         a.wmax = (const unsigned *)(op.bias + op.wrows);
-        // 0x200000: the two activation maxima follow the [B,H,W,in2_cs] offset / mask rows (csrc/dcn.hip)
-        if (op.reserved & 0x200000) a.amax = (const unsigned *)((const float *)op.in2 + (size_t)op.B * op.H * op.W * op.in2_cs);
+        // H3D_OPF_DCN_ACT_MAXIMA: the two activation maxima follow the [B,H,W,in2_cs] offset / mask rows (csrc/dcn.hip)
+        if (op.reserved & H3D_OPF_DCN_ACT_MAXIMA) a.amax = (const unsigned *)((const float *)op.in2 + (size_t)op.B * op.H * op.W * op.in2_cs);
         if (op.Cout <= 32) return launch_dcn2_cfg<x3_t, 1, 16, 2, 1>(a, st);
         return launch_dcn2_cfg<x3_t, 2, 16, 2, 1>(a, st);
     }

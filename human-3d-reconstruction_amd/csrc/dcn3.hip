@@ -35,13 +35,13 @@ struct Dcn3Args {
     int B, H, W, Cin, in_cs;
     int Cout, out_cs, relu, out_mode, wrows;
     int tiles_x, tiles_y;
-    int dbg;   // profiling ablation (h3d_op.reserved): 1 no phase-A MFMA, 2 no gather/blend, 4 no phase-B MFMA, 8 stage once, 16 no patch fill
+    int dbg;   // profiling ablation (h3d_op.reserved & H3D_TUNE_DCN_STREAM_ABLATE_MASK): 1 no phase-A MFMA, 2 no gather/blend, 4 no phase-B MFMA, 8 stage once, 16 no patch fill
     int G;     // WDMA: 32-row groups of the main filter image
     float wscale, oscale;   // f16x3 plans: 2^-wexp / 2^-wexp2 of the main / offset filters (h3d_op.wexp, wexp2); 1 otherwise
     const unsigned *wmax;   // f16x3, register-staged filters only (the stand-alone `DCN` module): the filters are PLAIN fp32 packs and [0] / [1] hold the
                             // bit patterns of max |main filter| / max |offset filter| (csrc/dcn.hip dcn_fused_pack_f32_if_kernel): scaled by a power of
                             // two and split while they are staged, as csrc/dcn2.hip does for the operator; nullptr = pre-split filters (network plans)
-    int xscaled;   // with wmax: the input was scaled by 2^dcn_act_exp(wmax[2]) (reserved 0x200000, the `DCN` module's f16x3 launch)
+    int xscaled;   // with wmax: the input was scaled by 2^dcn_act_exp(wmax[2]) (H3D_OPF_DCN_FUSED_SCALED_INPUT, the `DCN` module's f16x3 launch)
     int xcd;   // h3d_tile_id mode
     unsigned long long *stamps;   // profiling builds: in-kernel phase stamps (common.h H3D_STAMP)
 };
@@ -126,7 +126,7 @@ __device__ __forceinline__ u32x4 dcn3_patch_corner(const char *img, int bytes, i
 // `node` DeformConvs of IDAUp read a tensor only they consume (`node(up(proj(x)) + skip)`, model.py:384-390), so the up-sample + add
 // kernel writes it as fp16 (H3D_OUT_NHWC_F16) and the bf16 -> fp16 conversion of every staged apron vector (3 VALU per pair, between
 // the two barriers of a stage where all eight waves do the same thing) disappears; the sample is also more precise (11 significand
-// bits instead of 8).  Selected by h3d_op.reserved & 0x40000.
+// bits instead of 8).  Selected by H3D_OPF_DCN_STREAM_F16_INPUT.
 // STATS: the statistics launch of h3d_dcn_far_samples -- its own instantiation (phase A + geometry only; everything behind the
 // slot count is compiled out), so that a profiler lists it under its own name and the production kernel carries no switch for it.
 template <typename T, int MT, int CK, int MARGIN, int EPI = 0, bool WDMA = false, int NP = 0, bool PK = false, bool F16IN = false, bool STATS = false>   // EPI: 0 general, 1 lean NHWC, 2 LDS-transposed (bf16)
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
             }
         }
     }
-    // the `DCN` module's launch (0x200000): x arrives scaled below 2^14 (h3d_dcn_nchw_to_nhwc_scaled), so staging and splitting need no
+    // the `DCN` module's launch (H3D_OPF_DCN_FUSED_SCALED_INPUT): x arrives scaled below 2^14 (h3d_dcn_nchw_to_nhwc_scaled), so staging and splitting need no
     // clamp -- and take none, so that a NaN / inf activation stays non-finite through both contractions as it does in the reference
     [[maybe_unused]] const bool xraw = std::is_same_v<T, x3_t> && !WDMA && a.xscaled;
     [[maybe_unused]] auto prep_mem = [&](const typename X::frag &f) {      // a sample blended from values read straight from memory
@@ -1019,7 +1019,7 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
 }
 
 template <typename T, int MT, int CK, int MARGIN, bool WDMA = false, int NP = 0, bool PK = false, bool F16IN = false>
-static int launch_dcn3_cfg(const Dcn3Args &a0, hipStream_t st)
+static int launch_dcn3_cfg(const Dcn3Args &a0, hipStream_t st, bool stats = false)
 {
     using C = Dcn3Cfg<T, MT, CK, MARGIN, WDMA, NP, PK>;
     static_assert(!(WDMA && MT <= 2 && sizeof(T) == 2) || C::LDS * 2 <= 160 * 1024, "two workgroups per CU");
@@ -1041,7 +1041,7 @@ static int launch_dcn3_cfg(const Dcn3Args &a0, hipStream_t st)
                         WDMA ? "true" : "false", NP))
         return H3D_OK;
     if constexpr (NP > 0 && sizeof(T) == 2) {
-        if (a.dbg & 0x20000) {                  // h3d_dcn_far_samples
+        if (stats) {                            // h3d_dcn_far_samples
             hipLaunchKernelGGL((dcn3_kernel<T, MT, CK, MARGIN, 1, WDMA, NP, PK, F16IN, true>), dim3(grid.x), dim3(C::THREADS), 0, st, a);
             H3D_CHECK_LAUNCH("dcn3_kernel<stats>");
             return H3D_OK;
@@ -1071,48 +1071,81 @@ static int launch_dcn3_cfg(const Dcn3Args &a0, hipStream_t st)
 // channels per filter stage of H3D_OP_DCN_FUSED_STREAM: hosts pack the stage-major filter images with this CK
 extern "C" int h3d_dcn_fused_ck(int Cin, int Cout) { (void)Cin; (void)Cout; return 16; }
 
+// h3d_op.reserved of a fused DeformConv, decoded once (include/h3d.h: the H3D_OPF_DCN_STREAM_*, H3D_TUNE_DCN_STREAM_* and
+// H3D_*_DCN_FUSED_* groups).  One bit value carries different names under different kinds and dtypes, so the decode takes both.
+struct Dcn3Flags {
+    // 2-byte plans (bf16 / fp16)
+    bool no_slots, wide_margin, slots512;   // the tile variant: round 1's tiles | margin 4, packed apron | 512 slots, packed apron | (none) margin 2, 256 slots
+    bool f16_input;                         // bf16 plans: the input tensor holds fp16 values
+    bool narrow_wg;                         // > 64 output channels on 64-channel workgroups (h3d_dcn_narrow_wg: the grid, or forced either way)
+    bool stats;                             // h3d_dcn_far_samples
+    bool dcn5;                              // fp16 stream ops: the LDS-DMA apron kernel of csrc/dcn5.hip
+    // f16x3 plans
+    int margin;                             // forced apron margin, 0 = the launcher's rule
+    bool raw_pack, scaled_input;            // fused op of the stand-alone `DCN` module: fp32 packs + maxima behind the bias | input pre-scaled
+};
+static Dcn3Flags dcn3_decode(const h3d_op &op, bool wdma)
+{
+    const int r = op.reserved;
+    Dcn3Flags f = {};
+    if (op.dtype == H3D_BF16 || op.dtype == H3D_F16) {
+        f.no_slots = r & H3D_OPF_DCN_STREAM_NO_SLOTS;
+        f.wide_margin = r & H3D_OPF_DCN_STREAM_WIDE_MARGIN;
+        f.slots512 = r & H3D_OPF_DCN_STREAM_SLOTS512;
+        f.f16_input = op.dtype == H3D_BF16 && (r & H3D_OPF_DCN_STREAM_F16_INPUT);
+        f.narrow_wg = h3d_dcn_narrow_wg(op);
+        f.stats = r & H3D_OPF_DCN_STREAM_STATS;
+        f.dcn5 = op.dtype == H3D_F16 && wdma && (r & H3D_TUNE_DCN_STREAM_F16_DCN5) && !f.no_slots && !(r & H3D_TUNE_DCN_STREAM_F16_KEEP_DCN3);
+    } else if (op.dtype == H3D_F16X3 && wdma) {
+        f.margin = (r & H3D_TUNE_DCN_STREAM_X3_MARGIN2) ? 2 : (r & H3D_TUNE_DCN_STREAM_X3_MARGIN3) ? 3 : (r & H3D_TUNE_DCN_STREAM_X3_MARGIN4) ? 4 : 0;
+    } else if (op.dtype == H3D_F16X3) {
+        f.margin = (r & H3D_TUNE_DCN_FUSED_X3_MARGIN2) ? 2 : (r & H3D_TUNE_DCN_FUSED_X3_MARGIN4) ? 4 : (r & H3D_TUNE_DCN_FUSED_X3_MARGIN6) ? 6 : 0;
+        f.raw_pack = r & H3D_OPF_DCN_FUSED_RAW_PACK;
+        f.scaled_input = r & H3D_OPF_DCN_FUSED_SCALED_INPUT;
+    }
+    return f;
+}
+
 // 2-byte plans (bf16_t: the apron is converted to fp16 while it is staged; f16_t: it is fp16 already)
 template <typename T, bool F16IN = false>
-static int launch_dcn3_lowp(const h3d_op &op, const Dcn3Args &a, bool wdma, hipStream_t st)
+static int launch_dcn3_lowp(const h3d_op &op, const Dcn3Flags &f, const Dcn3Args &a, bool wdma, hipStream_t st)
 {
     if constexpr (F16IN) {
-        if (!wdma || (op.reserved & 0x1000) || op.Cin % 32 || op.Cout <= 32)
-            H3D_FAIL(H3D_ERR_UNSUPPORTED, "dcn_fused_stream: the fp16-input option (reserved & 0x40000) exists for the patch-slot variants with > 32 output channels");
+        if (!wdma || f.no_slots || op.Cin % 32 || op.Cout <= 32)
+            H3D_FAIL(H3D_ERR_UNSUPPORTED, "dcn_fused_stream: the fp16-input option (H3D_OPF_DCN_STREAM_F16_INPUT) exists for the patch-slot variants with > 32 output channels");
     }
     if (wdma) {
-        if ((op.reserved & 0x1000) || op.Cin % 32) {     // tuning override: round 1's configurations (no patches: every sample that
+        if (f.no_slots || op.Cin % 32) {                 // H3D_OPF_DCN_STREAM_NO_SLOTS: round 1's configurations (no patches: every sample that
                                                          // leaves the apron goes through pass 2); also Cin = 16 (mod 32): the
                                                          // patch variants' pipeline is unrolled by two stages
             if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 1, true>(a, st);
             if (op.Cout <= 64) return launch_dcn3_cfg<T, 2, 16, 1, true>(a, st);
             return launch_dcn3_cfg<T, 4, 16, 2, true>(a, st);
         }
-        const long wgs4w = (long)op.B * cdiv(op.H, 16) * cdiv(op.W, 16) * cdiv(op.Cout, 128);
-        if (op.reserved & 0x8000) {
+        // > 64 output channels: a layer whose 128-channel workgroups would leave CUs idle (16 x 16 maps at batch 64: 128 workgroups
+        // on 256 CUs) runs 64-channel workgroups instead: twice the gather / blend work, on CUs that had nothing to do
+        const bool mt2 = op.Cout <= 64 || f.narrow_wg;
+        if (f.wide_margin) {
             // wide margin on the packed apron (engine.dcn_wide_margin / DLAEngine.calibrate_dcn_margins: layers whose offsets send
             // many samples outside a margin-2 apron): margin 4 at two workgroups per CU (73 KB).  The 128-channel variant has
             // margin 4 anyway (a margin-6 packed apron needs a fourth staging register set: 14 spilled registers)
-            if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 4, true, 256, true>(a, st);
-            if (op.Cout <= 64 || ((wgs4w < 192 || (op.reserved & 0x200)) && !(op.reserved & 0x400))) return launch_dcn3_cfg<T, 2, 16, 4, true, 256, true, F16IN>(a, st);
-            return launch_dcn3_cfg<T, 4, 16, 4, true, 256, false, F16IN>(a, st);
+            if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 4, true, 256, true>(a, st, f.stats);
+            if (mt2) return launch_dcn3_cfg<T, 2, 16, 4, true, 256, true, F16IN>(a, st, f.stats);
+            return launch_dcn3_cfg<T, 4, 16, 4, true, 256, false, F16IN>(a, st, f.stats);
         }
         // <= 64 output channels: margin-2 apron, 16-channel stages, <= 128 VGPRs and 78 KB of LDS -> two workgroups
         // (16 waves) per CU, one computing while the other waits at its stage barriers; 256 patch slots per tile.
         // > 64: one workgroup per CU has the LDS for a margin-4 apron (26 x 26 pixels)
-        const long wgs4 = (long)op.B * cdiv(op.H, 16) * cdiv(op.W, 16) * cdiv(op.Cout, 128);
-        if (op.reserved & 0x10000) {
+        if (f.slots512) {
             // experiment / candidate default: margin 2 on the PACKED apron (15 KB instead of 28) with 512 patch slots per tile, the second
             // 256 filled in a second round per stage
-            if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 2, true, 512, true>(a, st);
-            if (op.Cout <= 64 || ((wgs4 < 192 || (op.reserved & 0x200)) && !(op.reserved & 0x400))) return launch_dcn3_cfg<T, 2, 16, 2, true, 512, true, F16IN>(a, st);
-            return launch_dcn3_cfg<T, 4, 16, 4, true, 512, false, F16IN>(a, st);
+            if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 2, true, 512, true>(a, st, f.stats);
+            if (mt2) return launch_dcn3_cfg<T, 2, 16, 2, true, 512, true, F16IN>(a, st, f.stats);
+            return launch_dcn3_cfg<T, 4, 16, 4, true, 512, false, F16IN>(a, st, f.stats);
         }
-        if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 2, true, 256>(a, st);
-        if (op.Cout <= 64) return launch_dcn3_cfg<T, 2, 16, 2, true, 256, false, F16IN>(a, st);
-        // a layer whose 128-channel workgroups would leave CUs idle (16 x 16 maps at batch 64: 128 workgroups on 256 CUs)
-        // runs 64-channel workgroups instead: twice the gather / blend work, on CUs that had nothing to do
-        if ((wgs4 < 192 || (op.reserved & 0x200)) && !(op.reserved & 0x400)) return launch_dcn3_cfg<T, 2, 16, 2, true, 256, false, F16IN>(a, st);
-        return launch_dcn3_cfg<T, 4, 16, 4, true, 256, false, F16IN>(a, st);
+        if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 2, true, 256>(a, st, f.stats);
+        if (mt2) return launch_dcn3_cfg<T, 2, 16, 2, true, 256, false, F16IN>(a, st, f.stats);
+        return launch_dcn3_cfg<T, 4, 16, 4, true, 256, false, F16IN>(a, st, f.stats);
     }
     if (op.Cin % 32 == 0 && op.Cout <= 64) {
         if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 32, 2>(a, st);
@@ -1120,10 +1153,8 @@ static int launch_dcn3_lowp(const h3d_op &op, const Dcn3Args &a, bool wdma, hipS
     }
     if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 2>(a, st);
     if (op.Cout <= 64) return launch_dcn3_cfg<T, 2, 16, 2>(a, st);
-    // a layer whose 128-channel workgroups would leave CUs idle (16x16 maps at batch 64: 128 workgroups) runs
-    // 64-channel workgroups instead: twice the gather / blend work, but on CUs that had nothing to do
-    const long wgs4 = (long)op.B * cdiv(op.H, 16) * cdiv(op.W, 16) * cdiv(op.Cout, 128);
-    if ((wgs4 < 192 || (op.reserved & 0x200)) && !(op.reserved & 0x400)) {
+    // (the small-grid rule as above)
+    if (f.narrow_wg) {
         if (op.Cin % 32 == 0) return launch_dcn3_cfg<T, 2, 32, 2>(a, st);
         return launch_dcn3_cfg<T, 2, 16, 2>(a, st);
     }
@@ -1153,7 +1184,7 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
     a.out = (char *)op.out; a.B = op.B; a.H = op.H; a.W = op.W; a.Cin = op.Cin; a.in_cs = op.in_cs;
     a.Cout = op.Cout; a.out_cs = op.out_cs; a.relu = op.relu; a.out_mode = op.out_mode; a.wrows = op.wrows;
     a.tiles_x = a.tiles_y = 0;
-    a.dbg = op.reserved;
+    a.dbg = op.reserved & H3D_TUNE_DCN_STREAM_ABLATE_MASK;
     a.G = op.wrows / 32;
     if (op.wexp < -60 || op.wexp > 60 || op.wexp2 < -60 || op.wexp2 > 60 || ((op.wexp || op.wexp2) && op.dtype != H3D_F16X3))
         H3D_FAIL(H3D_ERR_ARG, "dcn_fused: wexp %d / %d (H3D_F16X3 filter exponents)", op.wexp, op.wexp2);
@@ -1162,20 +1193,21 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
     a.wmax = nullptr;
     a.xscaled = 0;
     if (wdma && (size_t)op.H * op.W * op.in_cs * es >= 0x7ffffff0ull) H3D_FAIL(H3D_ERR_SHAPE, "dcn_fused_stream: image of 2 GiB or more");
-    if (op.dtype == H3D_BF16 && (op.reserved & 0x40000)) return launch_dcn3_lowp<bf16_t, true>(op, a, wdma, st);
-    if (op.dtype == H3D_BF16) return launch_dcn3_lowp<bf16_t>(op, a, wdma, st);
+    const Dcn3Flags f = dcn3_decode(op, wdma);
+    if (op.dtype == H3D_BF16 && f.f16_input) return launch_dcn3_lowp<bf16_t, true>(op, f, a, wdma, st);
+    if (op.dtype == H3D_BF16) return launch_dcn3_lowp<bf16_t>(op, f, a, wdma, st);
     // fp16 plans: the apron needs no conversion while it is staged.  csrc/dcn5.hip also moves it by LDS-DMA (double buffered, one
     // barrier per phase-A stage): measured 5.7 % SLOWER on the ten <= 64-channel launches of the batch-64 plan (1.519 vs 1.437 ms,
     // tools/ab_dcn5.py: an LDS-DMA piece costs its wave more issue cycles than two global loads + two ds_write_b128, and the
-    // kernel is bound by LDS reads and vector issue, not by the staging), so it runs only on request (tuning override 0x4000)
-    if (op.dtype == H3D_F16 && wdma && (op.reserved & 0x4000) && !(op.reserved & 0x3000)) {
+    // kernel is bound by LDS reads and vector issue, not by the staging), so it runs only on request (H3D_TUNE_DCN_STREAM_F16_DCN5)
+    if (f.dcn5) {
 #ifdef H3D_EXTRA
         return h3d_launch_dcn5(op, st);
 #else
-        H3D_FAIL(H3D_ERR_UNSUPPORTED, "dcn_fused_stream: the LDS-DMA apron variant (csrc/dcn5.hip, reserved & 0x4000) is built only by `make EXTRA=1`");
+        H3D_FAIL(H3D_ERR_UNSUPPORTED, "dcn_fused_stream: the LDS-DMA apron variant (csrc/dcn5.hip, H3D_TUNE_DCN_STREAM_F16_DCN5) is built only by `make EXTRA=1`");
 #endif
     }
-    if (op.dtype == H3D_F16) return launch_dcn3_lowp<f16_t>(op, a, wdma, st);
+    if (op.dtype == H3D_F16) return launch_dcn3_lowp<f16_t>(op, f, a, wdma, st);
     if (op.dtype == H3D_F32) {
         if (op.Cout <= 32) return launch_dcn3_cfg<float, 1, 16, 2>(a, st);
         return launch_dcn3_cfg<float, 2, 16, 2>(a, st);
@@ -1189,15 +1221,16 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
         // The in-kernel stamps of the margin-3 tiles (make ABLATE=1, tools/stamp_dcn.py --f16x3) showed pass 2 -- the tiles with more far
         // samples than patch slots -- at 21 % of the 256 -> 256 layer and 12 % of a 128 -> 128 one: the `node` DeformConvs (Cin == Cout: their
         // input is the up-sampled sum) have the largest offsets.  Margin 4 (26 x 26 apron, 160 KB) for them, margin 2 for the rest
-        // (tools/ab_op_reserved.py --kind 12 --codes 0x4000 0x8000 0x10000, batch 64, same process, margin 2 / 3 / 4: 256 -> 256 @32x32
+        // (tools/ab_op_reserved.py --kind 12 --codes X3_MARGIN2 X3_MARGIN3 X3_MARGIN4, batch 64, same process, margin 2 / 3 / 4: 256 -> 256 @32x32
         // 0.791 / 0.757 / 0.541 ms, 128 -> 128 @64x64 1.343 / 1.222 / 1.112 for the two launches, 64 -> 64 @128x128 2.849 / 3.001 / 3.178 for
         // the five (margin 3 was ahead there before phase B interleaved its vector work with the MFMAs), 256 -> 128 0.446 / 0.451 / 0.472,
-        // 512 -> 256 @16x16 0.186 / 0.199 / 0.215).  0x4000 / 0x8000 / 0x10000 force margin 2 / 3 / 4.
-        if (((op.Cin == op.Cout && op.Cout > 64) || (op.reserved & 0x10000)) && !(op.reserved & 0xc000)) {
+        // 512 -> 256 @16x16 0.186 / 0.199 / 0.215).  H3D_TUNE_DCN_STREAM_X3_MARGIN2 / 3 / 4 force a margin.
+        const int margin = f.margin ? f.margin : (op.Cin == op.Cout && op.Cout > 64) ? 4 : 2;
+        if (margin == 4) {
             if (op.Cout <= 32) return launch_dcn3_cfg<x3_t, 1, 16, 4, true, 256>(a, st);
             return launch_dcn3_cfg<x3_t, 2, 16, 4, true, 256>(a, st);
         }
-        if ((op.reserved & 0x8000) && !(op.reserved & 0x4000)) {
+        if (margin == 3) {
             if (op.Cout <= 32) return launch_dcn3_cfg<x3_t, 1, 16, 3, true, 256>(a, st);
             return launch_dcn3_cfg<x3_t, 2, 16, 3, true, 256>(a, st);
         }
@@ -1205,21 +1238,22 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
         return launch_dcn3_cfg<x3_t, 2, 16, 2, true, 256>(a, st);
     }
     if (op.dtype == H3D_F16X3) {            // the f32 plan's tiles (fp32 apron, register-staged pre-split filters) on 3 fp16 MFMAs per step
-        // 0x100000 (the stand-alone `DCN` module, h3d_amd/dcn_v2.py): plain fp32 filter packs of h3d_dcn_fused_pack_f32_cached, the two filter
-        // maxima behind the biases (bias[wrows + 32 ...]); the kernel scales and splits the filters while it stages them
-        if (op.reserved & 0x100000) {
+        // H3D_OPF_DCN_FUSED_RAW_PACK (the stand-alone `DCN` module, h3d_amd/dcn_v2.py): plain fp32 filter packs of h3d_dcn_fused_pack_f32_cached, the two filter
+        // maxima behind the biases (bias[wrows + H3D_DCN_FUSED_BIAS_WMAX ...]); the kernel scales and splits the filters while it stages them
+        if (f.raw_pack) {
             if (op.wexp || op.wexp2) H3D_FAIL(H3D_ERR_ARG, "dcn_fused (f16x3, raw filters): wexp must be 0 (the scale comes from the pack's maxima)");
-            a.wmax = (const unsigned *)(op.bias + op.wrows + 32);
-            a.xscaled = (op.reserved >> 21) & 1;
+            a.wmax = (const unsigned *)(op.bias + op.wrows + H3D_DCN_FUSED_BIAS_WMAX);
+            a.xscaled = f.scaled_input;
         }
-        if (op.reserved & 0x2000) {         // tuning override (tools/ab_flag.py): the f32 plan's margin-2 double-buffered tile
+        const int margin = f.margin ? f.margin : (op.Cout <= 64 && op.H >= 64) ? 6 : 4;
+        if (margin == 2) {                  // H3D_TUNE_DCN_FUSED_X3_MARGIN2 (tools/ab_flag.py): the f32 plan's margin-2 double-buffered tile
             if (op.Cout <= 32) return launch_dcn3_cfg<x3_t, 1, 16, 2>(a, st);
             return launch_dcn3_cfg<x3_t, 2, 16, 2>(a, st);
         }
         // margin 6 (30 x 30 apron, 115 KB with its filters) on the large maps with <= 64 output channels (tools/ab_op_reserved.py, batch
         // 64, same process, margin 4 / 2 / 6: 64 -> 64 @128x128 4.79 / 4.60 / 4.32 ms for the five launches, 128 -> 64 @64x64 1.58 / 1.76 /
-        // 1.49; the 128- and 256-channel layers 3.73 / 3.88 / 3.79: they stay on margin 4); 0x4000 / 0x8000: force margin 6 / margin 4
-        if (((op.Cout <= 64 && op.H >= 64) || (op.reserved & 0x4000)) && !(op.reserved & 0x8000)) {
+        // 1.49; the 128- and 256-channel layers 3.73 / 3.88 / 3.79: they stay on margin 4); H3D_TUNE_DCN_FUSED_X3_MARGIN6 / _MARGIN4 force either
+        if (margin == 6) {
             if (op.Cout <= 32) return launch_dcn3_cfg<x3_t, 1, 16, 6>(a, st);
             return launch_dcn3_cfg<x3_t, 2, 16, 6>(a, st);
         }
@@ -1233,10 +1267,10 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
 extern "C" int h3d_dcn_far_samples(const h3d_op *op_in, int32_t *per_tile, void *stream)
 {
     if (!op_in || !per_tile) H3D_FAIL(H3D_ERR_ARG, "dcn_far_samples: null pointer");
-    if (op_in->kind != H3D_OP_DCN_FUSED_STREAM || (op_in->dtype != H3D_BF16 && op_in->dtype != H3D_F16) || op_in->Cin % 32 || (op_in->reserved & 0x1000))
+    if (op_in->kind != H3D_OP_DCN_FUSED_STREAM || (op_in->dtype != H3D_BF16 && op_in->dtype != H3D_F16) || op_in->Cin % 32 || (op_in->reserved & H3D_OPF_DCN_STREAM_NO_SLOTS))
         H3D_FAIL(H3D_ERR_UNSUPPORTED, "dcn_far_samples: a 2-byte H3D_OP_DCN_FUSED_STREAM op of a patch-slot variant (Cin %% 32 == 0)");
     h3d_op op = *op_in;
-    op.reserved = (op.reserved & 0x58600) | 0x20000;      // variant bits (margin / slots / workgroup width) + the statistics switch
+    op.reserved = (op.reserved & H3D_OPF_DCN_STREAM_VARIANT_MASK) | H3D_OPF_DCN_STREAM_STATS;      // variant bits (margin / slots / fp16 input / workgroup width) + the statistics switch
     op.out = per_tile;
     op.out_mode = H3D_OUT_NHWC;
     return h3d_launch_dcn3(op, (hipStream_t)stream);

@@ -578,9 +578,9 @@ int h3d_launch_dcn4(const h3d_op &op, hipStream_t st)
     a.in = (const char *)op.in; a.wimg = (const char *)op.w; a.woff = (const char *)op.in2; a.bias = op.bias;
     a.out = (char *)op.out; a.B = op.B; a.H = op.H; a.W = op.W; a.in_cs = op.in_cs;
     a.Cout = op.Cout; a.out_cs = op.out_cs; a.relu = op.relu; a.out_mode = op.out_mode; a.wrows = op.wrows;
-    a.G = op.wrows / 32; a.tiles_x = a.tiles_y = 0; a.dbg = op.reserved & 0xff;
+    a.G = op.wrows / 32; a.tiles_x = a.tiles_y = 0; a.dbg = op.reserved & H3D_TUNE_DCN_F16_ABLATE_MASK;
     a.xlo = a.skip = nullptr; a.wup = nullptr; a.f = a.Hl = a.Wl = a.xlo_cs = a.skip_cs = 0;
-    const bool dense = !(op.reserved & 0x100);    // tuning override (tools/ab_conv.py): 0x100 = one workgroup per CU
+    const bool dense = !(op.reserved & H3D_TUNE_DCN_F16_ONE_WG_PER_CU);    // tuning override (tools/ab_conv.py): one workgroup per CU
     if (op.Cout <= 32) return dense ? launch_dcn4_cfg<1, 1>(a, st) : launch_dcn4_cfg<1, 0>(a, st);
     return dense ? launch_dcn4_cfg<2, 1>(a, st) : launch_dcn4_cfg<2, 0>(a, st);
 }
@@ -608,7 +608,7 @@ int h3d_launch_updcn(const h3d_op &op, hipStream_t st)
     a.in = nullptr; a.wimg = (const char *)op.w; a.woff = (const char *)d->w_off; a.bias = op.bias;
     a.out = (char *)op.out; a.B = op.B; a.H = op.Ho; a.W = op.Wo; a.in_cs = 64;
     a.Cout = op.Cout; a.out_cs = op.out_cs; a.relu = op.relu; a.out_mode = op.out_mode; a.wrows = op.wrows;
-    a.G = op.wrows / 32; a.tiles_x = a.tiles_y = 0; a.dbg = op.reserved & 0xff;
+    a.G = op.wrows / 32; a.tiles_x = a.tiles_y = 0; a.dbg = op.reserved & H3D_TUNE_DCN_F16_ABLATE_MASK;
     a.xlo = (const char *)op.in; a.skip = (const char *)d->skip; a.wup = d->w_up;
     a.f = f; a.Hl = op.H; a.Wl = op.W; a.xlo_cs = op.in_cs; a.skip_cs = d->skip_cs;
     if (op.Cout <= 32) return launch_dcn4_cfg<1, 1, 1>(a, st);

@@ -94,7 +94,7 @@ __device__ __forceinline__ u32x4 dcn5_corner(const char *img, int bytes, int vof
     return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
 }
 
-// XP: experiment bits (h3d_op.reserved >> 16; tools/ab_dcn5.py).  1: next stage's DMA issued after the second barrier; 2 / 4 / 8
+// XP: experiment bits (H3D_TUNE_DCN_STREAM_DCN5_XP in h3d_op.reserved; tools/ab_dcn5.py).  1: next stage's DMA issued after the second barrier; 2 / 4 / 8
 // (timing only, wrong results): no patch pixels / no apron DMA after stage 0 / no filter DMA after stage 0; 16: tap-ahead gathers
 template <int MT, int MARGIN, int EPI, int NP, int XP = 0>      // EPI: 0 general, 1 lean NHWC, 2 LDS-transposed
 __global__ __launch_bounds__(512, MT <= 2 ? 4 : 2) void dcn5_kernel(Dcn5Args a)
@@ -542,9 +542,9 @@ int h3d_launch_dcn5(const h3d_op &op, hipStream_t st)
     a.out = (char *)op.out; a.B = op.B; a.H = op.H; a.W = op.W; a.Cin = op.Cin; a.in_cs = op.in_cs;
     a.Cout = op.Cout; a.out_cs = op.out_cs; a.relu = op.relu; a.out_mode = op.out_mode; a.wrows = op.wrows;
     a.tiles_x = a.tiles_y = 0;
-    a.dbg = op.reserved;
+    a.dbg = 0;      // (the kernel has no ablation switches: its experiments are the XP template parameter)
     a.G = op.wrows / 32;
-    const int xp = (op.reserved >> 16) & 0xff;
+    const int xp = H3D_TUNE_DCN_STREAM_DCN5_XP_OF(op.reserved);
     if (xp && op.Cout > 32 && op.Cout <= 64) {
         switch (xp) {
         case 1: return launch_dcn5_cfg<2, 2, 256, 1>(a, st);
@@ -561,7 +561,6 @@ int h3d_launch_dcn5(const h3d_op &op, hipStream_t st)
     if (op.Cout <= 32) return launch_dcn5_cfg<1, 2, 256>(a, st);
     if (op.Cout <= 64) return launch_dcn5_cfg<2, 2, 256>(a, st);
     // a layer whose 128-channel workgroups would leave CUs idle runs 64-channel workgroups instead (as csrc/dcn3.hip)
-    const long wgs4 = (long)op.B * cdiv(op.H, 16) * cdiv(op.W, 16) * cdiv(op.Cout, 128);
-    if ((wgs4 < 192 || (op.reserved & 0x200)) && !(op.reserved & 0x400)) return launch_dcn5_cfg<2, 2, 256>(a, st);
+    if (h3d_dcn_narrow_wg(op)) return launch_dcn5_cfg<2, 2, 256>(a, st);
     return launch_dcn5_cfg<4, 4, 256>(a, st);
 }

@@ -265,7 +265,7 @@ template <> struct SE<x3_t> : SE<float> {
     static __device__ __forceinline__ void mma(f32x16 &acc, const wfrag &a, const bfrag &b) { ET<x3_t>::mma(acc, a, b); }
 };
 
-// The fp32 operator's ACTIVATION scale on the fp16 matrix cores (H3D_F16X3 behind 0x200000, csrc/dcn2.hip / dcn3.hip): the power of two
+// The fp32 operator's ACTIVATION scale on the fp16 matrix cores (H3D_F16X3 behind H3D_OPF_DCN_ACT_MAXIMA / H3D_OPF_DCN_FUSED_SCALED_INPUT, csrc/dcn2.hip / dcn3.hip): the power of two
 // 2^e that puts max |x| * max(1, max |mask|) -- both maxima over FINITE elements only, left on the device by csrc/dcn.hip as float bit
 // patterns -- below 2^14, so that a blended sample (a convex combination of x times the mask) stays far inside fp16's range and the
 // lo terms of its split stay normal fp16 numbers down to 2^-17 of max |x|.  0 when nothing finite is nonzero; e <= 100 - log2 max(1,
@@ -281,3 +281,12 @@ __device__ __forceinline__ int dcn_act_exp(unsigned xmax_bits, unsigned mmax_bit
 }
 
 __device__ __forceinline__ float dcn2_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }   // v_exp + v_rcp (1 ulp each)
+
+// Host side, the fused DeformConv launchers' small-grid rule (csrc/dcn3.hip, csrc/dcn5.hip): a layer with more than 64 output channels whose
+// 128-channel workgroups would leave CUs idle (16 x 16 maps at batch 64: 128 workgroups on 256 CUs) runs 64-channel workgroups instead:
+// twice the gather / blend work, on CUs that had nothing to do.  H3D_TUNE_DCN_STREAM_FORCE_NARROW_WG / _FORCE_WIDE_WG override the count.
+static inline bool h3d_dcn_narrow_wg(const h3d_op &op)
+{
+    const long wgs4 = (long)op.B * cdiv(op.H, 16) * cdiv(op.W, 16) * cdiv(op.Cout, 128);
+    return (wgs4 < 192 || (op.reserved & H3D_TUNE_DCN_STREAM_FORCE_NARROW_WG)) && !(op.reserved & H3D_TUNE_DCN_STREAM_FORCE_WIDE_WG);
+}

@@ -206,14 +206,14 @@ bool h3d_gemm1_takes(const h3d_op &op)
 {
     if ((op.dtype != H3D_BF16 && op.dtype != H3D_F16) || op.ksize != 1 || (op.stride != 1 && op.stride != 2) || op.out_mode != H3D_OUT_NHWC) return false;
     if (op.stride == 2 && (long long)op.B * op.H * op.W * op.in_cs * 2 >= 0x7ffffff0ll) return false;   // absolute 32-bit offsets
-    if (op.reserved & 0x3000) return false;                  // tuning overrides 0x1000 (tile shape), 0x2000: the halo-tile kernel of csrc/conv.hip
+    if (op.reserved & (H3D_TUNE_CONV_TILE | H3D_TUNE_CONV_HALO_TILE)) return false;   // tuning overrides: the halo-tile kernel of csrc/conv.hip (with / without a tile shape)
     const long long N = (long long)op.B * op.Ho * op.Wo;
     if (op.Cin % 64 || op.Cin < 128 || op.in_cs % 8 || op.Cout % 8 || op.out_cs % 8 || (N & 15)) return false;
     if (((uintptr_t)op.in & 15) || ((uintptr_t)op.out & 15) || ((uintptr_t)op.bias & 15) || ((uintptr_t)op.w & 15)) return false;
     if (op.in2 && (op.in2_cs % 8 || ((uintptr_t)op.in2 & 15) || N * op.in2_cs * 2 >= 0x7ffffff0ll)) return false;
     if ((long long)op.wrows * op.Cin * 2 >= 0x7ffffff0ll || (N >> 4) > 0x7fffffff || 256ll * op.in_cs * 2 >= 0x7ffffff0ll) return false;
     if (cdiv(op.Cout, 128) * 128 > op.wrows) return false;   // (h3d_launch_conv has checked this already)
-    if (op.reserved & 0x4000) return true;                   // tuning override: this kernel whatever the shape
+    if (op.reserved & H3D_TUNE_CONV_FORCE_GEMM) return true;                   // tuning override: this kernel whatever the shape
     // <= 64 output channels (DLA-34's level-2 root, ResNet's 256 -> 64): the layer streams its input once, the halo-tile
     // kernel's 4-wave tiles do that as fast or faster (tools/ab_gemm1.py: 0.075 vs 0.077-0.093 ms, 0.147 vs 0.149-0.163)
     if (op.Cout <= 64) return false;
@@ -231,12 +231,12 @@ int h3d_launch_gemm1(const h3d_op &op, hipStream_t st)
     // a tile's epilogue reads the bias of ALL its channel rows unguarded, and its filter rows must exist or lie past the end
     // of the bank: a channel block of BM rows needs cdiv(Cout, BM) * BM packed rows (128 is guaranteed, see above)
     const bool ok256 = cdiv(op.Cout, 256) * 256 <= op.wrows;
-    switch (op.reserved & 0xf00) {                           // tuning override (tests, tools/ab_gemm1.py)
-    case 0x100:
+    switch (op.reserved & H3D_TUNE_CONV_GEMM_TILE_MASK) {                           // tuning override (tests, tools/ab_gemm1.py)
+    case H3D_TUNE_CONV_GEMM_TILE(1):
         if (!ok256) H3D_FAIL(H3D_ERR_SHAPE, "conv 1x1 (gemm): the 256-channel tile needs %d packed rows, got %d", cdiv(op.Cout, 256) * 256, op.wrows);
         return launch_gemm1_cfg<4, 2, 2, 4, 2>(a, st);
-    case 0x200: return launch_gemm1_cfg<2, 2, 2, 4, 3>(a, st);
-    case 0x300: return launch_gemm1_cfg<2, 2, 2, 2, 2, 2>(a, st);
+    case H3D_TUNE_CONV_GEMM_TILE(2): return launch_gemm1_cfg<2, 2, 2, 4, 3>(a, st);
+    case H3D_TUNE_CONV_GEMM_TILE(3): return launch_gemm1_cfg<2, 2, 2, 2, 2, 2>(a, st);
     default: break;
     }
     // 256 x 256 (8 waves of 128 x 64, one workgroup per CU) when its grid fills the chip's 256 CUs in whole rounds;

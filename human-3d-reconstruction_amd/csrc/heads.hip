@@ -43,7 +43,7 @@ struct HeadsArgs {
     int nheads, head_conv;
     int B, H, W, in_cs;
     int tiles_x, tiles_y;
-    int dbg;   // profiling ablation (h3d_op.reserved): 1 = skip the weight loads after the prologue
+    int dbg;   // profiling ablation (h3d_op.reserved & H3D_TUNE_HEADS_ABLATE_MASK): 1 = skip the weight loads after the prologue
     int xcd;   // h3d_tile_id mode
     float s1;                // f16x3 plans: 2^-wexp of the 3x3 filters AND of b1 (h3d_heads_desc.wexp); 1 otherwise
     float s2[HEADS_MAX];     // ... 2^-wexp2 of a head's 1x1 filters
@@ -574,7 +574,7 @@ int h3d_launch_heads(const h3d_op &op, hipStream_t st)
     if (d->nheads <= 0 || d->nheads > HEADS_MAX) H3D_FAIL(H3D_ERR_SHAPE, "heads: %d heads (max %d)", d->nheads, HEADS_MAX);
     HeadsArgs a;
     a.in = (const char *)op.in; a.w1 = (const char *)op.w; a.b1 = op.bias;
-    a.dbg = op.reserved & 0xff;
+    a.dbg = op.reserved & H3D_TUNE_HEADS_ABLATE_MASK;
     a.xcd = h3d_xcd_mode();
 #ifdef H3D_ABLATE
     a.stamps = h3d_stamp_buffer();
@@ -603,7 +603,7 @@ int h3d_launch_heads(const h3d_op &op, hipStream_t st)
     const int th = es == 2 ? 16 : 8;
     a.tiles_x = cdiv(op.W, 32); a.tiles_y = cdiv(op.H, th);
     const dim3 grid(op.B * a.tiles_x * a.tiles_y), blk(512);
-    const bool biasc = !(op.reserved & 0x200);    // tuning override (tools/ab_heads.py): 0x200 = separate bias / zeroing pass
+    const bool biasc = !(op.reserved & H3D_TUNE_HEADS_SEPARATE_BIAS);    // tuning override (tools/ab_heads.py): separate bias / zeroing pass
     if (h3d_note_kernel(mixed ? "heads_kernel<%s, %d, %d, %s, true>" : "heads_kernel<%s, %d, %d, %s>",
                         op.dtype == H3D_BF16 ? "unsigned short" : op.dtype == H3D_F16 ? "f16_t" : op.dtype == H3D_F16X3 ? "x3_t" : "float", th, m2, biasc ? "true" : "false"))
         return H3D_OK;

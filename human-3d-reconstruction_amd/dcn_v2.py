@@ -275,14 +275,14 @@ class DCN(DCNv2):
                     _lib.check(L.h3d_nchw_f32_to_nhwc(_lib.ptr(x), _lib.ptr(xn), _lib.H3D_F32, B, C, H, W, C, _lib.stream_ptr()), "DCN: to NHWC")
                 else:
                     # the relayout scales x by the power of two the device derives from max |x| (into the word behind the filter maxima)
-                    _lib.check(L.h3d_dcn_nchw_to_nhwc_scaled(_lib.ptr(x), _lib.ptr(xn), B, C, H, W, bias.data_ptr() + 4 * (rows + 34),
+                    _lib.check(L.h3d_dcn_nchw_to_nhwc_scaled(_lib.ptr(x), _lib.ptr(xn), B, C, H, W, bias.data_ptr() + 4 * (rows + _lib.DCN_FUSED_BIAS_AMAX),
                                                              _lib.stream_ptr()), "DCN: to NHWC")
                 op = H3dOp()
                 # fp32 tensors, fp32 packs; since round 5 every product as three fp16 MFMAs on split operands (filters scaled and split while
-                # they are staged: reserved 0x100000; activations scaled in the relayout: 0x200000), or exact fmaf chains on the fp32 matrix
+                # they are staged: OPF_DCN_FUSED_RAW_PACK; activations scaled in the relayout: OPF_DCN_FUSED_SCALED_INPUT), or exact fmaf chains on the fp32 matrix
                 # instruction with OP_F32_MFMA
                 op.kind, op.dtype, op.B, op.H, op.W, op.Ho, op.Wo = _lib.OP_DCN_FUSED, (_lib.H3D_F32 if OP_F32_MFMA else _lib.H3D_F16X3), B, H, W, H, W
-                op.reserved = 0 if OP_F32_MFMA else 0x300000
+                op.reserved = 0 if OP_F32_MFMA else _lib.OPF_DCN_FUSED_RAW_PACK | _lib.OPF_DCN_FUSED_SCALED_INPUT
                 op.in_, op.in2, op.w, op.bias, op.out = xn.data_ptr(), wo.data_ptr(), wp.data_ptr(), bias.data_ptr(), out.data_ptr()
                 op.Cin, op.in_cs, op.Cout, op.out_cs, op.ksize, op.stride, op.relu = C, C, self.out_channels, self.out_channels, 3, 1, 0
                 op.out_mode, op.wrows = _lib.OUT_NCHW_F32, rows

@@ -26,7 +26,7 @@ from ._lib import H3dOp
 
 _TORCH_DT = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32, "f16x3": torch.float32}
 _H3D_DT = {"bf16": _lib.H3D_BF16, "f16": _lib.H3D_F16, "f32": _lib.H3D_F32, "f16x3": _lib.H3D_F16X3}
-DCN_F16IN = 0x40000         # h3d_op.reserved of a fused DeformConv in a bf16 plan: its input tensor holds fp16 values (csrc/dcn3.hip F16IN)
+DCN_F16IN = _lib.OPF_DCN_STREAM_F16_INPUT         # h3d_op.reserved of a fused DeformConv in a bf16 plan: its input tensor holds fp16 values (csrc/dcn3.hip F16IN)
 LOWP = ("bf16", "f16")      # the 2-byte plans: same kernels, lowering and tile choices; "f16" = BASELINE configs[4]'s arithmetic
 
 
@@ -121,7 +121,7 @@ class PackedWeights:
 
     @property
     def dcn_wide(self):
-        return {p for p, v in self.dcn_variant.items() if v == 0x8000}
+        return {p for p, v in self.dcn_variant.items() if v == _lib.OPF_DCN_STREAM_WIDE_MARGIN}
 
     def _fold(self, w, b, bn):
         """conv(+bias) followed by eval BatchNorm `bn` -> (w', b')."""
@@ -547,7 +547,7 @@ class Plan:
         tune = 0
         if (k == 1 and stride == 1 and self.conv1x1_th16_min_cin and cin >= self.conv1x1_th16_min_cin and cin % 64 == 0
                 and cout > 32 and self.pw.dtype in LOWP):
-            tune = 0x1000 | ((4 if cout > 64 else 2) << 4) | 2       # csrc/conv.hip tuning override: MT, TH = 16
+            tune = _lib.TUNE_CONV_1X1_TILE(4 if cout > 64 else 2, 16)       # csrc/conv.hip tuning override: MT, TH = 16
         self._op(_lib.OP_CONV, in_=x.ptr, in2=res.ptr if res is not None else None, w=wp.data_ptr(),
                  bias=bp.data_ptr(), out=optr, H=x.H, W=x.W, Cin=cin, in_cs=x.cs,
                  in2_cs=res.cs if res is not None else 0, Ho=Ho, Wo=Wo, Cout=cout, out_cs=ocs, ksize=k,
@@ -675,11 +675,11 @@ class Plan:
                 out = self._alloc(x.H, x.W, cout)
             var = 0
             if self.dcn_patches and cin % 32 == 0:
-                var = 0x8000 if self.dcn_wide_margin else 0x10000 if self.dcn_slots512 else self.pw.dcn_variant.get(p, 0)
+                var = _lib.OPF_DCN_STREAM_WIDE_MARGIN if self.dcn_wide_margin else _lib.OPF_DCN_STREAM_SLOTS512 if self.dcn_slots512 else self.pw.dcn_variant.get(p, 0)
             self._op(_lib.OP_DCN_FUSED_STREAM, in_=x.ptr, in2=woimg.data_ptr(), w=wimg.data_ptr(), bias=bias.data_ptr(),
                      out=out.ptr, H=x.H, W=x.W, Cin=cin, in_cs=x.cs, Ho=x.H, Wo=x.W, Cout=cout, out_cs=out.cs, ksize=3,
                      stride=1, relu=1, out_mode=_lib.OUT_NHWC, wrows=rows,
-                     reserved=(var | (DCN_F16IN if in_f16 else 0)) if self.dcn_patches else 0x1000)
+                     reserved=(var | (DCN_F16IN if in_f16 else 0)) if self.dcn_patches else _lib.OPF_DCN_STREAM_NO_SLOTS)
             self.dcn_layers.append((p, len(self.ops) - 1))
             return out
         assert not in_f16, p
@@ -1021,7 +1021,7 @@ class DLAEngine:
             self._keepalive[slot] = images
             return full
 
-    DCN_VARIANTS = {"narrow": 0, "slots512": 0x10000, "wide": 0x8000}      # h3d_op.reserved bits read by csrc/dcn3.hip's launcher
+    DCN_VARIANTS = {"narrow": 0, "slots512": _lib.OPF_DCN_STREAM_SLOTS512, "wide": _lib.OPF_DCN_STREAM_WIDE_MARGIN}      # h3d_op.reserved bits read by csrc/dcn3.hip's launcher
 
     # Cost model of the three tile variants, in units of "one tile of the `narrow` variant that stays within its slots"
     # (fitted once from round 3's timing table; tools/fit_dcn_rule.py prints model vs stopwatch per layer):
@@ -1053,7 +1053,7 @@ class DLAEngine:
             plan = self.plan(B, H, W)
             for p, i in plan.dcn_layers:
                 src = plan.ops[i]
-                if src.Cin % 32 or src.reserved & 0x1000:
+                if src.Cin % 32 or src.reserved & _lib.OPF_DCN_STREAM_NO_SLOTS:
                     continue
                 tiles = B * (-(-src.H // 16)) * (-(-src.W // 16))
                 rec = {}
@@ -1140,7 +1140,7 @@ class DLAEngine:
             plan = self.plan(B, H, W)
             n = len(plan.ops)
             ms = (ctypes.c_float * n)()
-            layers = [(p, i) for p, i in plan.dcn_layers if plan.ops[i].Cin % 32 == 0 and not plan.ops[i].reserved & 0x1000]
+            layers = [(p, i) for p, i in plan.dcn_layers if plan.ops[i].Cin % 32 == 0 and not plan.ops[i].reserved & _lib.OPF_DCN_STREAM_NO_SLOTS]
             saved = [plan.op_array[i].reserved for _, i in layers]
             times = {p: {} for p, _ in layers}
             for name, bits in self.DCN_VARIANTS.items():

@@ -50,7 +50,7 @@ int h3d_abi_version(void);
                                   Still 4 with dcn_v2_backward: three new entry points, nothing existing changed (additive), so a library built
                                   before them still serves every older caller and tools/ab_lib.py can load it as a baseline */
 /* How this library was built: H3D_BUILD_EXTRA = `make EXTRA=1` (the superseded kernel generations kept as A/B references are in:
- * H3D_OP_DCN_V1, H3D_OP_DCN_FUSED_F16, H3D_OP_UPDCN_F16, the 0x4000 DeformConv variant, h3d_smpl_verts2 -- without it they return
+ * H3D_OP_DCN_V1, H3D_OP_DCN_FUSED_F16, H3D_OP_UPDCN_F16, the H3D_TUNE_DCN_STREAM_F16_DCN5 DeformConv variant, h3d_smpl_verts2 -- without it they return
  * H3D_ERR_UNSUPPORTED); H3D_BUILD_ABLATE = `make ABLATE=1` (profiling switches and in-kernel stamps compiled in). */
 #define H3D_BUILD_EXTRA 1
 #define H3D_BUILD_ABLATE 2
@@ -157,8 +157,8 @@ int h3d_dcn_v2_pack_weights_cached(const float *weight, const float *bias, int C
 /* The four parameters of the stand-alone `DCN` module (dcn_v2.py:97-116; conv_offset_mask has 27 output channels) in the fp32 layout
  * of H3D_OP_DCN_FUSED: wp [rows = Cout padded to 128][9][C], wo [128][9][C] (rows permuted as the op expects), bias_out
  * [rows | 32 | 64]: the biases, then (round 5) 64 floats of which the first two words are the bit patterns of max |weight| and
- * max |off_weight| -- what an H3D_OP_DCN_FUSED of dtype H3D_F16X3 with reserved = 0x100000 derives its power-of-two filter scales
- * from (fp32 packs, split while they are staged); validated on the device like h3d_dcn_v2_pack_weights_cached (state: 16 zeroed bytes). */
+ * max |off_weight| -- what an H3D_OP_DCN_FUSED of dtype H3D_F16X3 with H3D_OPF_DCN_FUSED_RAW_PACK derives its power-of-two filter scales
+ * from (fp32 packs, split while they are staged; float offsets H3D_DCN_FUSED_BIAS_WMAX / _AMAX below); validated on the device like h3d_dcn_v2_pack_weights_cached (state: 16 zeroed bytes). */
 int h3d_dcn_fused_pack_f32_cached(const float *weight, const float *bias, const float *off_weight, const float *off_bias, int Cout, int C,
                                   float *wp, float *wo, float *bias_out, void *state, void *stream);
 size_t h3d_dcn_v2_packed_workspace_bytes(int B, int C, int H, int W, int flags);
@@ -174,7 +174,7 @@ size_t h3d_dcn_v2_packed_workspace_bytes(int B, int C, int H, int W, int flags);
  * non-finite when a non-finite pixel lies in rows oy-1 .. oy+2, columns ox-1 .. ox+2 (a gated or far sample still reads its undeformed
  * tap's 2x2 corners with weight zero).  No NaN becomes a finite number.  H3D_DCN_F32_MFMA follows the same rules with exact fmaf chains.
  * The stand-alone `DCN` module's launch (H3D_OP_DCN_FUSED; f16x3: h3d_dcn_nchw_to_nhwc_scaled -- max |x|, then x scaled by 2^e in the
- * relayout -- and reserved 0x300000, under which the kernel stages and splits without a clamp) keeps the same rules, its own offset
+ * relayout -- and H3D_OPF_DCN_FUSED_RAW_PACK | H3D_OPF_DCN_FUSED_SCALED_INPUT, under which the kernel stages and splits without a clamp) keeps the same rules, its own offset
  * convolution included: a NaN pixel gives NaN offsets and a sigmoid(NaN) mask, and 0 * NaN is NaN. */
 int h3d_dcn_nchw_to_nhwc_scaled(const float *src, float *dst, int B, int C, int H, int W, unsigned *amax, void *stream);
 int h3d_dcn_v2_forward_packed(const void *input, const void *packed, const float *offset, const float *mask, void *output,
@@ -303,9 +303,9 @@ typedef struct h3d_op {
     int32_t relu;       /* 1: ReLU epilogue                                                */
     int32_t out_mode;   /* H3D_OUT_*                                                       */
     int32_t wrows;      /* rows of the packed weight buffer (>= Cout, multiple of 128)     */
-    int32_t reserved;   /* 0 in production.  Profiling only: a per-kind tuning override (CONV_STREAM: MT << 8 | WAVES;
-                           UPADD: 1 = tap table from global memory, 2 = from LDS) and, in `make ABLATE=1` builds,
-                           ablation switches in the high bits (tools/ab_*.py)                              */
+    int32_t reserved;   /* per-kind flag word: H3D_OPF_* (operand / plan flags, set in production) | H3D_TUNE_* (tuning overrides of
+                           tests and tools/, ablation bits of `make ABLATE=1` builds) -- the catalogue below.  0 = the defaults;
+                           a bit no name covers for the op's kind and dtype is ignored                     */
     int32_t wexp;       /* H3D_F16X3 plans (ABI 2): the packed filters hold 2^wexp times the layer's filters -- chosen by the packer so
                            that max |w| lands in [2^13, 2^14) and the lo terms of all but vanishing filters are NORMAL fp16 numbers
                            (an unscaled 0.05 has a subnormal lo term: 3e-8 absolute, 2^-20.7 relative, five times the 2^-23 of the
@@ -313,13 +313,151 @@ typedef struct h3d_op {
     int32_t wexp2;      /* ... the same for the offset / mask filters of H3D_OP_DCN_FUSED (in2)                */
 } h3d_op;
 
+/* ---- h3d_op.reserved: the flag catalogue ------------------------------------------------------------------------------------------
+ * One enum per op kind (and dtype class where the launcher reads the word differently).  Two families:
+ *   H3D_OPF_<GROUP>_<NAME>   operand / plan flags: production sets them (engine.py's plans, the operator boundary of csrc/dcn.hip,
+ *                            dcn_v2.py).  Several change what the kernel READS: the buffer contract is stated with the flag, and a caller
+ *                            who sets one over buffers that do not meet it reads out of bounds.
+ *   H3D_TUNE_<GROUP>_<NAME>  tuning overrides: tests/ and tools/ set them to force an instantiation the launcher's rule would not pick
+ *                            (same operands, same result up to the summation order).  ..._ABLATE_MASK = the bits a `make ABLATE=1` build
+ *                            hands to the kernel's profiling switches (wrong results, timing only); every other build ignores them.
+ * One bit value may carry different names in different groups; a group's names only mean anything for that kind and dtype.
+ * Function-like macros build / take apart the multi-bit fields.  Kinds not listed read nothing from the word, with one exception:
+ * H3D_OP_STEM3 in an ABLATE build takes the whole word as a phase number (1 .. 3: return after that phase). */
+
+/* H3D_DCN_AUX_BYTES: what an fp32 DeformConv filter pack carries behind its [rows] fp32 biases (h3d_dcn_v2_pack_weights with H3D_F32,
+ * counted in h3d_dcn_v2_packed_weight_bytes / h3d_dcn_v2_workspace_bytes): word 0 = bit pattern of max |filter|, the rest zero.
+ * The packer zeroes and fills it on the caller's stream. */
+#define H3D_DCN_AUX_BYTES 256
+/* bias_out of h3d_dcn_fused_pack_f32_cached is [rows | 32 | 64] floats; float offsets behind `rows` (= op.wrows) of the 64-float tail: */
+#define H3D_DCN_FUSED_BIAS_WMAX 32   /* [+0] bits of max |weight|, [+1] bits of max |off_weight|: written by the packer                       */
+#define H3D_DCN_FUSED_BIAS_AMAX 34   /* bits of max |x| over the finite input elements: written by h3d_dcn_nchw_to_nhwc_scaled (its `amax`) */
+
+/* H3D_OP_DCN (csrc/dcn2.hip), every dtype */
+enum {
+    H3D_OPF_DCN_MASK_FINAL = 0x800,       /* in2 channels 18..26 hold the mask itself, not its logit (the operator boundary: the reference applies
+                                             the sigmoid in DCN.forward, dcn_v2.py:124).  No buffer requirement                                */
+    H3D_OPF_DCN_RAW_PACK = 0x100000,      /* H3D_F16X3 only (without it an f16x3 H3D_OP_DCN has no kernel): w is the plain fp32 pack [wrows][9][Cin]
+                                             of H3D_F32, and bias must extend to [wrows] floats + H3D_DCN_AUX_BYTES: the kernel reads the bit pattern
+                                             of max |w| at bias[wrows] and scales / splits the filters while it stages them.  wexp must be 0      */
+    H3D_OPF_DCN_ACT_MAXIMA = 0x200000,    /* with RAW_PACK only: in2 must extend 16 bytes past its B*H*W*in2_cs floats; the two words there are
+                                             the bit patterns of max |x| and max |mask| over the finite elements (the caller zeroes them, then
+                                             fills them on the same stream: csrc/dcn.hip dcn_om_pack); the kernel scales the activations by them */
+    H3D_TUNE_DCN_ABLATE_MASK = 0x1f       /* 2 no gather / blend, 4 no MFMA, 8 no slow path, 16 zero offsets                                     */
+};
+
+/* H3D_OP_DCN_FUSED (csrc/dcn3.hip), dtype H3D_F16X3 */
+enum {
+    H3D_OPF_DCN_FUSED_RAW_PACK = 0x100000,     /* w / in2 are the plain fp32 packs of h3d_dcn_fused_pack_f32_cached and bias its bias_out: [wrows | 32 |
+                                                  64] floats, of which the kernel reads the two filter maxima at bias[wrows + H3D_DCN_FUSED_BIAS_WMAX]
+                                                  and [+ 1].  A [wrows | 32] bias buffer is too short.  wexp and wexp2 must be 0                  */
+    H3D_OPF_DCN_FUSED_SCALED_INPUT = 0x200000, /* with RAW_PACK only: `in` was scaled by h3d_dcn_nchw_to_nhwc_scaled, whose amax word is
+                                                  bias[wrows + H3D_DCN_FUSED_BIAS_AMAX]; the kernel reads it and divides the scale out again      */
+    H3D_TUNE_DCN_FUSED_X3_MARGIN2 = 0x2000,    /* the f32 plan's margin-2 double-buffered tile                                                  */
+    H3D_TUNE_DCN_FUSED_X3_MARGIN6 = 0x4000,    /* force the margin-6 apron (default: Cout <= 64 on maps of 64 rows or more)                     */
+    H3D_TUNE_DCN_FUSED_X3_MARGIN4 = 0x8000,    /* force the margin-4 apron; wins over MARGIN6, loses to MARGIN2                                  */
+    H3D_TUNE_DCN_FUSED_X3_ABLATE_MASK = 0x1f   /* as H3D_TUNE_DCN_STREAM_ABLATE_MASK                                                             */
+};
+
+/* H3D_OP_DCN_FUSED_STREAM and H3D_OP_DCN_FUSED (csrc/dcn3.hip), the 2-byte dtypes H3D_BF16 / H3D_F16.  The variant flags select tiles of
+ * H3D_OP_DCN_FUSED_STREAM; of an H3D_OP_DCN_FUSED the launcher reads FORCE_NARROW_WG / FORCE_WIDE_WG, and rejects F16_INPUT.  No flag
+ * of this group changes what the buffers must hold except F16_INPUT. */
+enum {
+    H3D_OPF_DCN_STREAM_NO_SLOTS = 0x1000,      /* round 1's tiles without patch slots: every sample outside the apron goes through pass 2 (what a
+                                                  layer with Cin % 32 != 0 gets anyway).  Overrides the three variant flags below                */
+    H3D_OPF_DCN_STREAM_WIDE_MARGIN = 0x8000,   /* margin-4 tile on the packed apron, 256 patch slots (layers whose offsets reach far:
+                                                  DLAEngine.calibrate_dcn_margins).  Wins over SLOTS512                                          */
+    H3D_OPF_DCN_STREAM_SLOTS512 = 0x10000,     /* margin 2 on the packed apron, 512 patch slots per tile                                         */
+    H3D_OPF_DCN_STREAM_F16_INPUT = 0x40000,    /* H3D_BF16 plans: `in` holds IEEE fp16 values, not bf16 (an H3D_OP_UPADD with H3D_OUT_NHWC_F16 wrote it).
+                                                  Exists for the patch-slot tiles with Cin % 32 == 0, Cout > 32, NHWC output with Cout % 8 == 0;
+                                                  H3D_ERR_UNSUPPORTED elsewhere                                                                  */
+    H3D_OPF_DCN_STREAM_STATS = 0x20000,        /* set by h3d_dcn_far_samples on its private copy of the op, not by callers: a patch-slot tile that
+                                                  carries it runs phase A + geometry only and writes per-tile int32 counters to `out`             */
+    H3D_OPF_DCN_STREAM_VARIANT_MASK = 0x58600, /* what h3d_dcn_far_samples keeps of the caller's word: WIDE_MARGIN | SLOTS512 | F16_INPUT |
+                                                  FORCE_NARROW_WG | FORCE_WIDE_WG -- the bits that select the tile whose apron it measures        */
+    H3D_TUNE_DCN_STREAM_FORCE_NARROW_WG = 0x200, /* Cout > 64: 64-channel workgroups whatever the grid (default: below 192 128-channel workgroups)   */
+    H3D_TUNE_DCN_STREAM_FORCE_WIDE_WG = 0x400,   /* Cout > 64: 128-channel workgroups whatever the grid; wins over FORCE_NARROW_WG                   */
+    H3D_TUNE_DCN_STREAM_F16_DCN5 = 0x4000,     /* H3D_F16 stream ops: the LDS-DMA apron kernel of csrc/dcn5.hip (`make EXTRA=1` builds; H3D_ERR_UNSUPPORTED
+                                                  otherwise), unless NO_SLOTS or F16_KEEP_DCN3 is set                                             */
+    H3D_TUNE_DCN_STREAM_F16_KEEP_DCN3 = 0x2000, /* with F16_DCN5: stay on csrc/dcn3.hip                                                          */
+    H3D_TUNE_DCN_STREAM_ABLATE_MASK = 0x1f     /* dcn3: 1 no phase-A MFMA, 2 no gather / blend, 4 no phase-B MFMA, 8 stage once, 16 no patch fill  */
+};
+/* ... under F16_DCN5 bits 16..23 are the dcn5 experiment number instead (tools/ab_dcn5.py; <= 64 output channels) */
+#define H3D_TUNE_DCN_STREAM_DCN5_XP(xp) ((xp) << 16)
+#define H3D_TUNE_DCN_STREAM_DCN5_XP_OF(reserved) (((reserved) >> 16) & 0xff)
+
+/* H3D_OP_DCN_FUSED_STREAM (csrc/dcn3.hip), dtype H3D_F16X3: the apron margin (default 4 for Cin == Cout > 64, else 2) */
+enum {
+    H3D_TUNE_DCN_STREAM_X3_MARGIN2 = 0x4000,   /* MARGIN2 wins over MARGIN3 and MARGIN4, MARGIN3 over MARGIN4                                    */
+    H3D_TUNE_DCN_STREAM_X3_MARGIN3 = 0x8000,
+    H3D_TUNE_DCN_STREAM_X3_MARGIN4 = 0x10000,
+    H3D_TUNE_DCN_STREAM_X3_ABLATE_MASK = 0x1f
+};
+
+/* H3D_OP_DCN_FUSED_F16 and H3D_OP_UPDCN_F16 (csrc/dcn4.hip) */
+enum {
+    H3D_TUNE_DCN_F16_ONE_WG_PER_CU = 0x100,    /* H3D_OP_DCN_FUSED_F16 only                                                                      */
+    H3D_TUNE_DCN_F16_ABLATE_MASK = 0xff        /* a phase number 1 .. 4: return after that phase                                                */
+};
+
+/* H3D_OP_CONV_STREAM (csrc/conv2.hip).  The low 16 bits are a tile code, variant << 12 | MT << 8 | WAVES (MT = 32-channel row tiles per
+ * workgroup, WAVES = waves per workgroup).  Stride 1 variants: 0 two ring slots, 2 two N-tiles per wave, 3 three ring slots, 5 one ring
+ * slot, 6 fragment reads one tap ahead; an unknown code is H3D_ERR_ARG.  Stride 2 knows (4, 4, 4), (4, 4, 8), (4, 2, 4) = one ring slot
+ * and (2, 4, 4) = two ring slots, and ignores every other code. */
+#define H3D_TUNE_CONV_STREAM_TILE(variant, mt, waves) ((variant) << 12 | (mt) << 8 | (waves))
+#define H3D_TUNE_CONV_STREAM_ABLATE(bits) ((bits) << 16)
+#define H3D_TUNE_CONV_STREAM_ABLATE_OF(reserved) (((reserved) & H3D_TUNE_CONV_STREAM_ABLATE_MASK) >> 16)
+enum {
+    H3D_TUNE_CONV_STREAM_TILE_MASK = 0xffff,
+    H3D_TUNE_CONV_STREAM_AUTO = 1,             /* tile code "the launcher's own choice": carries ablation bits without an override               */
+    H3D_TUNE_CONV_STREAM_ROUND4_RULE = 0x10000000, /* stride 1, Cout > 96 on a small grid: round 4's 128-channel 4-wave tiles instead of narrower blocks */
+    H3D_TUNE_CONV_STREAM_ABLATE_MASK = 0x1f0000 /* << 16: 1 no DMA after stage 0, 2 no fragment reads / MFMA, 4 no LDS-transposed epilogue, 8 no
+                                                  input DMA, 16 no filter DMA                                                                   */
+};
+
+/* H3D_OP_CONV (csrc/conv.hip, csrc/gemm1.hip), the 2-byte dtypes.  A 1x1 conv goes to the GEMM kernel where its shape rule (csrc/gemm1.hip) takes it. */
+#define H3D_TUNE_CONV_1X1_TILE(mt, th) (H3D_TUNE_CONV_TILE | (mt) << 4 | (th) >> 3)   /* mt in {2, 4}, th in {8, 16} rows; other pairs: ignored */
+#define H3D_TUNE_CONV_1X1_TILE_MT(reserved) (((reserved) >> 4) & 15)
+#define H3D_TUNE_CONV_1X1_TILE_TH(reserved) (((reserved) & 15) * 8)
+#define H3D_TUNE_CONV_GEMM_TILE(n) ((n) << 8)   /* 1: 256 x 256, 8 waves, two slots; 2: 128 x 128, 8 waves, three slots; 3: 128 x 128, 4 waves, two
+                                                   workgroups per CU; others: the launcher's rule                                               */
+enum {
+    H3D_TUNE_CONV_TILE = 0x1000,               /* 1x1 stride 1, Cin % 64 == 0, Cout > 32: the halo-tile kernel with the tile of H3D_TUNE_CONV_1X1_TILE.
+                                                  engine.py sets it on the Root convs of the plans that keep them off the GEMM kernel          */
+    H3D_TUNE_CONV_HALO_TILE = 0x2000,          /* 1x1: the halo-tile kernel of csrc/conv.hip (its own tile rule), not the GEMM kernel             */
+    H3D_TUNE_CONV_FORCE_GEMM = 0x4000,         /* 1x1: the GEMM kernel whatever the shape (where its layout conditions hold); loses to the two above */
+    H3D_TUNE_CONV_GEMM_TILE_MASK = 0xf00
+};
+/* H3D_OP_CONV, dtype H3D_F16X3 */
+#define H3D_TUNE_CONV_X3_TILE(mt, waves, th) (H3D_TUNE_CONV_X3_TILED | (mt) << 8 | (waves) << 4 | (th) >> 3)   /* 3x3; unknown: H3D_ERR_ARG */
+enum {
+    H3D_TUNE_CONV_X3_TILED = 0x1000,           /* 3x3: the low 12 bits are a tile, see H3D_TUNE_CONV_X3_TILE                                      */
+    H3D_TUNE_CONV_X3_TILE_MASK = 0x1fff,
+    H3D_TUNE_CONV_X3_CK16 = 0x2000,            /* 1x1 stride 1: 16-channel chunks where 64-channel ones would be used                            */
+    H3D_TUNE_CONV_X3_MT2 = 0x4000              /* 1x1 stride 1: 64-channel tiles above 64 output channels too                                    */
+};
+
+/* H3D_OP_UPADD (csrc/conv.hip): the whole word, compared for equality */
+enum {
+    H3D_TUNE_UPADD_TAPS_GLOBAL = 1,            /* tap table read from global memory                                                              */
+    H3D_TUNE_UPADD_TAPS_LDS = 2                /* tap table in LDS whenever it fits 64 KiB                                                       */
+};
+
+/* H3D_OP_HEADS (csrc/heads.hip) */
+enum {
+    H3D_TUNE_HEADS_SEPARATE_BIAS = 0x200,      /* separate bias / zeroing pass (launches of equal-width heads only)                              */
+    H3D_TUNE_HEADS_ABLATE_MASK = 0xff          /* 1 no weight loads after the prologue, 2 no stage barrier, 4 / 8 one wave per SIMD, 64 per-wave stamps */
+};
+/* ---- end of the flag catalogue ---- */
+
 /* channels per filter stage H3D_OP_DCN_FUSED_STREAM expects for a layer (16) */
 int h3d_dcn_fused_ck(int Cin, int Cout);
 
 /* How far a fused DeformConv's samples reach, as the kernel itself sees it: per_tile[b * tiles_y * tiles_x + ty * tiles_x + tx]
  * (tiles of 16x16 output pixels, tiles_x = ceil(W/16)) = the number of (pixel, tap) samples of that tile that lie inside the image
- * but have a bilinear corner outside the tile's LDS apron, for the tile variant `op->reserved` selects (margin 2, or the wide margin
- * with 0x8000).  Phase A + geometry of the production kernel run, nothing else; op->out is not written.  A deterministic function of
+ * but have a bilinear corner outside the tile's LDS apron, for the tile variant `op->reserved` selects: of the caller's word
+ * H3D_OPF_DCN_STREAM_VARIANT_MASK is kept (margin 2, H3D_OPF_DCN_STREAM_WIDE_MARGIN or _SLOTS512, fp16 input, workgroup width), every
+ * other bit is dropped; a word with H3D_OPF_DCN_STREAM_NO_SLOTS is H3D_ERR_UNSUPPORTED.  Phase A + geometry of the production kernel run, nothing else; op->out is not written.  A deterministic function of
  * the layer's input: DLAEngine.calibrate_dcn_margins derives the per-layer variant from these counts (the reference operator,
  * dcn_v2_cuda.cu:43-173, has no data-dependent dispatch at all, so whatever replaces it must not depend on a stopwatch). */
 int h3d_dcn_far_samples(const h3d_op *op, int32_t *per_tile, void *stream);

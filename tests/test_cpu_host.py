@@ -217,3 +217,205 @@ def test_plan_faithful_emulation_rounds_where_the_plans_round():
     # plan_parts=[]: conv inputs and raw filters rounded, BatchNorm in fp32 -- the 'bf16' mode's arithmetic except for the depthwise
     # up-sampling weights (fp32 in every plan, rounded by emulate='bf16'): closer to it than either is to fp32
     assert float((none - old).abs().max()) < 0.5 * float((old - ref).abs().max())
+
+
+# ---- h3d_op.reserved: the flag catalogue of include/h3d.h ------------------------------------------------------------------------
+def _flag_catalogue():
+    """(groups, defines, macros) of the catalogue section of include/h3d.h: groups = one {name: value} per enum block."""
+    text = open(os.path.join(ROOT, "include", "h3d.h")).read()
+    text = text[text.index("h3d_op.reserved: the flag catalogue"):text.index("end of the flag catalogue")]
+    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    groups = [{n: int(v, 0) for n, v in re.findall(r"(H3D_\w+)\s*=\s*(0x[0-9a-fA-F]+|\d+)", body)} for body in re.findall(r"enum\s*\{(.*?)\}", code, flags=re.S)]
+    defines = {n: int(v, 0) for n, v in re.findall(r"^#define (H3D_\w+) (0x[0-9a-fA-F]+|\d+)\s*$", code, flags=re.M)}
+    macros = {n: (a.replace(" ", "").split(","), b) for n, a, b in re.findall(r"^#define (H3D_\w+)\(([\w, ]+)\) (.+?)\s*$", code, flags=re.M)}
+    return groups, defines, macros
+
+
+def test_flag_catalogue_is_mirrored_in_lib_and_no_two_flags_of_a_group_collide():
+    groups, defines, macros = _flag_catalogue()
+    assert len(groups) >= 10 and sum(len(g) for g in groups) >= 40 and len(macros) >= 8, (groups, macros)
+    for g in groups + [defines]:
+        for name, value in g.items():
+            assert getattr(_lib, name[len("H3D_"):]) == value, name
+    # the function-like macros: the C body is a Python expression too, over its arguments and the enumerators
+    names = {n: v for g in groups for n, v in g.items()}
+    for name, (args, body) in macros.items():
+        fn = getattr(_lib, name[len("H3D_"):])
+        for vals in ((1, 2, 16), (4, 8, 32), (6, 4, 8), (0x12345678, 2, 8)):
+            vals = vals[:len(args)]
+            assert fn(*vals) == eval(body, dict(names, **dict(zip(args, vals)))), (name, vals)
+    # within one group (one op kind and dtype class) and one family, no two flags share a bit (masks name several bits on purpose;
+    # H3D_OP_UPADD's two names are values of the whole word, not bits)
+    for g in groups:
+        for fam in ("H3D_OPF_", "H3D_TUNE_"):
+            flags = [(n, v) for n, v in g.items() if n.startswith(fam) and not n.endswith("_MASK") and not n.startswith("H3D_TUNE_UPADD_")]
+            for i, (n1, v1) in enumerate(flags):
+                for n2, v2 in flags[i + 1:]:
+                    assert not v1 & v2, (n1, n2)
+    assert _lib.OPF_DCN_STREAM_VARIANT_MASK == (_lib.OPF_DCN_STREAM_WIDE_MARGIN | _lib.OPF_DCN_STREAM_SLOTS512 | _lib.OPF_DCN_STREAM_F16_INPUT
+                                                | _lib.TUNE_DCN_STREAM_FORCE_NARROW_WG | _lib.TUNE_DCN_STREAM_FORCE_WIDE_WG)
+
+
+def _dry_op(kind, dtype, reserved, B, Cin, Cout, H, W, ksize, stride, keep):
+    """An h3d_op over fake device pointers: enough for h3d_op_kernel_name's dry run, which launches nothing."""
+    fake = 0x10000
+    op = _lib.H3dOp()
+    op.kind, op.dtype, op.reserved = kind, getattr(_lib, "H3D_" + dtype), reserved
+    op.in_, op.w, op.bias, op.out = fake, fake, fake, fake
+    up = kind == _lib.OP_UPADD
+    op.B, op.H, op.W, op.Cin, op.in_cs, op.Cout, op.out_cs = B, H, W, Cin, Cin, Cout, Cout
+    op.Ho, op.Wo = (H * stride, W * stride) if up else ((H - 1) // stride + 1, (W - 1) // stride + 1)
+    op.ksize, op.stride, op.relu, op.out_mode, op.wrows = ksize, stride, 1, _lib.OUT_NHWC, -(-Cout // 128) * 128
+    if kind == _lib.OP_HEADS:
+        d = _lib.H3dHeadsDesc()
+        d.nheads = 2
+        for i in range(2):
+            d.head[i].w2, d.head[i].b2, d.head[i].out, d.head[i].C = fake, fake, fake, 2
+        keep.append(d)
+        op.in2 = ctypes.addressof(d)
+    elif kind not in (_lib.OP_CONV, _lib.OP_CONV_STREAM):
+        op.in2, op.in2_cs = fake, Cin if up else 32
+    return op
+
+
+L = _lib
+S, F, D, C2, C, U, HD, F16K = L.OP_DCN_FUSED_STREAM, L.OP_DCN_FUSED, L.OP_DCN, L.OP_CONV_STREAM, L.OP_CONV, L.OP_UPADD, L.OP_HEADS, L.OP_DCN_FUSED_F16
+# (kind, dtype, reserved, B, Cin, Cout, H, W, ksize, stride, kernel name).  The names are what the library printed for the same words
+# written in hex BEFORE the flags had names (recorded from that build, pasted as literals): a word selects the kernel it always did.
+DISPATCH = [
+    # H3D_OP_DCN_FUSED_STREAM, bf16: 128 -> 64 @24x40 (two workgroups per CU)
+    (S, "BF16", 0, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 2, true, 256>"),
+    (S, "BF16", L.OPF_DCN_STREAM_NO_SLOTS, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 1, 2, true, 0>"),
+    (S, "BF16", L.OPF_DCN_STREAM_WIDE_MARGIN, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 4, 2, true, 256, true>"),
+    (S, "BF16", L.OPF_DCN_STREAM_SLOTS512, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 2, true, 512, true>"),
+    (S, "BF16", L.OPF_DCN_STREAM_F16_INPUT, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 2, true, 256, false, true>"),
+    (S, "BF16", L.TUNE_DCN_STREAM_FORCE_WIDE_WG, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 2, true, 256>"),
+    (S, "BF16", L.OPF_DCN_STREAM_WIDE_MARGIN | L.OPF_DCN_STREAM_F16_INPUT, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 4, 2, true, 256, true, true>"),
+    (S, "BF16", L.OPF_DCN_STREAM_SLOTS512 | L.OPF_DCN_STREAM_F16_INPUT, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 2, true, 512, true, true>"),
+    (S, "BF16", L.OPF_DCN_STREAM_WIDE_MARGIN | L.OPF_DCN_STREAM_SLOTS512, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 4, 2, true, 256, true>"),
+    (S, "BF16", L.OPF_DCN_STREAM_NO_SLOTS | L.OPF_DCN_STREAM_WIDE_MARGIN, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 1, 2, true, 0>"),
+    (S, "BF16", L.OPF_DCN_STREAM_STATS, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 2, true, 256>"),
+    # ... 256 -> 256 @16x16: a small grid, 64-channel workgroups unless forced wide
+    (S, "BF16", 0, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 2, true, 256>"),
+    (S, "BF16", L.TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<unsigned short, 4, 16, 4, 2, true, 256>"),
+    (S, "BF16", L.TUNE_DCN_STREAM_FORCE_NARROW_WG, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 2, true, 256>"),
+    (S, "BF16", L.TUNE_DCN_STREAM_FORCE_NARROW_WG | L.TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<unsigned short, 4, 16, 4, 2, true, 256>"),
+    (S, "BF16", L.OPF_DCN_STREAM_WIDE_MARGIN, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 4, 2, true, 256, true>"),
+    (S, "BF16", L.OPF_DCN_STREAM_WIDE_MARGIN | L.TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<unsigned short, 4, 16, 4, 2, true, 256>"),
+    (S, "BF16", L.OPF_DCN_STREAM_SLOTS512, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 2, true, 512, true>"),
+    (S, "BF16", L.OPF_DCN_STREAM_SLOTS512 | L.TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<unsigned short, 4, 16, 4, 2, true, 512>"),
+    (S, "BF16", L.OPF_DCN_STREAM_F16_INPUT | L.TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<unsigned short, 4, 16, 4, 2, true, 256, false, true>"),
+    (S, "BF16", L.OPF_DCN_STREAM_SLOTS512 | L.OPF_DCN_STREAM_F16_INPUT | L.TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<unsigned short, 4, 16, 4, 2, true, 512, false, true>"),
+    # ... 256 -> 256 @32x32 at batch 64: 512 wide workgroups, 128-channel workgroups unless forced narrow
+    (S, "BF16", 0, 64, 256, 256, 32, 32, 3, 1, "dcn3_kernel<unsigned short, 4, 16, 4, 2, true, 256>"),
+    (S, "BF16", L.TUNE_DCN_STREAM_FORCE_NARROW_WG, 64, 256, 256, 32, 32, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 2, true, 256>"),
+    (S, "BF16", L.OPF_DCN_STREAM_WIDE_MARGIN | L.TUNE_DCN_STREAM_FORCE_NARROW_WG, 64, 256, 256, 32, 32, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 4, 2, true, 256, true>"),
+    # ... <= 32 output channels
+    (S, "BF16", 0, 1, 64, 32, 20, 20, 3, 1, "dcn3_kernel<unsigned short, 1, 16, 2, 1, true, 256>"),
+    (S, "BF16", L.OPF_DCN_STREAM_NO_SLOTS, 1, 64, 32, 20, 20, 3, 1, "dcn3_kernel<unsigned short, 1, 16, 1, 1, true, 0>"),
+    (S, "BF16", L.OPF_DCN_STREAM_WIDE_MARGIN, 1, 64, 32, 20, 20, 3, 1, "dcn3_kernel<unsigned short, 1, 16, 4, 1, true, 256, true>"),
+    (S, "BF16", L.OPF_DCN_STREAM_SLOTS512, 1, 64, 32, 20, 20, 3, 1, "dcn3_kernel<unsigned short, 1, 16, 2, 1, true, 512, true>"),
+    # ... fp16 plans: F16_INPUT is not read; the dcn5 request is in DISPATCH_DCN5 below
+    (S, "F16", 0, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<f16_t, 2, 16, 2, 2, true, 256>"),
+    (S, "F16", L.OPF_DCN_STREAM_F16_INPUT, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<f16_t, 2, 16, 2, 2, true, 256>"),
+    (S, "F16", L.OPF_DCN_STREAM_WIDE_MARGIN, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<f16_t, 2, 16, 4, 2, true, 256, true>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_F16_KEEP_DCN3, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<f16_t, 2, 16, 2, 2, true, 256>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.OPF_DCN_STREAM_NO_SLOTS, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<f16_t, 2, 16, 1, 2, true, 0>"),
+    # H3D_OP_DCN_FUSED_STREAM, f16x3: the margins
+    (S, "F16X3", 0, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<x3_t, 2, 16, 2, 1, true, 256>"),
+    (S, "F16X3", L.TUNE_DCN_STREAM_X3_MARGIN2, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<x3_t, 2, 16, 2, 1, true, 256>"),
+    (S, "F16X3", L.TUNE_DCN_STREAM_X3_MARGIN3, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<x3_t, 2, 16, 3, 1, true, 256>"),
+    (S, "F16X3", L.TUNE_DCN_STREAM_X3_MARGIN4, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<x3_t, 2, 16, 4, 1, true, 256>"),
+    (S, "F16X3", 0, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<x3_t, 2, 16, 4, 1, true, 256>"),
+    (S, "F16X3", L.TUNE_DCN_STREAM_X3_MARGIN2, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<x3_t, 2, 16, 2, 1, true, 256>"),
+    (S, "F16X3", L.TUNE_DCN_STREAM_X3_MARGIN3 | L.TUNE_DCN_STREAM_X3_MARGIN4, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<x3_t, 2, 16, 3, 1, true, 256>"),
+    (S, "F16X3", L.TUNE_DCN_STREAM_X3_MARGIN2 | L.TUNE_DCN_STREAM_X3_MARGIN4, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<x3_t, 2, 16, 2, 1, true, 256>"),
+    (S, "F16X3", L.TUNE_DCN_STREAM_X3_MARGIN4, 1, 64, 32, 20, 20, 3, 1, "dcn3_kernel<x3_t, 1, 16, 4, 1, true, 256>"),
+    # H3D_OP_DCN_FUSED, f16x3: the margins and the `DCN` module's contract flags
+    (F, "F16X3", 0, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<x3_t, 2, 16, 4, 1, false, 0>"),
+    (F, "F16X3", L.OPF_DCN_FUSED_RAW_PACK | L.OPF_DCN_FUSED_SCALED_INPUT, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<x3_t, 2, 16, 4, 1, false, 0>"),
+    (F, "F16X3", L.TUNE_DCN_FUSED_X3_MARGIN2, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<x3_t, 2, 16, 2, 1, false, 0>"),
+    (F, "F16X3", L.TUNE_DCN_FUSED_X3_MARGIN6, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<x3_t, 2, 16, 6, 1, false, 0>"),
+    (F, "F16X3", L.TUNE_DCN_FUSED_X3_MARGIN4, 2, 128, 64, 24, 40, 3, 1, "dcn3_kernel<x3_t, 2, 16, 4, 1, false, 0>"),
+    (F, "F16X3", 0, 1, 64, 64, 64, 16, 3, 1, "dcn3_kernel<x3_t, 2, 16, 6, 1, false, 0>"),
+    (F, "F16X3", L.TUNE_DCN_FUSED_X3_MARGIN4, 1, 64, 64, 64, 16, 3, 1, "dcn3_kernel<x3_t, 2, 16, 4, 1, false, 0>"),
+    (F, "F16X3", L.TUNE_DCN_FUSED_X3_MARGIN6 | L.TUNE_DCN_FUSED_X3_MARGIN4, 1, 64, 64, 64, 16, 3, 1, "dcn3_kernel<x3_t, 2, 16, 4, 1, false, 0>"),
+    (F, "F16X3", L.TUNE_DCN_FUSED_X3_MARGIN6, 1, 32, 32, 16, 16, 3, 1, "dcn3_kernel<x3_t, 1, 16, 6, 1, false, 0>"),
+    # H3D_OP_DCN_FUSED, 2-byte: the workgroup width
+    (F, "BF16", 0, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<unsigned short, 2, 32, 2, 2, false, 0>"),
+    (F, "BF16", L.TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 16, 16, 3, 1, "dcn3_kernel<unsigned short, 4, 16, 2, 2, false, 0>"),
+    (F, "BF16", L.TUNE_DCN_STREAM_FORCE_NARROW_WG, 64, 256, 256, 32, 32, 3, 1, "dcn3_kernel<unsigned short, 2, 32, 2, 2, false, 0>"),
+    (F, "BF16", L.TUNE_DCN_STREAM_FORCE_NARROW_WG, 64, 144, 128, 32, 32, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 2, false, 0>"),
+    (F, "F16", L.TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 128, 128, 24, 40, 3, 1, "dcn3_kernel<f16_t, 4, 16, 2, 2, false, 0>"),
+    # H3D_OP_DCN: the operator boundary's word
+    (D, "F16X3", L.OPF_DCN_MASK_FINAL | L.OPF_DCN_RAW_PACK | L.OPF_DCN_ACT_MAXIMA, 2, 128, 64, 24, 40, 3, 1, "dcn2_kernel<x3_t, 2, 16, 2, 1>"),
+    (D, "F16X3", L.OPF_DCN_RAW_PACK, 1, 64, 32, 20, 20, 3, 1, "dcn2_kernel<x3_t, 1, 16, 2, 1>"),
+    (D, "F32", L.OPF_DCN_MASK_FINAL, 2, 128, 64, 24, 40, 3, 1, "dcn2_kernel<float, 2, 16, 2, 1>"),
+    (D, "BF16", L.OPF_DCN_MASK_FINAL, 2, 128, 64, 24, 40, 3, 1, "dcn2_kernel<unsigned short, 2, 32, 2, 1>"),
+    # H3D_OP_CONV_STREAM: tile codes of every variant nibble, the auto code, round 4's rule
+    (C2, "BF16", 0, 2, 64, 128, 40, 24, 3, 1, "conv2_kernel<unsigned short, 1, 4, 1, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_AUTO, 2, 64, 128, 40, 24, 3, 1, "conv2_kernel<unsigned short, 1, 4, 1, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(0, 4, 16), 2, 64, 128, 40, 24, 3, 1, "conv2_kernel<unsigned short, 4, 16, 2, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(0, 1, 4), 1, 48, 32, 10, 18, 3, 1, "conv2_kernel<unsigned short, 1, 4, 1, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(2, 4, 8), 1, 64, 128, 40, 24, 3, 1, "conv2_kernel<unsigned short, 4, 8, 2, 1, 2, 2>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(3, 2, 8), 1, 96, 64, 24, 24, 3, 1, "conv2_kernel<unsigned short, 2, 8, 2, 1, 3, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(5, 2, 8), 1, 64, 64, 24, 24, 3, 1, "conv2_kernel<unsigned short, 2, 8, 2, 1, 1, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(6, 4, 8), 1, 128, 128, 24, 40, 3, 1, "conv2_kernel<unsigned short, 4, 8, 2, 1, 2, 1, true>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(6, 2, 8), 2, 64, 64, 24, 40, 3, 1, "conv2_kernel<f16_t, 2, 8, 2, 1, 2, 1, true>"),
+    (C2, "BF16", 0, 1, 128, 256, 24, 24, 3, 2, "conv2_kernel<unsigned short, 4, 4, 2, 2, 1, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(2, 4, 4), 1, 128, 256, 24, 24, 3, 2, "conv2_kernel<unsigned short, 4, 4, 2, 2, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(4, 4, 8), 1, 64, 128, 40, 24, 3, 2, "conv2_kernel<unsigned short, 4, 8, 2, 2, 1, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(4, 2, 4), 1, 64, 64, 24, 40, 3, 2, "conv2_kernel<unsigned short, 2, 4, 2, 2, 1, 1>"),
+    (C2, "BF16", 0, 16, 128, 256, 4, 4, 3, 1, "conv2_kernel<unsigned short, 1, 4, 1, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_ROUND4_RULE, 16, 128, 256, 4, 4, 3, 1, "conv2_kernel<unsigned short, 4, 4, 2, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_AUTO | L.TUNE_CONV_STREAM_ABLATE(4), 2, 64, 128, 40, 24, 3, 1, "conv2_kernel<unsigned short, 1, 4, 1, 1, 2, 1>"),
+    # H3D_OP_CONV 1x1, 2-byte: GEMM kernel (three tiles, forced, refused) and the halo-tile kernel's tile override
+    (C, "BF16", 0, 2, 128, 256, 24, 24, 1, 1, "conv_kernel<unsigned short, 1, 1, 4, 64, 8, 4, 2>"),
+    (C, "BF16", L.TUNE_CONV_FORCE_GEMM, 2, 128, 64, 24, 24, 1, 1, "gemm1_kernel<unsigned short, 2, 2, 2, 2, 2, 2>"),
+    (C, "BF16", 0, 2, 128, 64, 24, 24, 1, 1, "conv_kernel<unsigned short, 1, 1, 2, 64, 8, 4, 2>"),
+    (C, "BF16", L.TUNE_CONV_FORCE_GEMM | L.TUNE_CONV_GEMM_TILE(1), 2, 128, 256, 24, 24, 1, 1, "gemm1_kernel<unsigned short, 4, 2, 2, 4, 2, 2>"),
+    (C, "BF16", L.TUNE_CONV_FORCE_GEMM | L.TUNE_CONV_GEMM_TILE(2), 2, 128, 256, 24, 24, 1, 1, "gemm1_kernel<unsigned short, 2, 2, 2, 4, 3, 2>"),
+    (C, "BF16", L.TUNE_CONV_FORCE_GEMM | L.TUNE_CONV_GEMM_TILE(3), 2, 128, 256, 24, 24, 1, 1, "gemm1_kernel<unsigned short, 2, 2, 2, 2, 2, 2>"),
+    (C, "BF16", L.TUNE_CONV_HALO_TILE, 2, 128, 256, 24, 24, 1, 1, "conv_kernel<unsigned short, 1, 1, 4, 64, 8, 4, 2>"),
+    (C, "BF16", L.TUNE_CONV_FORCE_GEMM | L.TUNE_CONV_HALO_TILE, 2, 128, 256, 24, 24, 1, 1, "conv_kernel<unsigned short, 1, 1, 4, 64, 8, 4, 2>"),
+    (C, "BF16", L.TUNE_CONV_1X1_TILE(4, 16), 2, 128, 256, 24, 24, 1, 1, "conv_kernel<unsigned short, 1, 1, 4, 64, 16, 4, 2>"),
+    (C, "BF16", L.TUNE_CONV_1X1_TILE(2, 8), 2, 128, 256, 24, 24, 1, 1, "conv_kernel<unsigned short, 1, 1, 2, 64, 8, 4, 2>"),
+    (C, "F16", L.TUNE_CONV_1X1_TILE(2, 16), 2, 128, 64, 24, 24, 1, 1, "conv_kernel<f16_t, 1, 1, 2, 64, 16, 4, 2>"),
+    # H3D_OP_CONV, f16x3: 3x3 tiles, the 1x1 chunk / tile overrides
+    (C, "F16X3", 0, 1, 64, 128, 32, 32, 3, 1, "conv_kernel<x3_t, 3, 1, 2, 16, 32, 8, 1>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(4, 8, 16), 1, 64, 128, 32, 32, 3, 1, "conv_kernel<x3_t, 3, 1, 4, 16, 16, 8, 1>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(1, 4, 16), 1, 64, 32, 32, 32, 3, 1, "conv_kernel<x3_t, 3, 1, 1, 16, 16, 4, 1>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(2, 4, 8), 1, 64, 64, 32, 32, 3, 2, "conv_kernel<x3_t, 3, 2, 2, 16, 8, 4, 1>"),
+    (C, "F16X3", 0, 1, 128, 128, 16, 16, 1, 1, "conv_kernel<x3_t, 1, 1, 4, 64, 8, 4, 1>"),
+    (C, "F16X3", L.TUNE_CONV_X3_CK16, 1, 128, 128, 16, 16, 1, 1, "conv_kernel<x3_t, 1, 1, 2, 16, 16, 4, 1>"),
+    (C, "F16X3", L.TUNE_CONV_X3_MT2, 1, 128, 128, 16, 16, 1, 1, "conv_kernel<x3_t, 1, 1, 2, 64, 8, 4, 1>"),
+    (C, "F16X3", L.TUNE_CONV_X3_CK16 | L.TUNE_CONV_X3_MT2, 1, 128, 128, 16, 16, 1, 1, "conv_kernel<x3_t, 1, 1, 2, 16, 16, 4, 1>"),
+    # H3D_OP_UPADD: the tap table's place (f = 2: ksize 4, stride 2)
+    (U, "BF16", 0, 1, 256, 256, 8, 8, 4, 2, "upadd_kernel<unsigned short, false, false>"),
+    (U, "BF16", L.TUNE_UPADD_TAPS_LDS, 1, 256, 256, 8, 8, 4, 2, "upadd_kernel<unsigned short, false, true>"),
+    (U, "BF16", 0, 1, 64, 64, 8, 8, 4, 2, "upadd_kernel<unsigned short, false, true>"),
+    (U, "BF16", L.TUNE_UPADD_TAPS_GLOBAL, 1, 64, 64, 8, 8, 4, 2, "upadd_kernel<unsigned short, false, false>"),
+    # H3D_OP_HEADS
+    (HD, "BF16", 0, 1, 64, 64, 16, 32, 3, 1, "heads_kernel<unsigned short, 16, 1, true>"),
+    (HD, "BF16", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, "heads_kernel<unsigned short, 16, 1, false>"),
+    (HD, "F32", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, "heads_kernel<float, 8, 1, false>"),
+]
+DISPATCH_EXTRA = [
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5, 2, 128, 64, 24, 40, 3, 1, "dcn5_kernel<2, 2, 2, 256>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5, 1, 64, 32, 20, 20, 3, 1, "dcn5_kernel<1, 2, 1, 256>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 16, 16, 3, 1, "dcn5_kernel<4, 4, 2, 256>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5, 1, 256, 256, 16, 16, 3, 1, "dcn5_kernel<2, 2, 2, 256>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_DCN5_XP(2), 2, 128, 64, 24, 40, 3, 1, "dcn5_kernel<2, 2, 2, 256, 2>"),
+    (F16K, "BF16", 0, 1, 64, 64, 24, 40, 3, 1, "dcn4_kernel<2, 2, 1, 0>"),
+    (F16K, "BF16", L.TUNE_DCN_F16_ONE_WG_PER_CU, 1, 64, 64, 24, 40, 3, 1, "dcn4_kernel<2, 2, 0, 0>"),
+]
+
+
+def test_flag_words_select_the_kernels_they_always_did():
+    lib, keep, buf = _lib.lib(), [], ctypes.create_string_buffer(200)
+    assert len(DISPATCH) >= 40
+    # the superseded generations: their names in a `make EXTRA=1` library, H3D_ERR_UNSUPPORTED (-4) in the default one
+    extra = DISPATCH_EXTRA if _lib.has_extra() else [c[:-1] + (-4,) for c in DISPATCH_EXTRA]
+    for case in DISPATCH + extra:
+        rc = lib.h3d_op_kernel_name(ctypes.byref(_dry_op(*case[:-1], keep)), buf, 200)
+        assert (buf.value.decode() if rc == 0 else rc) == case[-1], (case, rc, lib.h3d_last_error())

@@ -77,9 +77,9 @@ def test_conv_matches_torch(case, dtype):
     _check(got, ref.float(), dtype, str(case))
 
 
-# 1x1 stride-1 bf16 convolutions as a GEMM (csrc/gemm1.hip).  reserved: 0x4000 = take the GEMM kernel whatever the grid,
-# 0x100 / 0x200 / 0x300 = the 256x256 / 128x256 (three ring slots) / 128x128 (4 waves, two workgroups per CU) tile;
-# 0x2000 = the halo-tile kernel instead.
+# 1x1 stride-1 bf16 convolutions as a GEMM (csrc/gemm1.hip).  reserved of the table below: 0x4n00 = _lib.TUNE_CONV_FORCE_GEMM (take the
+# GEMM kernel whatever the grid) | _lib.TUNE_CONV_GEMM_TILE(n), n = 1 / 2 / 3 = the 256x256 / 128x256 (three ring slots) / 128x128 (4 waves, two
+# workgroups per CU) tile; _lib.TUNE_CONV_HALO_TILE = the halo-tile kernel instead.
 GEMM1_CASES = [
     # (B, Cin, Cout, H, W, relu, residual, reserved, in_pad, out_pad[, stride])
     (2, 128, 64, 24, 24, True, False, 0x4300, 0, 0),       # DLA level2 root class (auto leaves <= 64 channels to conv.hip); 1152 px = 9 tiles
@@ -135,19 +135,19 @@ def test_gemm1_matches_torch_and_halo_kernel(case, dtype):
     _check(got, ref.float(), dtype, str(case))
     assert untouched is None or untouched
     # the halo-tile kernel of csrc/conv.hip on the same operands: same MFMA instruction over K in the same order
-    assert conv(x, w, b, dtype, reserved=0x2000, name_only=True, **kw).startswith("conv_kernel<%s, " % TN[dtype])
-    old, _ = conv(x, w, b, dtype, reserved=0x2000, **kw)
+    assert conv(x, w, b, dtype, reserved=_lib.TUNE_CONV_HALO_TILE, name_only=True, **kw).startswith("conv_kernel<%s, " % TN[dtype])
+    old, _ = conv(x, w, b, dtype, reserved=_lib.TUNE_CONV_HALO_TILE, **kw)
     assert float((got - old).abs().max()) <= (2e-2 if dtype == "bf16" else 3e-3) * max(1.0, float(ref.abs().max()))
 
 
 def test_gemm1_declines_what_it_cannot_take():
     x, w, b = bf16_round(rnd("x", (1, 128, 9, 9))), bf16_round(rnd("w", (64, 128, 1, 1)) * 0.1), rnd("b", (64,))
-    assert conv(x, w, b, "bf16", reserved=0x4000, name_only=True).startswith("conv_kernel<")      # 81 pixels: not a multiple of 16
+    assert conv(x, w, b, "bf16", reserved=_lib.TUNE_CONV_FORCE_GEMM, name_only=True).startswith("conv_kernel<")      # 81 pixels: not a multiple of 16
     x = bf16_round(rnd("x", (1, 96, 16, 16)))
     w = bf16_round(rnd("w", (64, 96, 1, 1)) * 0.1)
-    assert conv(x, w, b, "bf16", reserved=0x4000, name_only=True).startswith("conv_kernel<")      # Cin % 64 != 0
+    assert conv(x, w, b, "bf16", reserved=_lib.TUNE_CONV_FORCE_GEMM, name_only=True).startswith("conv_kernel<")      # Cin % 64 != 0
     x, w = rnd("x", (1, 128, 16, 16)), rnd("w", (64, 128, 1, 1)) * 0.1
-    assert conv(x, w, b, "f32", reserved=0x4000, name_only=True).startswith("conv_kernel<")       # fp32 plans
+    assert conv(x, w, b, "f32", reserved=_lib.TUNE_CONV_FORCE_GEMM, name_only=True).startswith("conv_kernel<")       # fp32 plans
     assert conv(bf16_round(x), bf16_round(w), b, "bf16", name_only=True).startswith("conv_kernel<")   # <= 64 output channels
     w, b = bf16_round(rnd("w", (128, 128, 1, 1)) * 0.1), rnd("b", (128,))
     assert conv(bf16_round(x), w, b, "bf16", name_only=True).startswith("conv_kernel<")                  # 2 x 1 tiles: grid too small

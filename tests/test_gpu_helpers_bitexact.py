@@ -114,7 +114,7 @@ def test_upadd_bit_identical(case, dtype):
     wd = w.reshape(C, k * k).t().contiguous().to(DEV)
     modes = [(_lib.OUT_NHWC, td)] + ([(_lib.OUT_NHWC_F16, torch.float16)] if dtype == "bf16" else [])
     for out_mode, od in modes:
-        for reserved in (0, 1, 2):                       # the launcher's choice, tap table never / always in LDS
+        for reserved in (0, _lib.TUNE_UPADD_TAPS_GLOBAL, _lib.TUNE_UPADD_TAPS_LDS):                       # the launcher's choice, tap table never / always in LDS
             out = torch.zeros(2, H * f, W * f, C, dtype=td, device=DEV)
             run(mk(_lib.OP_UPADD, dtype, in_=xp, in2=sp, w=wd.data_ptr(), out=out.data_ptr(), B=2, H=H, W=W, Cin=C, in_cs=C,
                    in2_cs=C, Ho=H * f, Wo=W * f, Cout=C, out_cs=C, ksize=k, stride=f, out_mode=out_mode, reserved=reserved))

@@ -12,6 +12,7 @@ import torch
 
 import h3d_amd  # noqa: F401
 from h3d_amd import arch, model, synth
+from h3d_amd._lib import OPF_DCN_STREAM_F16_INPUT, OPF_DCN_STREAM_SLOTS512, OPF_DCN_STREAM_WIDE_MARGIN, TUNE_DCN_F16_ONE_WG_PER_CU
 from h3d_amd.detector import MultiPoseDetector, Opt
 from oracle import decode as odec
 from oracle import dla as odla
@@ -147,7 +148,7 @@ def test_dcn_wide_margin_flag_and_calibration():
     rep = eng.calibrate_dcn_margins(torch.from_numpy(x2).to(DEV))
     assert len(rep) == 16 and all(set(r["cost"]) == {"narrow", "slots512", "wide"} for r in rep.values()), rep
     chosen = dict(eng.pw.dcn_variant)
-    assert chosen and set(chosen.values()) <= {0x8000, 0x10000}, (chosen, rep)
+    assert chosen and set(chosen.values()) <= {OPF_DCN_STREAM_WIDE_MARGIN, OPF_DCN_STREAM_SLOTS512}, (chosen, rep)
     R = eng.DCN_RULE
     for p_, r in rep.items():                            # the choice IS the rule applied to the reported tile shares
         def over(f):
@@ -157,7 +158,7 @@ def test_dcn_wide_margin_flag_and_calibration():
              "wide": 1 + R["wide"] + over(r["tiles_over_256_wide"])}
         best = min(c, key=c.get)
         want = best if best != "narrow" and c[best] < (1 - R["min_gain"]) * c["narrow"] - 1e-3 else None
-        got = {0x8000: "wide", 0x10000: "slots512"}.get(chosen.get(p_))
+        got = {OPF_DCN_STREAM_WIDE_MARGIN: "wide", OPF_DCN_STREAM_SLOTS512: "slots512"}.get(chosen.get(p_))
         assert want is None or got == want, (p_, r, c)
         assert r["choice"] == (got or "narrow")
     # streams = 2 (forward() would run sub-plans and leave plan(B, H, W) untouched: ADVICE r3) and a repeat: the same choice
@@ -167,10 +168,10 @@ def test_dcn_wide_margin_flag_and_calibration():
     assert eng.pw.dcn_variant == chosen and rep2 == rep
     after = m2(torch.from_numpy(x2).to(DEV))[0]
     plan = eng.plan(2, 256, 256)
-    assert {p_: plan.ops[i].reserved & ~0x40000 for p_, i in plan.dcn_layers if plan.ops[i].reserved & ~0x40000} == eng.pw.dcn_variant    # (0x40000: fp16 input of the node layers)
+    assert {p_: plan.ops[i].reserved & ~OPF_DCN_STREAM_F16_INPUT for p_, i in plan.dcn_layers if plan.ops[i].reserved & ~OPF_DCN_STREAM_F16_INPUT} == eng.pw.dcn_variant    # (F16_INPUT: fp16 input of the node layers)
     names = {p_: kernel_name(plan.ops[i]) for p_, i in plan.dcn_layers}
     for p_, bits in eng.pw.dcn_variant.items():
-        assert ("512" in names[p_].split("<")[1]) == (bits == 0x10000) and (names[p_].endswith(", true>") or ", 4, 16, 4," in names[p_]), names[p_]
+        assert ("512" in names[p_].split("<")[1]) == (bits == OPF_DCN_STREAM_SLOTS512) and (names[p_].endswith(", true>") or ", 4, 16, 4," in names[p_]), names[p_]
     # the stopwatch (tools/fit_dcn_rule.py's yardstick) leaves the plan as it found it
     times = eng.time_dcn_variants(torch.from_numpy(x2).to(DEV), reps=1)
     assert len(times) == 16 and all(set(t) == {"narrow", "slots512", "wide"} and min(t.values()) > 0 for t in times.values()), times
@@ -482,7 +483,7 @@ def test_streamed_dcn_matches_dcn3(offset_scale, tol):
 @pytest.mark.parametrize("offset_scale", [0.5, 3.0, 12.0])
 def test_dcn4_two_workgroups_per_cu_matches_one(offset_scale):
     # csrc/dcn4.hip DENSE = 1 (margin-1 apron, single filter slot, the default) vs DENSE = 0 (margin 2, 3-slot ring;
-    # h3d_op.reserved = 0x100): same arithmetic per sample, only the split between the apron pass and the
+    # h3d_op.reserved = TUNE_DCN_F16_ONE_WG_PER_CU): same arithmetic per sample, only the split between the apron pass and the
     # global-gather pass 2 differs (offset_scale 3 puts samples between the two margins), i.e. fp32 summation order
     from h3d_amd import _lib
     sd = synth.synth_state_dict(arch.state_dict_shapes(HEADS, True), seed=0, offset_scale=offset_scale)
@@ -498,7 +499,7 @@ def test_dcn4_two_workgroups_per_cu_matches_one(offset_scale):
     assert idx
     try:
         for i in idx:
-            plan.op_array[i].reserved = 0x100
+            plan.op_array[i].reserved = TUNE_DCN_F16_ONE_WG_PER_CU
         one = {k: v.clone() for k, v in m(xs)[0].items()}
     finally:
         for i in idx:

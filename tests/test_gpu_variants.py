@@ -17,11 +17,15 @@ import torch.nn.functional as F
 
 from gpu_helpers import DEV, TN, Built, bf16_round, conv_stream_op, dcn_fused_op, dcn_fused_reference, kernel_name, lowp_round, rnd
 from h3d_amd import _lib
+from h3d_amd._lib import (OPF_DCN_STREAM_NO_SLOTS, OPF_DCN_STREAM_SLOTS512, OPF_DCN_STREAM_WIDE_MARGIN, TUNE_CONV_STREAM_ROUND4_RULE, TUNE_DCN_F16_ONE_WG_PER_CU,
+                          TUNE_DCN_FUSED_X3_MARGIN2, TUNE_DCN_FUSED_X3_MARGIN6, TUNE_DCN_STREAM_F16_DCN5, TUNE_DCN_STREAM_FORCE_NARROW_WG,
+                          TUNE_DCN_STREAM_FORCE_WIDE_WG, TUNE_DCN_STREAM_X3_MARGIN2, TUNE_DCN_STREAM_X3_MARGIN3, TUNE_DCN_STREAM_X3_MARGIN4)
 
 pytestmark = pytest.mark.gpu
 
 # ---- csrc/conv2.hip ------------------------------------------------------------------------------------
-# (override, B, Cin, Cout, H, W, stride, relu, residual, in_pad, out_pad)
+# (override, B, Cin, Cout, H, W, stride, relu, residual, in_pad, out_pad); override = _lib.TUNE_CONV_STREAM_TILE(variant, MT, WAVES) =
+# variant << 12 | MT << 8 | WAVES: 0x6410 = variant 6 (fragment reads one tap ahead), MT 4, 16 waves -- see include/h3d.h
 CONV2_CASES = [
     # forced variants on small, ragged tensors (H not a multiple of the tile height, W not of 16)
     (0x410, 2, 64, 128, 40, 24, 1, True, True, 0, 0),      # <4,16>: 32 x 16 px tiles, 16 waves
@@ -60,7 +64,7 @@ CONV2_CASES = [
     (0, 16, 256, 256, 8, 8, 1, True, True, 0, 0),          # 8 x 8 maps: <1,4> (128 workgroups even at 32 channels)
     (0, 16, 64, 512, 4, 4, 1, True, False, 0, 0),          # 512 output channels: 32-channel blocks make 256 workgroups on 16-row tiles: <1,8>
     (0, 16, 128, 384, 32, 32, 1, True, True, 0, 0),        # 32 x 32 maps, 16 images: <2,8,PIPE>
-    (0x10000000, 16, 128, 256, 4, 4, 1, True, False, 0, 0),  # ... round 4's rule on the same tensor: <4,4>
+    (TUNE_CONV_STREAM_ROUND4_RULE, 16, 128, 256, 4, 4, 1, True, False, 0, 0),  # ... round 4's rule on the same tensor: <4,4>
     # odd sizes (the C ABI takes any H, W)
     (0, 2, 128, 128, 13, 21, 1, True, True, 0, 0),
     (0, 1, 64, 64, 7, 5, 1, False, False, 0, 0),           # smaller than one tile both ways
@@ -81,9 +85,9 @@ def _conv2_built(case, dtype="bf16"):
 
 def test_conv2_small_grid_rule_selects_narrower_channel_blocks():
     # csrc/conv2.hip, round 5: below 256 workgroups at 128 channels per workgroup the launcher takes 64-channel 16-row tiles
-    # if THEY reach 256, else 32-channel ones; 0x10000000 keeps round 4's 128-channel 8-row tile
+    # if THEY reach 256, else 32-channel ones; TUNE_CONV_STREAM_ROUND4_RULE keeps round 4's 128-channel 8-row tile
     want = {(16, 128, 256, 4, 0): "conv2_kernel<unsigned short, 1, 4, ", (16, 256, 256, 8, 0): "conv2_kernel<unsigned short, 1, 4, ", (16, 64, 512, 4, 0): "conv2_kernel<unsigned short, 1, 8, ",
-            (16, 128, 384, 32, 0): "conv2_kernel<unsigned short, 2, 8, ", (16, 128, 256, 4, 0x10000000): "conv2_kernel<unsigned short, 4, 4, "}
+            (16, 128, 384, 32, 0): "conv2_kernel<unsigned short, 2, 8, ", (16, 128, 256, 4, TUNE_CONV_STREAM_ROUND4_RULE): "conv2_kernel<unsigned short, 4, 4, "}
     seen = 0
     for c in CONV2_CASES:
         key = (c[1], c[2], c[3], c[4], c[0])
@@ -132,11 +136,11 @@ def test_conv_stream_auto_selection_reaches_the_wide_variants():
 # ---- csrc/dcn3.hip, csrc/dcn4.hip ------------------------------------------------------------------------
 # (kind, dtype, override, B, Cin, Cout, H, W, offset_scale)
 DCN_CASES = [
-    ("fused", "bf16", 0x400, 1, 128, 128, 24, 40, 0.5),    # dcn3<bf16,4,16,2>: every >= 128-channel layer of the batch-64 plan
-    ("fused", "bf16", 0x400, 1, 256, 256, 16, 16, 3.0),
-    ("fused", "bf16", 0x400, 1, 512, 256, 16, 16, 12.0),   #   ... with most samples through pass 2 (global gather)
-    ("fused", "bf16", 0x200, 1, 256, 128, 24, 24, 0.5),    # dcn3<bf16,2,32,2> on a >64-channel layer (two channel groups)
-    ("fused", "bf16", 0x200, 1, 144, 128, 16, 16, 3.0),    # dcn3<bf16,2,16,2> (Cin not a multiple of 32)
+    ("fused", "bf16", TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 128, 128, 24, 40, 0.5),    # dcn3<bf16,4,16,2>: every >= 128-channel layer of the batch-64 plan
+    ("fused", "bf16", TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 16, 16, 3.0),
+    ("fused", "bf16", TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 512, 256, 16, 16, 12.0),   #   ... with most samples through pass 2 (global gather)
+    ("fused", "bf16", TUNE_DCN_STREAM_FORCE_NARROW_WG, 1, 256, 128, 24, 24, 0.5),    # dcn3<bf16,2,32,2> on a >64-channel layer (two channel groups)
+    ("fused", "bf16", TUNE_DCN_STREAM_FORCE_NARROW_WG, 1, 144, 128, 16, 16, 3.0),    # dcn3<bf16,2,16,2> (Cin not a multiple of 32)
     ("fused", "bf16", 0, 2, 128, 64, 24, 40, 0.5),         # dcn3<bf16,2,32,2>
     ("fused", "bf16", 0, 1, 48, 64, 20, 20, 3.0),          # dcn3<bf16,2,16,2>
     ("fused", "bf16", 0, 1, 64, 32, 20, 36, 3.0),          # dcn3<bf16,1,32,2>
@@ -148,19 +152,19 @@ DCN_CASES = [
     ("fused", "f16x3", 0, 1, 32, 32, 16, 16, 12.0),        # dcn3<x3_t,1,16,2>, most samples through pass 2
     ("fused", "f16x3", 0, 1, 256, 128, 16, 16, 3.0),       #   two channel groups
     ("fused", "f16x3", 0, 1, 64, 64, 64, 80, 3.0),         # dcn3<x3_t,2,16,6>: margin-6 apron on maps of >= 64 rows
-    ("fused", "f16x3", 0x4000, 1, 32, 32, 16, 16, 12.0),   # dcn3<x3_t,1,16,6>
-    ("fused", "f16x3", 0x2000, 1, 64, 64, 20, 24, 3.0),    # dcn3<x3_t,2,16,2>: the f32 plan's margin-2 double-buffered tile
+    ("fused", "f16x3", TUNE_DCN_FUSED_X3_MARGIN6, 1, 32, 32, 16, 16, 12.0),   # dcn3<x3_t,1,16,6>
+    ("fused", "f16x3", TUNE_DCN_FUSED_X3_MARGIN2, 1, 64, 64, 20, 24, 3.0),    # dcn3<x3_t,2,16,2>: the f32 plan's margin-2 double-buffered tile
     ("stream", "f16x3", 0, 2, 128, 64, 24, 40, 0.5),       # dcn3<x3_t,2,16,2,WDMA,256>: f16x3 with patch slots (fp32 list entries and patch units)
     ("stream", "f16x3", 0, 1, 256, 64, 16, 32, 3.0),       #   ... 4-13 % of the samples in patches, second fill round (entries >= 128)
     ("stream", "f16x3", 0, 2, 64, 64, 40, 24, 6.0),        #   ... more far samples than slots: patches AND pass 2
     ("stream", "f16x3", 0, 1, 64, 64, 16, 16, 40.0),       #   ... nearly every sample outside the apron or the image
     ("stream", "f16x3", 0, 1, 64, 32, 20, 20, 12.0),       # dcn3<x3_t,1,16,2,WDMA,256>
     ("stream", "f16x3", 0, 1, 256, 256, 16, 16, 3.0),      # dcn3<x3_t,2,16,4,WDMA,256>: margin 4 (a `node` layer above 64 channels), grid.y = 4
-    ("stream", "f16x3", 0x8000, 1, 256, 256, 16, 16, 3.0), # dcn3<x3_t,2,16,3,WDMA,256>: margin 3
-    ("stream", "f16x3", 0x10000, 1, 64, 32, 20, 20, 12.0), # dcn3<x3_t,1,16,4,WDMA,256>
-    ("stream", "f16x3", 0x10000, 2, 64, 64, 40, 24, 6.0),  #   margin 4 with more far samples than slots: patches AND pass 2
-    ("stream", "f16x3", 0x8000, 1, 64, 32, 20, 20, 12.0),  # dcn3<x3_t,1,16,3,WDMA,256>
-    ("stream", "f16x3", 0x4000, 1, 256, 128, 16, 16, 6.0), # dcn3<x3_t,2,16,2,WDMA,256> forced on a wide layer
+    ("stream", "f16x3", TUNE_DCN_STREAM_X3_MARGIN3, 1, 256, 256, 16, 16, 3.0), # dcn3<x3_t,2,16,3,WDMA,256>: margin 3
+    ("stream", "f16x3", TUNE_DCN_STREAM_X3_MARGIN4, 1, 64, 32, 20, 20, 12.0), # dcn3<x3_t,1,16,4,WDMA,256>
+    ("stream", "f16x3", TUNE_DCN_STREAM_X3_MARGIN4, 2, 64, 64, 40, 24, 6.0),  #   margin 4 with more far samples than slots: patches AND pass 2
+    ("stream", "f16x3", TUNE_DCN_STREAM_X3_MARGIN3, 1, 64, 32, 20, 20, 12.0),  # dcn3<x3_t,1,16,3,WDMA,256>
+    ("stream", "f16x3", TUNE_DCN_STREAM_X3_MARGIN2, 1, 256, 128, 16, 16, 6.0), # dcn3<x3_t,2,16,2,WDMA,256> forced on a wide layer
     ("stream", "f16x3", 0, 1, 64, 64, 13, 21, 3.0),        # odd map sizes (the C ABI takes any H, W)
     ("stream", "bf16", 0, 2, 64, 64, 13, 21, 3.0),
     ("stream", "bf16", 0, 1, 128, 128, 7, 5, 2.0),         # a map smaller than one tile both ways
@@ -170,19 +174,19 @@ DCN_CASES = [
     ("stream", "bf16", 0, 2, 64, 64, 40, 24, 6.0),         #   ... more samples leave the apron than a tile has slots: patches AND pass 2
     ("stream", "bf16", 0, 1, 64, 64, 16, 16, 40.0),        #   ... nearly every sample outside the apron or the image
     ("stream", "bf16", 0, 1, 64, 32, 20, 20, 12.0),        # dcn3<bf16,1,16,2,WDMA,256>
-    ("stream", "bf16", 0x400, 1, 128, 128, 16, 32, 3.0),   # dcn3<bf16,4,16,4,WDMA,256>: margin-4 apron (0x400: also for a small grid)
-    ("stream", "bf16", 0x400, 1, 256, 256, 24, 24, 8.0),
+    ("stream", "bf16", TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 128, 128, 16, 32, 3.0),   # dcn3<bf16,4,16,4,WDMA,256>: margin-4 apron (FORCE_WIDE_WG: also for a small grid)
+    ("stream", "bf16", TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 24, 24, 8.0),
     ("stream", "bf16", 0, 1, 256, 256, 16, 16, 3.0),       # small grid: 64-channel workgroups on a 256-channel layer (grid.y = 4)
     ("stream", "bf16", 0, 12, 128, 128, 64, 64, 0.5),      # >= 192 workgroups: the 128-channel variant without an override
     ("stream", "bf16", 0, 1, 48, 64, 20, 20, 3.0),         # Cin = 16 (mod 32): falls back to the configuration without patches
-    ("stream", "bf16", 0x1000, 2, 128, 64, 24, 40, 0.5),   # round 1's configurations: dcn3<bf16,2,16,1,WDMA,0>
-    ("stream", "bf16", 0x1000, 1, 64, 32, 20, 20, 12.0),   # dcn3<bf16,1,16,1,WDMA,0>
-    ("stream", "bf16", 0x1000, 1, 128, 128, 16, 32, 3.0),  # dcn3<bf16,4,16,2,WDMA,0>
+    ("stream", "bf16", OPF_DCN_STREAM_NO_SLOTS, 2, 128, 64, 24, 40, 0.5),   # round 1's configurations: dcn3<bf16,2,16,1,WDMA,0>
+    ("stream", "bf16", OPF_DCN_STREAM_NO_SLOTS, 1, 64, 32, 20, 20, 12.0),   # dcn3<bf16,1,16,1,WDMA,0>
+    ("stream", "bf16", OPF_DCN_STREAM_NO_SLOTS, 1, 128, 128, 16, 32, 3.0),  # dcn3<bf16,4,16,2,WDMA,0>
     ("f16", "bf16", 0, 2, 64, 64, 24, 40, 0.5),            # dcn4<2,.,1,0> DENSE
     ("f16", "bf16", 0, 1, 64, 64, 20, 20, 12.0),
-    ("f16", "bf16", 0x100, 1, 64, 64, 24, 40, 3.0),        # dcn4<2,.,0,0> one workgroup per CU
+    ("f16", "bf16", TUNE_DCN_F16_ONE_WG_PER_CU, 1, 64, 64, 24, 40, 3.0),        # dcn4<2,.,0,0> one workgroup per CU
     ("f16", "bf16", 0, 1, 64, 32, 20, 36, 3.0),            # dcn4<1,.,1,0>
-    ("f16", "bf16", 0x100, 1, 64, 32, 16, 16, 0.5),
+    ("f16", "bf16", TUNE_DCN_F16_ONE_WG_PER_CU, 1, 64, 32, 16, 16, 0.5),
     ("updcn2", "bf16", 0, 2, 64, 64, 12, 20, 0.5),         # dcn4<2,.,1,1>: 2x up-sampling + add folded in
     ("updcn2", "bf16", 0, 1, 64, 64, 10, 10, 12.0),
     ("updcn4", "bf16", 0, 1, 64, 64, 6, 10, 3.0),          # 4x (ida_up.up_2: 8x8 stride-4 deconv)
@@ -194,58 +198,58 @@ DCN_CASES = [
     ("stream", "f16", 0, 1, 256, 64, 16, 32, 3.0),
     ("stream", "f16", 0, 2, 64, 64, 40, 24, 6.0),          #   ... patches AND pass 2
     ("stream", "f16", 0, 1, 64, 32, 20, 20, 12.0),         # dcn3<f16,1,16,2,WDMA,256>
-    ("stream", "f16", 0x400, 1, 128, 128, 16, 32, 3.0),    # dcn3<f16,4,16,4,WDMA,256>: margin-4 apron
-    ("stream", "f16", 0x400, 1, 256, 256, 24, 24, 8.0),    #   (ResNet-101-DCN's first up-sampling stage in miniature)
-    # 0x8000: the wide-margin variants on the packed apron (margin 4 at two workgroups per CU; engine.dcn_wide_margin / calibration)
-    ("stream", "bf16", 0x8000, 2, 128, 64, 24, 40, 0.5),   # dcn3<bf16,2,16,4,WDMA,256,PK>
-    ("stream", "bf16", 0x8000, 1, 256, 64, 16, 32, 3.0),
-    ("stream", "bf16", 0x8000, 2, 64, 64, 40, 24, 6.0),    #   ... patches AND pass 2
-    ("stream", "bf16", 0x8000, 1, 64, 64, 16, 16, 40.0),
-    ("stream", "bf16", 0x8000, 1, 64, 32, 20, 20, 12.0),   # dcn3<bf16,1,16,4,WDMA,256,PK>
-    ("stream", "bf16", 0x8000, 1, 256, 256, 16, 16, 3.0),  # small grid: 64-channel workgroups, wide margin
-    ("stream", "bf16", 0x8400, 1, 128, 128, 16, 32, 3.0),  # the 128-channel variant has margin 4 anyway
-    ("stream", "f16", 0x8000, 2, 128, 64, 24, 40, 3.0),    # dcn3<f16,2,16,4,WDMA,256,PK>
-    ("stream", "f16", 0x8000, 1, 64, 32, 20, 20, 12.0),
-    # 0x10000: margin 2 on the packed apron with 512 patch slots, the second 256 filled in a second round per stage
-    ("stream", "bf16", 0x10000, 2, 128, 64, 24, 40, 0.5),  # dcn3<bf16,2,16,2,WDMA,512,PK>: one round
-    ("stream", "bf16", 0x10000, 2, 64, 64, 40, 24, 4.0),   #   ... tiles with 256-512 far samples: two rounds, no pass 2
-    ("stream", "bf16", 0x10000, 2, 64, 64, 40, 24, 9.0),   #   ... more than 512: two rounds AND pass 2
-    ("stream", "bf16", 0x10000, 1, 64, 32, 20, 20, 12.0),  # dcn3<bf16,1,16,2,WDMA,512,PK>
-    ("stream", "bf16", 0x10400, 1, 256, 256, 24, 24, 8.0), # dcn3<bf16,4,16,4,WDMA,512>
-    ("stream", "f16", 0x10000, 2, 64, 64, 40, 24, 4.0),
-    # stream16: bf16 plan, fp16 INPUT (reserved | 0x40000, csrc/dcn3.hip F16IN: the `node` DeformConvs behind an up-sample + add that
+    ("stream", "f16", TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 128, 128, 16, 32, 3.0),    # dcn3<f16,4,16,4,WDMA,256>: margin-4 apron
+    ("stream", "f16", TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 24, 24, 8.0),    #   (ResNet-101-DCN's first up-sampling stage in miniature)
+    # WIDE_MARGIN: the wide-margin variants on the packed apron (margin 4 at two workgroups per CU; engine.dcn_wide_margin / calibration)
+    ("stream", "bf16", OPF_DCN_STREAM_WIDE_MARGIN, 2, 128, 64, 24, 40, 0.5),   # dcn3<bf16,2,16,4,WDMA,256,PK>
+    ("stream", "bf16", OPF_DCN_STREAM_WIDE_MARGIN, 1, 256, 64, 16, 32, 3.0),
+    ("stream", "bf16", OPF_DCN_STREAM_WIDE_MARGIN, 2, 64, 64, 40, 24, 6.0),    #   ... patches AND pass 2
+    ("stream", "bf16", OPF_DCN_STREAM_WIDE_MARGIN, 1, 64, 64, 16, 16, 40.0),
+    ("stream", "bf16", OPF_DCN_STREAM_WIDE_MARGIN, 1, 64, 32, 20, 20, 12.0),   # dcn3<bf16,1,16,4,WDMA,256,PK>
+    ("stream", "bf16", OPF_DCN_STREAM_WIDE_MARGIN, 1, 256, 256, 16, 16, 3.0),  # small grid: 64-channel workgroups, wide margin
+    ("stream", "bf16", OPF_DCN_STREAM_WIDE_MARGIN | TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 128, 128, 16, 32, 3.0),  # the 128-channel variant has margin 4 anyway
+    ("stream", "f16", OPF_DCN_STREAM_WIDE_MARGIN, 2, 128, 64, 24, 40, 3.0),    # dcn3<f16,2,16,4,WDMA,256,PK>
+    ("stream", "f16", OPF_DCN_STREAM_WIDE_MARGIN, 1, 64, 32, 20, 20, 12.0),
+    # SLOTS512: margin 2 on the packed apron with 512 patch slots, the second 256 filled in a second round per stage
+    ("stream", "bf16", OPF_DCN_STREAM_SLOTS512, 2, 128, 64, 24, 40, 0.5),  # dcn3<bf16,2,16,2,WDMA,512,PK>: one round
+    ("stream", "bf16", OPF_DCN_STREAM_SLOTS512, 2, 64, 64, 40, 24, 4.0),   #   ... tiles with 256-512 far samples: two rounds, no pass 2
+    ("stream", "bf16", OPF_DCN_STREAM_SLOTS512, 2, 64, 64, 40, 24, 9.0),   #   ... more than 512: two rounds AND pass 2
+    ("stream", "bf16", OPF_DCN_STREAM_SLOTS512, 1, 64, 32, 20, 20, 12.0),  # dcn3<bf16,1,16,2,WDMA,512,PK>
+    ("stream", "bf16", OPF_DCN_STREAM_SLOTS512 | TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 24, 24, 8.0), # dcn3<bf16,4,16,4,WDMA,512>
+    ("stream", "f16", OPF_DCN_STREAM_SLOTS512, 2, 64, 64, 40, 24, 4.0),
+    # stream16: bf16 plan, fp16 INPUT (reserved | OPF_DCN_STREAM_F16_INPUT, csrc/dcn3.hip F16IN: the `node` DeformConvs behind an up-sample + add that
     # writes fp16); bf16 output
     ("stream16", "bf16", 0, 2, 64, 64, 40, 24, 0.5),       # dcn3<bf16,2,16,2,WDMA,256,false,F16IN>: the five 64 -> 64 @128x128 nodes
     ("stream16", "bf16", 0, 2, 64, 64, 40, 24, 6.0),       #   ... patches AND pass 2
     ("stream16", "bf16", 0, 1, 64, 64, 16, 16, 40.0),
-    ("stream16", "bf16", 0x400, 1, 128, 128, 16, 32, 3.0), # dcn3<bf16,4,16,4,WDMA,256,false,F16IN>: 128 -> 128 @64x64, 256 -> 256 @32x32
-    ("stream16", "bf16", 0x400, 1, 256, 256, 24, 24, 8.0),
+    ("stream16", "bf16", TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 128, 128, 16, 32, 3.0), # dcn3<bf16,4,16,4,WDMA,256,false,F16IN>: 128 -> 128 @64x64, 256 -> 256 @32x32
+    ("stream16", "bf16", TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 24, 24, 8.0),
     ("stream16", "bf16", 0, 1, 256, 256, 16, 16, 3.0),     # small grid: 64-channel workgroups
-    ("stream16", "bf16", 0x8000, 2, 64, 64, 40, 24, 6.0),  # wide margin, packed apron
-    ("stream16", "bf16", 0x10000, 2, 64, 64, 40, 24, 4.0), # 512 slots, two rounds
-    ("stream16", "bf16", 0x10400, 1, 256, 256, 24, 24, 8.0),
-    # 0x4000: csrc/dcn5.hip (apron AND filters by LDS-DMA; measured slower, kept selectable: DESIGN.md 2.2)
-    ("stream", "f16", 0x4000, 2, 128, 64, 24, 40, 0.5),    # dcn5<2,2,.,256>
-    ("stream", "f16", 0x4000, 1, 256, 64, 16, 32, 3.0),
-    ("stream", "f16", 0x4000, 2, 64, 64, 40, 24, 6.0),     #   ... patches AND pass 2
-    ("stream", "f16", 0x4000, 1, 64, 32, 20, 20, 12.0),    # dcn5<1,2,.,256>
-    ("stream", "f16", 0x4400, 1, 128, 128, 16, 32, 3.0),   # dcn5<4,4,.,256>
-    ("stream", "f16", 0x4400, 1, 256, 256, 24, 24, 8.0),
-    ("stream", "f16", 0x4000, 1, 48, 64, 20, 20, 3.0),     # three stages (no two-stage unrolling in dcn5)
-    ("stream", "f16", 0x4000, 1, 64, 64, 16, 16, 40.0),
+    ("stream16", "bf16", OPF_DCN_STREAM_WIDE_MARGIN, 2, 64, 64, 40, 24, 6.0),  # wide margin, packed apron
+    ("stream16", "bf16", OPF_DCN_STREAM_SLOTS512, 2, 64, 64, 40, 24, 4.0), # 512 slots, two rounds
+    ("stream16", "bf16", OPF_DCN_STREAM_SLOTS512 | TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 24, 24, 8.0),
+    # F16_DCN5: csrc/dcn5.hip (apron AND filters by LDS-DMA; measured slower, kept selectable: DESIGN.md 2.2)
+    ("stream", "f16", TUNE_DCN_STREAM_F16_DCN5, 2, 128, 64, 24, 40, 0.5),    # dcn5<2,2,.,256>
+    ("stream", "f16", TUNE_DCN_STREAM_F16_DCN5, 1, 256, 64, 16, 32, 3.0),
+    ("stream", "f16", TUNE_DCN_STREAM_F16_DCN5, 2, 64, 64, 40, 24, 6.0),     #   ... patches AND pass 2
+    ("stream", "f16", TUNE_DCN_STREAM_F16_DCN5, 1, 64, 32, 20, 20, 12.0),    # dcn5<1,2,.,256>
+    ("stream", "f16", TUNE_DCN_STREAM_F16_DCN5 | TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 128, 128, 16, 32, 3.0),   # dcn5<4,4,.,256>
+    ("stream", "f16", TUNE_DCN_STREAM_F16_DCN5 | TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 256, 256, 24, 24, 8.0),
+    ("stream", "f16", TUNE_DCN_STREAM_F16_DCN5, 1, 48, 64, 20, 20, 3.0),     # three stages (no two-stage unrolling in dcn5)
+    ("stream", "f16", TUNE_DCN_STREAM_F16_DCN5, 1, 64, 64, 16, 16, 40.0),
     ("stream", "f16", 0, 1, 256, 256, 16, 16, 3.0),        # small grid: 64-channel workgroups
     ("stream", "f16", 0, 1, 48, 64, 20, 20, 3.0),          # Cin = 16 (mod 32): no patches
     ("stream", "f16", 0, 1, 64, 64, 16, 16, 40.0),         #   ... nearly every sample outside the apron or the image
     ("stream", "f16", 0, 12, 128, 128, 64, 64, 0.5),       # >= 192 workgroups: the 128-channel variant without an override
-    ("stream", "f16", 0x1000, 1, 64, 32, 20, 20, 12.0),    # 0x1000: no patch slots, dcn3<f16,1,16,1,WDMA,0>
+    ("stream", "f16", OPF_DCN_STREAM_NO_SLOTS, 1, 64, 32, 20, 20, 12.0),    # no patch slots, dcn3<f16,1,16,1,WDMA,0>
     ("fused", "f16", 0, 1, 64, 32, 20, 36, 3.0),           # register-staged filters: dcn3<f16,1,32,2>
-    ("fused", "f16", 0x400, 1, 128, 128, 24, 40, 0.5),     # dcn3<f16,4,16,2>
+    ("fused", "f16", TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 128, 128, 24, 40, 0.5),     # dcn3<f16,4,16,2>
 ]
 
 
 def _is_extra(case):
-    """Cases of the superseded generations (csrc/dcn4.hip: kinds f16 / updcn*; csrc/dcn5.hip: fp16 stream cases with 0x4000): `make EXTRA=1`."""
-    return case[0] in ("f16", "updcn2", "updcn4") or (case[0] == "stream" and case[1] == "f16" and bool(case[2] & 0x4000))
+    """Cases of the superseded generations (csrc/dcn4.hip: kinds f16 / updcn*; csrc/dcn5.hip: fp16 stream cases with TUNE_DCN_STREAM_F16_DCN5): `make EXTRA=1`."""
+    return case[0] in ("f16", "updcn2", "updcn4") or (case[0] == "stream" and case[1] == "f16" and bool(case[2] & TUNE_DCN_STREAM_F16_DCN5))
 
 
 def _active_dcn_cases():
@@ -300,7 +304,7 @@ def test_dcn_fused_variant_matches_oracle(case):
     assert torch.equal(got, built.run()), built.name
 
 
-@pytest.mark.parametrize("dtype,ov", [("bf16", 0), ("f16", 0), pytest.param("f16", 0x4000, marks=pytest.mark.extra), ("bf16", 0x8000), ("bf16", 0x10000)])
+@pytest.mark.parametrize("dtype,ov", [("bf16", 0), ("f16", 0), pytest.param("f16", TUNE_DCN_STREAM_F16_DCN5, marks=pytest.mark.extra), ("bf16", OPF_DCN_STREAM_WIDE_MARGIN), ("bf16", OPF_DCN_STREAM_SLOTS512)])
 def test_dcn_tiles_with_more_far_samples_than_patch_slots_are_deterministic(dtype, ov):
     # A tile with more than NP samples outside its apron sends the surplus through pass 2 (another accumulation order).  Round 2
     # handed out the slots with an LDS atomic per wave, so WHICH samples were the surplus depended on the order the waves arrived
@@ -345,17 +349,17 @@ def test_dcn_wide_margin_variant_is_bit_identical_while_no_tile_overflows():
     # A sample inside the apron is blended from LDS in phase B; the same sample outside a narrower apron is blended by the same
     # fp16 chain when its patch pixel is filled and then read back with weights (1, 0, 0, 0): the same value.  So the margin-2 and the
     # margin-4 (packed apron) variants agree bit for bit as long as neither has a tile with more far samples than patch slots.
-    # The same holds for the 512-slot variant (0x10000: packed margin-2 apron, second patch round) -- which is why the timed calibration
+    # The same holds for the 512-slot variant (OPF_DCN_STREAM_SLOTS512: packed margin-2 apron, second patch round) -- which is why the timed calibration
     # (DLAEngine.calibrate_dcn_margins), whose choices can differ from run to run, does not change a plan's outputs unless a tile
     # overflows its slots (then pass 2 and a patch accumulate in different orders: only the tolerance against the oracle is shared).
     for dtype in ("bf16", "f16"):
         for shape in ((2, 128, 64, 40, 56, 1.5), (1, 64, 64, 48, 48, 2.5), (1, 64, 32, 24, 40, 1.5)):
             narrow = _dcn_built(("stream", dtype, 0) + shape)[5]
-            wide = _dcn_built(("stream", dtype, 0x8000) + shape)[5]
+            wide = _dcn_built(("stream", dtype, OPF_DCN_STREAM_WIDE_MARGIN) + shape)[5]
             assert ", 4, " in wide.name and wide.name.endswith(", true>") and not narrow.name.endswith(", true>"), (narrow.name, wide.name)
             ref = narrow.run().clone()
             assert torch.equal(ref, wide.run()), (dtype, shape)
-            more = _dcn_built(("stream", dtype, 0x10000) + shape)[5]
+            more = _dcn_built(("stream", dtype, OPF_DCN_STREAM_SLOTS512) + shape)[5]
             assert ", 512, true>" in more.name, more.name
             assert torch.equal(ref, more.run()), (dtype, shape, "512 slots")
 
@@ -364,12 +368,12 @@ def test_dcn_f16_stream_dispatch():
     from conftest import has_extra
     names = {c: _dcn_built(c)[5].name for c in _active_dcn_cases() if c[0] == "stream" and c[1] == "f16"}
     for c, n in names.items():
-        assert n.startswith("dcn5_kernel<" if c[2] & 0x4000 else "dcn3_kernel<f16_t"), (c, n)
-        assert n.endswith(", true>") == bool(c[2] & 0x18000 and not c[2] & 0x400), (c, n)
+        assert n.startswith("dcn5_kernel<" if c[2] & TUNE_DCN_STREAM_F16_DCN5 else "dcn3_kernel<f16_t"), (c, n)
+        assert n.endswith(", true>") == bool(c[2] & (OPF_DCN_STREAM_WIDE_MARGIN | OPF_DCN_STREAM_SLOTS512) and not c[2] & TUNE_DCN_STREAM_FORCE_WIDE_WG), (c, n)
     if has_extra():
         assert {"dcn5_kernel<2, 2, 2, 256>", "dcn5_kernel<1, 2, 1, 256>", "dcn5_kernel<4, 4, 2, 256>"} <= set(names.values()), names
-    else:       # the default library answers the 0x4000 request with a clear error instead of another kernel
-        c = [c for c in DCN_CASES if c[0] == "stream" and c[1] == "f16" and c[2] & 0x4000][0]
+    else:       # the default library answers the TUNE_DCN_STREAM_F16_DCN5 request with a clear error instead of another kernel
+        c = [c for c in DCN_CASES if c[0] == "stream" and c[1] == "f16" and c[2] & TUNE_DCN_STREAM_F16_DCN5][0]
         with pytest.raises(RuntimeError, match="EXTRA=1"):
             _dcn_built(c)[5].name
 

@@ -16,7 +16,7 @@ plan = det.model.engine(dev).plan(B, 512, 512)
 n = len(plan.ops)
 ms = (ctypes.c_float * n)()
 idx = [i for i, op in enumerate(plan.ops) if op.kind == _lib.OP_CONV_STREAM]
-cfgs = [int(c, 16) for c in sys.argv[1:]] or [0, 0x410, 0x408, 0x404, 0x208, 0x204]
+cfgs = [int(c, 16) for c in sys.argv[1:]] or [0, 0x410, 0x408, 0x404, 0x208, 0x204]      # _lib.TUNE_CONV_STREAM_TILE(variant, MT, WAVES) = variant << 12 | MT << 8 | WAVES
 res = {}
 for rep in range(2):
     for cfg in cfgs:

@@ -15,7 +15,7 @@ plan = det.model.engine(dev).plan(B, 512, 512)
 n = len(plan.ops)
 ms = (ctypes.c_float * n)()
 idx = [i for i, op in enumerate(plan.ops) if op.kind == _lib.OP_CONV and op.ksize == 1 and op.Cin % 64 == 0 and op.Cout > 32]
-cfgs = [0, 0x1000 | 4 << 4 | 2, 0x1000 | 4 << 4 | 1, 0x1000 | 2 << 4 | 2, 0x1000 | 2 << 4 | 1]
+cfgs = [0] + [_lib.TUNE_CONV_1X1_TILE(mt, th) for mt, th in ((4, 16), (4, 8), (2, 16), (2, 8))]
 res = {}
 for rep in range(3):
     for cfg in cfgs:

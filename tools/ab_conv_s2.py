@@ -15,7 +15,7 @@ plan = det.model.engine(dev).plan(B, 512, 512)
 n = len(plan.ops)
 ms = (ctypes.c_float * n)()
 idx = [i for i, op in enumerate(plan.ops) if op.kind == _lib.OP_CONV_STREAM and op.stride == 2]
-cfgs = [0, 0x2404, 0x4408, 0x4204]      # 0 = one slot (default), 0x2404 = two slots, ...
+cfgs = [0, 0x2404, 0x4408, 0x4204]      # _lib.TUNE_CONV_STREAM_TILE(variant, MT, WAVES) = variant << 12 | MT << 8 | WAVES; 0 = one slot (default), variant 2 = two slots, 4 = one
 res = {}
 for rep in range(3):
     for cfg in cfgs:

@@ -1,5 +1,5 @@
 """Profiling aid: tile configurations of the f16x3 3x3 convolutions (csrc/conv.hip launch_conv_t<x3_t>), A/B'd inside one process on the
-ops of the batch-64 f16x3 plan: reserved = 0x1000 | MT << 8 | WAVES << 4 | TH >> 3 (0 = the launcher's own choice).
+ops of the batch-64 f16x3 plan: reserved = _lib.TUNE_CONV_X3_TILE(MT, WAVES, TH), i.e. TUNE_CONV_X3_TILED | MT << 8 | WAVES << 4 | TH >> 3 (0 = the launcher's own choice).
 
     python tools/ab_conv_x3.py [--batch 64]
 """

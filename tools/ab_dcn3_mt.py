@@ -1,4 +1,4 @@
-"""Profiling aid: 128-channel workgroups (default) vs 64-channel workgroups (h3d_op.reserved = 0x200) on the register-staged
+"""Profiling aid: 128-channel workgroups (default) vs 64-channel workgroups (h3d_op.reserved = TUNE_DCN_STREAM_FORCE_NARROW_WG) on the register-staged
 fused DeformConvs of the bench plan, in ONE process."""
 import ctypes, sys, numpy as np, torch
 sys.path.insert(0, ".")
@@ -19,7 +19,7 @@ ms = (ctypes.c_float * n)()
 idx = [i for i, op in enumerate(plan.ops) if op.kind == _lib.OP_DCN_FUSED and op.Cout > 64]
 res = {}
 for rep in range(3):
-    for cfg in (0, 0x200, 0x400):
+    for cfg in (0, _lib.TUNE_DCN_STREAM_FORCE_NARROW_WG, _lib.TUNE_DCN_STREAM_FORCE_WIDE_WG):
         for i in idx:
             plan.op_array[i].reserved = cfg
         tot = np.zeros(n)
@@ -32,4 +32,4 @@ for i in idx:
 print("op (Cin,Cout,H): default  64-ch workgroups  128-ch workgroups")
 for i in idx:
     op = plan.ops[i]
-    print(i, (op.Cin, op.Cout, op.H), " ".join("%.3f" % res[c][i] for c in (0, 0x200, 0x400)))
+    print(i, (op.Cin, op.Cout, op.H), " ".join("%.3f" % res[c][i] for c in (0, _lib.TUNE_DCN_STREAM_FORCE_NARROW_WG, _lib.TUNE_DCN_STREAM_FORCE_WIDE_WG)))

@@ -1,5 +1,5 @@
 """Profiling aid: the <= 64-channel DeformConvs of the fp16 bench plan through csrc/dcn5.hip's experiment variants
-(h3d_op.reserved >> 16) and through csrc/dcn3.hip's register-staged apron (0x2000), in ONE process.
+(TUNE_DCN_STREAM_DCN5_XP) and through csrc/dcn3.hip's register-staged apron (0), in ONE process.
     python tools/ab_dcn5.py [batch] [xp ...]"""
 import ctypes, sys, numpy as np, torch
 sys.path.insert(0, ".")
@@ -12,7 +12,7 @@ opt = Opt(input_h=512, input_w=512, smpl=True, dtype="f16")
 sd = synth.synth_state_dict(arch.state_dict_shapes(opt.heads, True), seed=0, gain=1.25)
 det = MultiPoseDetector(opt, {k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()}, device=dev)
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
-xps = [int(v, 0) for v in sys.argv[2:]] or [0, 0x4000, 0x4000 | 1 << 16, 0x4000 | 2 << 16, 0x4000 | 17 << 16]      # 0 = csrc/dcn3.hip (default)
+xps = [int(v, 0) for v in sys.argv[2:]] or [0, _lib.TUNE_DCN_STREAM_F16_DCN5] + [_lib.TUNE_DCN_STREAM_F16_DCN5 | _lib.TUNE_DCN_STREAM_DCN5_XP(xp) for xp in (1, 2, 17)]      # 0 = csrc/dcn3.hip (default)
 x = torch.from_numpy(synth.synth_image_batch(B, 512, 512)).to(dev)
 det.run(x); torch.cuda.synchronize()
 plan = det.model.engine(dev).plan(B, 512, 512)

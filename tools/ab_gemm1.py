@@ -28,7 +28,8 @@ plan = det.model.engine(dev).plan(B, hw, hw)
 n = len(plan.ops)
 ms = (ctypes.c_float * n)()
 idx = [i for i, op in enumerate(plan.ops) if op.kind == _lib.OP_CONV and op.ksize == 1 and op.stride == 1 and op.Cin % 64 == 0 and op.Cin >= 128]
-cfgs = [0x2000, 0, 0x4100, 0x4200, 0x4300]
+HALO = _lib.TUNE_CONV_HALO_TILE
+cfgs = [HALO, 0, 0x4100, 0x4200, 0x4300]      # 0x4n00 = _lib.TUNE_CONV_FORCE_GEMM | _lib.TUNE_CONV_GEMM_TILE(n): the 256x256 / 128x256 / 128x128 tile
 idx_s2 = [i for i, op in enumerate(plan.ops) if op.kind == _lib.OP_CONV and op.ksize == 1 and op.stride == 2 and op.Cin % 64 == 0 and op.Cin >= 128]
 idx = idx + idx_s2
 res = {}
@@ -36,7 +37,7 @@ for rep in range(2):
     for cfg in cfgs:
         for i in idx:      # a forced tile needs cdiv(Cout, BM) * BM packed rows (the launcher refuses otherwise)
             bm = 256 if cfg == 0x4100 else 128
-            plan.op_array[i].reserved = cfg if -(-plan.ops[i].Cout // bm) * bm <= plan.ops[i].wrows or cfg in (0, 0x2000) else 0
+            plan.op_array[i].reserved = cfg if -(-plan.ops[i].Cout // bm) * bm <= plan.ops[i].wrows or cfg in (0, HALO) else 0
         tot = np.zeros(n)
         for _ in range(3):
             _lib.check(_lib.lib().h3d_run_ops_timed(plan.op_array, n, _lib.stream_ptr(), ms), "timed")
@@ -52,6 +53,6 @@ for i in idx:
     seen.setdefault(key, []).append(i)
 for key, ii in seen.items():
     t = {c: float(np.mean([res[c][i] for i in ii])) for c in cfgs}
-    print("%2d x %-28s %.3f | %s   [%.0f]" % (len(ii), key, t[0x2000], " ".join("%.3f" % t[c] for c in cfgs[1:]),
+    print("%2d x %-28s %.3f | %s   [%.0f]" % (len(ii), key, t[HALO], " ".join("%.3f" % t[c] for c in cfgs[1:]),
                                               op_flops(plan.ops[ii[0]]) / t[0] / 1e9))
 print("total ms: " + "  ".join("%#x %.3f" % (c, sum(res[c][i] for i in idx)) for c in cfgs))

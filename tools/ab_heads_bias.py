@@ -1,5 +1,5 @@
 """Profiling aid: heads kernel with the bias as the first MFMA's C operand (default) vs a separate bias / zeroing
-pass (h3d_op.reserved = 0x200), same process, interleaved."""
+pass (h3d_op.reserved = TUNE_HEADS_SEPARATE_BIAS), same process, interleaved."""
 import ctypes, sys, numpy as np, torch
 sys.path.insert(0, ".")
 import h3d_amd
@@ -17,9 +17,9 @@ plan = eng.plan(B, 512, 512)
 n = len(plan.ops)
 ms = (ctypes.c_float * n)()
 idx = [i for i, op in enumerate(plan.ops) if op.kind == _lib.OP_HEADS]
-res = {0: np.zeros(n), 0x200: np.zeros(n)}
+res = {0: np.zeros(n), _lib.TUNE_HEADS_SEPARATE_BIAS: np.zeros(n)}
 for rep in range(6):
-    for flag in (0, 0x200):
+    for flag in (0, _lib.TUNE_HEADS_SEPARATE_BIAS):
         for i in idx:
             plan.op_array[i].reserved = flag
         _lib.check(_lib.lib().h3d_run_ops_timed(plan.op_array, n, _lib.stream_ptr(), ms), "timed")
@@ -27,5 +27,5 @@ for rep in range(6):
             res[flag] += np.frombuffer(ms, dtype=np.float32, count=n)
 for i in idx:
     plan.op_array[i].reserved = 0
-for flag in (0, 0x200):
+for flag in (0, _lib.TUNE_HEADS_SEPARATE_BIAS):
     print("reserved=0x%x:" % flag, " ".join("%.3f" % (res[flag][i] / 5) for i in idx), "sum %.3f" % (res[flag][idx].sum() / 5))

@@ -1,6 +1,6 @@
 """Profiling aid: time the ops of one kind of a plan under several `h3d_op.reserved` tuning overrides inside ONE process.
 
-    python tools/ab_op_reserved.py --dtype f16x3 --kind 9 --codes 0 0x2000 0x4000        # H3D_OP_DCN_FUSED of the f16x3 plan: margin 4 / 2 / 6
+    python tools/ab_op_reserved.py --dtype f16x3 --kind 9 --codes 0 0x2000 0x4000        # H3D_OP_DCN_FUSED of the f16x3 plan: the rule / TUNE_DCN_FUSED_X3_MARGIN2 / _MARGIN6
 """
 import argparse, ctypes, sys, numpy as np, torch
 sys.path.insert(0, ".")
