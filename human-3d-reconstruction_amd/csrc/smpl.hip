@@ -232,7 +232,9 @@ __global__ __launch_bounds__(256) void smpl_verts_kernel(const float *__restrict
     float acc[PT][3];
     const float t0 = v_template[vc], t1 = v_template[Vpad + vc], t2 = v_template[2 * Vpad + vc];
 #pragma unroll
-    for (int q = 0; q < PT; ++q) { acc[q][0] = t0; acc[q][1] = t1; acc[q][2] = t2; }
+    // the chain starts from zero and the template is added once, after it (as generation 3 does): started from the template, every one of
+    // the 217 roundings is one of a body-sized number (2^-24 each, 4e-7 together) instead of one of the centimetre-sized displacement
+    for (int q = 0; q < PT; ++q) { acc[q][0] = 0.f; acc[q][1] = 0.f; acc[q][2] = 0.f; }
     const size_t V3 = (size_t)Vpad * 3;
 #pragma unroll 2
     for (int k = 0; k < NC; ++k) {
@@ -285,7 +287,7 @@ __global__ __launch_bounds__(256) void smpl_verts_kernel(const float *__restrict
                 for (int i = 0; i < 12; ++i) T[i] = fmaf(w, s_A[q][j * 12 + i], T[i]);
             }
         }
-        const float x = acc[q][0], y = acc[q][1], z = acc[q][2];
+        const float x = t0 + acc[q][0], y = t1 + acc[q][1], z = t2 + acc[q][2];
         if (v < V) {
             float *o = verts + ((size_t)p * V + v) * 3;
             o[0] = T[0] * x + T[1] * y + T[2] * z + T[3];

@@ -35,6 +35,11 @@ class SMPLModel:
         assert self.posedirs.shape == (V, 3, NUM_POSE_FEAT)
         assert self.J_regressor.shape == (NUM_JOINTS, V)
         assert self.weights.shape == (V, NUM_JOINTS)
+        # smpl_pose_kernel walks the joints in their stored order and fetches the parent's transform by a shuffle: parents first
+        par = self.parents
+        if par.shape != (NUM_JOINTS,) or par[0] != -1 or not all(0 <= par[j] < j for j in range(1, NUM_JOINTS)):
+            raise ValueError("SMPLModel: parents must be %d entries with parents[0] == -1 and 0 <= parents[j] < j (parents first), got %s"
+                             % (NUM_JOINTS, par.tolist()))
         self._dev = None
 
     @classmethod

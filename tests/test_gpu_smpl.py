@@ -61,7 +61,7 @@ def test_matrix_core_kernel_agrees_with_vector_kernel(model):
     betas = torch.from_numpy(synth.normalish("b", (P, 10), 0, 1, 5)).to(DEV)
     thetas = torch.from_numpy(synth.normalish("t", (P, 72), 0, 0.3, 5)).to(DEV)
     v3 = smpl.lbs(model, betas, thetas, kernel="gen3")
-    v2 = smpl.lbs(model, betas, thetas, kernel="gen1")          # the fp32 vector kernel (generation 2, the same arithmetic, is an EXTRA=1 build option)
+    v2 = smpl.lbs(model, betas, thetas, kernel="gen1")          # the fp32 vector kernel (generation 2, the same chain started from the template instead of from zero, is an EXTRA=1 build option)
     assert float((v3 - v2).abs().max()) < 1.5e-5
     # gen 3x (h3d_smpl_verts3_exact: all six products, 2^-24 relative -- ADVICE r2: the variant used to exist only behind a
     # compile-time switch no test built; the f32 parity-mode detectors run it) agrees with the fp32 vector kernel to 2e-6,
