@@ -17,8 +17,7 @@
 //  * f32 (parity) mode keeps the reference's float operation order (sum of 4 products, then *mask).
 #include "common.h"
 #include "epilogue.h"
-
-#include "dcn_traits.h"
+#include "dcn_tile.h"
 
 struct Dcn2Args {
     const char *in;
@@ -157,9 +156,8 @@ __global__ __launch_bounds__(512 / NT_) void dcn2_kernel(Dcn2Args a)
                 const int hl = (int)floorf(h_im), wl = (int)floorf(w_im);
                 const int ry = hl - hy0, rx = wl - hx0;
                 if (ry >= 0 && ry + 1 < C::HH && rx >= 0 && rx + 1 < C::HH) {
-                    const float lh = h_im - (float)hl, lw = w_im - (float)wl;
-                    const float hh = 1.f - lh, hw = 1.f - lw;
-                    const float w4[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
+                    float w4[4];
+                    dcn_bilinear_w(h_im, w_im, (float)hl, (float)wl, w4);
                     g = X::make_geo(w4, (a.mask_final ? omv[18 + tap] : dcn2_sigmoid(omv[18 + tap])) * xsc);
                     off = 8 * h * SS + ry * C::RBH + rx * C::SBH;
                 } else {
@@ -340,26 +338,9 @@ __global__ __launch_bounds__(512 / NT_) void dcn2_kernel(Dcn2Args a)
                     const float *omp = a.om + ((size_t)(b * a.H + oy) * a.W + ox) * a.om_cs;
                     const float h_im = (float)(oy - 1 + ti) + omp[2 * tap];
                     const float w_im = (float)(ox - 1 + tj) + omp[2 * tap + 1];
-                    if (!(h_im > -1.f && w_im > -1.f && h_im < (float)a.H && w_im < (float)a.W)) continue;
-                    const int hl = (int)floorf(h_im), wl = (int)floorf(w_im);
-                    const int ry = hl - hy0, rx = wl - hx0;
-                    if (ry >= 0 && ry + 1 < C::HH && rx >= 0 && rx + 1 < C::HH) continue;   // done in pass 1
-                    any = true;
-                    const float lh = h_im - (float)hl, lw = w_im - (float)wl;
-                    const float hh = 1.f - lh, hw = 1.f - lw;
-                    const float w4[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
-                    const typename X::geo g = X::make_geo(w4, (a.mask_final ? omp[18 + tap] : dcn2_sigmoid(omp[18 + tap])) * xsc);
-                    const bool okh0 = hl >= 0, okh1 = hl + 1 <= a.H - 1, okw0 = wl >= 0, okw1 = wl + 1 <= a.W - 1;
-                    const bool ok[4] = {okh0 && okw0, okh0 && okw1, okh1 && okw0, okh1 && okw1};
-                    const int pix[4] = {hl * a.W + wl, hl * a.W + wl + 1, (hl + 1) * a.W + wl, (hl + 1) * a.W + wl + 1};
-#pragma unroll
-                    for (int kk = 0; kk < CK / 16; ++kk) {
-                        typename X::frag v[4];
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            v[k] = ok[k] ? X::global8(img + ((size_t)pix[k] * a.in_cs + c0 + kk * 16 + 8 * h) * ES) : X::zero();
-                        fb[n][kk] = X::blend(v, g);
-                    }
+                    any |= dcn_far_gather<X, C::HH>(fb[n], true, h_im, w_im, hy0, hx0, a.H, a.W,
+                        [&] { return (a.mask_final ? omp[18 + tap] : dcn2_sigmoid(omp[18 + tap])) * xsc; },
+                        [&](int kk, int y, int x) { return X::global8(img + ((size_t)(y * a.W + x) * a.in_cs + c0 + kk * 16 + 8 * h) * ES); });
                 }
                 if (!__any(any)) continue;          // wave-uniform: no lane of this wave has a slow sample at this tap
 #pragma unroll
@@ -386,9 +367,7 @@ __global__ __launch_bounds__(512 / NT_) void dcn2_kernel(Dcn2Args a)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[m][n][i] = acc[m][n][i] * wun * xun;
     }
-    EpiArgs e;
-    e.bias = a.bias; e.res = nullptr; e.out = a.out; e.Ho = a.H; e.Wo = a.W; e.Cout = a.Cout;
-    e.out_cs = a.out_cs; e.res_cs = 0; e.relu = a.relu; e.out_mode = a.out_mode;
+    const EpiArgs e = dcn_epi_args(a);
     tile_epilogue<typename StoreT<T>::type, MT, NT>(acc, e, b, oy0, ox0, cout0, wv, r, h);
 }
 
@@ -410,24 +389,11 @@ static int launch_dcn2_cfg(const Dcn2Args &a0, hipStream_t st)
 
 int h3d_launch_dcn2(const h3d_op &op, hipStream_t st)
 {
-    if (!op.in || !op.w || !op.bias || !op.out || !op.in2) H3D_FAIL(H3D_ERR_ARG, "dcn: null pointer");
-    const int es = op.dtype == H3D_BF16 ? 2 : 4;
-    if (op.ksize != 3 || op.stride != 1 || op.Ho != op.H || op.Wo != op.W)
-        H3D_FAIL(H3D_ERR_UNSUPPORTED, "dcn op: network path covers 3x3 s1 p1 d1 dg1 only (k=%d s=%d)", op.ksize, op.stride);
-    if (op.Cin % 16 || op.in_cs % (16 / es) || op.Cin > op.in_cs || op.in2_cs < 28 || op.in2_cs % 4)
-        H3D_FAIL(H3D_ERR_SHAPE, "dcn: Cin=%d (stride %d) must be a multiple of 16; offset stride %d must be a multiple of 4, >= 28",
-                 op.Cin, op.in_cs, op.in2_cs);
-    if (op.H > 32767 || op.W > 32767) H3D_FAIL(H3D_ERR_SHAPE, "dcn: image larger than 32767");
-    if (op.wrows < ((op.Cout + 127) / 128) * 128)
-        H3D_FAIL(H3D_ERR_SHAPE, "dcn: packed weight rows %d < Cout %d padded to 128", op.wrows, op.Cout);
-    if (op.out_mode != H3D_OUT_NCHW_F32 && (op.out_cs % 4 || op.Cout > op.out_cs))
-        H3D_FAIL(H3D_ERR_SHAPE, "dcn: out channel stride %d", op.out_cs);
+    if (const int rc = dcn_check_op(op, "dcn", op.dtype == H3D_BF16 ? 2 : 4, true)) return rc;
     if ((long)op.H * op.W > (1L << 30)) H3D_FAIL(H3D_ERR_SHAPE, "dcn: image too large");
     Dcn2Args a;
-    a.in = (const char *)op.in; a.w = (const char *)op.w; a.bias = op.bias; a.om = (const float *)op.in2;
-    a.out = (char *)op.out; a.B = op.B; a.H = op.H; a.W = op.W; a.Cin = op.Cin; a.in_cs = op.in_cs;
-    a.om_cs = op.in2_cs; a.Cout = op.Cout; a.out_cs = op.out_cs; a.relu = op.relu; a.out_mode = op.out_mode;
-    a.tiles_x = a.tiles_y = 0;
+    dcn_fill_args(op, a);
+    a.w = (const char *)op.w; a.om = (const float *)op.in2; a.Cin = op.Cin; a.om_cs = op.in2_cs;
     a.dbg = op.reserved & H3D_TUNE_DCN_ABLATE_MASK;
     a.mask_final = (op.reserved & H3D_OPF_DCN_MASK_FINAL) ? 1 : 0;
     a.wmax = nullptr;

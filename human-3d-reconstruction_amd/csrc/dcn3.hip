@@ -23,8 +23,7 @@
 //            the phase-A accumulators, corners gathered from global memory.
 #include "common.h"
 #include "epilogue.h"
-#include "dcn_traits.h"
-#include <type_traits>
+#include "dcn_tile.h"
 
 struct Dcn3Args {
     const char *in;
@@ -100,27 +99,8 @@ struct Dcn3Cfg {
     static_assert(NP * (CK * SS / 16) <= 1024, "at most two 16-byte patch units per thread (the second one in a second fill round)");
 };
 
-// WDMA (bf16 plans): the filters are stage-major fp16 LDS images (H3D_OP_DCN_FUSED_STREAM) copied by LDS-DMA into a
+// WDMA (bf16 plans): the filters are stage-major fp16 LDS images (H3D_OP_DCN_FUSED_STREAM) copied by LDS-DMA (dcn_lds_dma) into a
 // two-slot ring one stage ahead; only the apron (which must be converted) still goes through registers.
-template <int PIECES>
-__device__ __forceinline__ void dcn3_issue_w(const char *base, int bytes, char *dst, int src, int lane16, int wv)
-{
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, bytes, 0x00020000);
-#pragma unroll
-    for (int j = 0; j < (PIECES + 7) / 8; ++j) {
-        const int p = wv + 8 * j;
-        if (p < PIECES)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)(dst + p * 1024), 16, lane16, src + p * 1024, 0, 0);
-    }
-}
-
-// one corner of a patch entry: 16 bytes at byte offset voff (+ soff, the stage's channel offset) of image `img`; an offset
-// beyond `bytes` (corner outside the image, idle thread) reads as zero
-__device__ __forceinline__ u32x4 dcn3_patch_corner(const char *img, int bytes, int voff, int soff)
-{
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)img, 0, bytes, 0x00020000);
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
-}
 
 // F16IN (round 4, bf16 plans): the INPUT tensor is fp16 although the plan (filters' companion type, output, epilogue) is bf16 -- the
 // `node` DeformConvs of IDAUp read a tensor only they consume (`node(up(proj(x)) + skip)`, model.py:384-390), so the up-sample + add
@@ -204,8 +184,8 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
     auto issue_w = [&](int s) {
         if constexpr (WDMA) {
             char *dst = s_w + (s & 1) * C::WSLOT;
-            if (s < nchunks) dcn3_issue_w<C::OPIECES>(a.woff, off_bytes, dst, s * C::WGRP, l * 16, wvu);
-            else dcn3_issue_w<C::WPIECES>(a.w, main_bytes, dst, ((s - nchunks) * a.G + (int)blockIdx.y * MT) * C::WGRP, l * 16, wvu);
+            if (s < nchunks) dcn_lds_dma<C::OPIECES>(a.woff, off_bytes, dst, s * C::WGRP, l * 16, wvu);
+            else dcn_lds_dma<C::WPIECES>(a.w, main_bytes, dst, ((s - nchunks) * a.G + (int)blockIdx.y * MT) * C::WGRP, l * 16, wvu);
         }
     };
 
@@ -299,7 +279,7 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
             constexpr int q = decltype(P)::value;
             const int c0 = (s < nchunks ? s : s - nchunks) * CK;
 #pragma unroll
-            for (int j = 0; j < NV; ++j) stg2[q][j] = dcn3_patch_corner(img, img_bytes, avoff[j], c0 * ES);
+            for (int j = 0; j < NV; ++j) stg2[q][j] = dcn_corner16(img, img_bytes, avoff[j], c0 * ES);
         }
     };
     auto store2 = [&](auto P, auto PHASE_A) {
@@ -427,9 +407,8 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
             const float fh = floorf(h_im), fw = floorf(w_im);
             const int hl = (int)fh, wl = (int)fw;
             const int ry = hl - hy0, rx = wl - hx0;
-            const float lh = h_im - fh, lw = w_im - fw;
-            const float hh = 1.f - lh, hw = 1.f - lw;
-            const float w4[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
+            float w4[4];
+            dcn_bilinear_w(h_im, w_im, fh, fw, w4);
             // a gated sample keeps zero weights times its mask: the reference's `val * mask` with val = 0 (im2col.cu:178), NaN for a NaN mask
             const float w4g[4] = {inside ? w4[0] : 0.f, inside ? w4[1] : 0.f, inside ? w4[2] : 0.f, inside ? w4[3] : 0.f};
             typename X::geo g = X::make_geo(w4g, dcn2_sigmoid(aoffs[3 * u + 2]));
@@ -560,7 +539,7 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int voff = pbase + ((k & 1) + (k >> 1) * a.W) * a.in_cs * ES;
-                pst[k] = dcn3_patch_corner(img, img_bytes, ((pok >> k) & 1) ? voff : 0x7ffffff0, c0 * ES);   // idle threads / corners outside: zeros
+                pst[k] = dcn_corner16(img, img_bytes, ((pok >> k) & 1) ? voff : 0x7ffffff0, c0 * ES);   // idle threads / corners outside: zeros
             }
         }
     };
@@ -613,7 +592,7 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
                 const int yy = hl + (k >> 1), xx = wl + (k & 1);
                 const bool ok = yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
                 const int voff = base2 + ((k & 1) + (k >> 1) * a.W) * a.in_cs * ES;
-                c[k] = dcn3_patch_corner(img, img_bytes, ok ? voff : 0x7ffffff0, c0 * ES);
+                c[k] = dcn_corner16(img, img_bytes, ok ? voff : 0x7ffffff0, c0 * ES);
             }
             *reinterpret_cast<u32x4 *>(s_h - C::PB + (R * C::VPP + tid) * 16) = blend4(c, g2);
         }
@@ -634,7 +613,7 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
                 const int yy = hl + (k >> 1), xx = wl + (k & 1);
                 const bool ok = yy >= 0 && yy < a.H && xx >= 0 && xx < a.W;
                 const int voff = base2 + ((k & 1) + (k >> 1) * a.W) * a.in_cs * ES;
-                v[k].v = __builtin_bit_cast(half8_t, X::convert16(dcn3_patch_corner(img, img_bytes, ok ? voff : 0x7ffffff0, c0 * ES)));
+                v[k].v = __builtin_bit_cast(half8_t, X::convert16(dcn_corner16(img, img_bytes, ok ? voff : 0x7ffffff0, c0 * ES)));
             }
             const typename X::frag o = X::blend(v, g2);
             *reinterpret_cast<half8_t *>(s_h - C::PB + (R * C::VPP + tid) * 16) = o.v;
@@ -857,9 +836,8 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
                 const int ti = tap / 3, tj = tap - ti * 3;
-                const int src = (tap < 5) ? r : r + 32, u = (tap < 5) ? tap : tap - 5;
-                const float d_h = __shfl(aoffs[3 * u], src), d_w = __shfl(aoffs[3 * u + 1], src), d_m = __shfl(aoffs[3 * u + 2], src);
-                const float h_im = (float)(oy - 1 + ti) + d_h, w_im = (float)(ox - 1 + tj) + d_w;
+                const DcnTapOffset d = dcn_tap_offset(aoffs, tap, r);
+                const float h_im = (float)(oy - 1 + ti) + d.d_h, w_im = (float)(ox - 1 + tj) + d.d_w;
                 qb[tap] = 0; qok[tap] = 0; qg[tap] = X::zero_geo();
                 bool pend = false;
                 if (live && h_im > -1.f && w_im > -1.f && h_im < (float)a.H && w_im < (float)a.W) {
@@ -867,13 +845,10 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
                     const int ry = hl - hy0, rx = wl - hx0;
                     if (!(ry >= 0 && ry + 1 < C::HH && rx >= 0 && rx + 1 < C::HH) && !((pmask >> tap) & 1)) {
                         pend = true;
-                        const float lh = h_im - (float)hl, lw = w_im - (float)wl;
-                        const float hh = 1.f - lh, hw = 1.f - lw;
-                        const float w4[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
-                        qg[tap] = X::make_geo(w4, dcn2_sigmoid(d_m));
+                        const DcnFar fs = dcn_far(h_im, w_im, hl, wl, a.H, a.W);
+                        qg[tap] = X::make_geo(fs.w, dcn2_sigmoid(d.d_m));
                         qb[tap] = ((hl * a.W + wl) * a.in_cs + 8 * h) * ES;
-                        qok[tap] = (hl >= 0 && wl >= 0 ? 1 : 0) | (hl >= 0 && wl + 1 <= a.W - 1 ? 2 : 0) |
-                                   (hl + 1 <= a.H - 1 && wl >= 0 ? 4 : 0) | (hl + 1 <= a.H - 1 && wl + 1 <= a.W - 1 ? 8 : 0);
+                        qok[tap] = fs.ok;
                     }
                 }
                 if (__any(pend)) wmask |= 1 << tap;
@@ -889,11 +864,11 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
                         for (int k = 0; k < 4; ++k)
 #pragma unroll
                             for (int cv = 0; cv < CV; ++cv)
-                                pv[j][k][cv] = dcn3_patch_corner(img, img_bytes, ((qok[t0 + j] >> k) & 1) ? qb[t0 + j] + (k & 1) * pxb + (k >> 1) * rowb + cv * 16 : 0x7ffffff0, c0 * ES);
+                                pv[j][k][cv] = dcn_corner16(img, img_bytes, ((qok[t0 + j] >> k) & 1) ? qb[t0 + j] + (k & 1) * pxb + (k >> 1) * rowb + cv * 16 : 0x7ffffff0, c0 * ES);
                     }
                 };
                 __syncthreads();
-                dcn3_issue_w<C::WPIECES>(a.w, main_bytes, s_w, ((c0 / CK) * a.G + (int)blockIdx.y * MT) * C::WGRP, l * 16, wvu);
+                dcn_lds_dma<C::WPIECES>(a.w, main_bytes, s_w, ((c0 / CK) * a.G + (int)blockIdx.y * MT) * C::WGRP, l * 16, wvu);
                 fetch(0);
                 __builtin_amdgcn_s_waitcnt(0x0f70);
                 __syncthreads();
@@ -929,7 +904,7 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
         for (int c0 = 0; c0 < a.Cin; c0 += CK) {
             __syncthreads();
             if constexpr (WDMA) {
-                dcn3_issue_w<C::WPIECES>(a.w, main_bytes, s_w, ((c0 / CK) * a.G + (int)blockIdx.y * MT) * C::WGRP, l * 16, wvu);
+                dcn_lds_dma<C::WPIECES>(a.w, main_bytes, s_w, ((c0 / CK) * a.G + (int)blockIdx.y * MT) * C::WGRP, l * 16, wvu);
                 __builtin_amdgcn_s_waitcnt(0x0f70);
             } else {
                 for (int i = tid; i < C::BN * WV; i += C::THREADS) {
@@ -943,38 +918,13 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
                 const int ti = tap / 3, tj = tap - ti * 3;
-                // raw (dh, dw, mask logit) of this tap live in the half that owns it: broadcast to both
-                const int src = (tap < 5) ? r : r + 32, u = (tap < 5) ? tap : tap - 5;
-                const float d_h = __shfl(aoffs[3 * u], src), d_w = __shfl(aoffs[3 * u + 1], src),
-                            d_m = __shfl(aoffs[3 * u + 2], src);
+                const DcnTapOffset d = dcn_tap_offset(aoffs, tap, r);
                 typename X::frag fb[CK / 16];
 #pragma unroll
                 for (int kk = 0; kk < CK / 16; ++kk) fb[kk] = X::zero();
-                bool any = false;
-                const float h_im = (float)(oy - 1 + ti) + d_h;
-                const float w_im = (float)(ox - 1 + tj) + d_w;
-                if (live && h_im > -1.f && w_im > -1.f && h_im < (float)a.H && w_im < (float)a.W) {
-                    const int hl = (int)floorf(h_im), wl = (int)floorf(w_im);
-                    const int ry = hl - hy0, rx = wl - hx0;
-                    if (!(ry >= 0 && ry + 1 < C::HH && rx >= 0 && rx + 1 < C::HH) && !((pmask >> tap) & 1)) {
-                        any = true;
-                        const float lh = h_im - (float)hl, lw = w_im - (float)wl;
-                        const float hh = 1.f - lh, hw = 1.f - lw;
-                        const float w4[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
-                        const typename X::geo g = X::make_geo(w4, dcn2_sigmoid(d_m));
-                        const bool okh0 = hl >= 0, okh1 = hl + 1 <= a.H - 1, okw0 = wl >= 0, okw1 = wl + 1 <= a.W - 1;
-                        const bool ok[4] = {okh0 && okw0, okh0 && okw1, okh1 && okw0, okh1 && okw1};
-                        const int pix[4] = {hl * a.W + wl, hl * a.W + wl + 1, (hl + 1) * a.W + wl, (hl + 1) * a.W + wl + 1};
-#pragma unroll
-                        for (int kk = 0; kk < CK / 16; ++kk) {
-                            typename X::frag v[4];
-#pragma unroll
-                            for (int k = 0; k < 4; ++k)
-                                v[k] = ok[k] ? X::global8(img + ((size_t)pix[k] * a.in_cs + c0 + kk * 16 + 8 * h) * ES) : X::zero();
-                            fb[kk] = X::blend(v, g);
-                        }
-                    }
-                }
+                const bool any = dcn_far_gather<X, C::HH>(fb, live && !((pmask >> tap) & 1), (float)(oy - 1 + ti) + d.d_h, (float)(ox - 1 + tj) + d.d_w, hy0, hx0, a.H, a.W,
+                    [&] { return dcn2_sigmoid(d.d_m); },
+                    [&](int kk, int y, int x) { return X::global8(img + ((size_t)(y * a.W + x) * a.in_cs + c0 + kk * 16 + 8 * h) * ES); });
                 if (!__any(any)) continue;
 #pragma unroll
                 for (int kk = 0; kk < CK / 16; ++kk) {
@@ -996,9 +946,7 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[m][0][i] *= wun;
     }
-    EpiArgs e;
-    e.bias = a.bias; e.res = nullptr; e.out = a.out; e.Ho = a.H; e.Wo = a.W; e.Cout = a.Cout;
-    e.out_cs = a.out_cs; e.res_cs = 0; e.relu = a.relu; e.out_mode = a.out_mode;
+    const EpiArgs e = dcn_epi_args(a);
     if constexpr (EPI == 2) {
         __syncthreads();                          // the apron and the filters are no longer read
         tile_epilogue_lds<T, MT>(acc, e, b, oy0, ox0, cout0, wv, l, smem + wv * epi_lds_stride<MT>());
@@ -1034,8 +982,7 @@ static int launch_dcn3_cfg(const Dcn3Args &a0, hipStream_t st, bool stats = fals
     a.stamps = nullptr;
 #endif
     dim3 grid(a.B * a.tiles_x * a.tiles_y, cdiv(a.Cout, C::BN));
-    const bool lean = a.out_mode == H3D_OUT_NHWC && a.Cout % 4 == 0 && ((uintptr_t)a.bias & 15) == 0;
-    const int epi = (sizeof(T) == 2 && MT >= 2 && lean && a.Cout % 8 == 0 && a.out_cs % 8 == 0 && ((uintptr_t)a.out & 15) == 0) ? 2 : lean ? 1 : 0;
+    const int epi = dcn_epi_mode(a, sizeof(T) == 2 && MT >= 2);
     if (h3d_note_kernel(F16IN ? (PK ? "dcn3_kernel<%s, %d, %d, %d, %d, %s, %d, true, true>" : "dcn3_kernel<%s, %d, %d, %d, %d, %s, %d, false, true>")
                               : PK ? "dcn3_kernel<%s, %d, %d, %d, %d, %s, %d, true>" : "dcn3_kernel<%s, %d, %d, %d, %d, %s, %d>", h3d_tname<T>(), MT, CK, MARGIN, epi,
                         WDMA ? "true" : "false", NP))
@@ -1118,47 +1065,40 @@ static int launch_dcn3_lowp(const h3d_op &op, const Dcn3Flags &f, const Dcn3Args
         if (f.no_slots || op.Cin % 32) {                 // H3D_OPF_DCN_STREAM_NO_SLOTS: round 1's configurations (no patches: every sample that
                                                          // leaves the apron goes through pass 2); also Cin = 16 (mod 32): the
                                                          // patch variants' pipeline is unrolled by two stages
-            if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 1, true>(a, st);
-            if (op.Cout <= 64) return launch_dcn3_cfg<T, 2, 16, 1, true>(a, st);
-            return launch_dcn3_cfg<T, 4, 16, 2, true>(a, st);
+            return dcn_by_mt(op.Cout, op.Cout <= 64, [&](auto mt) { return launch_dcn3_cfg<T, decltype(mt)::value, 16, decltype(mt)::value == 4 ? 2 : 1, true>(a, st); });
         }
         // > 64 output channels: a layer whose 128-channel workgroups would leave CUs idle (16 x 16 maps at batch 64: 128 workgroups
         // on 256 CUs) runs 64-channel workgroups instead: twice the gather / blend work, on CUs that had nothing to do
         const bool mt2 = op.Cout <= 64 || f.narrow_wg;
-        if (f.wide_margin) {
-            // wide margin on the packed apron (engine.dcn_wide_margin / DLAEngine.calibrate_dcn_margins: layers whose offsets send
-            // many samples outside a margin-2 apron): margin 4 at two workgroups per CU (73 KB).  The 128-channel variant has
-            // margin 4 anyway (a margin-6 packed apron needs a fourth staging register set: 14 spilled registers)
-            if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 4, true, 256, true>(a, st, f.stats);
-            if (mt2) return launch_dcn3_cfg<T, 2, 16, 4, true, 256, true, F16IN>(a, st, f.stats);
-            return launch_dcn3_cfg<T, 4, 16, 4, true, 256, false, F16IN>(a, st, f.stats);
-        }
+        // The patch-slot variants: NP slots per tile on a margin-M apron, packed (PK) or padded.  The 128-channel variant always has
+        // margin 4 on the padded apron (one workgroup per CU has the LDS for 26 x 26 pixels; a margin-6 packed apron needs a fourth
+        // staging register set: 14 spilled registers); the fp16-input option exists from 64-channel workgroups up.
+        // Rungs MT = 1 | 2 | 4 of each call below: <margin, slots, packed>; F16IN from MT = 2 up.
+        // wide margin on the packed apron (engine.dcn_wide_margin / DLAEngine.calibrate_dcn_margins: layers whose offsets send
+        // many samples outside a margin-2 apron): margin 4 at two workgroups per CU (73 KB)
+        if (f.wide_margin)
+            return dcn_by_mt(op.Cout, mt2, [&](auto mt) {
+                constexpr int MT = decltype(mt)::value;
+                return launch_dcn3_cfg<T, MT, 16, 4, true, 256, MT < 4, MT >= 2 && F16IN>(a, st, f.stats);
+            });
+        // experiment / candidate default: margin 2 on the PACKED apron (15 KB instead of 28) with 512 patch slots per tile, the second
+        // 256 filled in a second round per stage
+        if (f.slots512)
+            return dcn_by_mt(op.Cout, mt2, [&](auto mt) {
+                constexpr int MT = decltype(mt)::value;
+                return launch_dcn3_cfg<T, MT, 16, MT < 4 ? 2 : 4, true, 512, MT < 4, MT >= 2 && F16IN>(a, st, f.stats);
+            });
         // <= 64 output channels: margin-2 apron, 16-channel stages, <= 128 VGPRs and 78 KB of LDS -> two workgroups
-        // (16 waves) per CU, one computing while the other waits at its stage barriers; 256 patch slots per tile.
-        // > 64: one workgroup per CU has the LDS for a margin-4 apron (26 x 26 pixels)
-        if (f.slots512) {
-            // experiment / candidate default: margin 2 on the PACKED apron (15 KB instead of 28) with 512 patch slots per tile, the second
-            // 256 filled in a second round per stage
-            if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 2, true, 512, true>(a, st, f.stats);
-            if (mt2) return launch_dcn3_cfg<T, 2, 16, 2, true, 512, true, F16IN>(a, st, f.stats);
-            return launch_dcn3_cfg<T, 4, 16, 4, true, 512, false, F16IN>(a, st, f.stats);
-        }
-        if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 2, true, 256>(a, st, f.stats);
-        if (mt2) return launch_dcn3_cfg<T, 2, 16, 2, true, 256, false, F16IN>(a, st, f.stats);
-        return launch_dcn3_cfg<T, 4, 16, 4, true, 256, false, F16IN>(a, st, f.stats);
+        // (16 waves) per CU, one computing while the other waits at its stage barriers; 256 patch slots per tile
+        return dcn_by_mt(op.Cout, mt2, [&](auto mt) {
+            constexpr int MT = decltype(mt)::value;
+            return launch_dcn3_cfg<T, MT, 16, MT < 4 ? 2 : 4, true, 256, false, MT >= 2 && F16IN>(a, st, f.stats);
+        });
     }
-    if (op.Cin % 32 == 0 && op.Cout <= 64) {
-        if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 32, 2>(a, st);
-        return launch_dcn3_cfg<T, 2, 32, 2>(a, st);
-    }
-    if (op.Cout <= 32) return launch_dcn3_cfg<T, 1, 16, 2>(a, st);
-    if (op.Cout <= 64) return launch_dcn3_cfg<T, 2, 16, 2>(a, st);
-    // (the small-grid rule as above)
-    if (f.narrow_wg) {
-        if (op.Cin % 32 == 0) return launch_dcn3_cfg<T, 2, 32, 2>(a, st);
-        return launch_dcn3_cfg<T, 2, 16, 2>(a, st);
-    }
-    return launch_dcn3_cfg<T, 4, 16, 2>(a, st);
+    // register-staged filters: 32-channel stages where Cin allows and the workgroup has <= 64 channels (the small-grid rule as above)
+    const bool mt2 = op.Cout <= 64 || f.narrow_wg;
+    if (op.Cin % 32 == 0 && mt2) return dcn_by_mt<2>(op.Cout, true, [&](auto mt) { return launch_dcn3_cfg<T, decltype(mt)::value, 32, 2>(a, st); });
+    return dcn_by_mt(op.Cout, mt2, [&](auto mt) { return launch_dcn3_cfg<T, decltype(mt)::value, 16, 2>(a, st); });
 }
 
 int h3d_launch_dcn5(const h3d_op &op, hipStream_t st);      // csrc/dcn5.hip: fp16 plans, every operand by LDS-DMA
@@ -1167,23 +1107,11 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
 {
     const bool wdma = op.kind == H3D_OP_DCN_FUSED_STREAM;
     if (wdma && op.dtype != H3D_BF16 && op.dtype != H3D_F16 && op.dtype != H3D_F16X3) H3D_FAIL(H3D_ERR_DTYPE, "dcn_fused_stream: bf16 / fp16 / f16x3 plans only");
-    if (!op.in || !op.w || !op.bias || !op.out || !op.in2) H3D_FAIL(H3D_ERR_ARG, "dcn_fused: null pointer");
     const int es = h3d_dtype_bytes(op.dtype);
-    if (!es) H3D_FAIL(H3D_ERR_DTYPE, "dcn_fused: dtype %d", op.dtype);
-    if (op.ksize != 3 || op.stride != 1 || op.Ho != op.H || op.Wo != op.W)
-        H3D_FAIL(H3D_ERR_UNSUPPORTED, "dcn_fused: covers 3x3 s1 p1 d1 dg1 only (k=%d s=%d)", op.ksize, op.stride);
-    if (op.Cin % 16 || op.in_cs % (16 / es) || op.Cin > op.in_cs)
-        H3D_FAIL(H3D_ERR_SHAPE, "dcn_fused: Cin=%d (stride %d) must be a multiple of 16", op.Cin, op.in_cs);
-    if (op.H > 32767 || op.W > 32767) H3D_FAIL(H3D_ERR_SHAPE, "dcn_fused: image larger than 32767");
-    if (op.wrows < ((op.Cout + 127) / 128) * 128)
-        H3D_FAIL(H3D_ERR_SHAPE, "dcn_fused: packed weight rows %d < Cout %d padded to 128", op.wrows, op.Cout);
-    if (op.out_mode != H3D_OUT_NCHW_F32 && (op.out_cs % 4 || op.Cout > op.out_cs))
-        H3D_FAIL(H3D_ERR_SHAPE, "dcn_fused: out channel stride %d", op.out_cs);
+    if (const int rc = dcn_check_op(op, "dcn_fused", es, false)) return rc;
     Dcn3Args a;
-    a.in = (const char *)op.in; a.w = (const char *)op.w; a.woff = (const char *)op.in2; a.bias = op.bias;
-    a.out = (char *)op.out; a.B = op.B; a.H = op.H; a.W = op.W; a.Cin = op.Cin; a.in_cs = op.in_cs;
-    a.Cout = op.Cout; a.out_cs = op.out_cs; a.relu = op.relu; a.out_mode = op.out_mode; a.wrows = op.wrows;
-    a.tiles_x = a.tiles_y = 0;
+    dcn_fill_args(op, a);
+    a.w = (const char *)op.w; a.woff = (const char *)op.in2; a.Cin = op.Cin; a.wrows = op.wrows;
     a.dbg = op.reserved & H3D_TUNE_DCN_STREAM_ABLATE_MASK;
     a.G = op.wrows / 32;
     if (op.wexp < -60 || op.wexp > 60 || op.wexp2 < -60 || op.wexp2 > 60 || ((op.wexp || op.wexp2) && op.dtype != H3D_F16X3))
@@ -1209,8 +1137,7 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
     }
     if (op.dtype == H3D_F16) return launch_dcn3_lowp<f16_t>(op, f, a, wdma, st);
     if (op.dtype == H3D_F32) {
-        if (op.Cout <= 32) return launch_dcn3_cfg<float, 1, 16, 2>(a, st);
-        return launch_dcn3_cfg<float, 2, 16, 2>(a, st);
+        return dcn_by_mt<2>(op.Cout, true, [&](auto mt) { return launch_dcn3_cfg<float, decltype(mt)::value, 16, 2>(a, st); });
     }
     if (op.dtype == H3D_F16X3 && wdma) {
         // f16x3 with PATCH SLOTS (round 5): the 2-byte plans' pipeline -- filters as stage-major images by LDS-DMA (pre-split (hi | lo)
@@ -1226,16 +1153,10 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
         // the five (margin 3 was ahead there before phase B interleaved its vector work with the MFMAs), 256 -> 128 0.446 / 0.451 / 0.472,
         // 512 -> 256 @16x16 0.186 / 0.199 / 0.215).  H3D_TUNE_DCN_STREAM_X3_MARGIN2 / 3 / 4 force a margin.
         const int margin = f.margin ? f.margin : (op.Cin == op.Cout && op.Cout > 64) ? 4 : 2;
-        if (margin == 4) {
-            if (op.Cout <= 32) return launch_dcn3_cfg<x3_t, 1, 16, 4, true, 256>(a, st);
-            return launch_dcn3_cfg<x3_t, 2, 16, 4, true, 256>(a, st);
-        }
-        if (margin == 3) {
-            if (op.Cout <= 32) return launch_dcn3_cfg<x3_t, 1, 16, 3, true, 256>(a, st);
-            return launch_dcn3_cfg<x3_t, 2, 16, 3, true, 256>(a, st);
-        }
-        if (op.Cout <= 32) return launch_dcn3_cfg<x3_t, 1, 16, 2, true, 256>(a, st);
-        return launch_dcn3_cfg<x3_t, 2, 16, 2, true, 256>(a, st);
+        auto go = [&](auto m) { return dcn_by_mt<2>(op.Cout, true, [&](auto mt) { return launch_dcn3_cfg<x3_t, decltype(mt)::value, 16, decltype(m)::value, true, 256>(a, st); }); };
+        if (margin == 4) return go(std::integral_constant<int, 4>{});
+        if (margin == 3) return go(std::integral_constant<int, 3>{});
+        return go(std::integral_constant<int, 2>{});
     }
     if (op.dtype == H3D_F16X3) {            // the f32 plan's tiles (fp32 apron, register-staged pre-split filters) on 3 fp16 MFMAs per step
         // H3D_OPF_DCN_FUSED_RAW_PACK (the stand-alone `DCN` module, h3d_amd/dcn_v2.py): plain fp32 filter packs of h3d_dcn_fused_pack_f32_cached, the two filter
@@ -1246,19 +1167,13 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
             a.xscaled = f.scaled_input;
         }
         const int margin = f.margin ? f.margin : (op.Cout <= 64 && op.H >= 64) ? 6 : 4;
-        if (margin == 2) {                  // H3D_TUNE_DCN_FUSED_X3_MARGIN2 (tools/ab_flag.py): the f32 plan's margin-2 double-buffered tile
-            if (op.Cout <= 32) return launch_dcn3_cfg<x3_t, 1, 16, 2>(a, st);
-            return launch_dcn3_cfg<x3_t, 2, 16, 2>(a, st);
-        }
+        auto go = [&](auto m) { return dcn_by_mt<2>(op.Cout, true, [&](auto mt) { return launch_dcn3_cfg<x3_t, decltype(mt)::value, 16, decltype(m)::value>(a, st); }); };
+        if (margin == 2) return go(std::integral_constant<int, 2>{});      // H3D_TUNE_DCN_FUSED_X3_MARGIN2 (tools/ab_flag.py): the f32 plan's margin-2 double-buffered tile
         // margin 6 (30 x 30 apron, 115 KB with its filters) on the large maps with <= 64 output channels (tools/ab_op_reserved.py, batch
         // 64, same process, margin 4 / 2 / 6: 64 -> 64 @128x128 4.79 / 4.60 / 4.32 ms for the five launches, 128 -> 64 @64x64 1.58 / 1.76 /
         // 1.49; the 128- and 256-channel layers 3.73 / 3.88 / 3.79: they stay on margin 4); H3D_TUNE_DCN_FUSED_X3_MARGIN6 / _MARGIN4 force either
-        if (margin == 6) {
-            if (op.Cout <= 32) return launch_dcn3_cfg<x3_t, 1, 16, 6>(a, st);
-            return launch_dcn3_cfg<x3_t, 2, 16, 6>(a, st);
-        }
-        if (op.Cout <= 32) return launch_dcn3_cfg<x3_t, 1, 16, 4>(a, st);      // margin 4, one stage buffer (Dcn3Cfg::SINGLE)
-        return launch_dcn3_cfg<x3_t, 2, 16, 4>(a, st);
+        if (margin == 6) return go(std::integral_constant<int, 6>{});
+        return go(std::integral_constant<int, 4>{});      // margin 4, one stage buffer (Dcn3Cfg::SINGLE)
     }
     H3D_FAIL(H3D_ERR_DTYPE, "dcn_fused: dtype %d", op.dtype);
 }

@@ -18,7 +18,7 @@
 // MFMA) -> rare pass 2 for samples whose corners left the apron (global gather).
 #include "common.h"
 #include "epilogue.h"
-#include "dcn_traits.h"
+#include "dcn_tile.h"
 
 struct Dcn4Args {
     const char *in;     // fp16 NHWC
@@ -62,18 +62,6 @@ struct Dcn4Cfg {
 };
 
 typedef __attribute__((address_space(3))) void lds_void4;
-
-// one filter stage -> ring slot `dst` (linear copy of `pieces` KiB starting at byte `src` of buffer `base`)
-template <int PIECES>
-__device__ __forceinline__ void dcn4_issue_w(const char *base, int bytes, char *dst, int src, int woff, int wv)
-{
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, bytes, 0x00020000);
-#pragma unroll
-    for (int j = 0; j < (PIECES + 7) / 8; ++j) {
-        const int p = wv + 8 * j;
-        if (p < PIECES) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void4 *)(dst + p * 1024), 16, woff, src + p * 1024, 0, 0);
-    }
-}
 
 // UP, pass 2 only: 8 channels (c0 .. c0+7) of  skip + up(xlo)  at pixel (gy, gx) inside the image, straight from global
 // memory (tap table included): the same arithmetic as the apron prologue
@@ -149,7 +137,7 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void dcn4_kernel(Dcn4Args a)
     // the first OROUND offset-filter stages land in the (still idle) main-filter ring together with the apron; with
     // all four (DENSE = 0) phase A runs its 36 MFMAs per wave without a single wait (staged one by one, each 9-MFMA
     // stage exposed a full DMA round trip: the SQ counters showed the waves parked 52 % of the time)
-    dcn4_issue_w<C::OPIECES>(a.woff, off_bytes, s_ring, 0, woffl, wv);
+    dcn_lds_dma<C::OPIECES>(a.woff, off_bytes, s_ring, 0, woffl, wv);
     } else {
     // ---- UP: the apron is computed, not copied: apron[y][x][c] = skip[y][x][c] + sum of the 2x2 taps of the depthwise
     //      transposed convolution of xlo that reach (y, x) -- the arithmetic of upadd_kernel (csrc/conv.hip), same
@@ -318,7 +306,7 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void dcn4_kernel(Dcn4Args a)
             }
         }
         __syncthreads();                                        // apron complete, tap table no longer read
-        dcn4_issue_w<C::OPIECES>(a.woff, off_bytes, s_ring, 0, woffl, wv);
+        dcn_lds_dma<C::OPIECES>(a.woff, off_bytes, s_ring, 0, woffl, wv);
     }
 
     // ================= phase A: offsets/mask = conv3x3(x; 27 filters) ==================================
@@ -337,7 +325,7 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void dcn4_kernel(Dcn4Args a)
     for (int s = 0; s < C::NSTAGE; ++s) {
         if (s > 0 && s % C::OROUND == 0) {        // DENSE: stages 2,3 replace 0,1 (the CU's other workgroup covers the wait)
             __syncthreads();
-            dcn4_issue_w<C::OPIECES>(a.woff, off_bytes, s_ring, s * C::WGRP, woffl, wv);
+            dcn_lds_dma<C::OPIECES>(a.woff, off_bytes, s_ring, s * C::WGRP, woffl, wv);
             __builtin_amdgcn_s_waitcnt(0x0f70);
             __syncthreads();
         }
@@ -352,8 +340,8 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void dcn4_kernel(Dcn4Args a)
     }
     __syncthreads();                              // the ring is free: the first main stages fly while the geometry is computed
     if (H3D_DBG(a) == 2) { if (aoffs[0] == 1234.5f) a.out[0] = 1; return; }
-    dcn4_issue_w<C::WPIECES>(a.wimg, main_bytes, s_ring, g0 * C::WGRP, woffl, wv);
-    if (C::NSLOT > 1) dcn4_issue_w<C::WPIECES>(a.wimg, main_bytes, s_ring + C::WSLOT, (a.G + g0) * C::WGRP, woffl, wv);
+    dcn_lds_dma<C::WPIECES>(a.wimg, main_bytes, s_ring, g0 * C::WGRP, woffl, wv);
+    if (C::NSLOT > 1) dcn_lds_dma<C::WPIECES>(a.wimg, main_bytes, s_ring + C::WSLOT, (a.G + g0) * C::WGRP, woffl, wv);
 
     // ================= geometry (branch free): my taps (h=0: 0..4, h=1: 5..8), cross-half exchange ====
     int boff[9];
@@ -375,9 +363,8 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void dcn4_kernel(Dcn4Args a)
             const bool inap = (unsigned)ry < (unsigned)(C::HH - 1) && (unsigned)rx < (unsigned)(C::HH - 1);
             const bool use = inside && inap;
             slow |= inside && !inap;
-            const float lh = h_im - fh, lw = w_im - fw;
-            const float hh = 1.f - lh, hw = 1.f - lw;
-            const float w4[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
+            float w4[4];
+            dcn_bilinear_w(h_im, w_im, fh, fw, w4);
             typename X::geo g = X::make_geo(w4, dcn2_sigmoid(aoffs[3 * u + 2]));
             g.w01 = use ? g.w01 : 0u;
             g.w23 = use ? g.w23 : 0u;
@@ -417,11 +404,11 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void dcn4_kernel(Dcn4Args a)
             else __builtin_amdgcn_s_waitcnt(0x0f70);
             __syncthreads();
             if (s + 2 < C::NSTAGE)
-                dcn4_issue_w<C::WPIECES>(a.wimg, main_bytes, s_ring + ((s + 2) % C::NSLOT) * C::WSLOT, ((s + 2) * a.G + g0) * C::WGRP, woffl, wv);
+                dcn_lds_dma<C::WPIECES>(a.wimg, main_bytes, s_ring + ((s + 2) % C::NSLOT) * C::WSLOT, ((s + 2) * a.G + g0) * C::WGRP, woffl, wv);
         } else {
             if (s > 0) {
                 __syncthreads();
-                dcn4_issue_w<C::WPIECES>(a.wimg, main_bytes, s_ring, (s * a.G + g0) * C::WGRP, woffl, wv);
+                dcn_lds_dma<C::WPIECES>(a.wimg, main_bytes, s_ring, (s * a.G + g0) * C::WGRP, woffl, wv);
             }
             __builtin_amdgcn_s_waitcnt(0x0f70);
             __syncthreads();
@@ -473,30 +460,24 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void dcn4_kernel(Dcn4Args a)
     if (__syncthreads_or(slow ? 1 : 0)) {
         for (int s = 0; s < C::NSTAGE; ++s) {
             __syncthreads();
-            dcn4_issue_w<C::WPIECES>(a.wimg, main_bytes, s_ring, (s * a.G + g0) * C::WGRP, woffl, wv);
+            dcn_lds_dma<C::WPIECES>(a.wimg, main_bytes, s_ring, (s * a.G + g0) * C::WGRP, woffl, wv);
             __builtin_amdgcn_s_waitcnt(0x0f70);
             __syncthreads();
 #pragma unroll
             for (int tap = 0; tap < 9; ++tap) {
                 const int ti = tap / 3, tj = tap - ti * 3;
-                const int src = (tap < 5) ? r : r + 32, u = (tap < 5) ? tap : tap - 5;
-                const float d_h = __shfl(aoffs[3 * u], src), d_w = __shfl(aoffs[3 * u + 1], src),
-                            d_m = __shfl(aoffs[3 * u + 2], src);
+                const DcnTapOffset d = dcn_tap_offset(aoffs, tap, r);
                 typename X::frag fb = X::zero();
                 bool any = false;
-                const float h_im = (float)(oy - 1 + ti) + d_h;
-                const float w_im = (float)(ox - 1 + tj) + d_w;
+                const float h_im = (float)(oy - 1 + ti) + d.d_h;
+                const float w_im = (float)(ox - 1 + tj) + d.d_w;
                 if (live && h_im > -1.f && w_im > -1.f && h_im < (float)a.H && w_im < (float)a.W) {
                     const int hl = (int)floorf(h_im), wl = (int)floorf(w_im);
                     const int ry = hl - hy0, rx = wl - hx0;
                     if (!((unsigned)ry < (unsigned)(C::HH - 1) && (unsigned)rx < (unsigned)(C::HH - 1))) {
                         any = true;
-                        const float lh = h_im - (float)hl, lw = w_im - (float)wl;
-                        const float hh = 1.f - lh, hw = 1.f - lw;
-                        const float w4[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
-                        const typename X::geo g = X::make_geo(w4, dcn2_sigmoid(d_m));
-                        const bool okh0 = hl >= 0, okh1 = hl + 1 <= a.H - 1, okw0 = wl >= 0, okw1 = wl + 1 <= a.W - 1;
-                        const bool ok[4] = {okh0 && okw0, okh0 && okw1, okh1 && okw0, okh1 && okw1};
+                        const DcnFar fs = dcn_far(h_im, w_im, hl, wl, a.H, a.W);
+                        const typename X::geo g = X::make_geo(fs.w, dcn2_sigmoid(d.d_m));
                         const int pix[4] = {hl * a.W + wl, hl * a.W + wl + 1, (hl + 1) * a.W + wl, (hl + 1) * a.W + wl + 1};
                         typename X::frag v[4];
 #pragma unroll
@@ -504,13 +485,13 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void dcn4_kernel(Dcn4Args a)
                         {
                             if constexpr (UP) {
                                 v[k] = X::zero();
-                                if (ok[k]) {
+                                if ((fs.ok >> k) & 1) {
                                     const int yy = hl + (k >> 1), xx = wl + (k & 1);
                                     v[k].v = __builtin_bit_cast(decltype(v[k].v), dcn4_up8(a, a.xlo + (size_t)b * a.Hl * a.Wl * a.xlo_cs * 2,
                                                                                             a.skip + (size_t)b * a.H * a.W * a.skip_cs * 2, yy, xx, s * 16 + 8 * h));
                                 }
                             } else {
-                                v[k] = ok[k] ? X::lds(img + ((size_t)pix[k] * a.in_cs + s * 16 + 8 * h) * 2) : X::zero();   // fp16 input: plain 16-byte load
+                                v[k] = ((fs.ok >> k) & 1) ? X::lds(img + ((size_t)pix[k] * a.in_cs + s * 16 + 8 * h) * 2) : X::zero();   // fp16 input: plain 16-byte load
                             }
                         }
                         fb = X::blend(v, g);
@@ -526,9 +507,7 @@ __global__ __launch_bounds__(512, DENSE ? 4 : 2) void dcn4_kernel(Dcn4Args a)
         }
     }
 
-    EpiArgs e;
-    e.bias = a.bias; e.res = nullptr; e.out = a.out; e.Ho = a.H; e.Wo = a.W; e.Cout = a.Cout;
-    e.out_cs = a.out_cs; e.res_cs = 0; e.relu = a.relu; e.out_mode = a.out_mode;
+    const EpiArgs e = dcn_epi_args(a);
     if constexpr (EPI == 2) {
         __syncthreads();
         tile_epilogue_lds<bf16_t, MT>(acc, e, b, oy0, ox0, cout0, wv, l, smem + wv * epi_lds_stride<MT>());
@@ -548,8 +527,7 @@ static int launch_dcn4_cfg(const Dcn4Args &a0, hipStream_t st)
     a.tiles_x = cdiv(a.W, 16);
     a.tiles_y = cdiv(a.H, 16);
     dim3 grid(a.B * a.tiles_x * a.tiles_y, cdiv(cdiv(a.Cout, 32), MT));
-    const bool lean = a.out_mode == H3D_OUT_NHWC && a.Cout % 4 == 0 && ((uintptr_t)a.bias & 15) == 0;
-    const int epi = (MT >= 2 && lean && a.Cout % 8 == 0 && a.out_cs % 8 == 0 && ((uintptr_t)a.out & 15) == 0) ? 2 : lean ? 1 : 0;
+    const int epi = dcn_epi_mode(a, MT >= 2);
     if (h3d_note_kernel("dcn4_kernel<%d, %d, %d, %d>", MT, epi, DENSE, UP)) return H3D_OK;
     if (epi == 2)
         hipLaunchKernelGGL((dcn4_kernel<MT, 2, DENSE, UP>), grid, dim3(512), 0, st, a);
@@ -575,10 +553,9 @@ int h3d_launch_dcn4(const h3d_op &op, hipStream_t st)
     if (op.out_mode != H3D_OUT_NCHW_F32 && (op.out_cs % 4 || op.Cout > op.out_cs))
         H3D_FAIL(H3D_ERR_SHAPE, "dcn_fused_f16: out channel stride %d", op.out_cs);
     Dcn4Args a;
-    a.in = (const char *)op.in; a.wimg = (const char *)op.w; a.woff = (const char *)op.in2; a.bias = op.bias;
-    a.out = (char *)op.out; a.B = op.B; a.H = op.H; a.W = op.W; a.in_cs = op.in_cs;
-    a.Cout = op.Cout; a.out_cs = op.out_cs; a.relu = op.relu; a.out_mode = op.out_mode; a.wrows = op.wrows;
-    a.G = op.wrows / 32; a.tiles_x = a.tiles_y = 0; a.dbg = op.reserved & H3D_TUNE_DCN_F16_ABLATE_MASK;
+    dcn_fill_args(op, a);
+    a.wimg = (const char *)op.w; a.woff = (const char *)op.in2; a.wrows = op.wrows;
+    a.G = op.wrows / 32; a.dbg = op.reserved & H3D_TUNE_DCN_F16_ABLATE_MASK;
     a.xlo = a.skip = nullptr; a.wup = nullptr; a.f = a.Hl = a.Wl = a.xlo_cs = a.skip_cs = 0;
     const bool dense = !(op.reserved & H3D_TUNE_DCN_F16_ONE_WG_PER_CU);    // tuning override (tools/ab_conv.py): one workgroup per CU
     if (op.Cout <= 32) return dense ? launch_dcn4_cfg<1, 1>(a, st) : launch_dcn4_cfg<1, 0>(a, st);
@@ -605,10 +582,10 @@ int h3d_launch_updcn(const h3d_op &op, hipStream_t st)
     if (op.out_mode != H3D_OUT_NCHW_F32 && (op.out_cs % 4 || op.Cout > op.out_cs))
         H3D_FAIL(H3D_ERR_SHAPE, "updcn: out channel stride %d", op.out_cs);
     Dcn4Args a;
-    a.in = nullptr; a.wimg = (const char *)op.w; a.woff = (const char *)d->w_off; a.bias = op.bias;
-    a.out = (char *)op.out; a.B = op.B; a.H = op.Ho; a.W = op.Wo; a.in_cs = 64;
-    a.Cout = op.Cout; a.out_cs = op.out_cs; a.relu = op.relu; a.out_mode = op.out_mode; a.wrows = op.wrows;
-    a.G = op.wrows / 32; a.tiles_x = a.tiles_y = 0; a.dbg = op.reserved & H3D_TUNE_DCN_F16_ABLATE_MASK;
+    dcn_fill_args(op, a);
+    a.in = nullptr; a.H = op.Ho; a.W = op.Wo; a.in_cs = 64;      // the kernel's input is the up-sampled sum it computes: op.in is xlo
+    a.wimg = (const char *)op.w; a.woff = (const char *)d->w_off; a.wrows = op.wrows;
+    a.G = op.wrows / 32; a.dbg = op.reserved & H3D_TUNE_DCN_F16_ABLATE_MASK;
     a.xlo = (const char *)op.in; a.skip = (const char *)d->skip; a.wup = d->w_up;
     a.f = f; a.Hl = op.H; a.Wl = op.W; a.xlo_cs = op.in_cs; a.skip_cs = d->skip_cs;
     if (op.Cout <= 32) return launch_dcn4_cfg<1, 1, 1>(a, st);

@@ -20,8 +20,7 @@
 // Pieces of 1 KiB; the zeros a piece writes past the end of its image land in the slack of its own slot.
 #include "common.h"
 #include "epilogue.h"
-#include "dcn_traits.h"
-#include <type_traits>
+#include "dcn_tile.h"
 
 struct Dcn5Args {
     const char *in;
@@ -66,17 +65,6 @@ struct Dcn5Cfg {
 
 typedef __attribute__((address_space(3))) void lds_void5;
 
-// filters of one stage: PIECES KiB pieces, linear copy (lane offsets l * 16), piece p by wave p % 8
-template <int PIECES>
-__device__ __forceinline__ void dcn5_issue_w(const char *base, int bytes, char *dst, int src, int lane16, int wv)
-{
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, bytes, 0x00020000);
-#pragma unroll
-    for (int j = 0; j < (PIECES + 7) / 8; ++j) {
-        const int p = wv + 8 * j;
-        if (p < PIECES) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void5 *)(dst + p * 1024), 16, lane16, src + p * 1024, 0, 0);
-    }
-}
 // apron of one stage: piece p by wave p % 8, per-lane source offsets `voff` (swizzled half, out of range outside the image)
 template <int APIECES>
 __device__ __forceinline__ void dcn5_issue_a(const char *img, int bytes, char *dst, const int *voff, int soff, int wv)
@@ -87,11 +75,6 @@ __device__ __forceinline__ void dcn5_issue_a(const char *img, int bytes, char *d
         const int p = wv + 8 * j;
         if (p < APIECES) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void5 *)(dst + p * 1024), 16, voff[j], soff, 0, 0);
     }
-}
-__device__ __forceinline__ u32x4 dcn5_corner(const char *img, int bytes, int voff, int soff)
-{
-    const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)img, 0, bytes, 0x00020000);
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
 }
 
 // XP: experiment bits (H3D_TUNE_DCN_STREAM_DCN5_XP in h3d_op.reserved; tools/ab_dcn5.py).  1: next stage's DMA issued after the second barrier; 2 / 4 / 8
@@ -147,8 +130,8 @@ __global__ __launch_bounds__(512, MT <= 2 ? 4 : 2) void dcn5_kernel(Dcn5Args a)
         if (!((XP & 4) && s > 0)) dcn5_issue_a<C::APIECES>(img, img_bytes, smem + C::OFF_A + (s & 1) * C::ASLOT, avoff, c * CK * ES, wvu);
         char *dst = smem + C::OFF_F + (s & 1) * C::WSLOT;
         if ((XP & 8) && s > 0) return;
-        if (s < nchunks) dcn5_issue_w<C::OPIECES>(a.woff, off_bytes, dst, s * C::WGRP, l * 16, wvu);
-        else dcn5_issue_w<C::WPIECES>(a.w, main_bytes, dst, (c * a.G + (int)blockIdx.y * MT) * C::WGRP, l * 16, wvu);
+        if (s < nchunks) dcn_lds_dma<C::OPIECES>(a.woff, off_bytes, dst, s * C::WGRP, l * 16, wvu);
+        else dcn_lds_dma<C::WPIECES>(a.w, main_bytes, dst, (c * a.G + (int)blockIdx.y * MT) * C::WGRP, l * 16, wvu);
     };
 
     issue(0);
@@ -217,9 +200,8 @@ __global__ __launch_bounds__(512, MT <= 2 ? 4 : 2) void dcn5_kernel(Dcn5Args a)
                 hl = (int)floorf(h_im);
                 wl = (int)floorf(w_im);
                 const int ry = hl - hy0, rx = wl - hx0;
-                const float lh = h_im - (float)hl, lw = w_im - (float)wl;
-                const float hh = 1.f - lh, hw = 1.f - lw;
-                const float w4[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
+                float w4[4];
+                dcn_bilinear_w(h_im, w_im, (float)hl, (float)wl, w4);
                 g = X::make_geo(w4, dcn2_sigmoid(aoffs[3 * u + 2]));
                 if (ry >= 0 && ry + 1 < C::HH && rx >= 0 && rx + 1 < C::HH) {
                     off = ry * C::ROWB + rx * C::PXB + ((ry & 1) << 4);      // half 0's bytes; half 1 reads off ^ 16
@@ -316,7 +298,7 @@ __global__ __launch_bounds__(512, MT <= 2 ? 4 : 2) void dcn5_kernel(Dcn5Args a)
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int voff = pbase + ((k & 1) + (k >> 1) * a.W) * a.in_cs * ES;
-            pst[k] = dcn5_corner(img, img_bytes, ((pok >> k) & 1) ? voff : 0x7ffffff0, c0 * ES);
+            pst[k] = dcn_corner16(img, img_bytes, ((pok >> k) & 1) ? voff : 0x7ffffff0, c0 * ES);
         }
     };
     auto patch_commit = [&]() {
@@ -424,9 +406,8 @@ __global__ __launch_bounds__(512, MT <= 2 ? 4 : 2) void dcn5_kernel(Dcn5Args a)
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int ti = tap / 3, tj = tap - ti * 3;
-            const int src = (tap < 5) ? r : r + 32, u = (tap < 5) ? tap : tap - 5;
-            const float d_h = __shfl(aoffs[3 * u], src), d_w = __shfl(aoffs[3 * u + 1], src), d_m = __shfl(aoffs[3 * u + 2], src);
-            const float h_im = (float)(oy - 1 + ti) + d_h, w_im = (float)(ox - 1 + tj) + d_w;
+            const DcnTapOffset d = dcn_tap_offset(aoffs, tap, r);
+            const float h_im = (float)(oy - 1 + ti) + d.d_h, w_im = (float)(ox - 1 + tj) + d.d_w;
             qb[tap] = 0; qok[tap] = 0; qg[tap] = X::zero_geo();
             bool pend = false;
             if (live && h_im > -1.f && w_im > -1.f && h_im < (float)a.H && w_im < (float)a.W) {
@@ -434,13 +415,10 @@ __global__ __launch_bounds__(512, MT <= 2 ? 4 : 2) void dcn5_kernel(Dcn5Args a)
                 const int ry = hl - hy0, rx = wl - hx0;
                 if (!(ry >= 0 && ry + 1 < C::HH && rx >= 0 && rx + 1 < C::HH) && !((pmask >> tap) & 1)) {
                     pend = true;
-                    const float lh = h_im - (float)hl, lw = w_im - (float)wl;
-                    const float hh = 1.f - lh, hw = 1.f - lw;
-                    const float w4[4] = {hh * hw, hh * lw, lh * hw, lh * lw};
-                    qg[tap] = X::make_geo(w4, dcn2_sigmoid(d_m));
+                    const DcnFar fs = dcn_far(h_im, w_im, hl, wl, a.H, a.W);
+                    qg[tap] = X::make_geo(fs.w, dcn2_sigmoid(d.d_m));
                     qb[tap] = ((hl * a.W + wl) * a.in_cs + 8 * h) * ES;
-                    qok[tap] = (hl >= 0 && wl >= 0 ? 1 : 0) | (hl >= 0 && wl + 1 <= a.W - 1 ? 2 : 0) |
-                               (hl + 1 <= a.H - 1 && wl >= 0 ? 4 : 0) | (hl + 1 <= a.H - 1 && wl + 1 <= a.W - 1 ? 8 : 0);
+                    qok[tap] = fs.ok;
                 }
             }
             if (__any(pend)) wmask |= 1 << tap;
@@ -455,11 +433,11 @@ __global__ __launch_bounds__(512, MT <= 2 ? 4 : 2) void dcn5_kernel(Dcn5Args a)
                     if (!((wmask >> (t0 + j)) & 1)) continue;                // wave-uniform
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
-                        pv[j][k] = dcn5_corner(img, img_bytes, ((qok[t0 + j] >> k) & 1) ? qb[t0 + j] + (k & 1) * pxb + (k >> 1) * rowb : 0x7ffffff0, c0 * ES);
+                        pv[j][k] = dcn_corner16(img, img_bytes, ((qok[t0 + j] >> k) & 1) ? qb[t0 + j] + (k & 1) * pxb + (k >> 1) * rowb : 0x7ffffff0, c0 * ES);
                 }
             };
             __syncthreads();
-            dcn5_issue_w<C::WPIECES>(a.w, main_bytes, s_w, ((c0 / CK) * a.G + (int)blockIdx.y * MT) * C::WGRP, l * 16, wvu);
+            dcn_lds_dma<C::WPIECES>(a.w, main_bytes, s_w, ((c0 / CK) * a.G + (int)blockIdx.y * MT) * C::WGRP, l * 16, wvu);
             fetch(0);
             __builtin_amdgcn_s_waitcnt(0x0f70);
             __syncthreads();
@@ -488,9 +466,7 @@ __global__ __launch_bounds__(512, MT <= 2 ? 4 : 2) void dcn5_kernel(Dcn5Args a)
         }
     }
 
-    EpiArgs e;
-    e.bias = a.bias; e.res = nullptr; e.out = a.out; e.Ho = a.H; e.Wo = a.W; e.Cout = a.Cout;
-    e.out_cs = a.out_cs; e.res_cs = 0; e.relu = a.relu; e.out_mode = a.out_mode;
+    const EpiArgs e = dcn_epi_args(a);
     if constexpr (EPI == 2) {
         __syncthreads();                          // the apron and the filters are no longer read
         tile_epilogue_lds<T, MT>(acc, e, b, oy0, ox0, cout0, wvu, l, smem + wvu * epi_lds_stride<MT>());
@@ -517,8 +493,7 @@ static int launch_dcn5_cfg(const Dcn5Args &a0, hipStream_t st)
     a.tiles_y = cdiv(a.H, 16);
     a.xcd = h3d_xcd_mode();
     dim3 grid(a.B * a.tiles_x * a.tiles_y, cdiv(a.Cout, 32 * MT));
-    const bool lean = a.out_mode == H3D_OUT_NHWC && a.Cout % 4 == 0 && ((uintptr_t)a.bias & 15) == 0;
-    const int epi = (MT >= 2 && lean && a.Cout % 8 == 0 && a.out_cs % 8 == 0 && ((uintptr_t)a.out & 15) == 0) ? 2 : lean ? 1 : 0;
+    const int epi = dcn_epi_mode(a, MT >= 2);
     if (h3d_note_kernel(XP ? "dcn5_kernel<%d, %d, %d, %d, %d>" : "dcn5_kernel<%d, %d, %d, %d>", MT, MARGIN, epi, NP, XP)) return H3D_OK;
     if constexpr (MT >= 2) {
         if (epi == 2) {
@@ -538,10 +513,8 @@ static int launch_dcn5_cfg(const Dcn5Args &a0, hipStream_t st)
 int h3d_launch_dcn5(const h3d_op &op, hipStream_t st)
 {
     Dcn5Args a;
-    a.in = (const char *)op.in; a.w = (const char *)op.w; a.woff = (const char *)op.in2; a.bias = op.bias;
-    a.out = (char *)op.out; a.B = op.B; a.H = op.H; a.W = op.W; a.Cin = op.Cin; a.in_cs = op.in_cs;
-    a.Cout = op.Cout; a.out_cs = op.out_cs; a.relu = op.relu; a.out_mode = op.out_mode; a.wrows = op.wrows;
-    a.tiles_x = a.tiles_y = 0;
+    dcn_fill_args(op, a);
+    a.w = (const char *)op.w; a.woff = (const char *)op.in2; a.Cin = op.Cin; a.wrows = op.wrows;
     a.dbg = 0;      // (the kernel has no ablation switches: its experiments are the XP template parameter)
     a.G = op.wrows / 32;
     const int xp = H3D_TUNE_DCN_STREAM_DCN5_XP_OF(op.reserved);

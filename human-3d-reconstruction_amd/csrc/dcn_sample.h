@@ -1,5 +1,6 @@
 // Sampling geometry of one (pixel, tap) in the reference's float arithmetic (dcn_v2_im2col_cuda.cu:25-54, 163-185): shared by the operator
-// boundary's general kernel (csrc/dcn.hip) and the first-generation network kernel (csrc/dcn1.hip, `make EXTRA=1`).
+// boundary's general kernel (csrc/dcn.hip), the backward kernels (csrc/dcn_bwd.hip) and the first-generation network kernel
+// (csrc/dcn1.hip, `make EXTRA=1`).  The tiled generations (csrc/dcn2.hip ... dcn5.hip) take their geometry from csrc/dcn_tile.h.
 #pragma once
 #include "common.h"
 

@@ -586,7 +586,8 @@ class Plan:
         return out
 
     def upadd(self, x, skip, wkey, f16=False):
-        """f16: the sum is written as fp16 (same 2-byte NHWC buffer) for a csrc/dcn4.hip consumer."""
+        """f16: the sum is written as fp16 (same 2-byte NHWC buffer) for a DeformConv that reads fp16: the F16IN variants of
+        csrc/dcn3.hip (H3D_OPF_DCN_STREAM_F16_INPUT, the default) or csrc/dcn4.hip (stream_dcn, `make EXTRA=1`)."""
         w, k = self.pw.up(wkey)
         f = k // 2
         out = self._alloc(x.H * f, x.W * f, x.C)
