@@ -12,7 +12,9 @@ Reference-named entry points (same names / argument meaning as the reference's s
     models.decode.{_nms,_topk,_topk_channel,multi_pose_decode,ctdet_decode} -> h3d_amd.decode.*
     models.utils.{_sigmoid,_gather_feat,_transpose_and_gather_feat} -> h3d_amd.utils.*
     utils.post_process.multi_pose_post_process -> h3d_amd.detector.multi_pose_post_process
+    models.losses.{FocalLoss,RegL1Loss,RegLoss,NormRegL1Loss,RegWeightedL1Loss},
+        trains.trainer.{loss_multi_pose,loss_obj_detection} -> h3d_amd.losses.*
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth", "arch", "model", "engine", "decode", "utils", "dcn_v2", "smpl", "detector"]
+__all__ = ["synth", "arch", "model", "engine", "decode", "utils", "dcn_v2", "smpl", "detector", "losses"]

@@ -151,6 +151,10 @@ SIGNATURES = {
     "h3d_smpl_verts": [c_vp] * 8 + [c_i] * 4 + [c_vp, c_vp],
     "h3d_smpl_verts2": [c_vp] * 7 + [c_i] * 5 + [c_vp, c_vp],
     "h3d_sigmoid_clamp": [c_vp, c_vp, ctypes.c_size_t, c_vp],
+    # losses (h3d_amd/losses.py holds the mirror of `struct h3d_loss_term`)
+    "h3d_loss_workspace_bytes": [c_vp, c_i, ctypes.POINTER(ctypes.c_size_t)],
+    "h3d_loss_forward": [c_vp, c_i, c_vp, c_vp, ctypes.c_size_t, c_vp],
+    "h3d_loss_backward": [c_vp, c_i, c_vp, c_vp, c_vp],
 }
 
 _lib = None

@@ -305,6 +305,11 @@ template <> __device__ __forceinline__ void load4<f16_t>(const f16_t *p, float *
     EP<f16_t>::unpack2(v[1], o[2], o[3]);
 }
 
+// _sigmoid (utils.py:8-10): clamp(sigmoid(x), 1e-4, 1-1e-4); expf (not __expf) keeps full fp32 accuracy.  One definition for the decode
+// kernels (csrc/decode.hip) and the losses (csrc/loss.hip): the `pred` a loss stores is bit-identical to h3d_sigmoid_clamp's.
+__device__ __forceinline__ float sigmoid_plain(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ float sigmoid_clamp(float x) { return fminf(fmaxf(sigmoid_plain(x), 1e-4f), 1.0f - 1e-4f); }
+
 // Cooperative global -> LDS staging of TOTAL 16-byte vectors by NTHREADS threads: ALL loads are
 // issued before the first LDS store, so the vector-memory latency is paid once per stage instead
 // of once per vector (a plain `for (i = tid; ...) lds[i] = g[i]` loop serialises on s_waitcnt).

@@ -45,13 +45,6 @@ __device__ void bitonic_desc(u64 *s, int N, int tid, int nthreads)
     }
 }
 
-__device__ __forceinline__ float sigmoid_clamp(float x)
-{
-    // clamp(sigmoid(x), 1e-4, 1-1e-4); expf (not __expf) keeps full fp32 accuracy
-    float y = 1.0f / (1.0f + expf(-x));
-    return fminf(fmaxf(y, 1e-4f), 1.0f - 1e-4f);
-}
-
 constexpr int NMS_THREADS = 1024;   // 16 waves: a (b, c) map is one workgroup, so latency is hidden by waves, not by workgroups
 constexpr int NMS_WAVES = NMS_THREADS / 64;
 constexpr int NMS_MAXK = 1024;

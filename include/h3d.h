@@ -608,6 +608,61 @@ int h3d_smpl_verts2(const float *coefT, const float *A, const float *v_template,
                     const float *lbs_w, int nnz, int P, int Ppad, int V, int Vpad, float *verts,
                     void *stream);
 
+/* =====================================================================================
+ * 5. Losses (losses.py, trains/trainer.py:29-137): the focal term of `_neg_loss` (losses.py:42-67) and the four gathered regression
+ *    terms, forward and backward, in descriptor form: one h3d_loss_term per term, ALL terms of a call in one partial-sum launch plus
+ *    one finish launch (csrc/loss.hip).  No host synchronisation: where the reference branches on the host (`if num_pos == 0`) the
+ *    finish kernel selects on the device.  Every sum is taken in a fixed order (fp32 per thread, wave shuffles, LDS, one plain-stored
+ *    partial per workgroup, fp64 over the partials): the statistics are bit-identical from run to run.
+ *    kinds:
+ *      H3D_LOSS_FOCAL        x, gt [n] fp32.  p = x, or clamp(sigmoid(x), 1e-4, 1-1e-4) with H3D_LOSS_FROM_LOGITS (then `pred`, when not NULL,
+ *                            receives p: bit-identical to h3d_sigmoid_clamp).  gt == 1: pos += log(p) (1-p)^2, num_pos += 1; gt < 1:
+ *                            neg += log(1-p) p^2 (1-gt)^4; gt > 1 (or NaN): nothing.  loss = -neg if num_pos == 0, else -(pos+neg)/num_pos.
+ *                            aux = {pos, neg, num_pos}.  Any 4-byte aligned pointers, any n.
+ *      H3D_LOSS_REG_L1       RegL1Loss (losses.py:139-149): x = feat [B,C,HW] (NCHW, read in place at b C HW + c HW + ind), ind [B,M] int64,
+ *                            mask [B,M], gt = target [B,M,C]; per (b,m,c) with k = mask[b,m]: num += |p k - t k|, den += k (the sum of the
+ *                            EXPANDED mask).  loss = num / (den + 1e-4).  aux = {num, den, 0}
+ *      H3D_LOSS_REG_WEIGHTED_L1  RegWeightedL1Loss (losses.py:165-175): the same with mask [B,M,C]
+ *      H3D_LOSS_NORM_REG_L1  NormRegL1Loss (losses.py:151-163): mask [B,M]; num += |p / (t + 1e-4) k - k|
+ *      H3D_LOSS_REG_SL1      RegLoss (losses.py:97-112, 123-137): mask [B,M]; num += smooth_l1(p k - t k), den += k once per (b,m) (the
+ *                            UNEXPANDED mask)
+ *    mask_type: H3D_LOSS_MASK_U8 (uint8) or H3D_LOSS_MASK_F32.  DECIDED HERE: a slot whose ind lies outside [0,HW) reads nothing and adds
+ *    nothing to num or den (the reference gathers out of bounds).
+ *    Backward: grad (shaped like x; NULL = this term is skipped, nothing is written for it) = coef[t] * d loss_t / d x, the 1/num_pos or
+ *    1/(den + 1e-4) read from the forward's stats on the device.  FROM_LOGITS chains through the clamp (gradient passes for
+ *    1e-4 <= sigmoid(x) <= 1-1e-4, torch's rule) and p (1-p), p recomputed from x.  A regression term's grad is zero-filled in one
+ *    launch and scattered in the next (slots with mask 0 skipped; slots sharing an ind accumulate with float atomic adds: the order
+ *    of those adds varies, everything else is bit-identical from run to run).
+ *    A term with no elements (n == 0, or B C M HW == 0) launches nothing, reads no pointer and has loss 0; n_terms == 0 launches nothing and
+ *    sets the total to 0.  Negative sizes: H3D_ERR_SHAPE; NULL terms / stats / operands: H3D_ERR_ARG; more than H3D_LOSS_MAX_TERMS
+ *    terms: H3D_ERR_UNSUPPORTED; a NULL or short workspace: H3D_ERR_ARG ("workspace" in the message).
+ * ===================================================================================== */
+enum { H3D_LOSS_FOCAL = 1, H3D_LOSS_REG_L1 = 2, H3D_LOSS_REG_WEIGHTED_L1 = 3, H3D_LOSS_NORM_REG_L1 = 4, H3D_LOSS_REG_SL1 = 5 };
+enum { H3D_LOSS_MASK_U8 = 0, H3D_LOSS_MASK_F32 = 1 };
+#define H3D_LOSS_FROM_LOGITS 1       /* focal: x holds logits                                                                          */
+#define H3D_LOSS_TUNE_GRID8 0x100    /* tests: at most 8 workgroups for this term, so that the grid-stride loop wraps at small sizes   */
+#define H3D_LOSS_MAX_TERMS 16
+typedef struct h3d_loss_term {
+    int32_t kind;        /* H3D_LOSS_*                                                             */
+    int32_t flags;       /* H3D_LOSS_FROM_LOGITS | H3D_LOSS_TUNE_GRID8                              */
+    const float *x;      /* focal: logits or probabilities [n]; regression: feat [B,C,HW]          */
+    const float *gt;     /* focal: gt [n]; regression: target [B,M,C]                              */
+    float *pred;         /* focal + FROM_LOGITS: receives p [n], or NULL                           */
+    const int64_t *ind;  /* regression: [B,M]                                                      */
+    const void *mask;    /* regression: [B,M] ([B,M,C] for REG_WEIGHTED_L1) of mask_type           */
+    float *grad;         /* backward: d/dx, shaped like x; NULL = skip this term                   */
+    int64_t n;           /* focal: elements                                                        */
+    int32_t B, C, HW, M; /* regression                                                             */
+    int32_t mask_type;   /* H3D_LOSS_MASK_*                                                        */
+    float weight;        /* the term's weight in the total                                         */
+} h3d_loss_term;
+/* stats: 4 * n_terms + 1 floats of device memory: per term {loss, aux0, aux1, aux2}, then total = sum of weight_t * loss_t (in term
+ * order, fp64).  workspace: h3d_loss_workspace_bytes bytes (16 per workgroup of the partial launch), 16-byte aligned. */
+int h3d_loss_workspace_bytes(const h3d_loss_term *terms, int n_terms, size_t *bytes);
+int h3d_loss_forward(const h3d_loss_term *terms, int n_terms, float *stats, void *workspace, size_t workspace_bytes, void *stream);
+/* stats: what h3d_loss_forward wrote for the same terms; coef [n_terms]: device memory, the upstream coefficient of each term's loss. */
+int h3d_loss_backward(const h3d_loss_term *terms, int n_terms, const float *stats, const float *coef, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
