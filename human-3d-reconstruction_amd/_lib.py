@@ -155,6 +155,10 @@ SIGNATURES = {
     "h3d_loss_workspace_bytes": [c_vp, c_i, ctypes.POINTER(ctypes.c_size_t)],
     "h3d_loss_forward": [c_vp, c_i, c_vp, c_vp, ctypes.c_size_t, c_vp],
     "h3d_loss_backward": [c_vp, c_i, c_vp, c_vp, c_vp],
+    # SMPL backward (include/h3d.h section 4b)
+    "h3d_smpl_backward_workspace_bytes": [c_i] * 5 + [ctypes.POINTER(ctypes.c_size_t)],
+    "h3d_smpl_backward": [c_vp] * 12 + [c_i] * 4 + [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
+    "h3d_smpl_heads_backward": [c_vp] * 3 + [c_i] * 4 + [c_vp] * 10 + [c_i] * 3 + [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
 }
 
 _lib = None

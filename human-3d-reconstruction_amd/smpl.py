@@ -6,7 +6,8 @@ SMPL model is licence-gated, so this stage follows the published formulation (Lo
 the true tensor shapes for benchmarking.  A real model drops in through `SMPLModel.from_npz`.
 Parity for this stage is "unpinned by the reference" (DESIGN.md).
 
-Device compute: csrc/smpl.hip via `h3d_smpl_*` (include/h3d.h).
+Device compute: csrc/smpl.hip via `h3d_smpl_*` (include/h3d.h).  Gradients with respect to betas / thetas (or the `pose` / `shape`
+head maps): csrc/smpl_bwd.hip, through `lbs_backward` and, when an input requires grad, through autograd (include/h3d.h section 4b).
 """
 import numpy as np
 
@@ -51,7 +52,10 @@ class SMPLModel:
         S = synth.uniform("smpl.shapedirs", (V, 3, NUM_BETAS), -0.03, 0.03, seed)
         P = synth.uniform("smpl.posedirs", (V, 3, NUM_POSE_FEAT), -0.01, 0.01, seed)
         Jr = synth.uniform01("smpl.J_regressor", (NUM_JOINTS, V), seed)
-        Jr = np.where(Jr > 0.97, Jr, 0.0)
+        keep = Jr > 0.97
+        none = ~keep.any(1)                 # a small body can leave a joint without an entry above the threshold: it keeps its largest
+        keep[none] = Jr[none] == Jr[none].max(1, keepdims=True)
+        Jr = np.where(keep, Jr, 0.0)
         Jr = (Jr / Jr.sum(1, keepdims=True)).astype(np.float32)
         u = synth.uniform01("smpl.weights", (V, NUM_JOINTS), seed)
         kth = np.sort(u, axis=1)[:, -4][:, None]
@@ -127,11 +131,176 @@ def _dirs_k3(model, Vpad, device, KP=224):
     return out.contiguous().to(device)
 
 
+def _dirs_v3(model, Vpad, device, KP=224):
+    """[3 terms][KP][3][Vpad] bf16: the three-term split of _dirs_k3 (same rounding) with the vertices contiguous -- the direction
+    operand of the transposed contraction of csrc/smpl_bwd.hip (smpl_bwd_coef_kernel)."""
+    import torch
+    V = model.v_template.shape[0]
+    d = np.zeros((KP, 3, Vpad), np.float32)
+    d[:NUM_BETAS, :, :V] = model.shapedirs.transpose(2, 1, 0)                      # [V,3,10] -> [10,3,V]
+    d[NUM_BETAS:NUM_BETAS + NUM_POSE_FEAT, :, :V] = model.posedirs.transpose(2, 1, 0)
+    x = torch.from_numpy(d)
+    h = x.to(torch.bfloat16)
+    r1 = x - h.float()
+    m = r1.to(torch.bfloat16)
+    lo = (r1 - m.float()).to(torch.bfloat16)
+    return torch.stack([h, m, lo], dim=0).contiguous().to(device)
+
+
+def _pack_for(model, dev, backward=False):
+    """The device pack of `model` on `dev`; with backward=True also dirsV3, built on first use (once per model and device)."""
+    if model._dev is None or model._dev["v_template"].device != dev:
+        model._dev = _device_pack(model, dev)
+    d = model._dev
+    if backward and "dirsV3" not in d:
+        d["dirsV3"] = _dirs_v3(model, d["Vpad"], dev)
+    return d
+
+
+MAX_BACKWARD_NNZ = 4
+
+
+def lbs_backward(model, betas, thetas, grad_verts=None, grad_joints=None):
+    """The gradients of `lbs` (verts [P,V,3], joints [P,24,3]) with respect to betas [P,10] and thetas [P,72], given the upstream
+    gradients grad_verts [P,V,3] and / or grad_joints [P,24,3] (None = absent) -> (grad_betas [P,10], grad_thetas [P,72]), fp32.
+    Everything is recomputed from betas / thetas (h3d_smpl_backward, include/h3d.h section 4b); the sums run in a fixed order, so two
+    calls give the same bits.  Needs <= 4 skinning weights per vertex."""
+    import ctypes
+    import torch
+    from . import _lib
+    _lib.require_cuda(betas, thetas, grad_verts, grad_joints)
+    dev = betas.device
+    d = _pack_for(model, dev, backward=True)
+    if d["nnz"] > MAX_BACKWARD_NNZ:
+        raise RuntimeError("smpl backward: %d skinning weights per vertex, the limit is %d" % (d["nnz"], MAX_BACKWARD_NNZ))
+    betas = betas.detach().contiguous().float()
+    P = betas.shape[0]
+    thetas = thetas.detach().contiguous().float().view(P, 72)
+    if betas.shape != (P, NUM_BETAS):
+        raise RuntimeError("lbs_backward: betas [P,10], thetas [P,72]")
+    gv = None if grad_verts is None else grad_verts.detach().float().contiguous()       # (an expanded upstream becomes dense here)
+    gj = None if grad_joints is None else grad_joints.detach().float().contiguous()
+    if (gv is not None and gv.shape != (P, d["V"], 3)) or (gj is not None and gj.shape != (P, NUM_JOINTS, 3)):
+        raise RuntimeError("lbs_backward: grad_verts [P,V,3], grad_joints [P,24,3]")
+    gb = torch.empty(P, NUM_BETAS, dtype=torch.float32, device=dev)
+    gt = torch.empty(P, 72, dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.h3d_smpl_backward_workspace_bytes(P, d["V"], d["Vpad"], d["nnz"], int(gv is not None), ctypes.byref(nbytes)),
+               "smpl_backward_workspace_bytes")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if nbytes.value else None
+    with torch.cuda.device(dev):
+        st = _lib.stream_ptr()              # the current stream of `dev`, as the forward
+        _lib.check(L.h3d_smpl_backward(_lib.ptr(betas), _lib.ptr(thetas), _lib.ptr(gv), _lib.ptr(gj), _lib.ptr(d["j_template"]),
+                                       _lib.ptr(d["j_shapedirs"]), _lib.ptr(d["parents"]), _lib.ptr(d["v_template"]), _lib.ptr(d["dirsK3"]),
+                                       _lib.ptr(d["dirsV3"]), _lib.ptr(d["lbs_idx"]), _lib.ptr(d["lbs_w"]), d["nnz"], P, d["V"], d["Vpad"],
+                                       _lib.ptr(gb), _lib.ptr(gt), _lib.ptr(ws), nbytes.value, st), "smpl_backward")
+    return gb, gt
+
+
+def _heads_backward(model, pose_map, shape_map, inds, n, grad_verts, grad_joints):
+    """h3d_smpl_heads_backward: -> (grad_pose_map, grad_shape_map), shaped like the maps."""
+    import ctypes
+    import torch
+    from . import _lib
+    dev = pose_map.device
+    d = _pack_for(model, dev, backward=True)
+    B, K = inds.shape
+    HW = pose_map.shape[2] * pose_map.shape[3]
+    P = B * n
+    gv = None if grad_verts is None else grad_verts.detach().float().contiguous()
+    gj = None if grad_joints is None else grad_joints.detach().float().contiguous()
+    gp = torch.empty_like(pose_map)
+    gs = torch.empty_like(shape_map)
+    L = _lib.lib()
+    nbytes = ctypes.c_size_t(0)
+    _lib.check(L.h3d_smpl_backward_workspace_bytes(P, d["V"], d["Vpad"], d["nnz"], int(gv is not None), ctypes.byref(nbytes)),
+               "smpl_backward_workspace_bytes")
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if nbytes.value else None
+    with torch.cuda.device(dev):
+        st = _lib.stream_ptr()
+        _lib.check(L.h3d_smpl_heads_backward(_lib.ptr(pose_map), _lib.ptr(shape_map), _lib.ptr(inds), B, K, n, HW, _lib.ptr(gv), _lib.ptr(gj),
+                                             _lib.ptr(d["j_template"]), _lib.ptr(d["j_shapedirs"]), _lib.ptr(d["parents"]),
+                                             _lib.ptr(d["v_template"]), _lib.ptr(d["dirsK3"]), _lib.ptr(d["dirsV3"]), _lib.ptr(d["lbs_idx"]),
+                                             _lib.ptr(d["lbs_w"]), d["nnz"], d["V"], d["Vpad"], _lib.ptr(gp), _lib.ptr(gs), _lib.ptr(ws),
+                                             nbytes.value, st), "smpl_heads_backward")
+    return gp, gs
+
+
+_functions = None
+
+
+def _autograd_functions():
+    """(lbs Function, lbs_from_heads Function), defined on first use (torch is imported lazily in this module).  The forward inside is
+    the kernel the caller asked for; the backward recomputes from the inputs (once_differentiable: no second derivatives)."""
+    global _functions
+    if _functions is not None:
+        return _functions
+    import torch
+    from torch.autograd.function import once_differentiable
+
+    def _check_nnz(model, dev):
+        nnz = _pack_for(model, dev)["nnz"]
+        if nnz > MAX_BACKWARD_NNZ:
+            raise RuntimeError("smpl backward: %d skinning weights per vertex, the limit is %d (gradients were requested)"
+                               % (nnz, MAX_BACKWARD_NNZ))
+
+    class LbsFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, model, kernel, betas, thetas):
+            _check_nnz(model, betas.device)
+            ctx.model = model
+            ctx.set_materialize_grads(False)
+            ctx.save_for_backward(betas, thetas)
+            return _lbs_forward(model, betas.detach(), thetas.detach(), True, kernel)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_verts, grad_joints):
+            betas, thetas = ctx.saved_tensors
+            gb, gt = lbs_backward(ctx.model, betas, thetas, grad_verts, grad_joints)
+            return None, None, gb.to(betas.dtype).view_as(betas), gt.to(thetas.dtype).view_as(thetas)
+
+    class HeadsFunction(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, model, n, exact, inds, pose_map, shape_map):
+            ctx.model, ctx.n = model, n
+            ctx.set_materialize_grads(False)
+            ctx.save_for_backward(pose_map, shape_map, inds)
+            return _lbs_from_heads_forward(model, pose_map.detach(), shape_map.detach(), inds, n, True, exact)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad_verts, grad_joints):
+            pose_map, shape_map, inds = ctx.saved_tensors
+            gp, gs = _heads_backward(ctx.model, pose_map, shape_map, inds, ctx.n, grad_verts, grad_joints)
+            return None, None, None, None, gp, gs
+
+    _functions = (LbsFunction, HeadsFunction)
+    return _functions
+
+
 def lbs(model, betas, thetas, return_joints=False, kernel="auto"):
     """betas [P,10], thetas [P,72] (CUDA fp32) -> vertices [P,V,3] (and posed joints [P,24,3]).
+    With grad mode on and betas or thetas requiring grad the result carries a graph (gradients by csrc/smpl_bwd.hip, see
+    `lbs_backward`; <= 4 skinning weights per vertex); otherwise the call is the plain forward below, launch for launch.
     kernel: "gen3" = blend shapes on the matrix cores (3-term bf16 split; the three 2^-16 products dropped: 2e-6 abs on the displacement),
     "gen3x" = the same with all six products (2^-24: what the f32 parity-mode detectors run), "gen2" = LDS-streamed vector kernel (all
     need <= 4 skinning weights per vertex), "gen1" = register kernel, "auto" = gen3 when applicable and P >= 64, "auto_exact" = gen3x."""
+    import torch
+    if torch.is_grad_enabled() and (betas.requires_grad or thetas.requires_grad):
+        _lib_check_cuda(betas, thetas)
+        verts, joints = _autograd_functions()[0].apply(model, kernel, betas, thetas)
+        return (verts, joints) if return_joints else verts
+    return _lbs_forward(model, betas, thetas, return_joints, kernel)
+
+
+def _lib_check_cuda(*tensors):
+    from . import _lib
+    _lib.require_cuda(*tensors)
+
+
+def _lbs_forward(model, betas, thetas, return_joints, kernel):
     import torch
     from . import _lib
     _lib.require_cuda(betas, thetas)
@@ -182,7 +351,18 @@ def lbs_from_heads(model, pose_map, shape_map, inds, n, return_joints=False, exa
     head maps), inds [B,K] int64 (the decode's centre indices), the first `n` detections of every image -> vertices
     [B*n,V,3] (and joints [B*n,24,3]).  Two launches -- `h3d_smpl_pose_heads` (gathers + Rodrigues + kinematic chain + the
     generation-3 coefficient operand) and `h3d_smpl_verts3` -- instead of the five of `_transpose_and_gather_feat` x 2 + `lbs`;
-    bit-identical to them (tests/test_gpu_smpl.py).  Needs <= 4 skinning weights per vertex (generation 3)."""
+    bit-identical to them (tests/test_gpu_smpl.py).  Needs <= 4 skinning weights per vertex (generation 3).
+    With grad mode on and pose_map or shape_map requiring grad the result carries a graph: the gradients arrive at the maps
+    (h3d_smpl_heads_backward: zero off the gathered pixels, detections that share a pixel add up)."""
+    import torch
+    if torch.is_grad_enabled() and (pose_map.requires_grad or shape_map.requires_grad):
+        _lib_check_cuda(pose_map, shape_map, inds)
+        verts, joints = _autograd_functions()[1].apply(model, n, exact, inds, pose_map, shape_map)
+        return (verts, joints) if return_joints else verts
+    return _lbs_from_heads_forward(model, pose_map, shape_map, inds, n, return_joints, exact)
+
+
+def _lbs_from_heads_forward(model, pose_map, shape_map, inds, n, return_joints, exact):
     import torch
     from . import _lib
     _lib.require_cuda(pose_map, shape_map, inds)

@@ -609,6 +609,50 @@ int h3d_smpl_verts2(const float *coefT, const float *A, const float *v_template,
                     void *stream);
 
 /* =====================================================================================
+ * 4b. SMPL backward (csrc/smpl_bwd.hip): the gradients of the stage above with respect to betas / thetas (h3d_smpl_backward) or to the
+ *    `shape` / `pose` head maps (h3d_smpl_heads_backward), from upstream gradients at the vertices and / or the posed joints.
+ *    betas [P,10], thetas [P,72] as the forward read them; grad_verts [P,V,3] or NULL; grad_joints [P,24,3] or NULL; the model pack of the
+ *    forward (j_template, j_shapedirs, parents, v_template, dirsK3, lbs_idx, lbs_w) and dirsV3 [3 terms][224][3][Vpad] bf16, the same
+ *    three-term split of the directions (round-to-nearest-even) stored V-contiguous for the transposed contraction (h3d_amd/smpl.py:
+ *    _dirs_v3); grad_betas [P,10], grad_thetas [P,72], either may be NULL.
+ *    - Asynchronous on `stream`, no allocation, no global state.  Everything is recomputed from betas / thetas and the model pack:
+ *      nothing saved by the forward is needed.
+ *    - The gradient is that of the exact formulation (oracle/smpl.py, including angle = ||theta + 1e-8||, axis = theta / angle): the
+ *      same whichever forward generation produced the values.  v_posed is recomputed with all six products of the three-term split.
+ *    - grad_verts == NULL: no vertex kernel is launched, only joints -> chain -> Rodrigues (one small launch), and the model pointers
+ *      from v_template on and the workspace are not read.  Both upstream pointers NULL: the requested outputs are zero-filled.
+ *      P == 0: nothing is launched, H3D_OK.
+ *    - Reproducibility: grad_betas and grad_thetas are sums in a fixed order, bit-identical from run to run; no float atomics in
+ *      h3d_smpl_backward.  The sum over the vertices into the 24 x 12 transform gradients is taken in vertex order inside a tile group
+ *      (one plain-stored partial per group and person) and over the groups in order, in fp64; the sum over 3 Vpad into the 217 coefficient
+ *      gradients is one fp32 MFMA chain per split and fp64 over the splits in order.
+ *    - nnz > 4: H3D_ERR_UNSUPPORTED.  NULL required operands, or (with grad_verts) a NULL or short workspace: H3D_ERR_ARG, the latter
+ *      with "workspace" in the message.  Negative sizes, V <= 0, nnz <= 0, Vpad % 64 != 0, Vpad < V, an operand of 2 GiB: H3D_ERR_SHAPE.
+ *    - Out of scope: gradients with respect to the model tensors (shapedirs, posedirs, skinning weights, joint regressor), and second
+ *      derivatives (the Python binding is once_differentiable).
+ *    Workspace (device memory, 256-byte aligned; a256(x) = x rounded up to 256), with Ppad = P rounded up to 128,
+ *    NG = ceil(Vpad / 64 / 4) vertex-tile groups and NS = ceil(3 Vpad / 1536) splits of the coefficient contraction:
+ *      bytes = a256(4 P 207) [pose_feat] + a256(4 P 288) [A] + a256(4 P 72) [joints] + a256(1344 Ppad) [coefK3]
+ *            + a256(4 P 3 Vpad) [g_vp] + a256(4 NG P 288) [transform-gradient partials] + a256(4 NS P 224) [coefficient partials]
+ *    (6890 vertices: 83 kB + 31 kB + 12 kB per person beside the 3 kB of forward intermediates; `verts` itself is 83 kB), and 0 when
+ *    want_verts == 0 or P == 0.  The size query returns a status and hands the size back through `bytes`. */
+int h3d_smpl_backward_workspace_bytes(int P, int V, int Vpad, int nnz, int want_verts, size_t *bytes);
+int h3d_smpl_backward(const float *betas, const float *thetas, const float *grad_verts, const float *grad_joints,
+                      const float *j_template, const float *j_shapedirs, const int32_t *parents, const float *v_template,
+                      const void *dirsK3, const void *dirsV3, const int32_t *lbs_idx, const float *lbs_w, int nnz, int P, int V, int Vpad,
+                      float *grad_betas, float *grad_thetas, void *workspace, size_t workspace_bytes, void *stream);
+/* The same with the parameters read where h3d_smpl_pose_heads reads them (person p = detection p % n of image p / n, pixel
+ * inds[(p / n) * K + p % n] of pose_map [B,72,HW] / shape_map [B,10,HW]); P = B * n in the workspace formula.  grad_pose_map [B,72,HW] and
+ * grad_shape_map [B,10,HW] (either may be NULL) are zero-filled by the callee on `stream`, then every person's 72 + 10 values are added at
+ * its pixel with float atomic adds, because two detections of an image may share a pixel: the order of those adds varies (last bits of a
+ * shared pixel), everything else is bit-identical from run to run -- as h3d_loss_backward scatters. */
+int h3d_smpl_heads_backward(const float *pose_map, const float *shape_map, const int64_t *inds, int B, int K, int n, int HW,
+                            const float *grad_verts, const float *grad_joints, const float *j_template, const float *j_shapedirs,
+                            const int32_t *parents, const float *v_template, const void *dirsK3, const void *dirsV3,
+                            const int32_t *lbs_idx, const float *lbs_w, int nnz, int V, int Vpad, float *grad_pose_map,
+                            float *grad_shape_map, void *workspace, size_t workspace_bytes, void *stream);
+
+/* =====================================================================================
  * 5. Losses (losses.py, trains/trainer.py:29-137): the focal term of `_neg_loss` (losses.py:42-67) and the four gathered regression
  *    terms, forward and backward, in descriptor form: one h3d_loss_term per term, ALL terms of a call in one partial-sum launch plus
  *    one finish launch (csrc/loss.hip).  No host synchronisation: where the reference branches on the host (`if num_pos == 0`) the

@@ -1,0 +1,156 @@
+"""CPU: the yardstick of the SMPL gradient tests (tests/smpl_grad_ref.py) is the oracle's formulation, its float64 autograd is the
+derivative of tests/smpl_ref.lbs (central finite differences, two closed forms), and the C ABI of the backward (include/h3d.h section 4b)
+returns what its contract says on malformed calls -- everything here returns before the first launch, no GPU needed.
+
+Bounds (fixed, derived from fp64): restatement against smpl_ref.lbs 1e-12 relative (a few hundred fp64 roundings of 1.1e-16); finite
+differences with h = 1e-6: truncation h^2 f''' ~ 1e-12 and rounding 1.1e-16 |f| / h ~ 1e-8 of the gradient's scale, bound 1e-6 of the
+gradient's largest entry; closed forms 1e-12 relative."""
+import ctypes
+
+import numpy as np
+import torch
+
+import smpl_grad_ref as G
+import smpl_ref as R
+
+import h3d_amd  # noqa: F401
+from h3d_amd import _lib
+
+MODEL = R.jointed_model(100)
+
+
+def _rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.abs(a - b).max()) / max(float(np.abs(b).max()), 1e-300)
+
+
+def test_torch_restatement_equals_smpl_ref_in_float64():
+    betas, thetas = R.make_case(13, 3)
+    ref = R.lbs(betas, thetas, MODEL, np.float64)
+    got = G.lbs(torch.from_numpy(betas), torch.from_numpy(thetas), G.model_tensors(MODEL, torch.float64), torch.float64)
+    for nm, g, r in zip(R.NAMES, got, ref):
+        rel = _rel(g.numpy(), r)
+        print("%s: rel %.3g" % (nm, rel))
+        assert rel <= 1e-12, (nm, rel)
+
+
+def test_float64_autograd_agrees_with_central_differences_of_smpl_ref():
+    P, h = 4, 1e-6
+    betas, thetas = R.make_case(P, 5)
+    rs = np.random.RandomState(7)
+    gv, gj = rs.randn(P, 100, 3).astype(np.float32), rs.randn(P, 24, 3).astype(np.float32)
+    gb, gt = [g.numpy() for g in G.grads(betas, thetas, MODEL, gv, gj, torch.float64)]
+
+    def loss(b, t):
+        verts, joints, _, _ = R.lbs(b, t, MODEL, np.float64)
+        return float((verts * gv).sum() + (joints * gj).sum())
+
+    b64, t64 = betas.astype(np.float64), thetas.astype(np.float64)
+    for p in (0, 1):                                   # the rest pose and a random pose with one joint at rest: all 82 parameters of each
+        fd_b, fd_t = np.zeros(10), np.zeros(72)
+        for k in range(10):
+            d = np.zeros_like(b64); d[p, k] = h
+            fd_b[k] = (loss(b64 + d, t64) - loss(b64 - d, t64)) / (2 * h)
+        for k in range(72):
+            d = np.zeros_like(t64); d[p, k] = h
+            fd_t[k] = (loss(b64, t64 + d) - loss(b64, t64 - d)) / (2 * h)
+        eb = float(np.abs(fd_b - gb[p]).max()) / float(np.abs(gb[p]).max())
+        et = float(np.abs(fd_t - gt[p]).max()) / float(np.abs(gt[p]).max())
+        print("person %d: grad_betas rel %.3g, grad_thetas rel %.3g" % (p, eb, et))
+        assert eb <= 1e-6 and et <= 1e-6, (p, eb, et)
+
+
+def test_closed_form_rest_pose_vertex_gradient():
+    """theta = 0, no joint upstream: R = I, every A_j = [I | 0], verts_v = (sum_j w_vj) v_shaped, so
+    grad_betas[k] = sum gV . shapedirs[.., k] (times the row sum of the float32 skinning weights, which is 1 to 2^-24)."""
+    P = 3
+    betas = np.random.RandomState(1).randn(P, 10).astype(np.float32)
+    gv = np.random.RandomState(2).randn(P, 100, 3)
+    gb, gt = G.grads(betas, np.zeros((P, 72), np.float32), MODEL, gv, None, torch.float64)
+    rowsum = MODEL["weights"].astype(np.float64).sum(1)
+    want = np.einsum("pvc,vck->pk", gv * rowsum[None, :, None], MODEL["shapedirs"].astype(np.float64))
+    assert _rel(gb.numpy(), want) <= 1e-12
+
+
+def test_closed_form_root_joint_gradient():
+    """Upstream on joint 0 only: joints_0 = J_0 = J_regressor[0] . v_shaped, so grad_betas = j_shapedirs[0]^T gJ_0 and grad_thetas = 0."""
+    P = 3
+    betas, thetas = R.make_case(P, 9)
+    gj = np.zeros((P, 24, 3))
+    gj[:, 0] = np.random.RandomState(4).randn(P, 3)
+    gb, gt = G.grads(betas, thetas, MODEL, None, gj, torch.float64)
+    jsd = np.einsum("v,vck->ck", MODEL["J_regressor"][0].astype(np.float64), MODEL["shapedirs"].astype(np.float64))
+    assert _rel(gb.numpy(), gj[:, 0] @ jsd) <= 1e-12
+    assert float(gt.abs().max()) == 0.0
+
+
+# ---- the C ABI ---------------------------------------------------------------------------------------------------------------------
+OK, SHAPE, UNSUPPORTED, ARG = 0, -1, -4, -5
+NEW = ("h3d_smpl_backward_workspace_bytes", "h3d_smpl_backward", "h3d_smpl_heads_backward")
+
+
+def test_the_three_symbols_are_exported_and_declared():
+    L = _lib.lib()
+    for nm in NEW:
+        assert nm in _lib.SIGNATURES and getattr(L, nm) is not None
+    assert L.h3d_abi_version() == 4
+
+
+def _bwd(L, betas=0x1000, thetas=0x1000, gv=0x1000, gj=0x1000, model=0x1000, dirsV3=0x1000, nnz=4, P=8, V=100, Vpad=128, gb=0x1000,
+         gt=0x1000, ws=0x1000, ws_bytes=1 << 40):
+    """0x1000 stands for a device pointer that is never dereferenced: every call here returns before the first launch."""
+    return L.h3d_smpl_backward(betas, thetas, gv, gj, model, model, model, model, model, dirsV3, model, model, nnz, P, V, Vpad, gb, gt, ws,
+                               ws_bytes, None)
+
+
+def test_workspace_query_and_its_formula():
+    L = _lib.lib()
+    n = ctypes.c_size_t(7)
+    assert L.h3d_smpl_backward_workspace_bytes(8, 100, 128, 4, 1, None) == ARG
+    assert L.h3d_smpl_backward_workspace_bytes(8, 100, 128, 4, 1, ctypes.byref(n)) == OK
+    a256 = lambda x: (x + 255) // 256 * 256
+    P, Vpad, Ppad = 8, 128, 128
+    NG, NS = -(-(Vpad // 64) // 4), -(-3 * Vpad // 1536)
+    want = (a256(4 * P * 207) + a256(4 * P * 288) + a256(4 * P * 72) + a256(1344 * Ppad) + a256(4 * P * 3 * Vpad) + a256(4 * NG * P * 288)
+            + a256(4 * NS * P * 224))
+    assert n.value == want and n.value % 256 == 0
+    assert L.h3d_smpl_backward_workspace_bytes(8, 100, 128, 4, 0, ctypes.byref(n)) == OK and n.value == 0
+    assert L.h3d_smpl_backward_workspace_bytes(0, 100, 128, 4, 1, ctypes.byref(n)) == OK and n.value == 0
+    # the full mesh: the partials stay a small multiple of the size of verts (4 * 3 * 6890 bytes per person)
+    assert L.h3d_smpl_backward_workspace_bytes(128, 6890, 6912, 4, 1, ctypes.byref(n)) == OK and n.value / 128 < 2.0 * 4 * 3 * 6890
+    assert L.h3d_smpl_backward_workspace_bytes(8, 100, 100, 4, 1, ctypes.byref(n)) == SHAPE
+    assert L.h3d_smpl_backward_workspace_bytes(-1, 100, 128, 4, 1, ctypes.byref(n)) == SHAPE
+    assert L.h3d_smpl_backward_workspace_bytes(8, 100, 128, 5, 1, ctypes.byref(n)) == UNSUPPORTED
+
+
+def test_return_codes_of_the_backward():
+    L = _lib.lib()
+    n = ctypes.c_size_t(0)
+    assert L.h3d_smpl_backward_workspace_bytes(8, 100, 128, 4, 1, ctypes.byref(n)) == OK
+    assert _bwd(L, P=0) == OK                                                   # nothing to launch
+    assert _bwd(L, P=0, betas=None, thetas=None, gv=None, gj=None, ws=None, ws_bytes=0) == OK
+    for kw in ({"betas": None}, {"thetas": None}, {"model": None}, {"dirsV3": None}):
+        assert _bwd(L, **kw) == ARG, kw
+    assert _bwd(L, ws=None, ws_bytes=0) == ARG and b"workspace" in L.h3d_last_error()
+    assert _bwd(L, ws_bytes=n.value - 256) == ARG and b"workspace" in L.h3d_last_error()
+    assert _bwd(L, nnz=5) == UNSUPPORTED
+    assert _bwd(L, Vpad=100) == SHAPE                                            # not a multiple of 64
+    assert _bwd(L, V=200, Vpad=128) == SHAPE                                     # Vpad < V
+    assert _bwd(L, P=-1) == SHAPE and _bwd(L, V=-5) == SHAPE and _bwd(L, nnz=0) == SHAPE
+
+
+def _heads(L, B=2, K=5, n=3, HW=64, maps=0x1000, gv=0x1000, model=0x1000, nnz=4, V=100, Vpad=128, gp=None, gs=None, ws=0x1000,
+           ws_bytes=1 << 40):
+    # gp / gs default to NULL: the callee zero-fills the maps it is given before anything else, and that is a launch
+    return L.h3d_smpl_heads_backward(maps, maps, maps, B, K, n, HW, gv, None, model, model, model, model, model, model, model, model, nnz, V,
+                                     Vpad, gp, gs, ws, ws_bytes, None)
+
+
+def test_return_codes_of_the_heads_backward():
+    L = _lib.lib()
+    assert _heads(L, B=0) == OK
+    assert _heads(L, maps=None) == ARG and _heads(L, model=None) == ARG
+    assert _heads(L, ws=None, ws_bytes=0) == ARG and b"workspace" in L.h3d_last_error()
+    assert _heads(L, ws_bytes=256) == ARG and b"workspace" in L.h3d_last_error()
+    assert _heads(L, nnz=5) == UNSUPPORTED
+    assert _heads(L, Vpad=96) == SHAPE and _heads(L, n=6) == SHAPE and _heads(L, B=-1) == SHAPE and _heads(L, HW=-1) == SHAPE
