@@ -14,7 +14,9 @@ Reference-named entry points (same names / argument meaning as the reference's s
     utils.post_process.multi_pose_post_process -> h3d_amd.detector.multi_pose_post_process
     models.losses.{FocalLoss,RegL1Loss,RegLoss,NormRegL1Loss,RegWeightedL1Loss},
         trains.trainer.{loss_multi_pose,loss_obj_detection} -> h3d_amd.losses.*
+    datasets.coco_hp.COCOHP.{_get_label,_get_dataset}, the label block of datasets.coco.COCO.__getitem__,
+        utils.image.get_affine_transform -> h3d_amd.targets.{multi_pose_targets,ctdet_targets,get_affine_transform}
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth", "arch", "model", "engine", "decode", "utils", "dcn_v2", "smpl", "detector", "losses"]
+__all__ = ["synth", "arch", "model", "engine", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets"]

@@ -707,6 +707,58 @@ int h3d_loss_forward(const h3d_loss_term *terms, int n_terms, float *stats, void
 /* stats: what h3d_loss_forward wrote for the same terms; coef [n_terms]: device memory, the upstream coefficient of each term's loss. */
 int h3d_loss_backward(const h3d_loss_term *terms, int n_terms, const float *stats, const float *coef, void *stream);
 
+/* =====================================================================================
+ * 6. Training targets (csrc/targets.hip): the label half of the reference's dataset items, COCOHP._get_label (datasets/coco_hp.py:215-309)
+ *    and the ctdet block of COCO.__getitem__ (datasets/coco.py:203-248), for a whole batch in two launches: an objects kernel (one wave
+ *    per (image, object): box path, radius, rows, the compact gt_det) and a render kernel (one workgroup per 1024 pixels of one map: the
+ *    maximum over the splats that cover a pixel).  Asynchronous on `stream`, no allocation, no memset, no atomics: every element of every
+ *    requested output is stored exactly once, zeros included (hand in uninitialised memory), bit-identical from run to run.
+ *    Inputs (device memory):
+ *      boxes      [B,M,4] f32    COCO xywh of the annotations, M = the row stride of the inputs
+ *      keypoints  [B,M,J,3] f32  (x, y, visibility)                                  (multi_pose)
+ *      cls        [B,M] i32      class index in [0, num_classes); outside it the object is skipped          (ctdet)
+ *      num        [B] i32        annotations of the image; min(num, M, max_objs) are used, negative = 0
+ *      trans      [B,2,6] f64    row-major 2x3 matrices: [b,0] = trans_output, [b,1] = trans_output_rot (ctdet reads [b,0] only)
+ *      rot_flag   [B] i32        non-zero = the image's `rot != 0` (multi_pose); NULL = no image is rotated
+ *      flipped    [B] i32, width [B] i32   non-zero = mirrored, and the image width the mirror uses; flipped == NULL = none (then width may
+ *                                be NULL)
+ *      flip_pairs [n_flip_pairs,2] i32     the joint pairs a mirror swaps (flip_idx), applied in order; NULL with n_flip_pairs == 0
+ *    Arithmetic: float32 wherever numpy holds float32 (xywh -> xyxy, the mirror, the clip, h, w, ct, reg), float64 for the 2x3 matrix
+ *    times [x, y, 1] (rounded to float32 once) and for gaussian_radius (utils/image.py:97-117, its operation order); the splat value
+ *    exp(-(dx^2 + dy^2) / (2 sigma^2)), sigma = (2r + 1) / 6, in float64, rounded to float32, combined by maximum.  Not built because they
+ *    never change a value: the eps * max threshold of gaussian2D and the 0.9999 written for a person without keypoints.
+ *    Outputs (device memory; ANY may be NULL = not wanted, nothing is written for it), N = max_objs, dtypes of the reference:
+ *      multi_pose: hm [B,1,H,W] f32, hm_hp [B,J,H,W] f32, wh [B,N,2] f32, reg [B,N,2] f32, ind [B,N] i64, reg_mask [B,N] u8,
+ *                  kps [B,N,2J] f32, kps_mask [B,N,2J] u8, hp_offset [B,N*J,2] f32, hp_ind [B,N*J] i64, hp_mask [B,N*J] i64,
+ *                  gt_det [B,N,5+2J+1] f32 = [bbox(4), 1, pts(2J), 0] per LIVE object, compact in object order, zero rows behind them,
+ *                  gt_count [B] i32 = the live objects.  An image with rot_flag: hm = 0.9999 everywhere, reg_mask = kps_mask = 0.
+ *      ctdet:      hm [B,num_classes,H,W], wh, reg, ind, reg_mask as above, cat_spec_wh [B,N,2 num_classes] f32, cat_spec_mask (same
+ *                  shape) u8, gt_det [B,N,6] = [ct -+ w/2, ct -+ h/2, 1, cls], gt_count [B].
+ *    Pointers need the alignment of their element type only (maps are stored with 16-byte stores wherever 4 pixels share an aligned
+ *    16 bytes, whatever the base and the width).
+ *    Workspace: (1 + num_joints) * B * max_objs splat slots of 16 bytes {x, y, r, cls}, r < 0 = none (ctdet: num_joints = 0); 16-byte
+ *    aligned; needed only when a map is requested.  The size query returns a status and hands the size back through `bytes`.
+ *    options: H3D_TARGETS_MSE_LOSS (draw_msra_gaussian), H3D_TARGETS_DENSE_HP, H3D_TARGETS_DENSE_WH (draw_dense_reg depends on the object
+ *    order) are out of scope: H3D_ERR_UNSUPPORTED, as are J > 64 and max_objs > 512.  Negative sizes, Hout / Wout / max_objs <= 0 or
+ *    Hout, Wout > 16384, more than 65535 images or channels: H3D_ERR_SHAPE.  NULL required inputs, a misaligned pointer, a NULL or short
+ *    workspace ("workspace" in the message): H3D_ERR_ARG.  B == 0: nothing is launched, H3D_OK.
+ * ===================================================================================== */
+#define H3D_TARGETS_MSE_LOSS 1
+#define H3D_TARGETS_DENSE_HP 2
+#define H3D_TARGETS_DENSE_WH 4
+#define H3D_TARGETS_MAX_JOINTS 64
+#define H3D_TARGETS_MAX_OBJS 512
+int h3d_targets_workspace_bytes(int B, int max_objs, int num_joints, size_t *bytes);
+int h3d_multi_pose_targets(const float *boxes, const float *keypoints, const int32_t *num, const double *trans, const int32_t *rot_flag,
+                           const int32_t *flipped, const int32_t *width, const int32_t *flip_pairs, int n_flip_pairs, int B, int M, int J,
+                           int Hout, int Wout, int max_objs, float *hm, float *hm_hp, float *wh, float *reg, int64_t *ind,
+                           uint8_t *reg_mask, float *kps, uint8_t *kps_mask, float *hp_offset, int64_t *hp_ind, int64_t *hp_mask,
+                           float *gt_det, int32_t *gt_count, int options, void *workspace, size_t workspace_bytes, void *stream);
+int h3d_ctdet_targets(const float *boxes, const int32_t *cls, const int32_t *num, const double *trans, const int32_t *flipped,
+                      const int32_t *width, int B, int M, int Hout, int Wout, int num_classes, int max_objs, float *hm, float *wh,
+                      float *reg, int64_t *ind, uint8_t *reg_mask, float *cat_spec_wh, uint8_t *cat_spec_mask, float *gt_det,
+                      int32_t *gt_count, int options, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
