@@ -159,6 +159,9 @@ SIGNATURES = {
     "h3d_smpl_backward_workspace_bytes": [c_i] * 5 + [ctypes.POINTER(ctypes.c_size_t)],
     "h3d_smpl_backward": [c_vp] * 12 + [c_i] * 4 + [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
     "h3d_smpl_heads_backward": [c_vp] * 3 + [c_i] * 4 + [c_vp] * 10 + [c_i] * 3 + [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
+    # heads backward (include/h3d.h section 2b; h3d_amd/heads.py holds the mirror of `struct h3d_heads_bwd_head`)
+    "h3d_heads_backward_workspace_bytes": [c_i] * 5 + [c_vp, ctypes.POINTER(ctypes.c_size_t)],
+    "h3d_heads_backward": [c_vp] + [c_i] * 6 + [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
     # training targets (include/h3d.h section 6; h3d_amd/targets.py)
     "h3d_targets_workspace_bytes": [c_i] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
     "h3d_multi_pose_targets": [c_vp] * 8 + [c_i] * 7 + [c_vp] * 13 + [c_i, c_vp, ctypes.c_size_t, c_vp],

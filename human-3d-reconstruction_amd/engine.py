@@ -59,6 +59,28 @@ def x3_split(w):
     return g.reshape(-1, 2 * K).contiguous().view(torch.float32).reshape(w.shape)
 
 
+def heads_k_perm(hc):
+    """K order of a fused head's 1x1 filters (csrc/heads.hip): within every 32-channel group, position h*16 + r holds channel
+    (r&3) + 8*(r>>2) + 4*h, the MFMA accumulator row order."""
+    return torch.tensor([g * 32 + (r & 3) + 8 * (r >> 2) + 4 * h
+                         for g in range(hc // 32) for h in range(2) for r in range(16)])
+
+
+def pack_head_3x3(w):
+    """[head_conv,64,3,3] -> [head_conv][9][64] (PackedWeights.fused_heads and h3d_amd.heads.heads_autograd)."""
+    return w.permute(0, 2, 3, 1).reshape(w.shape[0], 9, w.shape[1])
+
+
+def pack_head_1x1(w, b, perm):
+    """[C,head_conv,1,1], [C] -> ([96 rows][head_conv] with K in `perm` order, [96]), zero beyond C; on the tensors' device."""
+    c, hc = w.shape[0], w.shape[1]
+    w2 = torch.zeros(96, hc, dtype=w.dtype, device=w.device)
+    w2[:c] = w.reshape(c, hc)[:, perm.to(w.device)]
+    b2 = torch.zeros(96, dtype=b.dtype, device=b.device)
+    b2[:c] = b
+    return w2, b2
+
+
 class View:
     """A [B,H,W,C] tensor living at channel offset `coff` of an NHWC buffer of channel stride `cs`."""
     __slots__ = ("buf", "H", "W", "C", "cs", "coff", "es")
@@ -360,17 +382,13 @@ class PackedWeights:
             hc = self.head_conv
             td = _TORCH_DT[self.dtype]
             w1, b1, per = [], [], []
-            perm = torch.tensor([g * 32 + (r & 3) + 8 * (r >> 2) + 4 * h
-                                 for g in range(hc // 32) for h in range(2) for r in range(16)])
+            perm = heads_k_perm(hc)
             for head in names:
                 c = self.heads[head]
                 w = self.sd[head + ".0.weight"]                      # [hc,64,3,3]
-                w1.append(w.permute(0, 2, 3, 1).reshape(hc, 9, w.shape[1]))
+                w1.append(pack_head_3x3(w))
                 b1.append(self.sd[head + ".0.bias"])
-                w2 = torch.zeros(96, hc)
-                w2[:c] = self.sd[head + ".2.weight"].reshape(c, hc)[:, perm]
-                b2 = torch.zeros(96)
-                b2[:c] = self.sd[head + ".2.bias"]
+                w2, b2 = pack_head_1x1(self.sd[head + ".2.weight"], self.sd[head + ".2.bias"], perm)
                 e2 = x3_exp(w2) if self.dtype == "f16x3" else 0
                 per.append((head, c, (x3_split(w2 * 2.0 ** e2) if self.dtype == "f16x3" else w2.to(td)).contiguous().to(self.device), b2.to(self.device)))
                 self.wexp[per[-1][2].data_ptr()] = e2
@@ -477,6 +495,8 @@ class Plan:
                                   # Cin % 32 == 0; False: the f32 plan's register-staged tiles, every far sample through pass 2
         stem_s2_direct=True,      # bf16 plans of the other backbones: the 7x7 stride-2 stem conv itself instead of im2col + 1x1 conv
         conv1x1_th16_min_cin=0,   # > 0: 1x1 convs with at least this many input channels (and > 32 outputs) use 16-row tiles
+        lower_heads=True,         # False: the plan ends at the 64-channel feature map `Plan.feat` (no heads ops, no head outputs): the
+                                  # frozen backbone of h3d_amd.heads.TrainableHeads
     )
 
     def __init__(self, pw, B, H, W, **flags):
@@ -787,7 +807,8 @@ class Plan:
         self._ida(ys, "ida_up", 0, 3)
         feat = ys[-1]
         self.feat = feat
-        self._lower_heads(feat)
+        if self.lower_heads:
+            self._lower_heads(feat)
 
     def _lower_heads(self, feat):
         """Output heads on the 64-channel map (model.py:451-460, 485-489; the ResNet-DCN heads have the same form)."""
@@ -864,7 +885,8 @@ class Plan:
             self._op(_lib.OP_DEPTH2SPACE, in_=t.ptr, out=x.ptr, H=t.H, W=t.W, Cin=4 * planes, in_cs=t.cs, Ho=x.H, Wo=x.W,
                      Cout=planes, out_cs=x.cs, ksize=1, stride=1)
         self.feat = x
-        self._lower_heads(x)
+        if self.lower_heads:
+            self._lower_heads(x)
 
     # -- Hourglass-104 (arch_hg.py; published CenterNet `exkp`) ---------------------------------------------------------
     def _hg_residual(self, x, p, cin, cout, stride):

@@ -480,6 +480,35 @@ int h3d_nhwc_to_nchw_f32(const void *src, int dtype, float *dst, int B, int C, i
                          int src_cs, void *stream);
 
 /* =====================================================================================
+ * 2b. Heads backward (csrc/heads_bwd.hip): the gradients of H3D_OP_HEADS' operator, per head
+ *         z = W2 relu(conv3x3(y, W1) + b1) + b2          (model.py:451-464, 485-489)
+ *    at W1, b1, W2, b2 and at the feature map y (summed over the heads, in head order).  ReLU gradient 0 where the
+ *    pre-activation is <= 0 (torch.relu).  fp32 throughout, contractions on v_mfma_f32_32x32x2_f32, no float atomics: every
+ *    output is bit-identical from run to run, whichever other outputs are requested, and is overwritten, never accumulated into.
+ *    - feat: fp32 NHWC, 64 channels at channel stride in_cs >= 64 (a multiple of 4), 16-byte aligned.  grad_feat: contiguous
+ *      [B,H,W,64], 16-byte aligned, may be NULL.
+ *    - a head's operands are in the reference's layouts: w1 [head_conv,64,3,3], b1 [head_conv] (16-byte aligned), w2 [C,head_conv]
+ *      (b2 is not read), grad_out [B,C,H,W] NCHW fp32; grad_w1 / grad_b1 / grad_w2 / grad_b2 in the layouts of w1 / b1 / w2 / b2, each
+ *      may be NULL.  A head whose grad_out is NULL is skipped: nothing of it is written and it adds nothing to grad_feat.  With no
+ *      live head grad_feat is zero.
+ *    - head_conv % 64 == 0 and <= 256, nheads <= H3D_HEADS_MAX, in_cs >= 64: H3D_ERR_SHAPE otherwise, like non-positive sizes.
+ *      1 <= C <= 96: H3D_ERR_UNSUPPORTED.  NULL feat / heads / a live head's operands, a misaligned pointer, a NULL or short workspace
+ *      ("workspace" in the message): H3D_ERR_ARG.  Every check runs before the first HIP call.
+ *    - workspace (256-byte aligned): with N = B*H*W, S = min(64, ceil(N / 512)) pixel splits, hc = head_conv, in floats
+ *      2 * 576 hc (filter images) + 2 * N hc (gh and h of ONE head, NHWC; reused head after head) + S * (576 hc + 96 hc + hc + 96)
+ *      (partials), each term rounded up to 256 bytes. */
+typedef struct h3d_heads_bwd_head {
+    const float *w1, *b1, *w2;
+    const float *grad_out;
+    float *grad_w1, *grad_b1, *grad_w2, *grad_b2;
+    int32_t C;
+    int32_t reserved;
+} h3d_heads_bwd_head;
+int h3d_heads_backward_workspace_bytes(int B, int H, int W, int head_conv, int nheads, const int *C, size_t *bytes);
+int h3d_heads_backward(const float *feat, int in_cs, int B, int H, int W, int head_conv, int nheads, const h3d_heads_bwd_head *heads,
+                       float *grad_feat, void *workspace, size_t workspace_bytes, void *stream);
+
+/* =====================================================================================
  * 3. Heat-map decode (decode.py, utils.py).  All tensors contiguous NCHW fp32 as the
  *    reference's heads (model.py:485-489).  Index outputs are int64 like torch.topk's.
  *    Tie rule: equal scores -> lowest flat index first (torch leaves it unspecified).
