@@ -21,4 +21,4 @@ Training the heads `Conv3x3 + ReLU + Conv1x1` (models.model.DLASeg.__init__ / fo
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth", "arch", "model", "engine", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets", "heads"]
+__all__ = ["synth", "arch", "model", "engine", "weights", "plan", "dcn_calibrate", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets", "heads"]

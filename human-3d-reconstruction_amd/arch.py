@@ -2,7 +2,7 @@
 
 The reference builds the network from nn.Module classes (models/model.py:225-292 DLA, 169-222
 Tree, 148-166 Root, 346-415 DeformConv/IDAUp/DLAUp, 429-473 DLASeg).  Here the same network is
-a table: the engine (engine.py) walks it to emit a launch plan, and model.py hangs parameters
+a table: the plan builder (plan.py) walks it to emit a launch plan, and model.py hangs parameters
 with the reference's state_dict names on it so reference checkpoints load unchanged
 (trains/trainer.py:475-509).
 """

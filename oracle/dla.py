@@ -31,7 +31,7 @@ class DLAOracle:
         self.sd = {k: (v if torch.is_tensor(v) else torch.from_numpy(np.asarray(v)))
                    for k, v in state_dict.items()}
         emulate = "bf16" if emulate_bf16 else emulate
-        # emulate = 'bf16_plan' | 'f16_plan' (round 5): the rounding points of the GPU's 2-byte launch plans (h3d_amd/engine.py), one
+        # emulate = 'bf16_plan' | 'f16_plan' (round 5): the rounding points of the GPU's 2-byte launch plans (h3d_amd/plan.py), one
         # by one -- eval BatchNorm folded into the filters in fp64 BEFORE they are rounded (PackedWeights._fold), every activation
         # the plan STORES rounded to the plan's type (so a residual / skip operand is a rounded tensor, not the fp32 value the
         # 'bf16' mode adds), DeformConv filters and samples in fp16 with the blend's four fp16 roundings (csrc/dcn_traits.h), the
@@ -64,7 +64,7 @@ class DLAOracle:
         return F.conv2d(self.q(x), self.sd[key + ".weight"], self.sd.get(key + ".bias"), stride, padding)
 
     def _fold(self, wkey, bkey, bn):
-        """conv (+bias) followed by eval BatchNorm `bn` -> (w', b') as engine.PackedWeights._fold computes them (fp64)."""
+        """conv (+bias) followed by eval BatchNorm `bn` -> (w', b') as weights.PackedWeights._fold computes them (fp64)."""
         k = (wkey, bn)
         if k not in self._folded:
             sd = self.sd
