@@ -57,6 +57,113 @@ unsigned long long *h3d_stamp_buffer();     // device buffer [65536][H3D_NSTAMP]
         if (e_ != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "%s: %s", name, hipGetErrorString(e_)); \
     } while (0)
 
+// ---- launch dispatch (host) -------------------------------------------------------------------
+// A launcher turns what it knows at run time (the op's dtype, an epilogue mode, a boolean variant) into template arguments with the
+// two dispatchers below and hands name and kernel to h3d_launch in one statement, both built from the same tags and constants: the
+// name h3d_op_kernel_name's dry run reports is the kernel that is launched.
+template <typename T> struct h3d_tag { using type = T; };     // an element type as a value: f(h3d_tag<T>{})
+template <auto... Vs> struct h3d_vals {};                     // a closed list of template-argument values
+// the epilogue modes a kernel is instantiated with: 2 (LDS-transposed) only where the variant has it
+template <bool LDS_OK> using h3d_epi_vals = std::conditional_t<LDS_OK, h3d_vals<0, 1, 2>, h3d_vals<0, 1>>;
+template <typename T> constexpr int h3d_dtype_of() { return std::is_same_v<T, float> ? H3D_F32 : std::is_same_v<T, f16_t> ? H3D_F16 : std::is_same_v<T, x3_t> ? H3D_F16X3 : H3D_BF16; }
+template <typename T> struct StoreT;
+
+// f(h3d_tag<T>{}) for the element type T among Ts of an h3d_op dtype; another dtype fails with `msg` (a format taking the dtype)
+template <typename... Ts, typename F>
+static inline int h3d_by_dtype(int dtype, const char *msg, F f)
+{
+    int rc = H3D_ERR_DTYPE;
+    if (!((dtype == h3d_dtype_of<Ts>() && ((rc = f(h3d_tag<Ts>{})), true)) || ...)) h3d_set_error(msg, dtype);
+    return rc;
+}
+// the same over storage types: H3D_F16X3 (x3_t in Ts) arrives as h3d_tag<float>
+template <typename... Ts, typename F>
+static inline int h3d_by_store_dtype(int dtype, const char *msg, F f)
+{
+    int rc = H3D_ERR_DTYPE;
+    if (!((dtype == h3d_dtype_of<Ts>() && ((rc = f(h3d_tag<typename StoreT<Ts>::type>{})), true)) || ...)) h3d_set_error(msg, dtype);
+    return rc;
+}
+
+// f(c...) with one std::integral_constant per (h3d_vals<...>{}, run-time value) pair that follows it: int and bool values, each out
+// of its closed list (a value outside it has no kernel)
+template <typename F> static inline int h3d_by_values(F f) { return f(); }
+template <typename F, auto... Vs, typename V, typename... Rest>
+static inline int h3d_by_values(F f, h3d_vals<Vs...>, V v, Rest... rest)
+{
+    int rc = H3D_ERR_UNSUPPORTED;
+    if (!((v == Vs && ((rc = h3d_by_values([&](auto... cs) { return f(std::integral_constant<decltype(Vs), Vs>{}, cs...); }, rest...)), true)) || ...))
+        h3d_set_error("no kernel instance for variant value %d", (int)v);
+    return rc;
+}
+
+// A kernel's name as rocprofv3 prints it, from the arguments that instantiate it: h3d_tag<T> -> h3d_tname, bool -> true / false,
+// int -> decimal (constants of h3d_by_values convert to either); h3d_opt(b) is a bool that is left out while it and every argument
+// after it are false (h3d_opt(n): an int, 0), as a trailing defaulted template argument is.
+struct h3d_opt {
+    int v;
+    bool is_int;
+    explicit h3d_opt(bool b) : v(b), is_int(false) {}
+    explicit h3d_opt(int n) : v(n), is_int(true) {}
+};
+struct h3d_kname {
+    char s[160];
+    int base, len, keep;      // bytes of the bare kernel name | written so far | up to the last argument that stays
+    template <typename... A> h3d_kname(const char *kernel, A... targs) : len(0)
+    {
+        put(kernel);
+        base = keep = len;
+        (arg(targs), ...);
+        s[len = keep] = 0;
+        if (len > base) put(">");
+    }
+    // records the name; true when the caller must not launch (h3d_op_kernel_name's dry run)
+    bool dry() const { return h3d_note_kernel("%s", s); }
+
+private:
+    void put(const char *t) { while (*t && len < (int)sizeof(s) - 1) s[len++] = *t++; s[len] = 0; }
+    void sep() { put(len == base ? "<" : ", "); }
+    template <typename T> void arg(h3d_tag<T>) { sep(); put(h3d_tname<T>()); keep = len; }
+    void arg(bool b) { sep(); put(b ? "true" : "false"); keep = len; }
+    void arg(h3d_opt o)
+    {
+        const int k = keep;
+        if (o.is_int) arg(o.v);
+        else arg(o.v != 0);
+        if (!o.v) keep = k;
+    }
+    void arg(int v)
+    {
+        char d[12], *p = d + 11;      // digits by hand: no snprintf per launch
+        *p = 0;
+        unsigned u = v < 0 ? 0u - (unsigned)v : (unsigned)v;
+        do *--p = (char)('0' + u % 10); while (u /= 10);
+        if (v < 0) *--p = '-';
+        sep(); put(p); keep = len;
+    }
+};
+
+// a kernel and its name, for launchers that check arguments between the dry run's return and the launch
+template <typename... KA> struct h3d_kernel {
+    h3d_kname name;
+    void (*fn)(KA...);
+    int launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, KA... args) const
+    {
+        hipLaunchKernelGGL(fn, grid, block, lds, st, args...);
+        hipError_t e_ = hipGetLastError();
+        if (e_ != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "%.*s: %s", name.base, name.s, hipGetErrorString(e_));
+        return H3D_OK;
+    }
+};
+template <typename... KA> static inline h3d_kernel<KA...> h3d_bind(const h3d_kname &name, void (*fn)(KA...)) { return {name, fn}; }
+// record the name, stop there in a dry run, launch, check
+template <typename... KA, typename... A>
+static inline int h3d_launch(const h3d_kname &name, void (*fn)(KA...), dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args)
+{
+    if (name.dry()) return H3D_OK;
+    return h3d_bind(name, fn).launch(grid, block, lds, st, args...);
+}
+
 // ---- element traits: the same kernel source runs in f32 ("parity mode", exact fmaf chain on
 //      v_mfma_f32_32x32x2_f32) and bf16 (v_mfma_f32_32x32x16_bf16, fp32 accumulate).
 //      A fragment = 8 consecutive K elements of one row/column per lane:

@@ -233,22 +233,10 @@ static int launch_conv_cfg(const ConvArgs &a0, hipStream_t st)
     const int epi = (C::EPI_LDS_OK && lean && a.Cout % 8 == 0 && a.out_cs % 8 == 0 && ((uintptr_t)a.out & 15) == 0 &&
                      (!a.res || (a.res_cs % 8 == 0 && ((uintptr_t)a.res & 15) == 0)))
                         ? 2 : lean ? 1 : 0;
-    if (h3d_note_kernel("conv_kernel<%s, %d, %d, %d, %d, %d, %d, %d>", h3d_tname<T>(), KS, STRIDE, MT,
-                        CK, TH, WAVES, epi))
-        return H3D_OK;
-    if constexpr (C::EPI_LDS_OK) {
-        if (epi == 2) {
-            hipLaunchKernelGGL((conv_kernel<T, KS, STRIDE, MT, CK, TH, WAVES, 2>), grid, dim3(C::THREADS), 0, st, a);
-            H3D_CHECK_LAUNCH("conv_kernel");
-            return H3D_OK;
-        }
-    }
-    if (epi == 1)
-        hipLaunchKernelGGL((conv_kernel<T, KS, STRIDE, MT, CK, TH, WAVES, 1>), grid, dim3(C::THREADS), 0, st, a);
-    else
-        hipLaunchKernelGGL((conv_kernel<T, KS, STRIDE, MT, CK, TH, WAVES, 0>), grid, dim3(C::THREADS), 0, st, a);
-    H3D_CHECK_LAUNCH("conv_kernel");
-    return H3D_OK;
+    return h3d_by_values([&](auto e) {
+        return h3d_launch({"conv_kernel", h3d_tag<T>{}, KS, STRIDE, MT, CK, TH, WAVES, e},
+                          conv_kernel<T, KS, STRIDE, MT, CK, TH, WAVES, e>, grid, dim3(C::THREADS), 0, st, a);
+    }, h3d_epi_vals<C::EPI_LDS_OK>{}, epi);
 }
 
 // 2-byte element types (bf16_t, f16_t): one tiling table
@@ -423,11 +411,7 @@ int h3d_launch_conv(const h3d_op &op, hipStream_t st)
     if (op.wexp < -60 || op.wexp > 60 || (op.wexp && op.dtype != H3D_F16X3)) H3D_FAIL(H3D_ERR_ARG, "conv: wexp %d (an H3D_F16X3 filter exponent)", op.wexp);
     a.wscale = ldexpf(1.f, -op.wexp);
     if (h3d_gemm1_takes(op)) return h3d_launch_gemm1(op, st);      // 1x1 stride 1, bf16: the GEMM kernel (csrc/gemm1.hip)
-    if (op.dtype == H3D_BF16) return launch_conv_t<bf16_t>(op, a, st);
-    if (op.dtype == H3D_F16) return launch_conv_t<f16_t>(op, a, st);
-    if (op.dtype == H3D_F32) return launch_conv_t<float>(op, a, st);
-    if (op.dtype == H3D_F16X3) return launch_conv_t<x3_t>(op, a, st);
-    H3D_FAIL(H3D_ERR_DTYPE, "conv: dtype %d", op.dtype);
+    return h3d_by_dtype<bf16_t, f16_t, float, x3_t>(op.dtype, "conv: dtype %d", [&](auto t) { return launch_conv_t<typename decltype(t)::type>(op, a, st); });
 }
 
 // =================================================================================================
@@ -612,37 +596,26 @@ int h3d_launch_stem(const h3d_op &op, hipStream_t st)
     if (op.dtype == H3D_BF16 || op.dtype == H3D_F16) {
         // op.w: bf16 / fp16 [16][7][32] (k = dx*4 + c, zero padded) -- see engine.PackedWeights.stem
         const int mx = cdiv(op.W, 64), my = cdiv(op.H, 16);
-        if (h3d_note_kernel("stem_mfma_kernel<%s>", op.dtype == H3D_F16 ? "f16_t" : "unsigned short")) return H3D_OK;
-        if (op.dtype == H3D_F16)
-            hipLaunchKernelGGL(stem_mfma_kernel<f16_t>, dim3(op.B * mx * my), dim3(256), 0, st, (const float *)op.in, (const f16_t *)op.w,
-                               op.bias, (f16_t *)op.out, op.B, op.H, op.W, op.out_cs, mx, my);
-        else
-            hipLaunchKernelGGL(stem_mfma_kernel<bf16_t>, dim3(op.B * mx * my), dim3(256), 0, st, (const float *)op.in, (const bf16_t *)op.w,
-                               op.bias, (bf16_t *)op.out, op.B, op.H, op.W, op.out_cs, mx, my);
-        H3D_CHECK_LAUNCH("stem_mfma_kernel");
-        return H3D_OK;
+        return h3d_by_dtype<bf16_t, f16_t>(op.dtype, "stem: dtype %d", [&](auto t) {
+            using T = typename decltype(t)::type;
+            return h3d_launch({"stem_mfma_kernel", t}, stem_mfma_kernel<T>, dim3(op.B * mx * my), dim3(256), 0, st, (const float *)op.in, (const T *)op.w,
+                              op.bias, (T *)op.out, op.B, op.H, op.W, op.out_cs, mx, my);
+        });
     }
     if (op.dtype == H3D_F16X3) {
         // op.w: the [16][7][32] (k = dx*4 + c, zero padded) filter bank times 2^wexp as (hi | lo) fp16 terms per 8 k -- engine.PackedWeights.stem
         if (op.wexp < -60 || op.wexp > 60) H3D_FAIL(H3D_ERR_ARG, "stem: wexp %d", op.wexp);
         const int mx = cdiv(op.W, 64), my = cdiv(op.H, 16);
-        if (h3d_note_kernel("stem_x3_kernel")) return H3D_OK;
-        hipLaunchKernelGGL(stem_x3_kernel, dim3(op.B * mx * my), dim3(256), 0, st, (const float *)op.in, (const char *)op.w, op.bias, (float *)op.out, op.B,
-                           op.H, op.W, op.out_cs, mx, my, ldexpf(1.f, -op.wexp));
-        H3D_CHECK_LAUNCH("stem_x3_kernel");
-        return H3D_OK;
+        return h3d_launch({"stem_x3_kernel"}, stem_x3_kernel, dim3(op.B * mx * my), dim3(256), 0, st, (const float *)op.in, (const char *)op.w, op.bias, (float *)op.out,
+                          op.B, op.H, op.W, op.out_cs, mx, my, ldexpf(1.f, -op.wexp));
     }
-    if (h3d_note_kernel("stem_kernel<%s>", op.dtype == H3D_BF16 ? "unsigned short" : "float")) return H3D_OK;
-    if (op.dtype == H3D_BF16)
-        hipLaunchKernelGGL(stem_kernel<bf16_t>, grid, dim3(256), 0, st, (const float *)op.in, (const float *)op.w,
-                           op.bias, (bf16_t *)op.out, op.B, op.H, op.W, op.out_cs, tx, ty);
-    else if (op.dtype == H3D_F32)
-        hipLaunchKernelGGL(stem_kernel<float>, grid, dim3(256), 0, st, (const float *)op.in, (const float *)op.w,
-                           op.bias, (float *)op.out, op.B, op.H, op.W, op.out_cs, tx, ty);
-    else
-        H3D_FAIL(H3D_ERR_DTYPE, "stem: dtype %d", op.dtype);
-    H3D_CHECK_LAUNCH("stem_kernel");
-    return H3D_OK;
+    // (a dry run has always named the fp32 kernel for a dtype that the launch then refuses)
+    if (op.dtype != H3D_F32 && h3d_kname{"stem_kernel", h3d_tag<float>{}}.dry()) return H3D_OK;
+    return h3d_by_dtype<bf16_t, float>(op.dtype, "stem: dtype %d", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return h3d_launch({"stem_kernel", t}, stem_kernel<T>, grid, dim3(256), 0, st, (const float *)op.in, (const float *)op.w, op.bias, (T *)op.out, op.B, op.H,
+                          op.W, op.out_cs, tx, ty);
+    });
 }
 
 // =================================================================================================
@@ -788,7 +761,6 @@ int h3d_launch_elementwise(const h3d_op &op, hipStream_t st)
     if (!op.in || !op.out) H3D_FAIL(H3D_ERR_ARG, "elementwise: null pointer");
     const int es = h3d_dtype_bytes(op.dtype);
     if (!es) H3D_FAIL(H3D_ERR_DTYPE, "elementwise: dtype %d", op.dtype);
-    const bool f16 = op.dtype == H3D_F16;
     const int n = 16 / es;
     if (op.Cin % n || op.in_cs % n || op.out_cs % n || op.Cin != op.Cout)
         H3D_FAIL(H3D_ERR_SHAPE, "elementwise: channels %d/%d strides %d/%d must be multiples of %d", op.Cin, op.Cout,
@@ -805,67 +777,41 @@ int h3d_launch_elementwise(const h3d_op &op, hipStream_t st)
     const bool up_wlds = op.reserved == H3D_TUNE_UPADD_TAPS_GLOBAL ? false : op.reserved == H3D_TUNE_UPADD_TAPS_LDS ? up_wbytes <= 64 * 1024 : (up_wbytes <= 8192 || (up_wbytes <= 16384 && op.Cin <= 64));
     // (measured and dropped in round 3: f = 2 tap weights in registers, rows in pairs with ten loads in flight -- 0.341 vs 0.325 ms
     //  over the six f = 2 launches of the batch-64 plan: the kernel sits at the 4.4-4.9 TB/s these mixed read / write streams reach)
-    if (h3d_note_kernel("%s<%s%s%s>", op.kind == H3D_OP_MAXPOOL ? "maxpool_kernel" : op.kind == H3D_OP_UPADD ? "upadd_kernel" : "copy_kernel",
-                        f16 ? "f16_t" : es == 2 ? "unsigned short" : "float", op.kind == H3D_OP_UPADD ? (f16out ? ", true" : ", false") : "",
-                        op.kind == H3D_OP_UPADD ? (up_wlds ? ", true" : ", false") : ""))
-        return H3D_OK;
-    if (op.kind == H3D_OP_MAXPOOL) {
-        if (op.Ho != op.H / 2 || op.Wo != op.W / 2) H3D_FAIL(H3D_ERR_SHAPE, "maxpool: output must be floor(H/2) x floor(W/2)");
-        if (f16)
-            hipLaunchKernelGGL(maxpool_kernel<f16_t>, grid, blk, 0, st, (const f16_t *)op.in, (f16_t *)op.out, op.B, op.H,
-                               op.W, op.Cin, op.in_cs, op.Ho, op.Wo, op.out_cs);
-        else if (es == 2)
-            hipLaunchKernelGGL(maxpool_kernel<bf16_t>, grid, blk, 0, st, (const bf16_t *)op.in, (bf16_t *)op.out, op.B, op.H,
-                               op.W, op.Cin, op.in_cs, op.Ho, op.Wo, op.out_cs);
-        else
-            hipLaunchKernelGGL(maxpool_kernel<float>, grid, blk, 0, st, (const float *)op.in, (float *)op.out, op.B, op.H,
-                               op.W, op.Cin, op.in_cs, op.Ho, op.Wo, op.out_cs);
-        H3D_CHECK_LAUNCH("maxpool_kernel");
-    } else if (op.kind == H3D_OP_UPADD) {
-        const int f = op.stride;
-        if (!op.in2 || !op.w) H3D_FAIL(H3D_ERR_ARG, "upadd: null pointer");
-        if (op.ksize != 2 * f || op.Ho != op.H * f || op.Wo != op.W * f || op.in2_cs % n)
-            H3D_FAIL(H3D_ERR_SHAPE, "upadd: expects k=2f, out = f*in (k=%d f=%d)", op.ksize, f);
-        const int vpc = op.Cin / n;
-        if (vpc > 256) H3D_FAIL(H3D_ERR_UNSUPPORTED, "upadd: C=%d", op.Cin);
-        const size_t wfl = (size_t)op.ksize * op.ksize * op.Cin;
-        // tap table in LDS when it fits the default 64 KiB (tuning override: H3D_TUNE_UPADD_TAPS_GLOBAL / _LDS)
-        const bool wlds = up_wlds;
-        const size_t lds = wlds ? (wfl + 4 * (size_t)op.ksize * op.ksize) * sizeof(float) : 0;     // rows of C + 4 floats
-        const dim3 ugrid(cdiv(op.Wo, 256 / vpc), op.B * cdiv(op.Ho, UP_ROWS));
-#define H3D_UPADD_LAUNCH(K, TT)                                                                                              \
-    do {                                                                                                                      \
-        hipLaunchKernelGGL(K, ugrid, blk, lds, st, (const TT *)op.in, (const TT *)op.in2, (const float *)op.w, (TT *)op.out, \
-                           op.B, op.H, op.W, op.Cin, op.in_cs, op.in2_cs, op.Ho, op.Wo, op.out_cs, f);                        \
-    } while (0)
-        if (wlds) {
-            if (f16out) H3D_UPADD_LAUNCH((upadd_kernel<bf16_t, true, true>), bf16_t);
-            else if (f16) H3D_UPADD_LAUNCH((upadd_kernel<f16_t, false, true>), f16_t);
-            else if (es == 2) H3D_UPADD_LAUNCH((upadd_kernel<bf16_t, false, true>), bf16_t);
-            else H3D_UPADD_LAUNCH((upadd_kernel<float, false, true>), float);
-        } else {
-            if (f16out) H3D_UPADD_LAUNCH((upadd_kernel<bf16_t, true, false>), bf16_t);
-            else if (f16) H3D_UPADD_LAUNCH((upadd_kernel<f16_t, false, false>), f16_t);
-            else if (es == 2) H3D_UPADD_LAUNCH((upadd_kernel<bf16_t, false, false>), bf16_t);
-            else H3D_UPADD_LAUNCH((upadd_kernel<float, false, false>), float);
+    return h3d_by_store_dtype<bf16_t, f16_t, float, x3_t>(op.dtype, "elementwise: dtype %d", [&](auto t) {
+        using T = typename decltype(t)::type;
+        const T *in = (const T *)op.in;
+        T *out = (T *)op.out;
+        if (op.kind == H3D_OP_MAXPOOL) {
+            const auto k = h3d_bind({"maxpool_kernel", t}, maxpool_kernel<T>);
+            if (k.name.dry()) return H3D_OK;
+            if (op.Ho != op.H / 2 || op.Wo != op.W / 2) H3D_FAIL(H3D_ERR_SHAPE, "maxpool: output must be floor(H/2) x floor(W/2)");
+            return k.launch(grid, blk, 0, st, in, out, op.B, op.H, op.W, op.Cin, op.in_cs, op.Ho, op.Wo, op.out_cs);
         }
-#undef H3D_UPADD_LAUNCH
-        H3D_CHECK_LAUNCH("upadd_kernel");
-    } else {
-        if (op.Ho != op.H || op.Wo != op.W) H3D_FAIL(H3D_ERR_SHAPE, "copy: shape");
-        const size_t npix = (size_t)op.B * op.H * op.W;
-        if (f16)
-            hipLaunchKernelGGL(copy_kernel<f16_t>, grid, blk, 0, st, (const f16_t *)op.in, (f16_t *)op.out, npix, op.Cin,
-                               op.in_cs, op.out_cs);
-        else if (es == 2)
-            hipLaunchKernelGGL(copy_kernel<bf16_t>, grid, blk, 0, st, (const bf16_t *)op.in, (bf16_t *)op.out, npix, op.Cin,
-                               op.in_cs, op.out_cs);
-        else
-            hipLaunchKernelGGL(copy_kernel<float>, grid, blk, 0, st, (const float *)op.in, (float *)op.out, npix, op.Cin,
-                               op.in_cs, op.out_cs);
-        H3D_CHECK_LAUNCH("copy_kernel");
-    }
-    return H3D_OK;
+        if (op.kind != H3D_OP_UPADD) {
+            const auto k = h3d_bind({"copy_kernel", t}, copy_kernel<T>);
+            if (k.name.dry()) return H3D_OK;
+            if (op.Ho != op.H || op.Wo != op.W) H3D_FAIL(H3D_ERR_SHAPE, "copy: shape");
+            return k.launch(grid, blk, 0, st, in, out, (size_t)op.B * op.H * op.W, op.Cin, op.in_cs, op.out_cs);
+        }
+        // F16OUT exists for bf16 plans only (checked above)
+        return h3d_by_values([&](auto f16o, auto wlds) {
+            const auto k = h3d_bind({"upadd_kernel", t, f16o, wlds},
+                                    upadd_kernel<T, f16o, wlds>);
+            if (k.name.dry()) return H3D_OK;
+            const int f = op.stride;
+            if (!op.in2 || !op.w) H3D_FAIL(H3D_ERR_ARG, "upadd: null pointer");
+            if (op.ksize != 2 * f || op.Ho != op.H * f || op.Wo != op.W * f || op.in2_cs % n)
+                H3D_FAIL(H3D_ERR_SHAPE, "upadd: expects k=2f, out = f*in (k=%d f=%d)", op.ksize, f);
+            const int vpc = op.Cin / n;
+            if (vpc > 256) H3D_FAIL(H3D_ERR_UNSUPPORTED, "upadd: C=%d", op.Cin);
+            const size_t wfl = (size_t)op.ksize * op.ksize * op.Cin;
+            // tap table in LDS when it fits the default 64 KiB (tuning override: H3D_TUNE_UPADD_TAPS_GLOBAL / _LDS)
+            const size_t lds = wlds ? (wfl + 4 * (size_t)op.ksize * op.ksize) * sizeof(float) : 0;     // rows of C + 4 floats
+            const dim3 ugrid(cdiv(op.Wo, 256 / vpc), op.B * cdiv(op.Ho, UP_ROWS));
+            return k.launch(ugrid, blk, lds, st, in, (const T *)op.in2, (const float *)op.w, out, op.B, op.H, op.W, op.Cin, op.in_cs, op.in2_cs, op.Ho, op.Wo,
+                            op.out_cs, f);
+        }, std::conditional_t<std::is_same_v<T, bf16_t>, h3d_vals<false, true>, h3d_vals<false>>{}, f16out, h3d_vals<false, true>{}, up_wlds);
+    });
 }
 
 // =================================================================================================
@@ -910,19 +856,10 @@ extern "C" int h3d_nchw_f32_to_nhwc(const float *src, void *dst, int dtype, int 
     if (!src || !dst) H3D_FAIL(H3D_ERR_ARG, "nchw_to_nhwc: null pointer");
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || dst_cs < C) H3D_FAIL(H3D_ERR_SHAPE, "nchw_to_nhwc: bad shape");
     dim3 grid(cdiv(H * W, 32), cdiv(C, 32), B);
-    if (dtype == H3D_BF16)
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, src, (bf16_t *)dst, B, C,
-                           H * W, dst_cs);
-    else if (dtype == H3D_F16)
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, src, (f16_t *)dst, B, C,
-                           H * W, dst_cs);
-    else if (dtype == H3D_F32)
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, src, (float *)dst, B, C,
-                           H * W, dst_cs);
-    else
-        H3D_FAIL(H3D_ERR_DTYPE, "nchw_to_nhwc: dtype %d", dtype);
-    H3D_CHECK_LAUNCH("nchw_to_nhwc_kernel");
-    return H3D_OK;
+    return h3d_by_dtype<bf16_t, f16_t, float>(dtype, "nchw_to_nhwc: dtype %d", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return h3d_launch({"nchw_to_nhwc_kernel", t}, nchw_to_nhwc_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, src, (T *)dst, B, C, H * W, dst_cs);
+    });
 }
 
 extern "C" int h3d_nhwc_to_nchw_f32(const void *src, int dtype, float *dst, int B, int C, int H, int W, int src_cs,
@@ -931,17 +868,8 @@ extern "C" int h3d_nhwc_to_nchw_f32(const void *src, int dtype, float *dst, int 
     if (!src || !dst) H3D_FAIL(H3D_ERR_ARG, "nhwc_to_nchw: null pointer");
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || src_cs < C) H3D_FAIL(H3D_ERR_SHAPE, "nhwc_to_nchw: bad shape");
     dim3 grid(cdiv(H * W, 32), cdiv(C, 32), B);
-    if (dtype == H3D_BF16)
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t *)src, dst,
-                           B, C, H * W, src_cs);
-    else if (dtype == H3D_F16)
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<f16_t>, grid, dim3(256), 0, (hipStream_t)stream, (const f16_t *)src, dst,
-                           B, C, H * W, src_cs);
-    else if (dtype == H3D_F32)
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, (const float *)src, dst, B,
-                           C, H * W, src_cs);
-    else
-        H3D_FAIL(H3D_ERR_DTYPE, "nhwc_to_nchw: dtype %d", dtype);
-    H3D_CHECK_LAUNCH("nhwc_to_nchw_kernel");
-    return H3D_OK;
+    return h3d_by_dtype<bf16_t, f16_t, float>(dtype, "nhwc_to_nchw: dtype %d", [&](auto t) {
+        using T = typename decltype(t)::type;
+        return h3d_launch({"nhwc_to_nchw_kernel", t}, nhwc_to_nchw_kernel<T>, grid, dim3(256), 0, (hipStream_t)stream, (const T *)src, dst, B, C, H * W, src_cs);
+    });
 }

@@ -237,29 +237,6 @@ __global__ __launch_bounds__(64 * WAVES) void conv2_kernel(Conv2Args a)
     }
 }
 
-template <typename T, int MT, int WAVES, int S, int SLOTS, int NT, bool PIPE>
-static int launch_conv2_t(const Conv2Args &a, dim3 grid, int epi, hipStream_t st)
-{
-    using C = Conv2Cfg<MT, WAVES, S, SLOTS, NT>;
-    if constexpr (PIPE) {
-        if (epi == 2) {
-            if (h3d_note_kernel("conv2_kernel<%s, %d, %d, %d, %d, %d, %d, true>", h3d_tname<T>(), MT, WAVES, epi, S, SLOTS, NT)) return H3D_OK;
-            hipLaunchKernelGGL((conv2_kernel<T, MT, WAVES, 2, S, SLOTS, NT, true>), grid, dim3(C::THREADS), 0, st, a);
-            H3D_CHECK_LAUNCH("conv2_kernel");
-            return H3D_OK;
-        }
-    }
-    if (h3d_note_kernel("conv2_kernel<%s, %d, %d, %d, %d, %d, %d>", h3d_tname<T>(), MT, WAVES, epi, S, SLOTS, NT)) return H3D_OK;
-    if (epi == 2)
-        hipLaunchKernelGGL((conv2_kernel<T, MT, WAVES, 2, S, SLOTS, NT>), grid, dim3(C::THREADS), 0, st, a);
-    else if (epi == 1)
-        hipLaunchKernelGGL((conv2_kernel<T, MT, WAVES, 1, S, SLOTS, NT>), grid, dim3(C::THREADS), 0, st, a);
-    else
-        hipLaunchKernelGGL((conv2_kernel<T, MT, WAVES, 0, S, SLOTS, NT>), grid, dim3(C::THREADS), 0, st, a);
-    H3D_CHECK_LAUNCH("conv2_kernel");
-    return H3D_OK;
-}
-
 template <int MT, int WAVES, int S = 1, int SLOTS = 2, int NT = 1, bool PIPE = false>
 static int launch_conv2_cfg(const Conv2Args &a0, hipStream_t st)
 {
@@ -277,8 +254,12 @@ static int launch_conv2_cfg(const Conv2Args &a0, hipStream_t st)
     dim3 grid(a.B * a.tiles_x * a.tiles_y, cdiv(cdiv(a.Cout, 32), MT));
     const bool lean = a.out_mode == H3D_OUT_NHWC && a.Cout % 4 == 0 && ((uintptr_t)a.bias & 15) == 0;
     const int epi = (MT >= 2 && lean && a.Cout % 8 == 0 && a.out_cs % 8 == 0 && ((uintptr_t)a.out & 15) == 0 && !(a.dbg & 4)) ? 2 : lean ? 1 : 0;
-    if (a.f16) return launch_conv2_t<f16_t, MT, WAVES, S, SLOTS, NT, PIPE>(a, grid, epi, st);
-    return launch_conv2_t<bf16_t, MT, WAVES, S, SLOTS, NT, PIPE>(a, grid, epi, st);
+    return h3d_by_values([&](auto f16, auto e) {
+        using T = std::conditional_t<f16, f16_t, bf16_t>;
+        constexpr bool pipe = PIPE && e == 2;      // the fragment reads one tap ahead exist with the LDS-transposed epilogue
+        return h3d_launch({"conv2_kernel", h3d_tag<T>{}, MT, WAVES, e, S, SLOTS, NT, h3d_opt(pipe)},
+                          conv2_kernel<T, MT, WAVES, e, S, SLOTS, NT, pipe>, grid, dim3(C::THREADS), 0, st, a);
+    }, h3d_vals<false, true>{}, a.f16 != 0, h3d_vals<0, 1, 2>{}, epi);
 }
 
 int h3d_launch_conv_stream(const h3d_op &op, hipStream_t st)

@@ -380,11 +380,8 @@ static int launch_dcn2_cfg(const Dcn2Args &a0, hipStream_t st)
     a.tiles_x = cdiv(a.W, 16);
     a.tiles_y = cdiv(a.H, 16);
     dim3 grid(a.B * a.tiles_x * a.tiles_y, cdiv(a.Cout, C::BN));
-    if (h3d_note_kernel("dcn2_kernel<%s, %d, %d, %d, %d>", h3d_tname<T>(), MT, CK, MARGIN, NT_))
-        return H3D_OK;
-    hipLaunchKernelGGL((dcn2_kernel<T, MT, CK, MARGIN, NT_>), grid, dim3(C::THREADS), 0, st, a);
-    H3D_CHECK_LAUNCH("dcn2_kernel");
-    return H3D_OK;
+    return h3d_launch({"dcn2_kernel", h3d_tag<T>{}, MT, CK, MARGIN, NT_},
+                      dcn2_kernel<T, MT, CK, MARGIN, NT_>, grid, dim3(C::THREADS), 0, st, a);
 }
 
 int h3d_launch_dcn2(const h3d_op &op, hipStream_t st)

@@ -982,37 +982,23 @@ static int launch_dcn3_cfg(const Dcn3Args &a0, hipStream_t st, bool stats = fals
     a.stamps = nullptr;
 #endif
     dim3 grid(a.B * a.tiles_x * a.tiles_y, cdiv(a.Cout, C::BN));
-    const int epi = dcn_epi_mode(a, sizeof(T) == 2 && MT >= 2);
-    if (h3d_note_kernel(F16IN ? (PK ? "dcn3_kernel<%s, %d, %d, %d, %d, %s, %d, true, true>" : "dcn3_kernel<%s, %d, %d, %d, %d, %s, %d, false, true>")
-                              : PK ? "dcn3_kernel<%s, %d, %d, %d, %d, %s, %d, true>" : "dcn3_kernel<%s, %d, %d, %d, %d, %s, %d>", h3d_tname<T>(), MT, CK, MARGIN, epi,
-                        WDMA ? "true" : "false", NP))
-        return H3D_OK;
-    if constexpr (NP > 0 && sizeof(T) == 2) {
-        if (stats) {                            // h3d_dcn_far_samples
-            hipLaunchKernelGGL((dcn3_kernel<T, MT, CK, MARGIN, 1, WDMA, NP, PK, F16IN, true>), dim3(grid.x), dim3(C::THREADS), 0, st, a);
-            H3D_CHECK_LAUNCH("dcn3_kernel<stats>");
-            return H3D_OK;
+    return dcn_by_epi<sizeof(T) == 2 && MT >= 2>(a, [&](auto e) {
+        const h3d_kname name{"dcn3_kernel", h3d_tag<T>{}, MT, CK, MARGIN, e, WDMA, NP, h3d_opt(PK), h3d_opt(F16IN)};
+        if constexpr (NP > 0 && sizeof(T) == 2) {
+            if (stats) {                            // h3d_dcn_far_samples: named as the kernel it counts for
+                if (name.dry()) return H3D_OK;
+                return h3d_bind({"dcn3_kernel<stats>"}, dcn3_kernel<T, MT, CK, MARGIN, 1, WDMA, NP, PK, F16IN, true>).launch(dim3(grid.x), dim3(C::THREADS), 0, st, a);
+            }
         }
-    }
-    if constexpr (sizeof(T) == 2 && MT >= 2) {
-        if (epi == 2) {
-            hipLaunchKernelGGL((dcn3_kernel<T, MT, CK, MARGIN, 2, WDMA, NP, PK, F16IN>), grid, dim3(C::THREADS), 0, st, a);
-            H3D_CHECK_LAUNCH("dcn3_kernel");
-            return H3D_OK;
+        if constexpr (F16IN && e != 2) {
+            // (only the LDS-transposed epilogue is instantiated for the fp16-input variants: every layer of the network that uses them
+            //  has Cout % 8 == 0 and an aligned NHWC output)
+            if (name.dry()) return H3D_OK;
+            H3D_FAIL(H3D_ERR_UNSUPPORTED, "dcn_fused_stream with an fp16 input: needs an NHWC output with Cout %% 8 == 0 (Cout=%d)", a.Cout);
+        } else {
+            return h3d_launch(name, dcn3_kernel<T, MT, CK, MARGIN, e, WDMA, NP, PK, F16IN>, grid, dim3(C::THREADS), 0, st, a);
         }
-    }
-    if constexpr (F16IN) {
-        // (only the LDS-transposed epilogue is instantiated for the fp16-input variants: every layer of the network that uses them
-        //  has Cout % 8 == 0 and an aligned NHWC output)
-        H3D_FAIL(H3D_ERR_UNSUPPORTED, "dcn_fused_stream with an fp16 input: needs an NHWC output with Cout %% 8 == 0 (Cout=%d)", a.Cout);
-    } else {
-    if (epi == 1)
-        hipLaunchKernelGGL((dcn3_kernel<T, MT, CK, MARGIN, 1, WDMA, NP, PK>), grid, dim3(C::THREADS), 0, st, a);
-    else
-        hipLaunchKernelGGL((dcn3_kernel<T, MT, CK, MARGIN, 0, WDMA, NP, PK>), grid, dim3(C::THREADS), 0, st, a);
-    }
-    H3D_CHECK_LAUNCH("dcn3_kernel");
-    return H3D_OK;
+    });
 }
 
 // channels per filter stage of H3D_OP_DCN_FUSED_STREAM: hosts pack the stage-major filter images with this CK
@@ -1122,8 +1108,7 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
     a.xscaled = 0;
     if (wdma && (size_t)op.H * op.W * op.in_cs * es >= 0x7ffffff0ull) H3D_FAIL(H3D_ERR_SHAPE, "dcn_fused_stream: image of 2 GiB or more");
     const Dcn3Flags f = dcn3_decode(op, wdma);
-    if (op.dtype == H3D_BF16 && f.f16_input) return launch_dcn3_lowp<bf16_t, true>(op, f, a, wdma, st);
-    if (op.dtype == H3D_BF16) return launch_dcn3_lowp<bf16_t>(op, f, a, wdma, st);
+    if (f.f16_input) return launch_dcn3_lowp<bf16_t, true>(op, f, a, wdma, st);      // (a flag of bf16 plans: dcn3_decode)
     // fp16 plans: the apron needs no conversion while it is staged.  csrc/dcn5.hip also moves it by LDS-DMA (double buffered, one
     // barrier per phase-A stage): measured 5.7 % SLOWER on the ten <= 64-channel launches of the batch-64 plan (1.519 vs 1.437 ms,
     // tools/ab_dcn5.py: an LDS-DMA piece costs its wave more issue cycles than two global loads + two ds_write_b128, and the
@@ -1135,7 +1120,6 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
         H3D_FAIL(H3D_ERR_UNSUPPORTED, "dcn_fused_stream: the LDS-DMA apron variant (csrc/dcn5.hip, H3D_TUNE_DCN_STREAM_F16_DCN5) is built only by `make EXTRA=1`");
 #endif
     }
-    if (op.dtype == H3D_F16) return launch_dcn3_lowp<f16_t>(op, f, a, wdma, st);
     if (op.dtype == H3D_F32) {
         return dcn_by_mt<2>(op.Cout, true, [&](auto mt) { return launch_dcn3_cfg<float, decltype(mt)::value, 16, 2>(a, st); });
     }
@@ -1175,7 +1159,7 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
         if (margin == 6) return go(std::integral_constant<int, 6>{});
         return go(std::integral_constant<int, 4>{});      // margin 4, one stage buffer (Dcn3Cfg::SINGLE)
     }
-    H3D_FAIL(H3D_ERR_DTYPE, "dcn_fused: dtype %d", op.dtype);
+    return h3d_by_dtype<bf16_t, f16_t>(op.dtype, "dcn_fused: dtype %d", [&](auto t) { return launch_dcn3_lowp<typename decltype(t)::type>(op, f, a, wdma, st); });
 }
 
 // Per-tile count of bilinear samples that leave the LDS apron of the variant `op` dispatches to (see include/h3d.h).

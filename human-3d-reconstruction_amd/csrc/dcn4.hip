@@ -527,16 +527,11 @@ static int launch_dcn4_cfg(const Dcn4Args &a0, hipStream_t st)
     a.tiles_x = cdiv(a.W, 16);
     a.tiles_y = cdiv(a.H, 16);
     dim3 grid(a.B * a.tiles_x * a.tiles_y, cdiv(cdiv(a.Cout, 32), MT));
-    const int epi = dcn_epi_mode(a, MT >= 2);
-    if (h3d_note_kernel("dcn4_kernel<%d, %d, %d, %d>", MT, epi, DENSE, UP)) return H3D_OK;
-    if (epi == 2)
-        hipLaunchKernelGGL((dcn4_kernel<MT, 2, DENSE, UP>), grid, dim3(512), 0, st, a);
-    else if (epi == 1)
-        hipLaunchKernelGGL((dcn4_kernel<MT, 1, DENSE, UP>), grid, dim3(512), 0, st, a);
-    else
-        hipLaunchKernelGGL((dcn4_kernel<MT, 0, DENSE, UP>), grid, dim3(512), 0, st, a);
-    H3D_CHECK_LAUNCH("dcn4_kernel");
-    return H3D_OK;
+    // (every MT has all three epilogues; dcn_epi_mode picks 2 from MT = 2 up)
+    return h3d_by_values([&](auto e) {
+        return h3d_launch({"dcn4_kernel", MT, e, DENSE, UP},
+                          dcn4_kernel<MT, e, DENSE, UP>, grid, dim3(512), 0, st, a);
+    }, h3d_vals<0, 1, 2>{}, dcn_epi_mode(a, MT >= 2));
 }
 
 int h3d_launch_dcn4(const h3d_op &op, hipStream_t st)

@@ -493,20 +493,15 @@ static int launch_dcn5_cfg(const Dcn5Args &a0, hipStream_t st)
     a.tiles_y = cdiv(a.H, 16);
     a.xcd = h3d_xcd_mode();
     dim3 grid(a.B * a.tiles_x * a.tiles_y, cdiv(a.Cout, 32 * MT));
-    const int epi = dcn_epi_mode(a, MT >= 2);
-    if (h3d_note_kernel(XP ? "dcn5_kernel<%d, %d, %d, %d, %d>" : "dcn5_kernel<%d, %d, %d, %d>", MT, MARGIN, epi, NP, XP)) return H3D_OK;
-    if constexpr (MT >= 2) {
-        if (epi == 2) {
-            hipLaunchKernelGGL((dcn5_kernel<MT, MARGIN, 2, NP, XP>), grid, dim3(C::THREADS), 0, st, a);
-            H3D_CHECK_LAUNCH("dcn5_kernel");
-            return H3D_OK;
+    return dcn_by_epi<MT >= 2>(a, [&](auto e) {
+        const h3d_kname name{"dcn5_kernel", MT, MARGIN, e, NP, h3d_opt(XP)};
+        if constexpr (XP != 0 && e != 2) {
+            if (name.dry()) return H3D_OK;
+            H3D_FAIL(H3D_ERR_UNSUPPORTED, "dcn5: experiment variants exist for the LDS-transposed epilogue only");
+        } else {
+            return h3d_launch(name, dcn5_kernel<MT, MARGIN, e, NP, XP>, grid, dim3(C::THREADS), 0, st, a);
         }
-    }
-    if constexpr (XP != 0) H3D_FAIL(H3D_ERR_UNSUPPORTED, "dcn5: experiment variants exist for the LDS-transposed epilogue only");
-    if (epi == 1) hipLaunchKernelGGL((dcn5_kernel<MT, MARGIN, 1, NP>), grid, dim3(C::THREADS), 0, st, a);
-    else hipLaunchKernelGGL((dcn5_kernel<MT, MARGIN, 0, NP>), grid, dim3(C::THREADS), 0, st, a);
-    H3D_CHECK_LAUNCH("dcn5_kernel");
-    return H3D_OK;
+    });
 }
 
 // H3D_OP_DCN_FUSED_STREAM of an fp16 plan (called by h3d_launch_dcn3 after its argument checks)

@@ -139,6 +139,12 @@ static inline int dcn_epi_mode(const A &a, bool lds_ok)
     const bool lean = a.out_mode == H3D_OUT_NHWC && a.Cout % 4 == 0 && ((uintptr_t)a.bias & 15) == 0;
     return (lds_ok && lean && a.Cout % 8 == 0 && a.out_cs % 8 == 0 && ((uintptr_t)a.out & 15) == 0) ? 2 : lean ? 1 : 0;
 }
+// ... as a constant: f(std::integral_constant<int, EPI>); only the modes the variant has are instantiated
+template <bool LDS_OK, typename A, typename F>
+static inline int dcn_by_epi(const A &a, F f)
+{
+    return h3d_by_values(f, h3d_epi_vals<LDS_OK>{}, dcn_epi_mode(a, LDS_OK));
+}
 
 // the workgroup-width ladder: f(std::integral_constant<int, MT>) for MT = 1 (Cout <= 32), 2 (`mt2`) or 4 32-channel tiles per
 // workgroup; MAXMT = 2 where a launcher has no 128-channel variant (only the rungs up to MAXMT are instantiated)

@@ -169,86 +169,51 @@ __global__ __launch_bounds__(256) void stem_s2_kernel(const float *__restrict__ 
 
 int h3d_launch_stem_s2(const h3d_op &op, hipStream_t st)
 {
-    if (op.dtype != H3D_BF16 && op.dtype != H3D_F16) H3D_FAIL(H3D_ERR_DTYPE, "stem (stride 2): bf16 / fp16 plans only (dtype %d)", op.dtype);
-    if (op.Cin != 3 || op.ksize != 7 || op.stride != 2 || op.Cout % 16 || op.out_cs % 4 || op.out_cs < op.Cout ||
-        op.Ho != (op.H - 1) / 2 + 1 || op.Wo != (op.W - 1) / 2 + 1)
-        H3D_FAIL(H3D_ERR_SHAPE, "stem (stride 2): expects 7x7 3->16n, output floor((H-1)/2)+1 (got k=%d %d->%d, %dx%d -> %dx%d)", op.ksize,
-                 op.Cin, op.Cout, op.H, op.W, op.Ho, op.Wo);
-    if (((uintptr_t)op.w & 15) || ((uintptr_t)op.out & 7)) H3D_FAIL(H3D_ERR_ARG, "stem (stride 2): weights must be 16-byte aligned");
-    const int tx = cdiv(op.Wo, 32), ty = cdiv(op.Ho, 8);
-    if (h3d_note_kernel("stem_s2_kernel<%s>", op.dtype == H3D_F16 ? "f16_t" : "unsigned short")) return H3D_OK;
-    if (op.dtype == H3D_F16)
-        hipLaunchKernelGGL(stem_s2_kernel<f16_t>, dim3(op.B * tx * ty, cdiv(op.Cout, 64)), dim3(256), 0, st, (const float *)op.in, (const f16_t *)op.w,
-                           op.bias, (f16_t *)op.out, op.B, op.H, op.W, op.Ho, op.Wo, op.Cout, op.out_cs, tx, ty);
-    else
-        hipLaunchKernelGGL(stem_s2_kernel<bf16_t>, dim3(op.B * tx * ty, cdiv(op.Cout, 64)), dim3(256), 0, st, (const float *)op.in, (const bf16_t *)op.w,
-                           op.bias, (bf16_t *)op.out, op.B, op.H, op.W, op.Ho, op.Wo, op.Cout, op.out_cs, tx, ty);
-    H3D_CHECK_LAUNCH("stem_s2_kernel");
-    return H3D_OK;
+    return h3d_by_dtype<bf16_t, f16_t>(op.dtype, "stem (stride 2): bf16 / fp16 plans only (dtype %d)", [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (op.Cin != 3 || op.ksize != 7 || op.stride != 2 || op.Cout % 16 || op.out_cs % 4 || op.out_cs < op.Cout ||
+            op.Ho != (op.H - 1) / 2 + 1 || op.Wo != (op.W - 1) / 2 + 1)
+            H3D_FAIL(H3D_ERR_SHAPE, "stem (stride 2): expects 7x7 3->16n, output floor((H-1)/2)+1 (got k=%d %d->%d, %dx%d -> %dx%d)", op.ksize,
+                     op.Cin, op.Cout, op.H, op.W, op.Ho, op.Wo);
+        if (((uintptr_t)op.w & 15) || ((uintptr_t)op.out & 7)) H3D_FAIL(H3D_ERR_ARG, "stem (stride 2): weights must be 16-byte aligned");
+        const int tx = cdiv(op.Wo, 32), ty = cdiv(op.Ho, 8);
+        return h3d_launch({"stem_s2_kernel", t}, stem_s2_kernel<T>, dim3(op.B * tx * ty, cdiv(op.Cout, 64)), dim3(256), 0, st, (const float *)op.in, (const T *)op.w,
+                          op.bias, (T *)op.out, op.B, op.H, op.W, op.Ho, op.Wo, op.Cout, op.out_cs, tx, ty);
+    });
 }
 
 int h3d_launch_extra(const h3d_op &op, hipStream_t st)
 {
     if (!op.in || !op.out) H3D_FAIL(H3D_ERR_ARG, "extra op: null pointer");
-    const int es = h3d_dtype_bytes(op.dtype);
-    if (!es) H3D_FAIL(H3D_ERR_DTYPE, "extra op: dtype %d", op.dtype);
-    const bool f16 = op.dtype == H3D_F16;
-    const int n = 16 / es;
     const dim3 blk(256);
-    if (op.kind == H3D_OP_IM2COL) {
-        const int K = op.Cin * op.ksize * op.ksize, pad = op.ksize / 2;
-        if (op.ksize < 1 || op.stride < 1 || op.Cout < K || op.Cout % n || op.out_cs % n || op.out_cs < op.Cout)
-            H3D_FAIL(H3D_ERR_SHAPE, "im2col: K = %d, padded K (Cout) = %d, stride %d", K, op.Cout, op.out_cs);
-        if (op.Ho != (op.H + 2 * pad - op.ksize) / op.stride + 1 || op.Wo != (op.W + 2 * pad - op.ksize) / op.stride + 1)
-            H3D_FAIL(H3D_ERR_SHAPE, "im2col: output %dx%d does not match (H+2p-k)/s+1", op.Ho, op.Wo);
-        if (h3d_note_kernel("im2col_kernel<%s>", f16 ? "f16_t" : es == 2 ? "unsigned short" : "float")) return H3D_OK;
-        const size_t total = (size_t)op.B * op.Ho * op.Wo * (op.Cout / n);
-        if (f16)
-            hipLaunchKernelGGL(im2col_kernel<f16_t>, dim3(ex_grid(total)), blk, 0, st, (const float *)op.in, (f16_t *)op.out, op.B, op.Cin,
-                               op.H, op.W, op.Ho, op.Wo, op.ksize, op.stride, pad, K, op.Cout, op.out_cs);
-        else if (es == 2)
-            hipLaunchKernelGGL(im2col_kernel<bf16_t>, dim3(ex_grid(total)), blk, 0, st, (const float *)op.in, (bf16_t *)op.out, op.B, op.Cin,
-                               op.H, op.W, op.Ho, op.Wo, op.ksize, op.stride, pad, K, op.Cout, op.out_cs);
-        else
-            hipLaunchKernelGGL(im2col_kernel<float>, dim3(ex_grid(total)), blk, 0, st, (const float *)op.in, (float *)op.out, op.B, op.Cin,
-                               op.H, op.W, op.Ho, op.Wo, op.ksize, op.stride, pad, K, op.Cout, op.out_cs);
-        H3D_CHECK_LAUNCH("im2col_kernel");
-        return H3D_OK;
-    }
-    if (op.Cin % n || op.in_cs % n || op.out_cs % n) H3D_FAIL(H3D_ERR_SHAPE, "extra op: channels %d strides %d/%d must be multiples of %d", op.Cin, op.in_cs, op.out_cs, n);
-    if (op.kind == H3D_OP_MAXPOOL3) {
-        if (op.Cin != op.Cout || op.Ho != (op.H - 1) / 2 + 1 || op.Wo != (op.W - 1) / 2 + 1)
-            H3D_FAIL(H3D_ERR_SHAPE, "maxpool3: output must be floor((H-1)/2)+1 (k3 s2 p1)");
-        if (h3d_note_kernel("maxpool3_kernel<%s>", f16 ? "f16_t" : es == 2 ? "unsigned short" : "float")) return H3D_OK;
-        const size_t total = (size_t)op.B * op.Ho * op.Wo * (op.Cin / n);
-        if (f16)
-            hipLaunchKernelGGL(maxpool3_kernel<f16_t>, dim3(ex_grid(total)), blk, 0, st, (const f16_t *)op.in, (f16_t *)op.out, op.B, op.H, op.W,
-                               op.Cin, op.in_cs, op.Ho, op.Wo, op.out_cs);
-        else if (es == 2)
-            hipLaunchKernelGGL(maxpool3_kernel<bf16_t>, dim3(ex_grid(total)), blk, 0, st, (const bf16_t *)op.in, (bf16_t *)op.out, op.B, op.H, op.W,
-                               op.Cin, op.in_cs, op.Ho, op.Wo, op.out_cs);
-        else
-            hipLaunchKernelGGL(maxpool3_kernel<float>, dim3(ex_grid(total)), blk, 0, st, (const float *)op.in, (float *)op.out, op.B, op.H, op.W,
-                               op.Cin, op.in_cs, op.Ho, op.Wo, op.out_cs);
-        H3D_CHECK_LAUNCH("maxpool3_kernel");
-        return H3D_OK;
-    }
-    if (op.kind == H3D_OP_DEPTH2SPACE) {
-        if (op.Cin != 4 * op.Cout || op.Cout % n || op.Ho != 2 * op.H || op.Wo != 2 * op.W)
-            H3D_FAIL(H3D_ERR_SHAPE, "depth2space: [B,H,W,4C] -> [B,2H,2W,C] expected (Cin=%d Cout=%d)", op.Cin, op.Cout);
-        if (h3d_note_kernel("depth2space_kernel<%s>", f16 ? "f16_t" : es == 2 ? "unsigned short" : "float")) return H3D_OK;
-        const size_t total = (size_t)op.B * op.Ho * op.Wo * (op.Cout / n);
-        if (f16)
-            hipLaunchKernelGGL(depth2space_kernel<f16_t>, dim3(ex_grid(total)), blk, 0, st, (const f16_t *)op.in, (f16_t *)op.out, op.B, op.H,
-                               op.W, op.Cout, op.in_cs, op.out_cs);
-        else if (es == 2)
-            hipLaunchKernelGGL(depth2space_kernel<bf16_t>, dim3(ex_grid(total)), blk, 0, st, (const bf16_t *)op.in, (bf16_t *)op.out, op.B, op.H,
-                               op.W, op.Cout, op.in_cs, op.out_cs);
-        else
-            hipLaunchKernelGGL(depth2space_kernel<float>, dim3(ex_grid(total)), blk, 0, st, (const float *)op.in, (float *)op.out, op.B, op.H,
-                               op.W, op.Cout, op.in_cs, op.out_cs);
-        H3D_CHECK_LAUNCH("depth2space_kernel");
-        return H3D_OK;
-    }
-    H3D_FAIL(H3D_ERR_ARG, "extra op: kind %d", op.kind);
+    return h3d_by_store_dtype<bf16_t, f16_t, float, x3_t>(op.dtype, "extra op: dtype %d", [&](auto t) {
+        using T = typename decltype(t)::type;
+        constexpr int n = 16 / sizeof(T);
+        if (op.kind == H3D_OP_IM2COL) {
+            const int K = op.Cin * op.ksize * op.ksize, pad = op.ksize / 2;
+            if (op.ksize < 1 || op.stride < 1 || op.Cout < K || op.Cout % n || op.out_cs % n || op.out_cs < op.Cout)
+                H3D_FAIL(H3D_ERR_SHAPE, "im2col: K = %d, padded K (Cout) = %d, stride %d", K, op.Cout, op.out_cs);
+            if (op.Ho != (op.H + 2 * pad - op.ksize) / op.stride + 1 || op.Wo != (op.W + 2 * pad - op.ksize) / op.stride + 1)
+                H3D_FAIL(H3D_ERR_SHAPE, "im2col: output %dx%d does not match (H+2p-k)/s+1", op.Ho, op.Wo);
+            const size_t total = (size_t)op.B * op.Ho * op.Wo * (op.Cout / n);
+            return h3d_launch({"im2col_kernel", t}, im2col_kernel<T>, dim3(ex_grid(total)), blk, 0, st, (const float *)op.in, (T *)op.out, op.B, op.Cin, op.H, op.W,
+                              op.Ho, op.Wo, op.ksize, op.stride, pad, K, op.Cout, op.out_cs);
+        }
+        if (op.Cin % n || op.in_cs % n || op.out_cs % n) H3D_FAIL(H3D_ERR_SHAPE, "extra op: channels %d strides %d/%d must be multiples of %d", op.Cin, op.in_cs, op.out_cs, n);
+        if (op.kind == H3D_OP_MAXPOOL3) {
+            if (op.Cin != op.Cout || op.Ho != (op.H - 1) / 2 + 1 || op.Wo != (op.W - 1) / 2 + 1)
+                H3D_FAIL(H3D_ERR_SHAPE, "maxpool3: output must be floor((H-1)/2)+1 (k3 s2 p1)");
+            const size_t total = (size_t)op.B * op.Ho * op.Wo * (op.Cin / n);
+            return h3d_launch({"maxpool3_kernel", t}, maxpool3_kernel<T>, dim3(ex_grid(total)), blk, 0, st, (const T *)op.in, (T *)op.out, op.B, op.H, op.W, op.Cin,
+                              op.in_cs, op.Ho, op.Wo, op.out_cs);
+        }
+        if (op.kind == H3D_OP_DEPTH2SPACE) {
+            if (op.Cin != 4 * op.Cout || op.Cout % n || op.Ho != 2 * op.H || op.Wo != 2 * op.W)
+                H3D_FAIL(H3D_ERR_SHAPE, "depth2space: [B,H,W,4C] -> [B,2H,2W,C] expected (Cin=%d Cout=%d)", op.Cin, op.Cout);
+            const size_t total = (size_t)op.B * op.Ho * op.Wo * (op.Cout / n);
+            return h3d_launch({"depth2space_kernel", t}, depth2space_kernel<T>, dim3(ex_grid(total)), blk, 0, st, (const T *)op.in, (T *)op.out, op.B, op.H, op.W,
+                              op.Cout, op.in_cs, op.out_cs);
+        }
+        H3D_FAIL(H3D_ERR_ARG, "extra op: kind %d", op.kind);
+    });
 }

@@ -193,11 +193,11 @@ static int launch_gemm1_cfg(const Gemm1Args &a0, hipStream_t st)
     a.tiles_n = (int)((a.N + C::BN - 1) / C::BN);
     a.blocks_m = cdiv(a.Cout, C::BM);
     a.xcd = h3d_xcd_mode();
-    if (h3d_note_kernel("gemm1_kernel<%s, %d, %d, %d, %d, %d, %d>", a.f16 ? "f16_t" : "unsigned short", MT, NT, WM, WN, SLOTS, OCC)) return H3D_OK;
-    if (a.f16) hipLaunchKernelGGL((gemm1_kernel<f16_t, MT, NT, WM, WN, SLOTS, OCC>), dim3(a.tiles_n * a.blocks_m), dim3(C::THREADS), 0, st, a);
-    else hipLaunchKernelGGL((gemm1_kernel<bf16_t, MT, NT, WM, WN, SLOTS, OCC>), dim3(a.tiles_n * a.blocks_m), dim3(C::THREADS), 0, st, a);
-    H3D_CHECK_LAUNCH("gemm1_kernel");
-    return H3D_OK;
+    return h3d_by_values([&](auto f16) {
+        using T = std::conditional_t<f16, f16_t, bf16_t>;
+        return h3d_launch({"gemm1_kernel", h3d_tag<T>{}, MT, NT, WM, WN, SLOTS, OCC},
+                          gemm1_kernel<T, MT, NT, WM, WN, SLOTS, OCC>, dim3(a.tiles_n * a.blocks_m), dim3(C::THREADS), 0, st, a);
+    }, h3d_vals<false, true>{}, a.f16 != 0);
 }
 
 // Does the GEMM kernel take this H3D_OP_CONV?  (bf16, 1x1 stride 1, whole 64-channel stages, more than 64 output channels,

@@ -600,48 +600,20 @@ int h3d_launch_heads(const h3d_op &op, hipStream_t st)
     }
     // heads of different widths in one launch: the kernel picks the 1 / 2 / 3-tile body per head (2-byte plans)
     const bool mixed = m2min != m2 && es == 2;
-    const int th = es == 2 ? 16 : 8;
-    a.tiles_x = cdiv(op.W, 32); a.tiles_y = cdiv(op.H, th);
-    const dim3 grid(op.B * a.tiles_x * a.tiles_y), blk(512);
     const bool biasc = !(op.reserved & H3D_TUNE_HEADS_SEPARATE_BIAS);    // tuning override (tools/ab_heads.py): separate bias / zeroing pass
-    if (h3d_note_kernel(mixed ? "heads_kernel<%s, %d, %d, %s, true>" : "heads_kernel<%s, %d, %d, %s>",
-                        op.dtype == H3D_BF16 ? "unsigned short" : op.dtype == H3D_F16 ? "f16_t" : op.dtype == H3D_F16X3 ? "x3_t" : "float", th, m2, biasc ? "true" : "false"))
-        return H3D_OK;
-    if (mixed) {
-        if (!biasc) H3D_FAIL(H3D_ERR_UNSUPPORTED, "heads: the separate-bias tuning override applies to launches of equal-width heads");
-        if (op.dtype == H3D_BF16) {
-            if (m2 == 2) hipLaunchKernelGGL((heads_kernel<bf16_t, 16, 2, true, true>), grid, blk, 0, st, a);
-            else hipLaunchKernelGGL((heads_kernel<bf16_t, 16, 3, true, true>), grid, blk, 0, st, a);
-        } else {
-            if (m2 == 2) hipLaunchKernelGGL((heads_kernel<f16_t, 16, 2, true, true>), grid, blk, 0, st, a);
-            else hipLaunchKernelGGL((heads_kernel<f16_t, 16, 3, true, true>), grid, blk, 0, st, a);
-        }
-        H3D_CHECK_LAUNCH("heads_kernel");
-        return H3D_OK;
-    }
-#define H3D_HEADS_LAUNCH(T, TH, M2)                                                                 \
-    do {                                                                                             \
-        if (biasc) hipLaunchKernelGGL((heads_kernel<T, TH, M2, true>), grid, blk, 0, st, a);         \
-        else hipLaunchKernelGGL((heads_kernel<T, TH, M2, false>), grid, blk, 0, st, a);              \
-    } while (0)
-    if (op.dtype == H3D_BF16) {
-        if (m2 == 1) H3D_HEADS_LAUNCH(bf16_t, 16, 1);
-        else if (m2 == 2) H3D_HEADS_LAUNCH(bf16_t, 16, 2);
-        else H3D_HEADS_LAUNCH(bf16_t, 16, 3);
-    } else if (op.dtype == H3D_F16) {
-        if (m2 == 1) H3D_HEADS_LAUNCH(f16_t, 16, 1);
-        else if (m2 == 2) H3D_HEADS_LAUNCH(f16_t, 16, 2);
-        else H3D_HEADS_LAUNCH(f16_t, 16, 3);
-    } else if (op.dtype == H3D_F16X3) {
-        if (m2 == 1) H3D_HEADS_LAUNCH(x3_t, 8, 1);
-        else if (m2 == 2) H3D_HEADS_LAUNCH(x3_t, 8, 2);
-        else H3D_HEADS_LAUNCH(x3_t, 8, 3);
-    } else {
-        if (m2 == 1) H3D_HEADS_LAUNCH(float, 8, 1);
-        else if (m2 == 2) H3D_HEADS_LAUNCH(float, 8, 2);
-        else H3D_HEADS_LAUNCH(float, 8, 3);
-    }
-#undef H3D_HEADS_LAUNCH
-    H3D_CHECK_LAUNCH("heads_kernel");
-    return H3D_OK;
+    return h3d_by_dtype<bf16_t, f16_t, float, x3_t>(op.dtype, "heads: dtype %d", [&](auto t) {
+        using T = typename decltype(t)::type;
+        constexpr int TH = sizeof(T) == 2 ? 16 : 8;
+        a.tiles_x = cdiv(op.W, 32); a.tiles_y = cdiv(op.H, TH);
+        const dim3 grid(op.B * a.tiles_x * a.tiles_y), blk(512);
+        return h3d_by_values([&](auto m2c, auto bc, auto mx) {
+            const h3d_kname name{"heads_kernel", t, TH, m2c, bc, h3d_opt(mx)};
+            if constexpr (mx && (m2c < 2 || !bc)) {       // MIXED is instantiated for 2 | 3 row tiles with the bias in the accumulators
+                if (name.dry()) return H3D_OK;
+                H3D_FAIL(H3D_ERR_UNSUPPORTED, "heads: the separate-bias tuning override applies to launches of equal-width heads");
+            } else {
+                return h3d_launch(name, heads_kernel<T, TH, m2c, bc, mx>, grid, blk, 0, st, a);
+            }
+        }, h3d_vals<1, 2, 3>{}, m2, h3d_vals<false, true>{}, biasc, std::conditional_t<sizeof(T) == 2, h3d_vals<false, true>, h3d_vals<false>>{}, mixed);
+    });
 }

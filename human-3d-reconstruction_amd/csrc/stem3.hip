@@ -381,7 +381,6 @@ int h3d_launch_stem3(const h3d_op &op, hipStream_t st)
     a.B = op.B; a.H = op.H; a.W = op.W; a.Ho = op.Ho; a.Wo = op.Wo; a.out_cs = op.out_cs;
     a.tiles_x = cdiv(op.Wo, 16); a.tiles_y = cdiv(op.Ho, 8);
     a.dbg = op.reserved;
-    if (h3d_note_kernel(proj ? "stem3_kernel<%s, true>" : "stem3_kernel<%s>", op.dtype == H3D_F16 ? "f16_t" : "unsigned short")) return H3D_OK;
     // as many tiles per workgroup as still give every one of the 512 workgroup slots (two per CU) a workgroup: batch 64 at 512 x 512 =
     // 32768 tiles -> 64 per workgroup (one round of equal workgroups: no tail, one prologue per slot); an 8-image shard (4096) -> 8
     const int ntiles = op.B * a.tiles_x * a.tiles_y;
@@ -390,11 +389,10 @@ int h3d_launch_stem3(const h3d_op &op, hipStream_t st)
     if (S3K_TPB_FORCE) tpb = S3K_TPB_FORCE;
     a.tpb = tpb;
     const dim3 grid(cdiv(ntiles, tpb));
-    if (proj) {
-        if (op.dtype == H3D_F16) hipLaunchKernelGGL((stem3_kernel<f16_t, true>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((stem3_kernel<bf16_t, true>), grid, dim3(512), 0, st, a);
-    } else if (op.dtype == H3D_F16) hipLaunchKernelGGL(stem3_kernel<f16_t>, grid, dim3(512), 0, st, a);
-    else hipLaunchKernelGGL(stem3_kernel<bf16_t>, grid, dim3(512), 0, st, a);
-    H3D_CHECK_LAUNCH("stem3_kernel");
-    return H3D_OK;
+    return h3d_by_dtype<bf16_t, f16_t>(op.dtype, "stem3: dtype %d", [&](auto t) {
+        return h3d_by_values([&](auto pj) {
+            return h3d_launch({"stem3_kernel", t, h3d_opt(pj)},
+                              stem3_kernel<typename decltype(t)::type, pj>, grid, dim3(512), 0, st, a);
+        }, h3d_vals<false, true>{}, proj);
+    });
 }

@@ -204,8 +204,5 @@ int h3d_launch_stem3x(const h3d_op &op, hipStream_t st)
     int tpb = 2;                                   // consecutive tiles per workgroup (the 21 filter fragment pairs are fetched once per workgroup)
     while (tpb < 64 && cdiv(ntiles, 2 * tpb) >= 256) tpb *= 2;
     a.tpb = tpb;
-    if (h3d_note_kernel("stem3x_kernel")) return H3D_OK;
-    hipLaunchKernelGGL(stem3x_kernel, dim3(cdiv(ntiles, tpb)), dim3(512), 0, st, a);
-    H3D_CHECK_LAUNCH("stem3x_kernel");
-    return H3D_OK;
+    return h3d_launch({"stem3x_kernel"}, stem3x_kernel, dim3(cdiv(ntiles, tpb)), dim3(512), 0, st, a);
 }

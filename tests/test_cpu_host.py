@@ -278,6 +278,25 @@ def _dry_op(kind, dtype, reserved, B, Cin, Cout, H, W, ksize, stride, keep):
     return op
 
 
+def _dry_op_with(case, over, keep):
+    """_dry_op, then the overrides: an h3d_op field by name, "heads": the widths of the heads, "updcn": an h3d_updcn_desc behind in2."""
+    op, fake = _dry_op(*case, keep), 0x10000
+    for k, v in over.items():
+        if k == "heads":
+            d = keep[-1]
+            d.nheads = len(v)
+            for i, c in enumerate(v):
+                d.head[i].w2, d.head[i].b2, d.head[i].out, d.head[i].C = fake, fake, fake, c
+        elif k == "updcn":
+            d = _lib.H3dUpdcnDesc()
+            d.skip, d.w_up, d.w_off, d.skip_cs = fake, fake, fake, v
+            keep.append(d)
+            op.in2 = ctypes.addressof(d)
+        else:
+            setattr(op, k, v)
+    return op
+
+
 L = _lib
 S, F, D, C2, C, U, HD, F16K = L.OP_DCN_FUSED_STREAM, L.OP_DCN_FUSED, L.OP_DCN, L.OP_CONV_STREAM, L.OP_CONV, L.OP_UPADD, L.OP_HEADS, L.OP_DCN_FUSED_F16
 # (kind, dtype, reserved, B, Cin, Cout, H, W, ksize, stride, kernel name).  The names are what the library printed for the same words
@@ -399,6 +418,372 @@ DISPATCH = [
     (HD, "BF16", 0, 1, 64, 64, 16, 32, 3, 1, "heads_kernel<unsigned short, 16, 1, true>"),
     (HD, "BF16", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, "heads_kernel<unsigned short, 16, 1, false>"),
     (HD, "F32", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, "heads_kernel<float, 8, 1, false>"),
+    # Every other kernel instantiation of the op launchers (csrc: conv, conv2, gemm1, stem3, extra, heads, dcn2, dcn3) that neither a row
+    # above nor an op of tests/golden/plan_ops.json.gz names, each with the smallest op found for it.  Names recorded from the library
+    # BEFORE the launchers took name and kernel from one site (the parent commit's dry run).
+    (S, "F16", 0, 1, 16, 16, 4, 4, 3, 1, "dcn3_kernel<f16_t, 1, 16, 1, 1, true, 0>"),
+    (S, "F16", 0, 1, 32, 16, 4, 4, 3, 1, "dcn3_kernel<f16_t, 1, 16, 2, 1, true, 256>"),
+    (S, "F16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 16, 4, 4, 3, 1, "dcn3_kernel<f16_t, 1, 16, 2, 1, true, 512, true>"),
+    (S, "F16", L.OPF_DCN_STREAM_WIDE_MARGIN, 1, 32, 16, 4, 4, 3, 1, "dcn3_kernel<f16_t, 1, 16, 4, 1, true, 256, true>"),
+    (S, "F16", 0, 1, 16, 36, 4, 4, 3, 1, "dcn3_kernel<f16_t, 2, 16, 1, 1, true, 0>"),
+    (S, "F16", 0, 1, 32, 36, 4, 4, 3, 1, "dcn3_kernel<f16_t, 2, 16, 2, 1, true, 256>"),
+    (S, "F16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 36, 4, 4, 3, 1, "dcn3_kernel<f16_t, 2, 16, 2, 1, true, 512, true>"),
+    (S, "F16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 64, 4, 4, 3, 1, "dcn3_kernel<f16_t, 2, 16, 2, 2, true, 512, true>"),
+    (S, "F16", L.OPF_DCN_STREAM_WIDE_MARGIN, 1, 32, 36, 4, 4, 3, 1, "dcn3_kernel<f16_t, 2, 16, 4, 1, true, 256, true>"),
+    (S, "F16", 0, 1, 16, 68, 4, 4, 3, 1, "dcn3_kernel<f16_t, 4, 16, 2, 1, true, 0>"),
+    (S, "F16", 0, 1, 32, 260, 128, 128, 3, 1, "dcn3_kernel<f16_t, 4, 16, 4, 1, true, 256>"),
+    (S, "F16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 260, 128, 128, 3, 1, "dcn3_kernel<f16_t, 4, 16, 4, 1, true, 512>"),
+    (S, "F16", 0, 1, 32, 512, 128, 128, 3, 1, "dcn3_kernel<f16_t, 4, 16, 4, 2, true, 256>"),
+    (S, "F16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 512, 128, 128, 3, 1, "dcn3_kernel<f16_t, 4, 16, 4, 2, true, 512>"),
+    (S, "BF16", 0, 1, 16, 36, 4, 4, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 1, 1, true, 0>"),
+    (S, "BF16", 0, 1, 32, 36, 4, 4, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 1, true, 256>"),
+    (S, "BF16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 36, 4, 4, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 1, true, 512, true>"),
+    (S, "BF16", L.OPF_DCN_STREAM_WIDE_MARGIN, 1, 32, 36, 4, 4, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 4, 1, true, 256, true>"),
+    (S, "BF16", 0, 1, 16, 68, 4, 4, 3, 1, "dcn3_kernel<unsigned short, 4, 16, 2, 1, true, 0>"),
+    (S, "BF16", 0, 1, 32, 260, 128, 128, 3, 1, "dcn3_kernel<unsigned short, 4, 16, 4, 1, true, 256>"),
+    (S, "BF16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 260, 128, 128, 3, 1, "dcn3_kernel<unsigned short, 4, 16, 4, 1, true, 512>"),
+    (S, "F16X3", 0, 1, 32, 16, 4, 4, 3, 1, "dcn3_kernel<x3_t, 1, 16, 2, 1, true, 256>"),
+    (S, "F16X3", L.TUNE_DCN_STREAM_X3_MARGIN3, 1, 32, 16, 4, 4, 3, 1, "dcn3_kernel<x3_t, 1, 16, 3, 1, true, 256>"),
+    (F, "F16", 0, 1, 16, 16, 4, 4, 3, 1, "dcn3_kernel<f16_t, 1, 16, 2, 1, false, 0>"),
+    (F, "F16", 0, 1, 32, 16, 4, 4, 3, 1, "dcn3_kernel<f16_t, 1, 32, 2, 1, false, 0>"),
+    (F, "F16", 0, 1, 16, 36, 4, 4, 3, 1, "dcn3_kernel<f16_t, 2, 16, 2, 1, false, 0>"),
+    (F, "F16", 0, 1, 16, 64, 4, 4, 3, 1, "dcn3_kernel<f16_t, 2, 16, 2, 2, false, 0>"),
+    (F, "F16", 0, 1, 32, 36, 4, 4, 3, 1, "dcn3_kernel<f16_t, 2, 32, 2, 1, false, 0>"),
+    (F, "F16", 0, 1, 32, 64, 4, 4, 3, 1, "dcn3_kernel<f16_t, 2, 32, 2, 2, false, 0>"),
+    (F, "F16", 0, 1, 16, 260, 128, 128, 3, 1, "dcn3_kernel<f16_t, 4, 16, 2, 1, false, 0>"),
+    (F, "F32", 0, 1, 16, 16, 4, 4, 3, 1, "dcn3_kernel<float, 1, 16, 2, 1, false, 0>"),
+    (F, "BF16", 0, 1, 16, 16, 4, 4, 3, 1, "dcn3_kernel<unsigned short, 1, 16, 2, 1, false, 0>"),
+    (F, "BF16", 0, 1, 32, 16, 4, 4, 3, 1, "dcn3_kernel<unsigned short, 1, 32, 2, 1, false, 0>"),
+    (F, "BF16", 0, 1, 16, 36, 4, 4, 3, 1, "dcn3_kernel<unsigned short, 2, 16, 2, 1, false, 0>"),
+    (F, "BF16", 0, 1, 32, 36, 4, 4, 3, 1, "dcn3_kernel<unsigned short, 2, 32, 2, 1, false, 0>"),
+    (F, "BF16", 0, 1, 16, 260, 128, 128, 3, 1, "dcn3_kernel<unsigned short, 4, 16, 2, 1, false, 0>"),
+    (F, "F16X3", L.TUNE_DCN_FUSED_X3_MARGIN2, 1, 16, 16, 4, 4, 3, 1, "dcn3_kernel<x3_t, 1, 16, 2, 1, false, 0>"),
+    (F, "F16X3", 0, 1, 16, 16, 4, 4, 3, 1, "dcn3_kernel<x3_t, 1, 16, 4, 1, false, 0>"),
+    (D, "F32", 0, 1, 16, 16, 4, 4, 3, 1, "dcn2_kernel<float, 1, 16, 2, 1>"),
+    (D, "BF16", 0, 1, 16, 16, 4, 4, 3, 1, "dcn2_kernel<unsigned short, 1, 16, 2, 2>"),
+    (D, "BF16", 0, 1, 32, 16, 4, 4, 3, 1, "dcn2_kernel<unsigned short, 1, 32, 2, 2>"),
+    (D, "BF16", 0, 1, 16, 36, 4, 4, 3, 1, "dcn2_kernel<unsigned short, 2, 16, 2, 2>"),
+    (C2, "F16", 0, 1, 16, 16, 4, 4, 3, 2, "conv2_kernel<f16_t, 1, 4, 1, 2, 2, 1>"),
+    (C2, "F16", 0, 64, 16, 16, 24, 40, 3, 1, "conv2_kernel<f16_t, 1, 8, 1, 1, 1, 1>"),
+    (C2, "F16", 0, 1, 16, 128, 128, 128, 3, 1, "conv2_kernel<f16_t, 1, 8, 1, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(3, 1, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<f16_t, 1, 8, 1, 1, 3, 1>"),
+    (C2, "F16", 0, 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<f16_t, 2, 4, 1, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(4, 2, 4), 1, 16, 36, 4, 4, 3, 2, "conv2_kernel<f16_t, 2, 4, 1, 2, 1, 1>"),
+    (C2, "F16", 0, 1, 16, 36, 4, 4, 3, 2, "conv2_kernel<f16_t, 2, 4, 1, 2, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(4, 2, 4), 1, 16, 16, 4, 4, 3, 2, "conv2_kernel<f16_t, 2, 4, 2, 2, 1, 1>"),
+    (C2, "F16", 0, 1, 16, 64, 4, 4, 3, 2, "conv2_kernel<f16_t, 2, 4, 2, 2, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(5, 2, 8), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<f16_t, 2, 8, 1, 1, 1, 1>"),
+    (C2, "F16", 0, 1, 16, 260, 128, 128, 3, 1, "conv2_kernel<f16_t, 2, 8, 1, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(2, 2, 8), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<f16_t, 2, 8, 1, 1, 2, 2>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(3, 2, 8), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<f16_t, 2, 8, 1, 1, 3, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(5, 2, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<f16_t, 2, 8, 2, 1, 1, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(0, 2, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<f16_t, 2, 8, 2, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(2, 2, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<f16_t, 2, 8, 2, 1, 2, 2>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(3, 2, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<f16_t, 2, 8, 2, 1, 3, 1>"),
+    (C2, "F16", 0, 64, 16, 132, 32, 32, 3, 1, "conv2_kernel<f16_t, 4, 16, 1, 1, 2, 1>"),
+    (C2, "F16", 0, 2, 16, 512, 128, 128, 3, 1, "conv2_kernel<f16_t, 4, 16, 2, 1, 2, 1, true>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(0, 4, 16), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<f16_t, 4, 16, 2, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(0, 4, 4), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<f16_t, 4, 4, 1, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(3, 4, 4), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<f16_t, 4, 4, 1, 1, 3, 1>"),
+    (C2, "F16", 0, 1, 16, 132, 4, 4, 3, 2, "conv2_kernel<f16_t, 4, 4, 1, 2, 1, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(2, 4, 4), 1, 16, 132, 4, 4, 3, 2, "conv2_kernel<f16_t, 4, 4, 1, 2, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(6, 4, 4), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<f16_t, 4, 4, 2, 1, 2, 1, true>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(0, 4, 4), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<f16_t, 4, 4, 2, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(3, 4, 4), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<f16_t, 4, 4, 2, 1, 3, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(2, 4, 4), 1, 16, 128, 4, 4, 3, 2, "conv2_kernel<f16_t, 4, 4, 2, 2, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(5, 4, 8), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<f16_t, 4, 8, 1, 1, 1, 1>"),
+    (C2, "F16", 0, 2, 16, 132, 128, 128, 3, 1, "conv2_kernel<f16_t, 4, 8, 1, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(2, 4, 8), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<f16_t, 4, 8, 1, 1, 2, 2>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(4, 4, 8), 1, 16, 36, 4, 4, 3, 2, "conv2_kernel<f16_t, 4, 8, 1, 2, 1, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(5, 4, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<f16_t, 4, 8, 2, 1, 1, 1>"),
+    (C2, "F16", 0, 1, 16, 512, 128, 128, 3, 1, "conv2_kernel<f16_t, 4, 8, 2, 1, 2, 1, true>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(0, 4, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<f16_t, 4, 8, 2, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(2, 4, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<f16_t, 4, 8, 2, 1, 2, 2>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(4, 4, 8), 1, 16, 16, 4, 4, 3, 2, "conv2_kernel<f16_t, 4, 8, 2, 2, 1, 1>"),
+    (C2, "BF16", 0, 1, 16, 16, 4, 4, 3, 2, "conv2_kernel<unsigned short, 1, 4, 1, 2, 2, 1>"),
+    (C2, "BF16", 0, 64, 16, 16, 24, 40, 3, 1, "conv2_kernel<unsigned short, 1, 8, 1, 1, 1, 1>"),
+    (C2, "BF16", 0, 1, 16, 128, 128, 128, 3, 1, "conv2_kernel<unsigned short, 1, 8, 1, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(3, 1, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<unsigned short, 1, 8, 1, 1, 3, 1>"),
+    (C2, "BF16", 0, 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<unsigned short, 2, 4, 1, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(4, 2, 4), 1, 16, 36, 4, 4, 3, 2, "conv2_kernel<unsigned short, 2, 4, 1, 2, 1, 1>"),
+    (C2, "BF16", 0, 1, 16, 36, 4, 4, 3, 2, "conv2_kernel<unsigned short, 2, 4, 1, 2, 2, 1>"),
+    (C2, "BF16", 0, 1, 16, 64, 4, 4, 3, 2, "conv2_kernel<unsigned short, 2, 4, 2, 2, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(5, 2, 8), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<unsigned short, 2, 8, 1, 1, 1, 1>"),
+    (C2, "BF16", 0, 1, 16, 260, 128, 128, 3, 1, "conv2_kernel<unsigned short, 2, 8, 1, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(2, 2, 8), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<unsigned short, 2, 8, 1, 1, 2, 2>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(3, 2, 8), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<unsigned short, 2, 8, 1, 1, 3, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(0, 2, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<unsigned short, 2, 8, 2, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(2, 2, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<unsigned short, 2, 8, 2, 1, 2, 2>"),
+    (C2, "BF16", 0, 64, 16, 132, 32, 32, 3, 1, "conv2_kernel<unsigned short, 4, 16, 1, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(0, 4, 4), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<unsigned short, 4, 4, 1, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(3, 4, 4), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<unsigned short, 4, 4, 1, 1, 3, 1>"),
+    (C2, "BF16", 0, 1, 16, 132, 4, 4, 3, 2, "conv2_kernel<unsigned short, 4, 4, 1, 2, 1, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(2, 4, 4), 1, 16, 132, 4, 4, 3, 2, "conv2_kernel<unsigned short, 4, 4, 1, 2, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(6, 4, 4), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<unsigned short, 4, 4, 2, 1, 2, 1, true>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(3, 4, 4), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<unsigned short, 4, 4, 2, 1, 3, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(5, 4, 8), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<unsigned short, 4, 8, 1, 1, 1, 1>"),
+    (C2, "BF16", 0, 2, 16, 132, 128, 128, 3, 1, "conv2_kernel<unsigned short, 4, 8, 1, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(2, 4, 8), 1, 16, 36, 4, 4, 3, 1, "conv2_kernel<unsigned short, 4, 8, 1, 1, 2, 2>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(4, 4, 8), 1, 16, 36, 4, 4, 3, 2, "conv2_kernel<unsigned short, 4, 8, 1, 2, 1, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(5, 4, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<unsigned short, 4, 8, 2, 1, 1, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(0, 4, 8), 1, 16, 16, 4, 4, 3, 1, "conv2_kernel<unsigned short, 4, 8, 2, 1, 2, 1>"),
+    (C, "F16", 0, 1, 16, 16, 4, 4, 1, 1, "conv_kernel<f16_t, 1, 1, 1, 16, 16, 4, 1>"),
+    (C, "F16", 0, 1, 64, 16, 4, 4, 1, 1, "conv_kernel<f16_t, 1, 1, 1, 64, 16, 4, 1>"),
+    (C, "F16", 0, 1, 16, 36, 4, 4, 1, 1, "conv_kernel<f16_t, 1, 1, 2, 16, 16, 4, 1>"),
+    (C, "F16", L.TUNE_CONV_1X1_TILE(2, 16), 1, 64, 36, 4, 4, 1, 1, "conv_kernel<f16_t, 1, 1, 2, 64, 16, 4, 1>"),
+    (C, "F16", 0, 1, 64, 36, 4, 4, 1, 1, "conv_kernel<f16_t, 1, 1, 2, 64, 8, 4, 1>"),
+    (C, "F16", 0, 1, 16, 68, 4, 4, 1, 1, "conv_kernel<f16_t, 1, 1, 4, 16, 16, 4, 1>"),
+    (C, "F16", 0, 1, 16, 128, 4, 4, 1, 1, "conv_kernel<f16_t, 1, 1, 4, 16, 16, 4, 2>"),
+    (C, "F16", L.TUNE_CONV_1X1_TILE(4, 16), 1, 64, 36, 4, 4, 1, 1, "conv_kernel<f16_t, 1, 1, 4, 64, 16, 4, 1>"),
+    (C, "F16", L.TUNE_CONV_1X1_TILE(4, 16), 1, 64, 64, 4, 4, 1, 1, "conv_kernel<f16_t, 1, 1, 4, 64, 16, 4, 2>"),
+    (C, "F16", 0, 1, 64, 68, 4, 4, 1, 1, "conv_kernel<f16_t, 1, 1, 4, 64, 8, 4, 1>"),
+    (C, "F16", 0, 1, 16, 16, 4, 4, 1, 2, "conv_kernel<f16_t, 1, 2, 1, 16, 8, 4, 1>"),
+    (C, "F16", 0, 1, 16, 36, 4, 4, 1, 2, "conv_kernel<f16_t, 1, 2, 2, 16, 8, 4, 1>"),
+    (C, "F16", 0, 1, 16, 64, 4, 4, 1, 2, "conv_kernel<f16_t, 1, 2, 2, 16, 8, 4, 2>"),
+    (C, "F16", 0, 1, 16, 68, 4, 4, 1, 2, "conv_kernel<f16_t, 1, 2, 4, 16, 8, 4, 1>"),
+    (C, "F16", 0, 1, 16, 128, 4, 4, 1, 2, "conv_kernel<f16_t, 1, 2, 4, 16, 8, 4, 2>"),
+    (C, "F16", 0, 1, 32, 16, 4, 4, 3, 1, "conv_kernel<f16_t, 3, 1, 1, 32, 16, 4, 1>"),
+    (C, "F16", 0, 1, 16, 36, 4, 4, 3, 1, "conv_kernel<f16_t, 3, 1, 2, 16, 16, 4, 1>"),
+    (C, "F16", 0, 1, 16, 64, 4, 4, 3, 1, "conv_kernel<f16_t, 3, 1, 2, 16, 16, 4, 2>"),
+    (C, "F16", 0, 64, 32, 36, 64, 64, 3, 1, "conv_kernel<f16_t, 3, 1, 2, 32, 16, 8, 1>"),
+    (C, "F16", 0, 64, 32, 64, 64, 64, 3, 1, "conv_kernel<f16_t, 3, 1, 2, 32, 16, 8, 2>"),
+    (C, "F16", 0, 1, 32, 36, 4, 4, 3, 1, "conv_kernel<f16_t, 3, 1, 2, 32, 8, 4, 1>"),
+    (C, "F16", 0, 1, 16, 68, 4, 4, 3, 1, "conv_kernel<f16_t, 3, 1, 4, 16, 16, 4, 1>"),
+    (C, "F16", 0, 1, 16, 128, 4, 4, 3, 1, "conv_kernel<f16_t, 3, 1, 4, 16, 16, 4, 2>"),
+    (C, "F16", 0, 64, 32, 132, 24, 40, 3, 1, "conv_kernel<f16_t, 3, 1, 4, 16, 8, 4, 1>"),
+    (C, "F16", 0, 2, 32, 512, 128, 128, 3, 1, "conv_kernel<f16_t, 3, 1, 4, 16, 8, 4, 2>"),
+    (C, "F16", 0, 64, 32, 68, 64, 64, 3, 1, "conv_kernel<f16_t, 3, 1, 4, 32, 16, 8, 1>"),
+    (C, "F16", 0, 64, 32, 128, 64, 64, 3, 1, "conv_kernel<f16_t, 3, 1, 4, 32, 16, 8, 2>"),
+    (C, "F16", 0, 1, 16, 36, 4, 4, 3, 2, "conv_kernel<f16_t, 3, 2, 2, 16, 8, 4, 1>"),
+    (C, "F16", 0, 64, 16, 68, 128, 128, 3, 2, "conv_kernel<f16_t, 3, 2, 4, 16, 8, 4, 1>"),
+    (C, "F16", 0, 64, 16, 128, 128, 128, 3, 2, "conv_kernel<f16_t, 3, 2, 4, 16, 8, 4, 2>"),
+    (C, "F32", 0, 1, 16, 16, 4, 4, 1, 1, "conv_kernel<float, 1, 1, 1, 16, 16, 4, 1>"),
+    (C, "F32", 0, 1, 16, 16, 4, 4, 1, 2, "conv_kernel<float, 1, 2, 1, 16, 8, 4, 1>"),
+    (C, "BF16", 0, 1, 16, 16, 4, 4, 1, 1, "conv_kernel<unsigned short, 1, 1, 1, 16, 16, 4, 1>"),
+    (C, "BF16", 0, 1, 64, 16, 4, 4, 1, 1, "conv_kernel<unsigned short, 1, 1, 1, 64, 16, 4, 1>"),
+    (C, "BF16", 0, 1, 16, 36, 4, 4, 1, 1, "conv_kernel<unsigned short, 1, 1, 2, 16, 16, 4, 1>"),
+    (C, "BF16", L.TUNE_CONV_1X1_TILE(2, 16), 1, 64, 36, 4, 4, 1, 1, "conv_kernel<unsigned short, 1, 1, 2, 64, 16, 4, 1>"),
+    (C, "BF16", 0, 1, 64, 36, 4, 4, 1, 1, "conv_kernel<unsigned short, 1, 1, 2, 64, 8, 4, 1>"),
+    (C, "BF16", 0, 1, 16, 68, 4, 4, 1, 1, "conv_kernel<unsigned short, 1, 1, 4, 16, 16, 4, 1>"),
+    (C, "BF16", 0, 1, 16, 128, 4, 4, 1, 1, "conv_kernel<unsigned short, 1, 1, 4, 16, 16, 4, 2>"),
+    (C, "BF16", L.TUNE_CONV_1X1_TILE(4, 16), 1, 64, 36, 4, 4, 1, 1, "conv_kernel<unsigned short, 1, 1, 4, 64, 16, 4, 1>"),
+    (C, "BF16", 0, 1, 64, 68, 4, 4, 1, 1, "conv_kernel<unsigned short, 1, 1, 4, 64, 8, 4, 1>"),
+    (C, "BF16", 0, 1, 16, 16, 4, 4, 1, 2, "conv_kernel<unsigned short, 1, 2, 1, 16, 8, 4, 1>"),
+    (C, "BF16", 0, 1, 16, 36, 4, 4, 1, 2, "conv_kernel<unsigned short, 1, 2, 2, 16, 8, 4, 1>"),
+    (C, "BF16", 0, 1, 16, 64, 4, 4, 1, 2, "conv_kernel<unsigned short, 1, 2, 2, 16, 8, 4, 2>"),
+    (C, "BF16", 0, 1, 16, 68, 4, 4, 1, 2, "conv_kernel<unsigned short, 1, 2, 4, 16, 8, 4, 1>"),
+    (C, "BF16", 0, 1, 32, 16, 4, 4, 3, 1, "conv_kernel<unsigned short, 3, 1, 1, 32, 16, 4, 1>"),
+    (C, "BF16", 0, 1, 16, 36, 4, 4, 3, 1, "conv_kernel<unsigned short, 3, 1, 2, 16, 16, 4, 1>"),
+    (C, "BF16", 0, 1, 16, 64, 4, 4, 3, 1, "conv_kernel<unsigned short, 3, 1, 2, 16, 16, 4, 2>"),
+    (C, "BF16", 0, 64, 32, 36, 64, 64, 3, 1, "conv_kernel<unsigned short, 3, 1, 2, 32, 16, 8, 1>"),
+    (C, "BF16", 0, 64, 32, 64, 64, 64, 3, 1, "conv_kernel<unsigned short, 3, 1, 2, 32, 16, 8, 2>"),
+    (C, "BF16", 0, 1, 32, 36, 4, 4, 3, 1, "conv_kernel<unsigned short, 3, 1, 2, 32, 8, 4, 1>"),
+    (C, "BF16", 0, 1, 16, 68, 4, 4, 3, 1, "conv_kernel<unsigned short, 3, 1, 4, 16, 16, 4, 1>"),
+    (C, "BF16", 0, 1, 16, 128, 4, 4, 3, 1, "conv_kernel<unsigned short, 3, 1, 4, 16, 16, 4, 2>"),
+    (C, "BF16", 0, 64, 32, 132, 24, 40, 3, 1, "conv_kernel<unsigned short, 3, 1, 4, 16, 8, 4, 1>"),
+    (C, "BF16", 0, 2, 32, 512, 128, 128, 3, 1, "conv_kernel<unsigned short, 3, 1, 4, 16, 8, 4, 2>"),
+    (C, "BF16", 0, 64, 32, 68, 64, 64, 3, 1, "conv_kernel<unsigned short, 3, 1, 4, 32, 16, 8, 1>"),
+    (C, "BF16", 0, 64, 32, 128, 64, 64, 3, 1, "conv_kernel<unsigned short, 3, 1, 4, 32, 16, 8, 2>"),
+    (C, "BF16", 0, 1, 16, 36, 4, 4, 3, 2, "conv_kernel<unsigned short, 3, 2, 2, 16, 8, 4, 1>"),
+    (C, "BF16", 0, 64, 16, 68, 128, 128, 3, 2, "conv_kernel<unsigned short, 3, 2, 4, 16, 8, 4, 1>"),
+    (C, "BF16", 0, 64, 16, 128, 128, 128, 3, 2, "conv_kernel<unsigned short, 3, 2, 4, 16, 8, 4, 2>"),
+    (C, "F16X3", 0, 1, 16, 16, 4, 4, 1, 1, "conv_kernel<x3_t, 1, 1, 1, 16, 16, 4, 1>"),
+    (C, "F16X3", 0, 1, 16, 16, 4, 4, 1, 2, "conv_kernel<x3_t, 1, 2, 1, 16, 8, 4, 1>"),
+    (C, "F16X3", 0, 1, 16, 36, 4, 4, 1, 2, "conv_kernel<x3_t, 1, 2, 2, 16, 8, 4, 1>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(2, 4, 16), 1, 16, 16, 4, 4, 3, 1, "conv_kernel<x3_t, 3, 1, 2, 16, 16, 4, 1>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(2, 4, 8), 1, 16, 16, 4, 4, 3, 1, "conv_kernel<x3_t, 3, 1, 2, 16, 8, 4, 1>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(4, 8, 32), 1, 16, 16, 4, 4, 3, 1, "conv_kernel<x3_t, 3, 1, 4, 16, 32, 8, 1>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(4, 4, 8), 1, 16, 16, 4, 4, 3, 1, "conv_kernel<x3_t, 3, 1, 4, 16, 8, 4, 1>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(1, 8, 16), 1, 16, 16, 4, 4, 3, 2, "conv_kernel<x3_t, 3, 2, 1, 16, 16, 8, 1>"),
+    (C, "F16", 0, 1, 128, 128, 128, 128, 1, 1, "gemm1_kernel<f16_t, 2, 2, 2, 2, 2, 2>"),
+    (C, "F16", L.TUNE_CONV_FORCE_GEMM | L.TUNE_CONV_GEMM_TILE(2), 1, 128, 16, 4, 4, 1, 1, "gemm1_kernel<f16_t, 2, 2, 2, 4, 3, 2>"),
+    (C, "F16", 0, 2, 128, 512, 128, 128, 1, 1, "gemm1_kernel<f16_t, 4, 2, 2, 4, 2, 2>"),
+    (L.OP_COPY, "F16", 0, 1, 64, 64, 8, 8, 1, 1, "copy_kernel<f16_t>"),
+    (L.OP_COPY, "F32", 0, 1, 64, 64, 8, 8, 1, 1, "copy_kernel<float>"),
+    (L.OP_COPY, "BF16", 0, 1, 64, 64, 8, 8, 1, 1, "copy_kernel<unsigned short>"),
+    (L.OP_STEM, "F16", 0, 1, 3, 64, 16, 16, 7, 2, "stem_s2_kernel<f16_t>"),
+    (L.OP_IM2COL, "F16", 0, 1, 3, 160, 16, 16, 7, 2, "im2col_kernel<f16_t>"),
+    (L.OP_MAXPOOL3, "F16", 0, 1, 64, 64, 16, 16, 3, 2, "maxpool3_kernel<f16_t>"),
+]
+# ... and those that need an op _dry_op does not build: (..., stride, overrides, kernel name) with the overrides of _dry_op_with: "out_mode"
+# (anything but NHWC takes the general epilogue, EPI = 0; H3D_OUT_NHWC_F16 is upadd's fp16 output), "heads", "in2_cs", "Ho" / "Wo"
+DISPATCH_WITH = [
+    (S, "F16", 0, 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 1, 16, 1, 0, true, 0>"),
+    (S, "F16", 0, 1, 32, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 1, 16, 2, 0, true, 256>"),
+    (S, "F16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 1, 16, 2, 0, true, 512, true>"),
+    (S, "F16", L.OPF_DCN_STREAM_WIDE_MARGIN, 1, 32, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 1, 16, 4, 0, true, 256, true>"),
+    (S, "F16", 0, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 2, 16, 1, 0, true, 0>"),
+    (S, "F16", 0, 1, 32, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 2, 16, 2, 0, true, 256>"),
+    (S, "F16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 2, 16, 2, 0, true, 512, true>"),
+    (S, "F16", L.OPF_DCN_STREAM_WIDE_MARGIN, 1, 32, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 2, 16, 4, 0, true, 256, true>"),
+    (S, "F16", 0, 1, 16, 68, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 4, 16, 2, 0, true, 0>"),
+    (S, "F16", 0, 1, 32, 260, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 4, 16, 4, 0, true, 256>"),
+    (S, "F16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 260, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 4, 16, 4, 0, true, 512>"),
+    (S, "BF16", 0, 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 1, 16, 1, 0, true, 0>"),
+    (S, "BF16", 0, 1, 32, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 1, 16, 2, 0, true, 256>"),
+    (S, "BF16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 1, 16, 2, 0, true, 512, true>"),
+    (S, "BF16", L.OPF_DCN_STREAM_WIDE_MARGIN, 1, 32, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 1, 16, 4, 0, true, 256, true>"),
+    (S, "BF16", 0, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 2, 16, 1, 0, true, 0>"),
+    (S, "BF16", 0, 1, 32, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 2, 16, 2, 0, true, 256>"),
+    (S, "BF16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 2, 16, 2, 0, true, 512, true>"),
+    (S, "BF16", L.OPF_DCN_STREAM_WIDE_MARGIN, 1, 32, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 2, 16, 4, 0, true, 256, true>"),
+    (S, "BF16", 0, 1, 16, 68, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 4, 16, 2, 0, true, 0>"),
+    (S, "BF16", 0, 1, 32, 260, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 4, 16, 4, 0, true, 256>"),
+    (S, "BF16", L.OPF_DCN_STREAM_SLOTS512, 1, 32, 260, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 4, 16, 4, 0, true, 512>"),
+    (S, "F16X3", 0, 1, 32, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<x3_t, 1, 16, 2, 0, true, 256>"),
+    (S, "F16X3", L.TUNE_DCN_STREAM_X3_MARGIN3, 1, 32, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<x3_t, 1, 16, 3, 0, true, 256>"),
+    (S, "F16X3", L.TUNE_DCN_STREAM_X3_MARGIN4, 1, 32, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<x3_t, 1, 16, 4, 0, true, 256>"),
+    (S, "F16X3", 0, 1, 32, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<x3_t, 2, 16, 2, 0, true, 256>"),
+    (S, "F16X3", L.TUNE_DCN_STREAM_X3_MARGIN3, 1, 32, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<x3_t, 2, 16, 3, 0, true, 256>"),
+    (S, "F16X3", 0, 1, 128, 128, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<x3_t, 2, 16, 4, 0, true, 256>"),
+    (F, "F16", 0, 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 1, 16, 2, 0, false, 0>"),
+    (F, "F16", 0, 1, 32, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 1, 32, 2, 0, false, 0>"),
+    (F, "F16", 0, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 2, 16, 2, 0, false, 0>"),
+    (F, "F16", 0, 1, 32, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 2, 32, 2, 0, false, 0>"),
+    (F, "F16", 0, 1, 16, 260, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<f16_t, 4, 16, 2, 0, false, 0>"),
+    (F, "F32", 0, 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<float, 1, 16, 2, 0, false, 0>"),
+    (F, "F32", 0, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<float, 2, 16, 2, 0, false, 0>"),
+    (F, "BF16", 0, 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 1, 16, 2, 0, false, 0>"),
+    (F, "BF16", 0, 1, 32, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 1, 32, 2, 0, false, 0>"),
+    (F, "BF16", 0, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 2, 16, 2, 0, false, 0>"),
+    (F, "BF16", 0, 1, 32, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 2, 32, 2, 0, false, 0>"),
+    (F, "BF16", 0, 1, 16, 260, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<unsigned short, 4, 16, 2, 0, false, 0>"),
+    (F, "F16X3", L.TUNE_DCN_FUSED_X3_MARGIN2, 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<x3_t, 1, 16, 2, 0, false, 0>"),
+    (F, "F16X3", 0, 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<x3_t, 1, 16, 4, 0, false, 0>"),
+    (F, "F16X3", 0, 1, 16, 16, 64, 64, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<x3_t, 1, 16, 6, 0, false, 0>"),
+    (F, "F16X3", L.TUNE_DCN_FUSED_X3_MARGIN2, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<x3_t, 2, 16, 2, 0, false, 0>"),
+    (F, "F16X3", 0, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<x3_t, 2, 16, 4, 0, false, 0>"),
+    (F, "F16X3", 0, 1, 16, 36, 64, 64, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn3_kernel<x3_t, 2, 16, 6, 0, false, 0>"),
+    (C2, "F16", 0, 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 1, 4, 0, 1, 2, 1>"),
+    (C2, "F16", 0, 1, 16, 16, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 1, 4, 0, 2, 2, 1>"),
+    (C2, "F16", 0, 64, 16, 16, 24, 40, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 1, 8, 0, 1, 1, 1>"),
+    (C2, "F16", 0, 1, 16, 128, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 1, 8, 0, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(3, 1, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 1, 8, 0, 1, 3, 1>"),
+    (C2, "F16", 0, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 2, 4, 0, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(4, 2, 4), 1, 16, 16, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 2, 4, 0, 2, 1, 1>"),
+    (C2, "F16", 0, 1, 16, 36, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 2, 4, 0, 2, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(5, 2, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 2, 8, 0, 1, 1, 1>"),
+    (C2, "F16", 0, 1, 16, 256, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 2, 8, 0, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(2, 2, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 2, 8, 0, 1, 2, 2>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(3, 2, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 2, 8, 0, 1, 3, 1>"),
+    (C2, "F16", 0, 2, 16, 512, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 4, 16, 0, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(0, 4, 4), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 4, 4, 0, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(3, 4, 4), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 4, 4, 0, 1, 3, 1>"),
+    (C2, "F16", 0, 1, 16, 128, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 4, 4, 0, 2, 1, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(2, 4, 4), 1, 16, 128, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 4, 4, 0, 2, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(5, 4, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 4, 8, 0, 1, 1, 1>"),
+    (C2, "F16", 0, 1, 16, 512, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 4, 8, 0, 1, 2, 1>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(2, 4, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 4, 8, 0, 1, 2, 2>"),
+    (C2, "F16", L.TUNE_CONV_STREAM_TILE(4, 4, 8), 1, 16, 16, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<f16_t, 4, 8, 0, 2, 1, 1>"),
+    (C2, "BF16", 0, 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 1, 4, 0, 1, 2, 1>"),
+    (C2, "BF16", 0, 1, 16, 16, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 1, 4, 0, 2, 2, 1>"),
+    (C2, "BF16", 0, 64, 16, 16, 24, 40, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 1, 8, 0, 1, 1, 1>"),
+    (C2, "BF16", 0, 1, 16, 128, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 1, 8, 0, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(3, 1, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 1, 8, 0, 1, 3, 1>"),
+    (C2, "BF16", 0, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 2, 4, 0, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(4, 2, 4), 1, 16, 16, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 2, 4, 0, 2, 1, 1>"),
+    (C2, "BF16", 0, 1, 16, 36, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 2, 4, 0, 2, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(5, 2, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 2, 8, 0, 1, 1, 1>"),
+    (C2, "BF16", 0, 1, 16, 256, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 2, 8, 0, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(2, 2, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 2, 8, 0, 1, 2, 2>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(3, 2, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 2, 8, 0, 1, 3, 1>"),
+    (C2, "BF16", 0, 2, 16, 512, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 4, 16, 0, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(0, 4, 4), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 4, 4, 0, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(3, 4, 4), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 4, 4, 0, 1, 3, 1>"),
+    (C2, "BF16", 0, 1, 16, 128, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 4, 4, 0, 2, 1, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(2, 4, 4), 1, 16, 128, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 4, 4, 0, 2, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(5, 4, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 4, 8, 0, 1, 1, 1>"),
+    (C2, "BF16", 0, 1, 16, 512, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 4, 8, 0, 1, 2, 1>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(2, 4, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 4, 8, 0, 1, 2, 2>"),
+    (C2, "BF16", L.TUNE_CONV_STREAM_TILE(4, 4, 8), 1, 16, 16, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv2_kernel<unsigned short, 4, 8, 0, 2, 1, 1>"),
+    (C, "F16", 0, 1, 16, 16, 4, 4, 1, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 1, 1, 1, 16, 16, 4, 0>"),
+    (C, "F16", 0, 1, 16, 36, 4, 4, 1, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 1, 1, 2, 16, 16, 4, 0>"),
+    (C, "F16", L.TUNE_CONV_1X1_TILE(2, 16), 1, 64, 36, 4, 4, 1, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 1, 1, 2, 64, 16, 4, 0>"),
+    (C, "F16", 0, 1, 16, 68, 4, 4, 1, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 1, 1, 4, 16, 16, 4, 0>"),
+    (C, "F16", L.TUNE_CONV_1X1_TILE(4, 16), 1, 64, 36, 4, 4, 1, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 1, 1, 4, 64, 16, 4, 0>"),
+    (C, "F16", 0, 1, 16, 16, 4, 4, 1, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 1, 2, 1, 16, 8, 4, 0>"),
+    (C, "F16", 0, 1, 16, 36, 4, 4, 1, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 1, 2, 2, 16, 8, 4, 0>"),
+    (C, "F16", 0, 1, 16, 68, 4, 4, 1, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 1, 2, 4, 16, 8, 4, 0>"),
+    (C, "F16", 0, 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 3, 1, 1, 16, 16, 4, 0>"),
+    (C, "F16", 0, 1, 32, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 3, 1, 1, 32, 16, 4, 0>"),
+    (C, "F16", 0, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 3, 1, 2, 16, 16, 4, 0>"),
+    (C, "F16", 0, 64, 32, 36, 64, 64, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 3, 1, 2, 32, 16, 8, 0>"),
+    (C, "F16", 0, 1, 32, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 3, 1, 2, 32, 8, 4, 0>"),
+    (C, "F16", 0, 1, 16, 68, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 3, 1, 4, 16, 16, 4, 0>"),
+    (C, "F16", 0, 2, 32, 512, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 3, 1, 4, 16, 8, 4, 0>"),
+    (C, "F16", 0, 64, 32, 68, 64, 64, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 3, 1, 4, 32, 16, 8, 0>"),
+    (C, "F16", 0, 1, 16, 16, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 3, 2, 1, 16, 8, 4, 0>"),
+    (C, "F16", 0, 1, 16, 36, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 3, 2, 2, 16, 8, 4, 0>"),
+    (C, "F16", 0, 64, 16, 68, 128, 128, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<f16_t, 3, 2, 4, 16, 8, 4, 0>"),
+    (C, "F32", 0, 1, 16, 16, 4, 4, 1, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<float, 1, 2, 1, 16, 8, 4, 0>"),
+    (C, "F32", 0, 1, 16, 36, 4, 4, 1, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<float, 1, 2, 2, 16, 8, 4, 0>"),
+    (C, "F32", 0, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<float, 3, 1, 2, 16, 16, 4, 0>"),
+    (C, "F32", 0, 1, 16, 16, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<float, 3, 2, 1, 16, 8, 4, 0>"),
+    (C, "F32", 0, 1, 16, 36, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<float, 3, 2, 2, 16, 8, 4, 0>"),
+    (C, "BF16", 0, 1, 16, 16, 4, 4, 1, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 1, 1, 1, 16, 16, 4, 0>"),
+    (C, "BF16", 0, 1, 16, 36, 4, 4, 1, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 1, 1, 2, 16, 16, 4, 0>"),
+    (C, "BF16", L.TUNE_CONV_1X1_TILE(2, 16), 1, 64, 36, 4, 4, 1, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 1, 1, 2, 64, 16, 4, 0>"),
+    (C, "BF16", 0, 1, 16, 68, 4, 4, 1, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 1, 1, 4, 16, 16, 4, 0>"),
+    (C, "BF16", L.TUNE_CONV_1X1_TILE(4, 16), 1, 64, 36, 4, 4, 1, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 1, 1, 4, 64, 16, 4, 0>"),
+    (C, "BF16", 0, 1, 16, 16, 4, 4, 1, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 1, 2, 1, 16, 8, 4, 0>"),
+    (C, "BF16", 0, 1, 16, 36, 4, 4, 1, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 1, 2, 2, 16, 8, 4, 0>"),
+    (C, "BF16", 0, 1, 16, 68, 4, 4, 1, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 1, 2, 4, 16, 8, 4, 0>"),
+    (C, "BF16", 0, 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 3, 1, 1, 16, 16, 4, 0>"),
+    (C, "BF16", 0, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 3, 1, 2, 16, 16, 4, 0>"),
+    (C, "BF16", 0, 64, 32, 36, 64, 64, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 3, 1, 2, 32, 16, 8, 0>"),
+    (C, "BF16", 0, 1, 32, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 3, 1, 2, 32, 8, 4, 0>"),
+    (C, "BF16", 0, 1, 16, 68, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 3, 1, 4, 16, 16, 4, 0>"),
+    (C, "BF16", 0, 2, 32, 512, 128, 128, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 3, 1, 4, 16, 8, 4, 0>"),
+    (C, "BF16", 0, 64, 32, 68, 64, 64, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 3, 1, 4, 32, 16, 8, 0>"),
+    (C, "BF16", 0, 1, 16, 16, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 3, 2, 1, 16, 8, 4, 0>"),
+    (C, "BF16", 0, 1, 16, 36, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 3, 2, 2, 16, 8, 4, 0>"),
+    (C, "BF16", 0, 64, 16, 68, 128, 128, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<unsigned short, 3, 2, 4, 16, 8, 4, 0>"),
+    (C, "F16X3", 0, 1, 16, 36, 4, 4, 1, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 1, 1, 2, 16, 16, 4, 0>"),
+    (C, "F16X3", 0, 1, 16, 16, 4, 4, 1, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 1, 2, 1, 16, 8, 4, 0>"),
+    (C, "F16X3", 0, 1, 16, 36, 4, 4, 1, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 1, 2, 2, 16, 8, 4, 0>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(1, 4, 16), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 3, 1, 1, 16, 16, 4, 0>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(2, 4, 16), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 3, 1, 2, 16, 16, 4, 0>"),
+    (C, "F16X3", 0, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 3, 1, 2, 16, 16, 8, 0>"),
+    (C, "F16X3", 0, 1, 16, 68, 32, 32, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 3, 1, 2, 16, 32, 8, 0>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(2, 4, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 3, 1, 2, 16, 8, 4, 0>"),
+    (C, "F16X3", 0, 1, 16, 68, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 3, 1, 4, 16, 16, 8, 0>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(4, 8, 32), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 3, 1, 4, 16, 32, 8, 0>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(4, 4, 8), 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 3, 1, 4, 16, 8, 4, 0>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(1, 8, 16), 1, 16, 16, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 3, 2, 1, 16, 16, 8, 0>"),
+    (C, "F16X3", 0, 1, 16, 16, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 3, 2, 1, 16, 8, 4, 0>"),
+    (C, "F16X3", 0, 1, 16, 36, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 3, 2, 2, 16, 16, 8, 0>"),
+    (C, "F16X3", L.TUNE_CONV_X3_TILE(2, 4, 8), 1, 16, 16, 4, 4, 3, 2, {"out_mode": L.OUT_NCHW_F32}, "conv_kernel<x3_t, 3, 2, 2, 16, 8, 4, 0>"),
+    (HD, "F16", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, {"heads": (2, 2)}, "heads_kernel<f16_t, 16, 1, false>"),
+    (HD, "F16", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, {"heads": (40, 40)}, "heads_kernel<f16_t, 16, 2, false>"),
+    (HD, "F16", 0, 1, 64, 64, 16, 32, 3, 1, {"heads": (2, 40)}, "heads_kernel<f16_t, 16, 2, true, true>"),
+    (HD, "F16", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, {"heads": (70, 70)}, "heads_kernel<f16_t, 16, 3, false>"),
+    (HD, "F16", 0, 1, 64, 64, 16, 32, 3, 1, {"heads": (2, 70)}, "heads_kernel<f16_t, 16, 3, true, true>"),
+    (HD, "F32", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, {"heads": (40, 40)}, "heads_kernel<float, 8, 2, false>"),
+    (HD, "F32", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, {"heads": (70, 70)}, "heads_kernel<float, 8, 3, false>"),
+    (HD, "BF16", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, {"heads": (40, 40)}, "heads_kernel<unsigned short, 16, 2, false>"),
+    (HD, "BF16", 0, 1, 64, 64, 16, 32, 3, 1, {"heads": (2, 40)}, "heads_kernel<unsigned short, 16, 2, true, true>"),
+    (HD, "BF16", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, {"heads": (70, 70)}, "heads_kernel<unsigned short, 16, 3, false>"),
+    (HD, "F16X3", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, {"heads": (2, 2)}, "heads_kernel<x3_t, 8, 1, false>"),
+    (HD, "F16X3", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, {"heads": (40, 40)}, "heads_kernel<x3_t, 8, 2, false>"),
+    (HD, "F16X3", L.TUNE_HEADS_SEPARATE_BIAS, 1, 64, 64, 16, 32, 3, 1, {"heads": (70, 70)}, "heads_kernel<x3_t, 8, 3, false>"),
+    # the fused residual branch of the fp16 stem (in2 = its 64-channel output); depth2space's [B,2H,2W,C] output
+    (L.OP_DEPTH2SPACE, "F16", 0, 1, 64, 16, 8, 8, 1, 1, {"Ho": 16, "Wo": 16}, "depth2space_kernel<f16_t>"),
+    (L.OP_STEM3, "F16", 0, 1, 3, 32, 16, 16, 3, 2, {"in2_cs": 64}, "stem3_kernel<f16_t, true>"),
+]
+DISPATCH_EXTRA_WITH = [
+    # "updcn": H3D_OP_UPDCN_F16's descriptor behind in2 (the value is its skip stride); Ho / Wo = f * the input's
+    (F16K, "BF16", L.TUNE_DCN_F16_ONE_WG_PER_CU, 1, 64, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn4_kernel<1, 0, 0, 0>"),
+    (F16K, "BF16", 0, 1, 64, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn4_kernel<1, 0, 1, 0>"),
+    (L.OP_UPDCN_F16, "BF16", 0, 1, 64, 16, 4, 4, 3, 2, {"updcn": 64, "Ho": 8, "Wo": 8, "out_mode": L.OUT_NCHW_F32}, "dcn4_kernel<1, 0, 1, 1>"),
+    (L.OP_UPDCN_F16, "BF16", 0, 1, 64, 16, 4, 4, 3, 2, {"updcn": 64, "Ho": 8, "Wo": 8}, "dcn4_kernel<1, 1, 1, 1>"),
+    (F16K, "BF16", L.TUNE_DCN_F16_ONE_WG_PER_CU, 1, 64, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn4_kernel<2, 0, 0, 0>"),
+    (F16K, "BF16", 0, 1, 64, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn4_kernel<2, 0, 1, 0>"),
+    (L.OP_UPDCN_F16, "BF16", 0, 1, 64, 36, 4, 4, 3, 2, {"updcn": 64, "Ho": 8, "Wo": 8, "out_mode": L.OUT_NCHW_F32}, "dcn4_kernel<2, 0, 1, 1>"),
+    (L.OP_UPDCN_F16, "BF16", 0, 1, 64, 36, 4, 4, 3, 2, {"updcn": 64, "Ho": 8, "Wo": 8}, "dcn4_kernel<2, 1, 1, 1>"),
+    (L.OP_UPDCN_F16, "BF16", 0, 1, 64, 64, 4, 4, 3, 2, {"updcn": 64, "Ho": 8, "Wo": 8}, "dcn4_kernel<2, 2, 1, 1>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5, 1, 16, 16, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn5_kernel<1, 2, 0, 256>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5, 1, 16, 36, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn5_kernel<2, 2, 0, 256>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 16, 68, 4, 4, 3, 1, {"out_mode": L.OUT_NCHW_F32}, "dcn5_kernel<4, 4, 0, 256>"),
 ]
 DISPATCH_EXTRA = [
     (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5, 2, 128, 64, 24, 40, 3, 1, "dcn5_kernel<2, 2, 2, 256>"),
@@ -408,6 +793,27 @@ DISPATCH_EXTRA = [
     (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_DCN5_XP(2), 2, 128, 64, 24, 40, 3, 1, "dcn5_kernel<2, 2, 2, 256, 2>"),
     (F16K, "BF16", 0, 1, 64, 64, 24, 40, 3, 1, "dcn4_kernel<2, 2, 1, 0>"),
     (F16K, "BF16", L.TUNE_DCN_F16_ONE_WG_PER_CU, 1, 64, 64, 24, 40, 3, 1, "dcn4_kernel<2, 2, 0, 0>"),
+    # every other instantiation of csrc/dcn1.hip, dcn4.hip and dcn5.hip an op reaches, names from the parent commit's `make EXTRA=1` library
+    (F16K, "BF16", L.TUNE_DCN_F16_ONE_WG_PER_CU, 1, 64, 16, 4, 4, 3, 1, "dcn4_kernel<1, 1, 0, 0>"),
+    (F16K, "BF16", 0, 1, 64, 16, 4, 4, 3, 1, "dcn4_kernel<1, 1, 1, 0>"),
+    (F16K, "BF16", L.TUNE_DCN_F16_ONE_WG_PER_CU, 1, 64, 36, 4, 4, 3, 1, "dcn4_kernel<2, 1, 0, 0>"),
+    (F16K, "BF16", 0, 1, 64, 36, 4, 4, 3, 1, "dcn4_kernel<2, 1, 1, 0>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5, 1, 16, 36, 4, 4, 3, 1, "dcn5_kernel<2, 2, 1, 256>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_DCN5_XP(12), 1, 16, 64, 4, 4, 3, 1, "dcn5_kernel<2, 2, 2, 256, 12>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_DCN5_XP(14), 1, 16, 64, 4, 4, 3, 1, "dcn5_kernel<2, 2, 2, 256, 14>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_DCN5_XP(17), 1, 16, 64, 4, 4, 3, 1, "dcn5_kernel<2, 2, 2, 256, 17>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_DCN5_XP(1), 1, 16, 64, 4, 4, 3, 1, "dcn5_kernel<2, 2, 2, 256, 1>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_DCN5_XP(3), 1, 16, 64, 4, 4, 3, 1, "dcn5_kernel<2, 2, 2, 256, 3>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_DCN5_XP(4), 1, 16, 64, 4, 4, 3, 1, "dcn5_kernel<2, 2, 2, 256, 4>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_DCN5_XP(8), 1, 16, 64, 4, 4, 3, 1, "dcn5_kernel<2, 2, 2, 256, 8>"),
+    (S, "F16", L.TUNE_DCN_STREAM_F16_DCN5 | L.TUNE_DCN_STREAM_FORCE_WIDE_WG, 1, 16, 68, 4, 4, 3, 1, "dcn5_kernel<4, 4, 1, 256>"),
+    (L.OP_DCN_V1, "F32", 0, 1, 16, 16, 4, 4, 3, 1, "dcn_kernel<float, 1, 16>"),
+    (L.OP_DCN_V1, "F32", 0, 1, 16, 36, 4, 4, 3, 1, "dcn_kernel<float, 2, 16>"),
+    (L.OP_DCN_V1, "BF16", 0, 1, 16, 16, 4, 4, 3, 1, "dcn_kernel<unsigned short, 1, 16>"),
+    (L.OP_DCN_V1, "BF16", 0, 1, 32, 16, 4, 4, 3, 1, "dcn_kernel<unsigned short, 1, 32>"),
+    (L.OP_DCN_V1, "BF16", 0, 1, 16, 36, 4, 4, 3, 1, "dcn_kernel<unsigned short, 2, 16>"),
+    (L.OP_DCN_V1, "BF16", 0, 1, 32, 36, 4, 4, 3, 1, "dcn_kernel<unsigned short, 2, 32>"),
+    (L.OP_DCN_V1, "BF16", 0, 1, 16, 68, 4, 4, 3, 1, "dcn_kernel<unsigned short, 4, 16>"),
 ]
 
 
@@ -418,4 +824,9 @@ def test_flag_words_select_the_kernels_they_always_did():
     extra = DISPATCH_EXTRA if _lib.has_extra() else [c[:-1] + (-4,) for c in DISPATCH_EXTRA]
     for case in DISPATCH + extra:
         rc = lib.h3d_op_kernel_name(ctypes.byref(_dry_op(*case[:-1], keep)), buf, 200)
+        assert (buf.value.decode() if rc == 0 else rc) == case[-1], (case, rc, lib.h3d_last_error())
+    extra_with = DISPATCH_EXTRA_WITH if _lib.has_extra() else [c[:-1] + (-4,) for c in DISPATCH_EXTRA_WITH]
+    for case in DISPATCH_WITH + extra_with:
+        op = _dry_op_with(case[:-2], case[-2], keep)
+        rc = lib.h3d_op_kernel_name(ctypes.byref(op), buf, 200)
         assert (buf.value.decode() if rc == 0 else rc) == case[-1], (case, rc, lib.h3d_last_error())
