@@ -1,0 +1,272 @@
+"""Integer-lattice operands and exact references for the forward matrix-core ops (conv, gemm1, conv2, stems, heads, up-sample + add,
+fused DeformConv).  CPU only: nothing here loads the HIP library.
+
+Why a lattice: with x in {-3..3} and w in {-1, 0, 1} * 2^e every product is exact in bf16, fp16, fp32 and as an f16x3 hi/lo split
+(lo = 0; the filter pre-scale is a power of two), every fp32 partial sum is an integer (times a fixed power of two) far below 2^24,
+so the accumulation is exact in ANY order, and the only rounding left is the one round-to-nearest-even into the storage type where the
+kernel stores.  The comparison is then torch.equal(kernel, round(fp64 reference)): a dropped, duplicated or misplaced tap, a wrong halo
+pixel or a channel read from its neighbour changes most of the pixels it touches instead of hiding under a 2^-8 * max|ref| tolerance.
+
+tests/test_oracle_lattice.py pins the conditions above for every case tests/test_gpu_lattice.py runs."""
+import functools
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+import h3d_amd  # noqa: F401
+from h3d_amd import synth
+
+TD = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "f16x3": torch.float32}
+EXACT_RANGE = {"bf16": 256.0, "f16": 2048.0}        # integers up to here are representable (8 / 11 significand bits)
+RELU_SHIFT_SIGMAS = 0.8                             # bias shift in standard deviations: a normal output clips Phi(-0.8) = 21 %
+RELU_CLIP = (0.05, 0.40)
+MAX_OUTSIDE = 0.02
+W_DENSITY = 2.0 / 3.0
+W_DENSITY_K = 1536.0                                # contractions longer than 2304 get sparser filters: density = min(2/3, 1536 / K)
+
+
+def lowp_round(t, dtype):
+    """One round-to-nearest-even into the plan's storage type (f32 / f16x3 store fp32: unchanged)."""
+    t = t.float()
+    return t if dtype in ("f32", "f16x3") else t.to(TD[dtype]).float()
+
+
+def _ints(key, shape, lo, hi):
+    """Uniform integers in [lo, hi], a pure function of (key, shape)."""
+    n = hi - lo + 1
+    u = synth.uniform01(key, tuple(shape))
+    return torch.from_numpy((np.minimum(np.floor(u * n), n - 1) + lo).astype(np.float32))
+
+
+def lattice_x(shape, key="lx"):
+    return _ints(key, shape, -3, 3)
+
+
+def lattice_w(shape, key="lw", exp=0, density=None):
+    """Filters in {-1, 0, 1} * 2^exp; `density` = share of non-zero taps (default: 2/3, less for contractions beyond 2304 terms so that
+    the outputs stay inside the exactly representable range of bf16)."""
+    K = int(np.prod(shape[1:]))
+    d = min(W_DENSITY, W_DENSITY_K / K) if density is None else density
+    u = torch.from_numpy(synth.uniform01(key, tuple(shape)))
+    w = torch.zeros(tuple(shape), dtype=torch.float64)
+    w[u < d / 2] = -1.0
+    w[u >= 1.0 - d / 2] = 1.0
+    return (w * 2.0 ** exp).float()
+
+
+def lattice_bias(co, key="lb"):
+    return _ints(key, (co,), -4, 4)
+
+
+def lattice_res(shape, key="lr"):
+    return _ints(key, shape, -8, 8)
+
+
+def lattice_image(shape, key="limg"):
+    """The stems' fp32 image on the grid k/256 in [-2, 2): 9 significand bits, so the kernel's own conversion to bf16 rounds (ties
+    included); exact in fp16 and as an f16x3 split."""
+    return _ints(key, shape, -512, 511) / 256.0
+
+
+def lattice_up_w(shape, key="lup"):
+    """Depthwise transposed-conv (bilinear-like) weights on the grid k/8 in [0, 1]."""
+    return _ints(key, shape, 0, 8) / 8.0
+
+
+def pre_conv(x, w, b=None, stride=1, pad=0, res=None):
+    """fp64 conv + bias + residual, before ReLU and rounding."""
+    y = F.conv2d(x.double(), w.double(), None if b is None else b.double(), stride, pad)
+    return y if res is None else y + res.double()
+
+
+def relu_shift(pre, sigmas=RELU_SHIFT_SIGMAS):
+    """Integer bias shift that moves a zero-centred output up by 0.8 of the reference's own standard deviation, so that ReLU clips about
+    a fifth of the outputs instead of half of them."""
+    return float(int(round(sigmas * float(pre.double().std()))))
+
+
+def exact_conv(x, w, b=None, stride=1, pad=0, relu=False, res=None, dtype="f32"):
+    """The op's result as the kernel must store it: fp64 conv + bias + residual + ReLU, rounded ONCE to the plan's storage type."""
+    y = pre_conv(x, w, b, stride, pad, res)
+    return lowp_round(F.relu(y) if relu else y, dtype)
+
+
+def conditions(x, w, b=None, stride=1, pad=0, res=None, unit=1.0):
+    """What makes a zero tolerance legitimate for one contraction, measured on the CPU:
+         fp32_exact   fp32 F.conv2d (+ bias, residual) equals the fp64 result bit for bit
+         max_units    max over outputs of (sum |x| |w| + |b| + |res|) / unit -- every fp32 partial sum, in any order, is an integer
+                      number of `unit`s of at most this size (must stay below 2^24)
+         outside      {dtype: share of pre-rounding outputs beyond the exactly representable range}
+         pre          the fp64 result (before ReLU)"""
+    pre = pre_conv(x, w, b, stride, pad, res)
+    y32 = F.conv2d(x.float(), w.float(), None if b is None else b.float(), stride, pad)
+    if res is not None:
+        y32 = y32 + res.float()
+    bound = F.conv2d(x.double().abs(), w.double().abs(), None if b is None else b.double().abs(), stride, pad)
+    if res is not None:
+        bound = bound + res.double().abs()
+    units = pre / unit
+    return {"fp32_exact": torch.equal(y32.double(), pre), "max_units": float(bound.max()) / unit,
+            "on_grid": bool((units == units.round()).all()),
+            "outside": {d: float((pre.abs() > r * unit).double().mean()) for d, r in EXACT_RANGE.items()}, "pre": pre}
+
+
+def clipped_share(pre):
+    return float((pre <= 0).double().mean())
+
+
+# ---- operands per family ---------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def conv_operands(B, Ci, Co, H, W, k, stride, relu, use_res):
+    """(x, w, b, res) of one conv case; with ReLU the bias carries the shift of `relu_shift`.  Identical for every arithmetic: the
+    lattice is exact in all of them."""
+    x = lattice_x((B, Ci, H, W))
+    w = lattice_w((Co, Ci, k, k))
+    b = lattice_bias(Co)
+    Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
+    res = lattice_res((B, Co, Ho, Wo)) if use_res else None
+    if relu:
+        b = b + relu_shift(pre_conv(x, w, b, stride, k // 2, res))
+    return x, w, b, res
+
+
+@functools.lru_cache(maxsize=None)
+def stem_operands(B, Co, H, W, stride):
+    """(image on k/256, w [Co,3,7,7], b) of a 7x7 stem + ReLU."""
+    x = lattice_image((B, 3, H, W))
+    w = lattice_w((Co, 3, 7, 7), "lws")
+    b = lattice_bias(Co, "lbs")
+    return x, w, b + relu_shift(pre_conv(x, w, b, stride, 3))
+
+
+def exact_stem(x, w, b, stride, dtype):
+    """7x7 stem + ReLU: the kernel converts the fp32 image to the plan's 2-byte type itself (round to nearest even)."""
+    return exact_conv(lowp_round(x, dtype), w, b, stride, 3, True, None, dtype)
+
+
+STEM3_LAYERS = (("base.base_layer", 16, 3, 7, 1, 0), ("base.level0", 16, 16, 3, 1, -3), ("base.level1", 32, 16, 3, 2, -3))
+#                 name, Cout, Cin, k, stride, filter exponent: 2^-3 keeps level0 / level1 near the magnitude of the layer before
+
+
+def identity_bn(prefix, b):
+    """Eval BatchNorm that only adds `b`: gamma 1, mean 0, var 1 - eps (tests/gpu_helpers._dcn_sd)."""
+    co = b.shape[0]
+    return {prefix + ".weight": torch.ones(co), prefix + ".bias": b.clone(), prefix + ".running_mean": torch.zeros(co),
+            prefix + ".running_var": torch.full((co,), 1.0 - 1e-5)}
+
+
+@functools.lru_cache(maxsize=None)
+def stem3_operands(B, H, W):
+    """(image, state dict of the three conv + BatchNorm layers, [(w, b, k, stride)]) of the fused stem.  The bias shifts come from the
+    unrounded (fp32-plan) chain; the 2-byte chains clip the same share within a fraction of a percent (test_oracle_lattice)."""
+    x = lattice_image((B, 3, H, W))
+    sd, layers, t = {}, [], x.double()
+    for name, co, ci, k, s, e in STEM3_LAYERS:
+        w = lattice_w((co, ci, k, k), name + "w", e)
+        b = lattice_bias(co, name + "b")
+        b = b + relu_shift(pre_conv(t, w, b, s, k // 2))
+        t = F.relu(pre_conv(t, w, b, s, k // 2))
+        sd[name + ".0.weight"] = w
+        sd.update(identity_bn(name + ".1", b))
+        layers.append((w, b, k, s))
+    return x, sd, layers
+
+
+def stem3_chain(x, layers, dtype):
+    """[(input as the layer reads it, w, b, k, stride)] of the fused stem: the 2-byte plans round the image and both intermediates
+    to the storage type (csrc/stem3.hip keeps them in LDS as bf16 / fp16); fp32 and f16x3 plans round nothing."""
+    t, out = lowp_round(x, dtype), []
+    for w, b, k, s in layers:
+        out.append((t, w, b, k, s))
+        t = exact_conv(t, w, b, s, k // 2, True, None, dtype)
+    return out, t
+
+
+def exact_stem3(x, layers, dtype):
+    return stem3_chain(x, layers, dtype)[1]
+
+
+HEADS = {"hm": 1, "hps": 34, "pose": 72, "wh": 2}
+
+
+@functools.lru_cache(maxsize=None)
+def heads_operands(B, H, W):
+    """(feature map, state dict) of the fused heads: Conv3x3(64 -> 256) + bias + ReLU -> Conv1x1(256 -> C) + bias per head."""
+    x = lattice_x((B, 64, H, W), "lfeat")
+    sd = {}
+    for h, c in HEADS.items():
+        w1 = lattice_w((256, 64, 3, 3), h + "w1")
+        b1 = lattice_bias(256, h + "b1")
+        sd[h + ".0.weight"] = w1
+        sd[h + ".0.bias"] = b1 + relu_shift(pre_conv(x, w1, b1, 1, 1))
+        sd[h + ".2.weight"] = lattice_w((c, 256, 1, 1), h + "w2")
+        sd[h + ".2.bias"] = lattice_bias(c, h + "b2")
+    return x, sd
+
+
+def heads_intermediate(x, sd, h, dtype):
+    """The 256-channel intermediate as the 1x1 conv reads it: rounded to the storage type in bf16 / fp16 plans only (csrc/heads.hip
+    hands it back to the matrix core in the plan's operand type; f32 / f16x3 keep fp32)."""
+    return exact_conv(x, sd[h + ".0.weight"], sd[h + ".0.bias"], 1, 1, True, None, dtype)
+
+
+def exact_head(x, sd, h, dtype):
+    """fp32 output map of head `h` (never rounded: the heads write fp32 in every plan)."""
+    return pre_conv(heads_intermediate(x, sd, h, dtype), sd[h + ".2.weight"], sd[h + ".2.bias"]).float()
+
+
+@functools.lru_cache(maxsize=None)
+def upadd_operands(B, C, h, w, f):
+    x = lattice_x((B, C, h, w), "lu")
+    skip = lattice_res((B, C, h * f, w * f), "ls")
+    return x, skip, lattice_up_w((C, 1, 2 * f, 2 * f))
+
+
+def exact_upadd(x, skip, w, f, dtype):
+    y = F.conv_transpose2d(x.double(), w.double(), None, stride=f, padding=f // 2, groups=x.shape[1]) + skip.double()
+    return lowp_round(y, dtype)
+
+
+# ---- fused DeformConv with integer offsets ------------------------------------------------------------------------------------------
+DCN_OFFSET_SCALES = (1, 2, 4)
+DCN_RELU_SHIFT_SIGMAS = 1.3                         # masked-off taps and samples outside the image already hide a tap at some pixels: clip 10 %, not 21 %
+DCN_MASK_ON, DCN_MASK_OFF = 32.0, -128.0           # sigmoid(32) rounds to exactly 1 in fp32, sigmoid(-128) is exactly 0
+
+
+@functools.lru_cache(maxsize=None)
+def dcn_operands(B, Ci, Co, H, W):
+    """(x, w, b, wo, bo) of a fused DeformConv whose offsets are integers that differ from pixel to pixel.
+    Offset rows of conv_offset_mask: ONE non-zero tap each, the centre tap of one input channel, times 1, 2 or 4 -- the offset of a
+    pixel is that channel's own value there: an integer in +-3, +-6 or +-12 (inside the apron, in patch slots, in pass 2, outside the
+    image).  Mask rows: zero filters, bias +32 or -128 per tap, so sigmoid is exactly 1 or 0.  The bilinear weights are then 0 or 1."""
+    x = lattice_x((B, Ci, H, W), "ldx")
+    w = lattice_w((Co, Ci, 3, 3), "ldw")
+    b = lattice_bias(Co, "ldb")
+    wo = torch.zeros(27, Ci, 3, 3)
+    bo = torch.zeros(27)
+    ch = _ints("ldc", (18,), 0, Ci - 1).long()
+    sc = _ints("lds", (18,), 0, len(DCN_OFFSET_SCALES) - 1).long()
+    sg = _ints("ldg", (18,), 0, 1)
+    for r in range(18):
+        scale = 1 if r in (8, 9) else DCN_OFFSET_SCALES[sc[r]]          # (the centre tap moves by at most 3: most of its samples stay in the image)
+        wo[r, ch[r], 1, 1] = float(scale) * (1.0 if sg[r] else -1.0)
+    on = _ints("ldm", (9,), 0, 3)                   # three taps in four are on
+    bo[18:] = torch.where(on > 0, torch.tensor(DCN_MASK_ON), torch.tensor(DCN_MASK_OFF))
+    bo[18 + 4] = DCN_MASK_ON                        # (the centre tap always)
+    return x, w, b + relu_shift(dcn_pre(x, w, b, wo, bo), DCN_RELU_SHIFT_SIGMAS), wo, bo     # DCN layers end in BatchNorm + ReLU
+
+
+def dcn_offsets(x, wo, bo):
+    """fp64 conv_offset_mask output [B,27,H,W]."""
+    return F.conv2d(x.double(), wo.double(), bo.double(), 1, 1)
+
+
+def dcn_pre(x, w, b, wo, bo, acc_dtype=torch.float64):
+    """DeformConv output before ReLU from the oracle (oracle/dcn.py), as tests/gpu_helpers.dcn_fused_reference; acc_dtype=None: the
+    contraction in fp32."""
+    from oracle import dcn as odcn
+    om = dcn_offsets(x, wo, bo).float()
+    o1, o2, mask = torch.chunk(om, 3, dim=1)
+    return odcn.dcn_v2_forward(x, w, b, torch.cat((o1, o2), dim=1).contiguous(), torch.sigmoid(mask).contiguous(), 3, 3, 1, 1, 1, 1, 1, 1, 1,
+                               acc_dtype=acc_dtype).double()
