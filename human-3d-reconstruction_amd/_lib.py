@@ -221,6 +221,16 @@ def check(rc, what):
         raise RuntimeError("%s failed (%s error): %s" % (what, _ERR_NAMES.get(rc, rc), msg))
 
 
+def workspace(size_fn, *args, device, min_bytes=0, what=None):
+    """A uint8 workspace on `device` of what `size_fn(*args, &bytes)` asks for, at least `min_bytes`; None when that is nothing.
+    `what` names the call in an error (default: the function's name)."""
+    import torch
+    n = ctypes.c_size_t(0)
+    check(size_fn(*args, ctypes.byref(n)), what or size_fn.__name__)
+    nbytes = max(n.value, min_bytes)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
 def stream_ptr():
     """Raw hipStream_t of torch's current stream (the reference launches on the current
     stream too, dcn_v2_cuda.cu:108)."""

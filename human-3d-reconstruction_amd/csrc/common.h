@@ -51,11 +51,27 @@ unsigned long long *h3d_stamp_buffer();     // device buffer [65536][H3D_NSTAMP]
         h3d_set_error(__VA_ARGS__); \
         return (code);             \
     } while (0)
-#define H3D_CHECK_LAUNCH(name)                                                          \
-    do {                                                                                \
-        hipError_t e_ = hipGetLastError();                                              \
-        if (e_ != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "%s: %s", name, hipGetErrorString(e_)); \
+// a step of an entry point that returns an H3D_* code (a launch, another entry point): leave with it unless it is H3D_OK
+#define H3D_TRY(call)                     \
+    do {                                  \
+        const int rc_ = (call);           \
+        if (rc_ != H3D_OK) return rc_;    \
     } while (0)
+
+// ---- workspace layout (host) ------------------------------------------------------------------
+// A caller-provided workspace is cut into regions by ONE function per entry point, which returns the regions' offsets and `total`: the
+// *_workspace_bytes function reports `total`, the entry point addresses `ws + L.region`, so size and carving cannot disagree.
+static inline size_t h3d_align256(size_t x) { return (x + 255) & ~(size_t)255; }
+struct h3d_ws_layout {
+    size_t total = 0;
+    // the offset of a region of `bytes`, which ends on a multiple of `align` (a power of two; the workspace itself is 256-byte aligned)
+    size_t take(size_t bytes, size_t align = 256)
+    {
+        const size_t at = total;
+        total += (bytes + align - 1) & ~(align - 1);
+        return at;
+    }
+};
 
 // ---- launch dispatch (host) -------------------------------------------------------------------
 // A launcher turns what it knows at run time (the op's dtype, an epilogue mode, a boolean variant) into template arguments with the

@@ -136,9 +136,7 @@ extern "C" int h3d_dcn_offset_mask(const float *input, const float *off_weight, 
     a.Wo = (W + 2 * pad_w - kernel_w) / stride_w + 1;
     if (a.Ho <= 0 || a.Wo <= 0) H3D_FAIL(H3D_ERR_SHAPE, "dcn_offset_mask: empty output %dx%d", a.Ho, a.Wo);
     dim3 grid(cdiv(a.Ho * a.Wo, 64), cdiv(a.Cout, 64), B);
-    hipLaunchKernelGGL(dcn_nchw_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    H3D_CHECK_LAUNCH("dcn_nchw_kernel");
-    return H3D_OK;
+    return h3d_launch({"dcn_nchw_kernel"}, dcn_nchw_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
 }
 
 extern "C" int h3d_dcn_v2_forward(const float *input, const float *weight, const float *bias, const float *offset,
@@ -160,9 +158,7 @@ extern "C" int h3d_dcn_v2_forward(const float *input, const float *weight, const
     a.Wo = (W + 2 * pad_w - (dilation_w * (kernel_w - 1) + 1)) / stride_w + 1;
     if (a.Ho <= 0 || a.Wo <= 0) H3D_FAIL(H3D_ERR_SHAPE, "dcn_v2_forward: empty output %dx%d", a.Ho, a.Wo);
     dim3 grid(cdiv(a.Ho * a.Wo, 64), cdiv(Cout, 64), B);
-    hipLaunchKernelGGL(dcn_nchw_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
-    H3D_CHECK_LAUNCH("dcn_nchw_kernel");
-    return H3D_OK;
+    return h3d_launch({"dcn_nchw_kernel"}, dcn_nchw_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
 }
 
 
@@ -174,15 +170,19 @@ extern "C" int h3d_dcn_v2_forward(const float *input, const float *weight, const
 // (LDS apron gather, sampling geometry once per pixel instead of once per pixel AND channel as
 // dcn_v2_im2col_cuda.cu:170-172 does, exact fmaf chains on v_mfma_f32_32x32x2_f32), which writes the NCHW output itself.
 int h3d_launch_dcn2(const h3d_op &op, hipStream_t st);
-static size_t ws_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // max |v| over the FINITE values a wave holds, as the bit pattern of the float (monotonic for non-negative values), into *out with one
 // atomicMax per wave -- skipped when the word already holds as much (it only grows: thousands of waves contending for one address cost
 // more than the reads they reduce); *out was zeroed in front (stream ordered).  Every lane of the wave must call it.
-__device__ __forceinline__ void dcn_absmax_commit(unsigned *out, unsigned m)
+__device__ __forceinline__ unsigned dcn_wave_max(unsigned m)
 {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, d));
+    return m;
+}
+__device__ __forceinline__ void dcn_absmax_commit(unsigned *out, unsigned m)
+{
+    m = dcn_wave_max(m);
     if ((threadIdx.x & 63) == 0 && m && m > __atomic_load_n(out, __ATOMIC_RELAXED)) atomicMax(out, m);
 }
 __device__ __forceinline__ unsigned dcn_finite_abs_bits(float v)
@@ -208,8 +208,7 @@ __global__ __launch_bounds__(256) void dcn_absmax_kernel(const float *__restrict
     }
     // one atomic per workgroup: the workgroups finish together, and a word thousands of waves update at once costs more than the read
     __shared__ unsigned s_m[4];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, d));
+    m = dcn_wave_max(m);
     if ((threadIdx.x & 63) == 0) s_m[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -223,10 +222,8 @@ static int dcn_absmax(const float *p, size_t n, unsigned *out, hipStream_t st)
     const bool vec = ((uintptr_t)p & 15) == 0 && n % 4 == 0;
     const size_t items = vec ? n / 4 : n;
     const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((items + 4 * 256 - 1) / (4 * 256), 1), 512);
-    if (vec) hipLaunchKernelGGL(dcn_absmax_kernel<true>, dim3(blocks), dim3(256), 0, st, p, n, out);
-    else hipLaunchKernelGGL(dcn_absmax_kernel<false>, dim3(blocks), dim3(256), 0, st, p, n, out);
-    H3D_CHECK_LAUNCH("dcn_absmax_kernel");
-    return H3D_OK;
+    if (vec) return h3d_launch({"dcn_absmax_kernel", true}, dcn_absmax_kernel<true>, dim3(blocks), dim3(256), 0, st, p, n, out);
+    return h3d_launch({"dcn_absmax_kernel", false}, dcn_absmax_kernel<false>, dim3(blocks), dim3(256), 0, st, p, n, out);
 }
 
 // mmax != nullptr: max |mask| over the finite mask values as well (the activation scale's headroom for a caller's mask outside [0, 1])
@@ -257,18 +254,15 @@ __global__ void dcn_om_pack_kernel(const float *__restrict__ off, const float *_
 
 // The offset / mask rows of the fp32 fast path, followed by the two activation maxima (max |x|, max |mask|) the f16x3 kernel scales by
 // (H3D_OPF_DCN_ACT_MAXIMA in csrc/dcn2.hip): zeroed, then filled by dcn_absmax and the om pack kernel -- all on the caller's stream.
-static size_t dcn_om_bytes(size_t px) { return ws_align(px * 32 * 4 + 16); }
+static size_t dcn_om_bytes(size_t px) { return px * 32 * 4 + 16; }
 static int dcn_om_pack(const float *x, size_t nx, const float *offset, const float *mask, float *om, int HW, size_t px, bool f16x3, hipStream_t st)
 {
     unsigned *amax = f16x3 ? (unsigned *)(om + px * 32) : nullptr;
     if (amax) {
         if (hipMemsetAsync(amax, 0, 16, st) != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "dcn_v2_forward: memset");
-        int rc = dcn_absmax(x, nx, amax, st);
-        if (rc != H3D_OK) return rc;
+        H3D_TRY(dcn_absmax(x, nx, amax, st));
     }
-    hipLaunchKernelGGL(dcn_om_pack_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, offset, mask, om, HW, px, amax ? amax + 1 : nullptr);
-    H3D_CHECK_LAUNCH("dcn_om_pack_kernel");
-    return H3D_OK;
+    return h3d_launch({"dcn_om_pack_kernel"}, dcn_om_pack_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, st, offset, mask, om, HW, px, amax ? amax + 1 : nullptr);
 }
 
 // max |filter| of an fp32 pack, as the bit pattern of the float (monotonic for non-negative values; a NaN sorts above everything and
@@ -277,42 +271,38 @@ static int dcn_om_pack(const float *x, size_t nx, const float *offset, const flo
 // (H3D_DCN_AUX_BYTES behind the bias of an fp32 pack, word 0 = max |filter| bits: include/h3d.h)
 __device__ __forceinline__ void dcn_wmax_accumulate(unsigned *wmax, float v)
 {
-    unsigned m = __float_as_uint(fabsf(v));
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, d));
+    const unsigned m = dcn_wave_max(__float_as_uint(fabsf(v)));
     if ((threadIdx.x & 63) == 0 && m) atomicMax(wmax, m);
 }
 
-__global__ void dcn_w_pack_kernel(const float *__restrict__ w, const float *__restrict__ bias, float *__restrict__ wp, float *__restrict__ bp,
-                                  int Cout, int C, int rows, unsigned *__restrict__ wmax)
+// element i of a pack [rows][9][C] <- w [Cout][C][3][3]: i = (o * 9 + tap) * C + c; rows beyond Cout are zero
+struct DcnPackIndex { int o, tap, c; };
+__device__ __forceinline__ DcnPackIndex dcn_pack_index(size_t i, int C)
 {
-    // wp [rows][9][C] <- w [Cout][C][3][3]; rows beyond Cout are zero
+    return {(int)(i / ((size_t)9 * C)), (int)((i / C) % 9), (int)(i % C)};
+}
+__device__ __forceinline__ float dcn_pack_source(const float *__restrict__ w, int nout, int C, const DcnPackIndex &k)
+{
+    return k.o < nout ? w[((size_t)k.o * C + k.c) * 9 + k.tap] : 0.f;
+}
+
+// WT = float: the fp32 pack, max |filter| into *wmax (zeroed in front).  WT = f16_t: the filter format of the bf16 DeformConv kernels
+// (csrc/dcn2.hip), clamped to the fp16 range, no maximum.  VALIDATED: a pack that checks on the device whether it is stale (below).
+template <typename WT, bool VALIDATED>
+__global__ void dcn_w_pack_kernel(const float *__restrict__ w, const float *__restrict__ bias, WT *__restrict__ wp, float *__restrict__ bp, int Cout, int C,
+                                  int rows, const unsigned long long *__restrict__ state, unsigned *__restrict__ wmax)
+{
+    if constexpr (VALIDATED)
+        if (state[0] == state[1]) return;                  // the packed image was built from exactly these bytes
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     const size_t total = (size_t)rows * 9 * C;
     if (i < (size_t)rows) bp[i] = i < (size_t)Cout ? bias[i] : 0.f;
     float v = 0.f;
     if (i < total) {
-        const int c = (int)(i % C);
-        const int tap = (int)((i / C) % 9);
-        const int o = (int)(i / ((size_t)9 * C));
-        v = o < Cout ? w[((size_t)o * C + c) * 9 + tap] : 0.f;
-        wp[i] = v;
+        v = dcn_pack_source(w, Cout, C, dcn_pack_index(i, C));
+        wp[i] = ET<WT>::from_f32(v);
     }
-    dcn_wmax_accumulate(wmax, v);          // (every lane of the wave takes part in the shuffles)
-}
-
-// fp16 twin of dcn_w_pack_kernel: the filter format of the bf16 DeformConv kernels (csrc/dcn2.hip)
-__global__ void dcn_w_pack_f16_kernel(const float *__restrict__ w, const float *__restrict__ bias, _Float16 *__restrict__ wp, float *__restrict__ bp,
-                                      int Cout, int C, int rows)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t total = (size_t)rows * 9 * C;
-    if (i < (size_t)rows) bp[i] = i < (size_t)Cout ? bias[i] : 0.f;
-    if (i >= total) return;
-    const int c = (int)(i % C);
-    const int tap = (int)((i / C) % 9);
-    const int o = (int)(i / ((size_t)9 * C));
-    wp[i] = (_Float16)(o < Cout ? __builtin_amdgcn_fmed3f(w[((size_t)o * C + c) * 9 + tap], -65504.f, 65504.f) : 0.f);
+    if constexpr (std::is_same_v<WT, float>) dcn_wmax_accumulate(wmax, v);          // (every lane of the wave takes part in the shuffles)
 }
 
 // Layout of a DeformConv filter pack (h3d_dcn_v2_pack_weights[_cached]; the tail of h3d_dcn_v2_forward_ws's workspace), in bytes:
@@ -321,16 +311,48 @@ __global__ void dcn_w_pack_f16_kernel(const float *__restrict__ w, const float *
 struct DcnPackLayout {
     int rows;
     size_t wtotal;                  // filter elements
-    size_t bias, aux, bytes;
+    size_t bias, aux, bytes;        // (the filters are at offset 0)
 };
 static DcnPackLayout dcn_pack_layout(int Cout, int C, int dtype)
 {
     DcnPackLayout L;
     L.rows = (Cout + 127) / 128 * 128;
     L.wtotal = (size_t)L.rows * 9 * C;
-    L.bias = ws_align(L.wtotal * (dtype == H3D_F32 ? 4 : 2));
-    L.aux = L.bias + (size_t)L.rows * 4;
-    L.bytes = L.aux + (dtype == H3D_F32 ? H3D_DCN_AUX_BYTES : 0);
+    h3d_ws_layout ws;
+    ws.take(L.wtotal * (dtype == H3D_F32 ? 4 : 2));
+    L.bias = ws.take((size_t)L.rows * 4);
+    L.aux = ws.take(dtype == H3D_F32 ? H3D_DCN_AUX_BYTES : 0);
+    L.bytes = ws.total;
+    return L;
+}
+template <typename WT, bool VALIDATED>
+static int dcn_w_pack(const float *weight, const float *bias, void *packed, const DcnPackLayout &L, int Cout, int C, const unsigned long long *state,
+                      unsigned *wmax, hipStream_t st)
+{
+    return h3d_launch({"dcn_w_pack_kernel", h3d_tag<WT>{}, VALIDATED}, dcn_w_pack_kernel<WT, VALIDATED>, dim3((unsigned)((L.wtotal + 255) / 256)), dim3(256), 0,
+                      st, weight, bias, (WT *)packed, (float *)((char *)packed + L.bias), Cout, C, L.rows, state, wmax);
+}
+
+// The operator's workspaces.  h3d_dcn_v2_forward_ws: the NHWC input | the offset / mask rows and maxima (dcn_om_bytes) | a filter pack;
+// h3d_dcn_v2_forward_packed: the rows and maxima | the NHWC input, unless the caller's is channels-last already.
+struct DcnWsLayout { size_t x, om, pack, total; };
+static DcnWsLayout dcn_ws_layout(size_t px, int C, size_t pack_bytes)
+{
+    DcnWsLayout L;
+    h3d_ws_layout ws;
+    L.x = ws.take(px * C * 4);
+    L.om = ws.take(dcn_om_bytes(px));
+    L.pack = ws.take(pack_bytes);
+    L.total = ws.total;
+    return L;
+}
+static DcnWsLayout dcn_packed_ws_layout(size_t px, int C, int flags)
+{
+    DcnWsLayout L;
+    h3d_ws_layout ws;
+    L.om = ws.take(dcn_om_bytes(px));
+    L.x = ws.take((flags & H3D_DCN_INPUT_NHWC) ? 0 : px * C * 4);
+    L.pack = L.total = ws.total;
     return L;
 }
 
@@ -352,8 +374,7 @@ static int dcn_launch_boundary_op(int dtype, bool f16x3, const void *x, const fl
 extern "C" size_t h3d_dcn_v2_workspace_bytes(int B, int C, int H, int W, int Cout)
 {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-    const size_t px = (size_t)B * H * W;
-    return ws_align(px * C * 4) + dcn_om_bytes(px) + dcn_pack_layout(Cout, C, H3D_F32).bytes;
+    return dcn_ws_layout((size_t)B * H * W, C, dcn_pack_layout(Cout, C, H3D_F32).bytes).total;
 }
 
 // The arithmetic of the operator's fp32 fast path: three fp16 MFMAs on split operands per fp32 product (H3D_F16X3: 2^-22 relative per
@@ -380,20 +401,15 @@ extern "C" int h3d_dcn_v2_forward_ws(const float *input, const float *weight, co
     hipStream_t st = (hipStream_t)stream;
     const DcnPackLayout L = dcn_pack_layout(Cout, C, H3D_F32);
     const size_t px = (size_t)B * H * W;
+    const DcnWsLayout WL = dcn_ws_layout(px, C, L.bytes);
     char *ws = (char *)workspace;
-    float *x_nhwc = (float *)ws;                ws += ws_align(px * C * 4);
-    float *om = (float *)ws;                    ws += dcn_om_bytes(px);
-    float *wp = (float *)ws;                    // the filter pack
-    float *bp = (float *)(ws + L.bias);
-    unsigned *wmax = (unsigned *)(ws + L.aux);
+    float *x_nhwc = (float *)(ws + WL.x), *om = (float *)(ws + WL.om), *wp = (float *)(ws + WL.pack);
+    unsigned *wmax = (unsigned *)(ws + WL.pack + L.aux);
     if (hipMemsetAsync(wmax, 0, H3D_DCN_AUX_BYTES, st) != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "dcn_v2_forward: memset");
-    int rc = h3d_nchw_f32_to_nhwc(input, x_nhwc, H3D_F32, B, C, H, W, C, stream);
-    if (rc != H3D_OK) return rc;
+    H3D_TRY(h3d_nchw_f32_to_nhwc(input, x_nhwc, H3D_F32, B, C, H, W, C, stream));
     const bool f16x3 = !dcn_op_f32_mfma();
-    rc = dcn_om_pack(input, px * C, offset, mask, om, H * W, px, f16x3, st);
-    if (rc != H3D_OK) return rc;
-    hipLaunchKernelGGL(dcn_w_pack_kernel, dim3((unsigned)((L.wtotal + 255) / 256)), dim3(256), 0, st, weight, bias, wp, bp, Cout, C, L.rows, wmax);
-    H3D_CHECK_LAUNCH("dcn_w_pack_kernel");
+    H3D_TRY(dcn_om_pack(input, px * C, offset, mask, om, H * W, px, f16x3, st));
+    H3D_TRY((dcn_w_pack<float, false>(weight, bias, wp, L, Cout, C, nullptr, wmax, st)));
     return dcn_launch_boundary_op(H3D_F32, f16x3, x_nhwc, om, wp, L, output, H3D_OUT_NCHW_F32, B, C, H, W, Cout, st);
 }
 
@@ -416,16 +432,11 @@ extern "C" int h3d_dcn_v2_pack_weights(const float *weight, const float *bias, i
     if (Cout <= 0 || C <= 0 || C % 16) H3D_FAIL(H3D_ERR_SHAPE, "dcn_v2_pack_weights: C=%d must be a positive multiple of 16", C);
     if (dtype != H3D_F32 && dtype != H3D_BF16) H3D_FAIL(H3D_ERR_DTYPE, "dcn_v2_pack_weights: dtype %d (f32 | bf16)", dtype);
     const DcnPackLayout L = dcn_pack_layout(Cout, C, dtype);
-    float *bp = (float *)((char *)packed + L.bias);
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype != H3D_F32) return dcn_w_pack<f16_t, false>(weight, bias, packed, L, Cout, C, nullptr, nullptr, st);
     unsigned *wmax = (unsigned *)((char *)packed + L.aux);
-    if (dtype == H3D_F32) {
-        if (hipMemsetAsync(wmax, 0, H3D_DCN_AUX_BYTES, (hipStream_t)stream) != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "dcn_v2_pack_weights: memset");
-        hipLaunchKernelGGL(dcn_w_pack_kernel, dim3((unsigned)((L.wtotal + 255) / 256)), dim3(256), 0, (hipStream_t)stream, weight, bias, (float *)packed, bp, Cout, C, L.rows,
-                           wmax);
-    } else
-        hipLaunchKernelGGL(dcn_w_pack_f16_kernel, dim3((unsigned)((L.wtotal + 255) / 256)), dim3(256), 0, (hipStream_t)stream, weight, bias, (_Float16 *)packed, bp, Cout, C, L.rows);
-    H3D_CHECK_LAUNCH("dcn_w_pack_kernel");
-    return H3D_OK;
+    if (hipMemsetAsync(wmax, 0, H3D_DCN_AUX_BYTES, st) != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "dcn_v2_pack_weights: memset");
+    return dcn_w_pack<float, false>(weight, bias, packed, L, Cout, C, nullptr, wmax, st);
 }
 
 // ---- packs that VALIDATE themselves on the device (round 4) -------------------------------------------------------------
@@ -477,9 +488,7 @@ static int sig_begin(unsigned long long *state, const void *const *bufs, const s
         most = std::max<size_t>(most, (size_t)b.nwords[k]);
     }
     const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((most + 1023) / 1024, 1), 512);
-    hipLaunchKernelGGL(sig_kernel, dim3(blocks), dim3(256), 0, st, b, state + 1);
-    H3D_CHECK_LAUNCH("sig_kernel");
-    return H3D_OK;
+    return h3d_launch({"sig_kernel"}, sig_kernel, dim3(blocks), dim3(256), 0, st, b, state + 1);
 }
 
 __global__ void dcn_wmax_reset_if_kernel(const unsigned long long *__restrict__ state, unsigned *__restrict__ wmax)
@@ -487,24 +496,12 @@ __global__ void dcn_wmax_reset_if_kernel(const unsigned long long *__restrict__ 
     if (state[0] != state[1]) wmax[0] = wmax[1] = 0u;      // the pack kernel behind this one rebuilds the image and its maxima (two words: main, offset filters)
 }
 
-__global__ void dcn_w_pack_if_kernel(const float *__restrict__ w, const float *__restrict__ bias, void *__restrict__ wp_, float *__restrict__ bp,
-                                     int Cout, int C, int rows, int f16, const unsigned long long *__restrict__ state, unsigned *__restrict__ wmax)
+// reset, pack if stale, commit: what follows sig_begin in both validated packs
+static int dcn_wmax_reset_if(const unsigned long long *state, unsigned *wmax, hipStream_t st)
 {
-    if (state[0] == state[1]) return;                      // the packed image was built from exactly these bytes
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t total = (size_t)rows * 9 * C;
-    if (i < (size_t)rows) bp[i] = i < (size_t)Cout ? bias[i] : 0.f;
-    float v = 0.f;
-    if (i < total) {
-        const int c = (int)(i % C);
-        const int tap = (int)((i / C) % 9);
-        const int o = (int)(i / ((size_t)9 * C));
-        v = o < Cout ? w[((size_t)o * C + c) * 9 + tap] : 0.f;
-        if (f16) ((_Float16 *)wp_)[i] = (_Float16)__builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);
-        else ((float *)wp_)[i] = v;
-    }
-    if (!f16) dcn_wmax_accumulate(wmax, v);
+    return h3d_launch({"dcn_wmax_reset_if_kernel"}, dcn_wmax_reset_if_kernel, dim3(1), dim3(1), 0, st, state, wmax);
 }
+static int sig_commit(unsigned long long *state, hipStream_t st) { return h3d_launch({"sig_commit_kernel"}, sig_commit_kernel, dim3(1), dim3(1), 0, st, state); }
 
 extern "C" int h3d_dcn_v2_pack_weights_cached(const float *weight, const float *bias, int Cout, int C, int dtype, void *packed, void *state_,
                                               void *stream)
@@ -516,21 +513,16 @@ extern "C" int h3d_dcn_v2_pack_weights_cached(const float *weight, const float *
     unsigned long long *state = (unsigned long long *)state_;
     const void *bufs[2] = {weight, bias};
     const size_t nb[2] = {(size_t)Cout * C * 9 * 4, (size_t)Cout * 4};
-    int rc = sig_begin(state, bufs, nb, 2, st);
-    if (rc != H3D_OK) return rc;
+    H3D_TRY(sig_begin(state, bufs, nb, 2, st));
     const DcnPackLayout L = dcn_pack_layout(Cout, C, dtype);
-    float *bp = (float *)((char *)packed + L.bias);
-    unsigned *wmax = dtype == H3D_F32 ? (unsigned *)((char *)packed + L.aux) : nullptr;
-    if (wmax) {
-        hipLaunchKernelGGL(dcn_wmax_reset_if_kernel, dim3(1), dim3(1), 0, st, state, wmax);
-        H3D_CHECK_LAUNCH("dcn_wmax_reset_if_kernel");
+    if (dtype == H3D_F32) {
+        unsigned *wmax = (unsigned *)((char *)packed + L.aux);
+        H3D_TRY(dcn_wmax_reset_if(state, wmax, st));
+        H3D_TRY((dcn_w_pack<float, true>(weight, bias, packed, L, Cout, C, state, wmax, st)));
+    } else {
+        H3D_TRY((dcn_w_pack<f16_t, true>(weight, bias, packed, L, Cout, C, state, nullptr, st)));
     }
-    hipLaunchKernelGGL(dcn_w_pack_if_kernel, dim3((unsigned)((L.wtotal + 255) / 256)), dim3(256), 0, st, weight, bias, packed, bp, Cout, C, L.rows,
-                       dtype == H3D_F32 ? 0 : 1, state, wmax);
-    H3D_CHECK_LAUNCH("dcn_w_pack_if_kernel");
-    hipLaunchKernelGGL(sig_commit_kernel, dim3(1), dim3(1), 0, st, state);
-    H3D_CHECK_LAUNCH("sig_commit_kernel");
-    return H3D_OK;
+    return sig_commit(state, st);
 }
 
 // The stand-alone `DCN` module's four parameters (dcn_v2.py:97-116: weight, bias, conv_offset_mask.{weight,bias}) in the fp32 layout of
@@ -559,15 +551,13 @@ __global__ void dcn_fused_pack_f32_if_kernel(const float *__restrict__ w, const 
     float v = 0.f;
     if (i < total) {
         const size_t j = off ? i - main_total : i;
-        const int c = (int)(j % C);
-        const int tap = (int)((j / C) % 9);
-        const int o = (int)(j / ((size_t)9 * C));
+        DcnPackIndex k = dcn_pack_index(j, C);
         if (!off) {
-            v = o < Cout ? w[((size_t)o * C + c) * 9 + tap] : 0.f;
+            v = dcn_pack_source(w, Cout, C, k);
             wp[j] = v;
         } else {
-            const int ch = src_channel(o);
-            v = ch >= 0 ? ow[((size_t)ch * C + c) * 9 + tap] : 0.f;
+            k.o = src_channel(k.o);             // (an unused row: -1, and the source reads as 27 output channels)
+            v = k.o >= 0 ? dcn_pack_source(ow, 27, C, k) : 0.f;
             wo[j] = v;
         }
     }
@@ -583,25 +573,19 @@ extern "C" int h3d_dcn_fused_pack_f32_cached(const float *weight, const float *b
     unsigned long long *state = (unsigned long long *)state_;
     const void *bufs[4] = {weight, bias, off_weight, off_bias};
     const size_t nb[4] = {(size_t)Cout * C * 9 * 4, (size_t)Cout * 4, (size_t)27 * C * 9 * 4, (size_t)27 * 4};
-    int rc = sig_begin(state, bufs, nb, 4, st);
-    if (rc != H3D_OK) return rc;
+    H3D_TRY(sig_begin(state, bufs, nb, 4, st));
     const int rows = (Cout + 127) / 128 * 128;
     const size_t total = ((size_t)rows + 128) * 9 * C;
-    hipLaunchKernelGGL(dcn_wmax_reset_if_kernel, dim3(1), dim3(1), 0, st, state, (unsigned *)(bias_out + rows + H3D_DCN_FUSED_BIAS_WMAX));
-    H3D_CHECK_LAUNCH("dcn_wmax_reset_if_kernel");
-    hipLaunchKernelGGL(dcn_fused_pack_f32_if_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, weight, bias, off_weight, off_bias, wp, wo,
-                       bias_out, Cout, C, rows, state);
-    H3D_CHECK_LAUNCH("dcn_fused_pack_f32_if_kernel");
-    hipLaunchKernelGGL(sig_commit_kernel, dim3(1), dim3(1), 0, st, state);
-    H3D_CHECK_LAUNCH("sig_commit_kernel");
-    return H3D_OK;
+    H3D_TRY(dcn_wmax_reset_if(state, (unsigned *)(bias_out + rows + H3D_DCN_FUSED_BIAS_WMAX), st));
+    H3D_TRY(h3d_launch({"dcn_fused_pack_f32_if_kernel"}, dcn_fused_pack_f32_if_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, weight, bias,
+                       off_weight, off_bias, wp, wo, bias_out, Cout, C, rows, state));
+    return sig_commit(state, st);
 }
 
 extern "C" size_t h3d_dcn_v2_packed_workspace_bytes(int B, int C, int H, int W, int flags)
 {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t px = (size_t)B * H * W;
-    return dcn_om_bytes(px) + ((flags & H3D_DCN_INPUT_NHWC) ? 0 : ws_align(px * C * 4));
+    return dcn_packed_ws_layout((size_t)B * H * W, C, flags).total;
 }
 
 extern "C" int h3d_dcn_v2_forward_packed(const void *input, const void *packed, const float *offset, const float *mask, void *output, int B,
@@ -618,17 +602,16 @@ extern "C" int h3d_dcn_v2_forward_packed(const void *input, const void *packed, 
         H3D_FAIL(H3D_ERR_ARG, "dcn_v2_forward_packed: workspace of %zu bytes, %zu needed", workspace_bytes, h3d_dcn_v2_packed_workspace_bytes(B, C, H, W, flags));
     hipStream_t st = (hipStream_t)stream;
     const size_t px = (size_t)B * H * W;
+    const DcnWsLayout WL = dcn_packed_ws_layout(px, C, flags);
     char *ws = (char *)workspace;
-    float *om = (float *)ws;                    ws += dcn_om_bytes(px);
+    float *om = (float *)(ws + WL.om);
     const void *x = input;
     if (!(flags & H3D_DCN_INPUT_NHWC)) {
-        int rc = h3d_nchw_f32_to_nhwc((const float *)input, ws, H3D_F32, B, C, H, W, C, stream);
-        if (rc != H3D_OK) return rc;
-        x = ws;
+        H3D_TRY(h3d_nchw_f32_to_nhwc((const float *)input, ws + WL.x, H3D_F32, B, C, H, W, C, stream));
+        x = ws + WL.x;
     }
     const bool f16x3 = dtype == H3D_F32 && !(flags & H3D_DCN_F32_MFMA) && !dcn_op_f32_mfma();
-    int rc = dcn_om_pack((const float *)input, px * C, offset, mask, om, H * W, px, f16x3, st);      // (max |x| from the caller's tensor, either layout)
-    if (rc != H3D_OK) return rc;
+    H3D_TRY(dcn_om_pack((const float *)input, px * C, offset, mask, om, H * W, px, f16x3, st));      // (max |x| from the caller's tensor, either layout)
     return dcn_launch_boundary_op(dtype, f16x3, x, om, packed, dcn_pack_layout(Cout, C, dtype), output,
                                   (flags & H3D_DCN_OUTPUT_NHWC) ? H3D_OUT_NHWC : H3D_OUT_NCHW_F32, B, C, H, W, Cout, st);
 }
@@ -660,9 +643,7 @@ extern "C" int h3d_dcn_nchw_to_nhwc_scaled(const float *src, float *dst, int B, 
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) H3D_FAIL(H3D_ERR_SHAPE, "dcn_nchw_to_nhwc_scaled: bad shape");
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(amax, 0, 4, st) != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "dcn_nchw_to_nhwc_scaled: memset");
-    int rc = dcn_absmax(src, (size_t)B * C * H * W, amax, st);
-    if (rc != H3D_OK) return rc;
-    hipLaunchKernelGGL(dcn_nchw_to_nhwc_scaled_kernel, dim3(cdiv(H * W, 32), cdiv(C, 32), B), dim3(256), 0, st, src, dst, C, H * W, amax);
-    H3D_CHECK_LAUNCH("dcn_nchw_to_nhwc_scaled_kernel");
-    return H3D_OK;
+    H3D_TRY(dcn_absmax(src, (size_t)B * C * H * W, amax, st));
+    return h3d_launch({"dcn_nchw_to_nhwc_scaled_kernel"}, dcn_nchw_to_nhwc_scaled_kernel, dim3(cdiv(H * W, 32), cdiv(C, 32), B), dim3(256), 0, st, src, dst, C,
+                      H * W, amax);
 }

@@ -19,9 +19,8 @@
 // grad_input is a scatter by float atomic adds to global memory (the order of the adds, hence the last bits, varies).
 #include "common.h"
 #include "dcn_sample.h"
+#include "split_sum.h"
 #include <algorithm>
-
-static size_t bwd_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct DcnBwdArgs {
     const float *in, *w, *off, *mask, *go;
@@ -170,7 +169,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_kernel(DcnBwdArgs a)
 
 // ================================================================================================================================
 // GENERAL, grad_weight.  Workgroup = 64 output channels x 64 filter elements k = (c, tap), one split of the B*Ho*Wo pixels walked 16 at
-// a time: sampled columns and grad_output meet in LDS.  Partials [S][Cout][K] go to the workspace and are summed in split order.
+// a time: sampled columns and grad_output meet in LDS.  Partials [S][Cout][K] go to the workspace and are summed in split order (csrc/split_sum.h).
 __global__ __launch_bounds__(256) void dcn_bwd_weight_kernel(DcnBwdArgs a)
 {
     constexpr int TK = 64, TC = 64, PC = 16;
@@ -244,16 +243,6 @@ __global__ __launch_bounds__(256) void dcn_bwd_weight_kernel(DcnBwdArgs a)
             if (k < K) a.part[((size_t)sp * a.Cout + co) * K + k] = acc[i][j];
         }
     }
-}
-
-// grad_weight[i] = sum over splits, in split order
-__global__ void dcn_bwd_weight_reduce_kernel(const float *__restrict__ part, float *__restrict__ gw, size_t n, int S)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float v = 0.f;
-    for (int s = 0; s < S; ++s) v += part[(size_t)s * n + i];
-    gw[i] = v;
 }
 
 // ================================================================================================================================
@@ -459,20 +448,6 @@ __global__ __launch_bounds__(192) void dcn_bwd_weight_mfma_kernel(DcnBwdArgs a)
     }
 }
 
-// grad_weight[co][c][t] = sum over splits of part[split][t][co][c], in split order
-__global__ void dcn_bwd_weight_mfma_reduce_kernel(const float *__restrict__ part, float *__restrict__ gw, int Cout, int C, int S)
-{
-    const size_t n = (size_t)9 * Cout * C;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float v = 0.f;
-    for (int s = 0; s < S; ++s) v += part[(size_t)s * n + i];
-    const int c = (int)(i % C);
-    const int co = (int)((i / C) % Cout);
-    const int t = (int)(i / ((size_t)C * Cout));
-    gw[((size_t)co * C + c) * 9 + t] = v;
-}
-
 // ================================================================================================================================
 // Host side.
 struct BwdPlan {
@@ -480,7 +455,8 @@ struct BwdPlan {
     int Ho, Wo;
     int Sg; long long Lg;       // general grad_weight: splits of the B*Ho*Wo pixels, pixels per split (multiple of 16)
     int SP, Lf;                 // fast grad_weight: splits per image, pixels per split (multiple of 8)
-    size_t part_g, xn, wp, part_f, total;
+    // workspace: the general partials [Sg][Cout][K] at offset 0, or (overlaid) the matrix-core path's NHWC input, packed filters and partials
+    size_t xn, wp, part_f, total;
 };
 
 static bool bwd_plan(BwdPlan &pl, int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg)
@@ -495,7 +471,8 @@ static bool bwd_plan(BwdPlan &pl, int B, int C, int H, int W, int Cout, int kh, 
     Sg = std::min<long long>(Sg, 64);
     pl.Lg = ((NPX + Sg - 1) / Sg + 15) / 16 * 16;
     pl.Sg = (int)((NPX + pl.Lg - 1) / pl.Lg);
-    pl.part_g = bwd_align((size_t)pl.Sg * Cout * K * 4);
+    h3d_ws_layout general, mfma;
+    general.take((size_t)pl.Sg * Cout * K * 4);
     // the matrix-core kernels: the model's configuration; the tile of grad_output (Cout rounded up to 8, x 32 pixels) must fit in LDS
     pl.fast = kh == 3 && kw == 3 && sh == 1 && sw == 1 && ph == 1 && pw == 1 && dh == 1 && dw == 1 && dg == 1 && C % 16 == 0 && Cout <= 1024 &&
               H <= 32767 && W <= 32767;
@@ -506,11 +483,11 @@ static bool bwd_plan(BwdPlan &pl, int B, int C, int H, int W, int Cout, int kh, 
         long long SP = std::min<long long>(std::max<long long>((1024 + (long long)CT * COB * B - 1) / ((long long)CT * COB * B), 1), std::max(HW / 512, 1));
         pl.Lf = (int)(((HW + SP - 1) / SP + 7) / 8 * 8);
         pl.SP = (HW + pl.Lf - 1) / pl.Lf;
-        pl.xn = bwd_align((size_t)B * HW * C * 4);
-        pl.wp = bwd_align((size_t)9 * CT * CO8 * 256 * 4);
-        pl.part_f = bwd_align((size_t)B * pl.SP * 9 * Cout * C * 4);
+        pl.xn = mfma.take((size_t)B * HW * C * 4);
+        pl.wp = mfma.take((size_t)9 * CT * CO8 * 256 * 4);
+        pl.part_f = mfma.take((size_t)B * pl.SP * 9 * Cout * C * 4);
     }
-    pl.total = std::max(pl.part_g, pl.xn + pl.wp + pl.part_f);
+    pl.total = std::max(general.total, mfma.total);
     return true;
 }
 
@@ -562,58 +539,38 @@ static int dcn_v2_backward_impl(bool allow_fast, const float *input, const float
     a.B = B; a.C = C; a.H = H; a.W = W; a.Cout = Cout; a.kh = kernel_h; a.kw = kernel_w; a.sh = stride_h; a.sw = stride_w;
     a.ph = pad_h; a.pw = pad_w; a.dh = dilation_h; a.dw = dilation_w; a.dg = deformable_group; a.Ho = pl.Ho; a.Wo = pl.Wo;
     if (grad_input && hipMemsetAsync(grad_input, 0, (size_t)B * C * H * W * 4, st) != hipSuccess) H3D_FAIL(H3D_ERR_LAUNCH, "dcn_v2_backward: memset");
-    if (grad_bias) {
-        hipLaunchKernelGGL(dcn_bwd_bias_kernel, dim3(Cout), dim3(256), 0, st, grad_output, grad_bias, B, Cout, HoWo);
-        H3D_CHECK_LAUNCH("dcn_bwd_bias_kernel");
-    }
+    if (grad_bias) H3D_TRY(h3d_launch({"dcn_bwd_bias_kernel"}, dcn_bwd_bias_kernel, dim3(Cout), dim3(256), 0, st, grad_output, grad_bias, B, Cout, HoWo));
     if (!fast) {
-        if (data) {
-            hipLaunchKernelGGL(dcn_bwd_data_kernel, dim3(cdiv(HoWo, 64), B), dim3(256), 0, st, a);
-            H3D_CHECK_LAUNCH("dcn_bwd_data_kernel");
-        }
+        if (data) H3D_TRY(h3d_launch({"dcn_bwd_data_kernel"}, dcn_bwd_data_kernel, dim3(cdiv(HoWo, 64), B), dim3(256), 0, st, a));
         if (grad_weight) {
             const int K = C * kernel_h * kernel_w;
             a.part = pl.Sg == 1 ? grad_weight : (float *)workspace;
             a.S = pl.Sg; a.L = (int)std::min<long long>(pl.Lg, 0x7fffffff);
             if (pl.Lg > 0x7fffffff) H3D_FAIL(H3D_ERR_SHAPE, "dcn_v2_backward: %lld pixels per split", pl.Lg);
-            hipLaunchKernelGGL(dcn_bwd_weight_kernel, dim3(cdiv(K, 64), cdiv(Cout, 64), pl.Sg), dim3(256), 0, st, a);
-            H3D_CHECK_LAUNCH("dcn_bwd_weight_kernel");
-            if (pl.Sg > 1) {
-                const size_t n = (size_t)Cout * K;
-                hipLaunchKernelGGL(dcn_bwd_weight_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float *)workspace, grad_weight, n, pl.Sg);
-                H3D_CHECK_LAUNCH("dcn_bwd_weight_reduce_kernel");
-            }
+            H3D_TRY(h3d_launch({"dcn_bwd_weight_kernel"}, dcn_bwd_weight_kernel, dim3(cdiv(K, 64), cdiv(Cout, 64), pl.Sg), dim3(256), 0, st, a));
+            if (pl.Sg > 1) H3D_TRY(h3d_split_sum((const float *)workspace, grad_weight, (size_t)Cout * K, pl.Sg, st));
         }
         return H3D_OK;
     }
     const int CT = (C + 31) / 32, CO8 = (Cout + 7) / 8;
     char *ws = (char *)workspace;
-    float *xn = (float *)ws;        ws += pl.xn;
-    float *wp = (float *)ws;        ws += pl.wp;
-    float *part = (float *)ws;
+    float *xn = (float *)(ws + pl.xn), *wp = (float *)(ws + pl.wp), *part = (float *)(ws + pl.part_f);
     a.xn = xn; a.wp = wp; a.part = part;
-    if (grad_weight || grad_offset || grad_mask) {      // (grad_input alone needs no input values)
-        rc = h3d_nchw_f32_to_nhwc(input, xn, H3D_F32, B, C, H, W, C, stream);
-        if (rc != H3D_OK) return rc;
-    }
+    if (grad_weight || grad_offset || grad_mask)        // (grad_input alone needs no input values)
+        H3D_TRY(h3d_nchw_f32_to_nhwc(input, xn, H3D_F32, B, C, H, W, C, stream));
     if (data) {
         const size_t wtotal = (size_t)9 * CT * CO8 * 256;
-        hipLaunchKernelGGL(dcn_bwd_wpack_kernel, dim3((unsigned)((wtotal + 255) / 256)), dim3(256), 0, st, weight, wp, Cout, C, CT, CO8);
-        H3D_CHECK_LAUNCH("dcn_bwd_wpack_kernel");
+        H3D_TRY(h3d_launch({"dcn_bwd_wpack_kernel"}, dcn_bwd_wpack_kernel, dim3((unsigned)((wtotal + 255) / 256)), dim3(256), 0, st, weight, wp, Cout, C, CT, CO8));
         const size_t lds = ((size_t)CO8 * 256 + 9 * 4 * 3 * 32) * 4;
         if (lds > 48 * 1024 &&
             hipFuncSetAttribute((const void *)dcn_bwd_data_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
             H3D_FAIL(H3D_ERR_LAUNCH, "dcn_v2_backward: %zu bytes of LDS", lds);
-        hipLaunchKernelGGL(dcn_bwd_data_mfma_kernel, dim3(cdiv(H * W, 32), B), dim3(256), lds, st, a);
-        H3D_CHECK_LAUNCH("dcn_bwd_data_mfma_kernel");
+        H3D_TRY(h3d_launch({"dcn_bwd_data_mfma_kernel"}, dcn_bwd_data_mfma_kernel, dim3(cdiv(H * W, 32), B), dim3(256), lds, st, a));
     }
     if (grad_weight) {
         a.S = B * pl.SP; a.L = pl.Lf;
-        hipLaunchKernelGGL(dcn_bwd_weight_mfma_kernel, dim3(CT, cdiv(Cout, 64), B * pl.SP), dim3(192), 0, st, a);
-        H3D_CHECK_LAUNCH("dcn_bwd_weight_mfma_kernel");
-        const size_t n = (size_t)9 * Cout * C;
-        hipLaunchKernelGGL(dcn_bwd_weight_mfma_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, grad_weight, Cout, C, B * pl.SP);
-        H3D_CHECK_LAUNCH("dcn_bwd_weight_mfma_reduce_kernel");
+        H3D_TRY(h3d_launch({"dcn_bwd_weight_mfma_kernel"}, dcn_bwd_weight_mfma_kernel, dim3(CT, cdiv(Cout, 64), B * pl.SP), dim3(192), 0, st, a));
+        H3D_TRY(h3d_split_sum(part, grad_weight, (size_t)9 * Cout * C, B * pl.SP, st, Cout, C));      // [tap][co][c] -> the reference's [co][c][tap]
     }
     return H3D_OK;
 }

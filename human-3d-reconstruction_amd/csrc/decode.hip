@@ -396,10 +396,8 @@ static int nms_topk_launch(const NmsJob &j0, const NmsJob &j1, int H_img, int W,
             H3D_FAIL(H3D_ERR_LAUNCH, "nms_topk: cannot reserve %zu bytes of LDS", lds);
         max_set = lds;
     }
-    hipLaunchKernelGGL(nms_topk_kernel, dim3((j0.nblk + j1.nblk) * nbands), dim3(NMS_THREADS), lds, (hipStream_t)stream, j0, j1, H_img, W, K, N, flags,
-                       band_rows, nbands, (int)cap);
-    H3D_CHECK_LAUNCH("nms_topk_kernel");
-    return H3D_OK;
+    return h3d_launch({"nms_topk_kernel"}, nms_topk_kernel, dim3((j0.nblk + j1.nblk) * nbands), dim3(NMS_THREADS), lds, (hipStream_t)stream, j0, j1, H_img, W, K,
+                      N, flags, band_rows, nbands, (int)cap);
 }
 
 extern "C" int h3d_nms_topk(const float *heat, int B, int C, int H, int W, int K, int flags, float *scores,
@@ -437,12 +435,27 @@ static int nms_bands(int H, int W, int K, int *band_rows, int *nbands)
     return H3D_OK;
 }
 
+// per map and band K candidates, then the band id of every output; 256 spare bytes behind them, as the size always had
+struct NmsLargeLayout { size_t ind, score, y, x, band, total; };
+static NmsLargeLayout nms_large_layout(int B, int C, int nb, int K)
+{
+    const size_t n = (size_t)B * C * nb * K;
+    NmsLargeLayout L;
+    h3d_ws_layout ws;
+    L.ind = ws.take(n * 8, 8);          // (8-byte items first: alignment)
+    L.score = ws.take(n * 4, 4);
+    L.y = ws.take(n * 4, 4);
+    L.x = ws.take(n * 4, 4);
+    L.band = ws.take((size_t)B * C * K * 4, 4);
+    L.total = ws.total + 256;
+    return L;
+}
+
 extern "C" size_t h3d_nms_topk_large_workspace_bytes(int B, int C, int H, int W, int K)
 {
     int br = 0, nb = 0;
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0 || W > NMS_MAXHW / 3 || nms_bands(H, W, K, &br, &nb) != H3D_OK) return 0;
-    const size_t n = (size_t)B * C * nb * K;
-    return n * (4 + 8 + 4 + 4) + (size_t)B * C * K * 4 + 256;
+    return nms_large_layout(B, C, nb, K).total;
 }
 
 extern "C" int h3d_nms_topk_large(const float *heat, int B, int C, int H, int W, int K, int flags, float *scores, int64_t *inds,
@@ -457,13 +470,11 @@ extern "C" int h3d_nms_topk_large(const float *heat, int B, int C, int H, int W,
     if ((long)nb * K > 8192) H3D_FAIL(H3D_ERR_UNSUPPORTED, "nms_topk_large: %d bands x K=%d candidates per map (max 8192)", nb, K);
     if (!workspace || workspace_bytes < h3d_nms_topk_large_workspace_bytes(B, C, H, W, K))
         H3D_FAIL(H3D_ERR_ARG, "nms_topk_large: workspace of %zu bytes, %zu needed", workspace_bytes, h3d_nms_topk_large_workspace_bytes(B, C, H, W, K));
-    const size_t n = (size_t)B * C * nb * K;
+    const NmsLargeLayout L = nms_large_layout(B, C, nb, K);
     char *ws = (char *)workspace;
-    int64_t *t_ind = (int64_t *)ws;         ws += n * 8;        // (8-byte items first: alignment)
-    float *t_score = (float *)ws;           ws += n * 4;
-    float *t_y = (float *)ws;               ws += n * 4;
-    float *t_x = (float *)ws;               ws += n * 4;
-    int32_t *t_band = (int32_t *)ws;
+    int64_t *t_ind = (int64_t *)(ws + L.ind);
+    float *t_score = (float *)(ws + L.score), *t_y = (float *)(ws + L.y), *t_x = (float *)(ws + L.x);
+    int32_t *t_band = (int32_t *)(ws + L.band);
     const NmsJob j0 = {heat, t_score, t_ind, t_y, t_x, B * C}, j1 = {nullptr, nullptr, nullptr, nullptr, nullptr, 0};
     int rc = nms_topk_launch(j0, j1, H, W, K, flags, stream, br, nb);
     if (rc != H3D_OK) return rc;
@@ -502,9 +513,7 @@ extern "C" int h3d_nms(const float *heat, int B, int C, int H, int W, float *out
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) H3D_FAIL(H3D_ERR_SHAPE, "nms: bad shape");
     const size_t total = (size_t)B * C * H * W;
     const int grid = (int)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
-    hipLaunchKernelGGL(nms_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, heat, H, W, out, total);
-    H3D_CHECK_LAUNCH("nms_kernel");
-    return H3D_OK;
+    return h3d_launch({"nms_kernel"}, nms_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, heat, H, W, out, total);
 }
 
 __global__ void sigmoid_clamp_kernel(const float *__restrict__ in, float *__restrict__ out, size_t n)
@@ -518,9 +527,7 @@ extern "C" int h3d_sigmoid_clamp(const float *in, float *out, size_t n, void *st
     if (!in || !out) H3D_FAIL(H3D_ERR_ARG, "sigmoid_clamp: null pointer");
     if (n == 0) return H3D_OK;
     const int grid = (int)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256);
-    hipLaunchKernelGGL(sigmoid_clamp_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, out, n);
-    H3D_CHECK_LAUNCH("sigmoid_clamp_kernel");
-    return H3D_OK;
+    return h3d_launch({"sigmoid_clamp_kernel"}, sigmoid_clamp_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, in, out, n);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -558,10 +565,8 @@ extern "C" int h3d_topk_merge(const float *scores, const int64_t *inds, const fl
     if ((long)C * K > 8192) H3D_FAIL(H3D_ERR_UNSUPPORTED, "topk_merge: C*K=%ld > 8192", (long)C * K);
     int N = 1;
     while (N < C * K) N <<= 1;
-    hipLaunchKernelGGL(topk_merge_kernel, dim3(B), dim3(256), (size_t)N * 8, (hipStream_t)stream, scores, inds, ys, xs, C, K,
-                       N, o_score, o_ind, o_cls, o_y, o_x);
-    H3D_CHECK_LAUNCH("topk_merge_kernel");
-    return H3D_OK;
+    return h3d_launch({"topk_merge_kernel"}, topk_merge_kernel, dim3(B), dim3(256), (size_t)N * 8, (hipStream_t)stream, scores, inds, ys, xs, C, K, N, o_score,
+                      o_ind, o_cls, o_y, o_x);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -585,10 +590,7 @@ extern "C" int h3d_gather_feat(const float *feat, const int64_t *ind, int B, int
     const size_t total = (size_t)B * N * C;
     const int grid = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
     const long sb = (long)C * HW, sc = channels_last ? 1 : HW, sp = channels_last ? C : 1;
-    hipLaunchKernelGGL(gather_feat_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feat, ind, C, HW, N, sb, sc, sp,
-                       out, total);
-    H3D_CHECK_LAUNCH("gather_feat_kernel");
-    return H3D_OK;
+    return h3d_launch({"gather_feat_kernel"}, gather_feat_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, feat, ind, C, HW, N, sb, sc, sp, out, total);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -680,10 +682,8 @@ extern "C" int h3d_multi_pose_assemble(const float *c_score, const int64_t *c_in
     if (B <= 0 || J <= 0 || H <= 0 || W <= 0 || K <= 0) H3D_FAIL(H3D_ERR_SHAPE, "multi_pose_assemble: bad shape");
     const size_t lds = (size_t)K * 9 * sizeof(float);
     if (lds > 64 * 1024) H3D_FAIL(H3D_ERR_UNSUPPORTED, "multi_pose_assemble: K too large (%d)", K);
-    hipLaunchKernelGGL(pose_assemble_kernel, dim3(B * (J + 1)), dim3(PA_THREADS), lds, (hipStream_t)stream, c_score, c_ind, c_cls, c_y, c_x,
-                       hp_score, hp_ind, hp_y, hp_x, wh, hps, reg, hp_offset, J, H * W, K, dets);
-    H3D_CHECK_LAUNCH("pose_assemble_kernel");
-    return H3D_OK;
+    return h3d_launch({"pose_assemble_kernel"}, pose_assemble_kernel, dim3(B * (J + 1)), dim3(PA_THREADS), lds, (hipStream_t)stream, c_score, c_ind, c_cls, c_y,
+                      c_x, hp_score, hp_ind, hp_y, hp_x, wh, hps, reg, hp_offset, J, H * W, K, dets);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -718,10 +718,8 @@ extern "C" int h3d_ctdet_assemble(const float *c_score, const int64_t *c_ind, co
     if (!c_score || !c_ind || !c_cls || !c_y || !c_x || !wh || !dets) H3D_FAIL(H3D_ERR_ARG, "ctdet_assemble: null pointer");
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || K <= 0) H3D_FAIL(H3D_ERR_SHAPE, "ctdet_assemble: bad shape");
     const int total = B * K;
-    hipLaunchKernelGGL(ctdet_assemble_kernel, dim3(cdiv(total, 128)), dim3(128), 0, (hipStream_t)stream, c_score, c_ind,
-                       c_cls, c_y, c_x, wh, reg, C, H * W, K, cat_spec_wh, total, dets);
-    H3D_CHECK_LAUNCH("ctdet_assemble_kernel");
-    return H3D_OK;
+    return h3d_launch({"ctdet_assemble_kernel"}, ctdet_assemble_kernel, dim3(cdiv(total, 128)), dim3(128), 0, (hipStream_t)stream, c_score, c_ind, c_cls, c_y,
+                      c_x, wh, reg, C, H * W, K, cat_spec_wh, total, dets);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -756,8 +754,6 @@ extern "C" int h3d_multi_pose_post_process(const float *dets, const float *c, co
     if (!dets || !c || !s || !out) H3D_FAIL(H3D_ERR_ARG, "post_process: null pointer");
     if (B <= 0 || K <= 0 || J < 0 || out_h <= 0 || out_w <= 0) H3D_FAIL(H3D_ERR_SHAPE, "post_process: bad shape");
     const int total = B * K;
-    hipLaunchKernelGGL(post_process_kernel, dim3(cdiv(total, 128)), dim3(128), 0, (hipStream_t)stream, dets, c, s, K, J,
-                       out_h, out_w, total, out);
-    H3D_CHECK_LAUNCH("post_process_kernel");
-    return H3D_OK;
+    return h3d_launch({"post_process_kernel"}, post_process_kernel, dim3(cdiv(total, 128)), dim3(128), 0, (hipStream_t)stream, dets, c, s, K, J, out_h, out_w,
+                      total, out);
 }

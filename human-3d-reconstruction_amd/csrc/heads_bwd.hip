@@ -20,8 +20,9 @@
 //                              64 channels of gh halo at a time through LDS.  The one workgroup that owns a pixel tile writes (first
 //                              live head) or load-add-stores (later heads) grad_feat.
 //   4. heads_bwd_w1_kernel / heads_bwd_w2_kernel / heads_bwd_bias_kernel   K = pixels: one split of the B*H*W pixels per workgroup,
-//                              partials to the workspace, then heads_bwd_reduce_kernel sums them in split order.
+//                              partials to the workspace, then h3d_split_sum_kernel (csrc/split_sum.h) sums them in split order.
 #include "common.h"
+#include "split_sum.h"
 #include <algorithm>
 
 constexpr int HB_TH = 4, HB_TW = 32;              // pixel tile of a workgroup (4 waves, one row each)
@@ -370,26 +371,10 @@ __global__ __launch_bounds__(256) void heads_bwd_bias_kernel(HeadsBwdArgs a, int
     }
 }
 
-// out[i] = sum over splits of part[split][i], in split order.  w1_hc != 0: part is [split][tap][o][c], out the reference's [o][c][tap].
-__global__ void heads_bwd_reduce_kernel(const float *__restrict__ part, float *__restrict__ out, int n, int S, int w1_hc)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float v = 0.f;
-    for (int s = 0; s < S; ++s) v += part[(size_t)s * n + i];
-    if (w1_hc) {
-        const int c = i & 63, o = (i >> 6) % w1_hc, t = (i >> 6) / w1_hc;
-        out[((size_t)o * 64 + c) * 9 + t] = v;
-    } else {
-        out[i] = v;
-    }
-}
-
-static size_t hb_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
+// the splits of the K = pixels contractions and the workspace: the two packed images of W1, gh, h, the four sets of partials
 struct HbPlan {
     int NPX, S, L;
-    size_t pack, act, p_w1, p_w2, p_b1, p_b2, total;
+    size_t w1p, w1f, gh, hh, p_w1, p_w2, p_b1, p_b2, total;
 };
 
 static int hb_check(const char *what, int B, int H, int W, int head_conv, int nheads)
@@ -408,13 +393,16 @@ static void hb_plan(HbPlan &pl, int B, int H, int W, int hc)
     int S = std::min(HB_SPLIT_MAX, cdiv(pl.NPX, HB_SPLIT_PIXELS));
     pl.L = cdiv(cdiv(pl.NPX, S), 8) * 8;
     pl.S = cdiv(pl.NPX, pl.L);
-    pl.pack = hb_align((size_t)576 * hc * 4);
-    pl.act = hb_align((size_t)pl.NPX * hc * 4);
-    pl.p_w1 = hb_align((size_t)pl.S * 576 * hc * 4);
-    pl.p_w2 = hb_align((size_t)pl.S * HB_CMAX * hc * 4);
-    pl.p_b1 = hb_align((size_t)pl.S * hc * 4);
-    pl.p_b2 = hb_align((size_t)pl.S * HB_CMAX * 4);
-    pl.total = 2 * pl.pack + 2 * pl.act + pl.p_w1 + pl.p_w2 + pl.p_b1 + pl.p_b2;
+    h3d_ws_layout ws;
+    pl.w1p = ws.take((size_t)576 * hc * 4);
+    pl.w1f = ws.take((size_t)576 * hc * 4);
+    pl.gh = ws.take((size_t)pl.NPX * hc * 4);
+    pl.hh = ws.take((size_t)pl.NPX * hc * 4);
+    pl.p_w1 = ws.take((size_t)pl.S * 576 * hc * 4);
+    pl.p_w2 = ws.take((size_t)pl.S * HB_CMAX * hc * 4);
+    pl.p_b1 = ws.take((size_t)pl.S * hc * 4);
+    pl.p_b2 = ws.take((size_t)pl.S * HB_CMAX * 4);
+    pl.total = ws.total;
 }
 
 extern "C" int h3d_heads_backward_workspace_bytes(int B, int H, int W, int head_conv, int nheads, const int *C, size_t *bytes)
@@ -461,14 +449,10 @@ extern "C" int h3d_heads_backward(const float *feat, int in_cs, int B, int H, in
     }
     HeadsBwdArgs a = {};
     char *ws = (char *)workspace;
-    a.w1p = (float *)ws; ws += pl.pack;
-    a.w1f = (float *)ws; ws += pl.pack;
-    a.gh = (float *)ws;  ws += pl.act;
-    a.hh = (float *)ws;  ws += pl.act;
-    a.p_w1 = (float *)ws; ws += pl.p_w1;
-    a.p_w2 = (float *)ws; ws += pl.p_w2;
-    a.p_b1 = (float *)ws; ws += pl.p_b1;
-    a.p_b2 = (float *)ws;
+    a.w1p = (float *)(ws + pl.w1p); a.w1f = (float *)(ws + pl.w1f);
+    a.gh = (float *)(ws + pl.gh); a.hh = (float *)(ws + pl.hh);
+    a.p_w1 = (float *)(ws + pl.p_w1); a.p_w2 = (float *)(ws + pl.p_w2);
+    a.p_b1 = (float *)(ws + pl.p_b1); a.p_b2 = (float *)(ws + pl.p_b2);
     a.feat = feat; a.in_cs = in_cs; a.B = B; a.H = H; a.W = W; a.hc = head_conv;
     a.tiles_x = cdiv(W, HB_TW); a.tiles_y = cdiv(H, HB_TH);
     a.NPX = pl.NPX; a.S = pl.S; a.L = pl.L;
@@ -483,42 +467,26 @@ extern "C" int h3d_heads_backward(const float *feat, int in_cs, int B, int H, in
         a.want_gh = grad_feat || h.grad_w1 || h.grad_b1;
         a.want_h = h.grad_w2 != nullptr;
         if (a.want_gh || a.want_h) {
-            hipLaunchKernelGGL(heads_bwd_pack_kernel, dim3(cdiv(576 * hc, 256)), dim3(256), 0, st, h.w1, a.w1p, a.w1f, hc);
-            H3D_CHECK_LAUNCH("heads_bwd_pack_kernel");
-            hipLaunchKernelGGL(heads_bwd_gh_kernel, tile_grid, dim3(256), 0, st, a);
-            H3D_CHECK_LAUNCH("heads_bwd_gh_kernel");
+            H3D_TRY(h3d_launch({"heads_bwd_pack_kernel"}, heads_bwd_pack_kernel, dim3(cdiv(576 * hc, 256)), dim3(256), 0, st, h.w1, a.w1p, a.w1f, hc));
+            H3D_TRY(h3d_launch({"heads_bwd_gh_kernel"}, heads_bwd_gh_kernel, tile_grid, dim3(256), 0, st, a));
         }
         if (grad_feat) {
             a.gy_add = first ? 0 : 1;
-            hipLaunchKernelGGL(heads_bwd_gy_kernel, tile_grid, dim3(256), 0, st, a);
-            H3D_CHECK_LAUNCH("heads_bwd_gy_kernel");
+            H3D_TRY(h3d_launch({"heads_bwd_gy_kernel"}, heads_bwd_gy_kernel, tile_grid, dim3(256), 0, st, a));
             first = false;
         }
         if (h.grad_w1) {
-            hipLaunchKernelGGL(heads_bwd_w1_kernel, dim3(2, hc / 64, pl.S), dim3(192), 0, st, a);
-            H3D_CHECK_LAUNCH("heads_bwd_w1_kernel");
-            const int n = 576 * hc;
-            hipLaunchKernelGGL(heads_bwd_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const float *)a.p_w1, h.grad_w1, n, pl.S, hc);
-            H3D_CHECK_LAUNCH("heads_bwd_reduce_kernel");
+            H3D_TRY(h3d_launch({"heads_bwd_w1_kernel"}, heads_bwd_w1_kernel, dim3(2, hc / 64, pl.S), dim3(192), 0, st, a));
+            H3D_TRY(h3d_split_sum(a.p_w1, h.grad_w1, (size_t)576 * hc, pl.S, st, hc, 64));       // [tap][o][c] -> the reference's [o][c][tap]
         }
         if (h.grad_w2) {
-            hipLaunchKernelGGL(heads_bwd_w2_kernel, dim3(hc / 32, pl.S), dim3(64), 0, st, a);
-            H3D_CHECK_LAUNCH("heads_bwd_w2_kernel");
-            const int n = h.C * hc;
-            hipLaunchKernelGGL(heads_bwd_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, (const float *)a.p_w2, h.grad_w2, n, pl.S, 0);
-            H3D_CHECK_LAUNCH("heads_bwd_reduce_kernel");
+            H3D_TRY(h3d_launch({"heads_bwd_w2_kernel"}, heads_bwd_w2_kernel, dim3(hc / 32, pl.S), dim3(64), 0, st, a));
+            H3D_TRY(h3d_split_sum(a.p_w2, h.grad_w2, (size_t)h.C * hc, pl.S, st));
         }
         if (h.grad_b1 || h.grad_b2) {
-            hipLaunchKernelGGL(heads_bwd_bias_kernel, dim3(pl.S), dim3(256), 0, st, a, h.grad_b1 ? 1 : 0, h.grad_b2 ? 1 : 0);
-            H3D_CHECK_LAUNCH("heads_bwd_bias_kernel");
-            if (h.grad_b1) {
-                hipLaunchKernelGGL(heads_bwd_reduce_kernel, dim3(cdiv(hc, 256)), dim3(256), 0, st, (const float *)a.p_b1, h.grad_b1, hc, pl.S, 0);
-                H3D_CHECK_LAUNCH("heads_bwd_reduce_kernel");
-            }
-            if (h.grad_b2) {
-                hipLaunchKernelGGL(heads_bwd_reduce_kernel, dim3(cdiv(h.C, 256)), dim3(256), 0, st, (const float *)a.p_b2, h.grad_b2, h.C, pl.S, 0);
-                H3D_CHECK_LAUNCH("heads_bwd_reduce_kernel");
-            }
+            H3D_TRY(h3d_launch({"heads_bwd_bias_kernel"}, heads_bwd_bias_kernel, dim3(pl.S), dim3(256), 0, st, a, h.grad_b1 ? 1 : 0, h.grad_b2 ? 1 : 0));
+            if (h.grad_b1) H3D_TRY(h3d_split_sum(a.p_b1, h.grad_b1, hc, pl.S, st));
+            if (h.grad_b2) H3D_TRY(h3d_split_sum(a.p_b2, h.grad_b2, h.C, pl.S, st));
         }
     }
     return H3D_OK;

@@ -429,13 +429,8 @@ extern "C" int h3d_loss_forward(const h3d_loss_term *terms, int n_terms, float *
         if (a.t[i].nblocks) p.t[p.n++] = a.t[i];
         f.t[i] = LossFinishTerm{terms[i].kind, a.t[i].block0, a.t[i].nblocks, terms[i].weight};
     }
-    if (total) {
-        hipLaunchKernelGGL(loss_partial_kernel, dim3(total), dim3(LOSS_THREADS), 0, st, p, (f32x4 *)workspace);
-        H3D_CHECK_LAUNCH("loss_partial_kernel");
-    }
-    hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(64 * H3D_LOSS_MAX_TERMS), 0, st, f, (const f32x4 *)workspace, stats);
-    H3D_CHECK_LAUNCH("loss_finish_kernel");
-    return H3D_OK;
+    if (total) H3D_TRY(h3d_launch({"loss_partial_kernel"}, loss_partial_kernel, dim3(total), dim3(LOSS_THREADS), 0, st, p, (f32x4 *)workspace));
+    return h3d_launch({"loss_finish_kernel"}, loss_finish_kernel, dim3(1), dim3(64 * H3D_LOSS_MAX_TERMS), 0, st, f, (const f32x4 *)workspace, stats);
 }
 
 extern "C" int h3d_loss_backward(const h3d_loss_term *terms, int n_terms, const float *stats, const float *coef, void *stream)
@@ -466,13 +461,7 @@ extern "C" int h3d_loss_backward(const h3d_loss_term *terms, int n_terms, const 
         }
     }
     const hipStream_t st = (hipStream_t)stream;
-    if (nd) {
-        hipLaunchKernelGGL(loss_bwd_dense_kernel, dim3(nd), dim3(LOSS_THREADS), 0, st, dense, stats, coef);
-        H3D_CHECK_LAUNCH("loss_bwd_dense_kernel");
-    }
-    if (ns) {
-        hipLaunchKernelGGL(loss_bwd_scatter_kernel, dim3(ns), dim3(LOSS_THREADS), 0, st, scat, stats, coef);
-        H3D_CHECK_LAUNCH("loss_bwd_scatter_kernel");
-    }
+    if (nd) H3D_TRY(h3d_launch({"loss_bwd_dense_kernel"}, loss_bwd_dense_kernel, dim3(nd), dim3(LOSS_THREADS), 0, st, dense, stats, coef));
+    if (ns) H3D_TRY(h3d_launch({"loss_bwd_scatter_kernel"}, loss_bwd_scatter_kernel, dim3(ns), dim3(LOSS_THREADS), 0, st, scat, stats, coef));
     return H3D_OK;
 }

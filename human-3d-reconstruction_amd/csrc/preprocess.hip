@@ -47,8 +47,6 @@ extern "C" int h3d_preprocess(const uint8_t *images, int B, int h, int w, int ro
     if (B <= 0 || h <= 0 || w <= 0 || res_h <= 0 || res_w <= 0 || row_bytes < 3 * w)
         H3D_FAIL(H3D_ERR_SHAPE, "preprocess: B=%d %dx%d (row %d bytes) -> %dx%d", B, h, w, row_bytes, res_h, res_w);
     if (h > 32767 || w > 32767) H3D_FAIL(H3D_ERR_SHAPE, "preprocess: image larger than 32767 (fixed-point warp)");
-    hipLaunchKernelGGL(preprocess_kernel, dim3(cdiv(res_w, 128), res_h, B), dim3(128), 0, (hipStream_t)stream, images, h, w,
-                       row_bytes, (size_t)h * row_bytes, minv, mean, stdv, res_h, res_w, out);
-    H3D_CHECK_LAUNCH("preprocess_kernel");
-    return H3D_OK;
+    return h3d_launch({"preprocess_kernel"}, preprocess_kernel, dim3(cdiv(res_w, 128), res_h, B), dim3(128), 0, (hipStream_t)stream, images, h, w,
+                      row_bytes, (size_t)h * row_bytes, minv, mean, stdv, res_h, res_w, out);
 }

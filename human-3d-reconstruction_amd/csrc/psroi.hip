@@ -196,12 +196,8 @@ static int psroi_launch(const char *what, const float *input, const float *bbox,
     a.vec = ((uintptr_t)output % 16 == 0) && (count == nullptr || (uintptr_t)count % 16 == 0);
     const size_t lds = (size_t)P2 * a.S2c * sizeof(int4) + (size_t)(P2 + 3) / 4 * 16;
     const int grid = (int)(a.total < (1 << 20) ? a.total : (1 << 20));
-    if (count)
-        hipLaunchKernelGGL(psroi_kernel<false>, dim3(grid), dim3(PSROI_THREADS), lds, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(psroi_kernel<true>, dim3(grid), dim3(PSROI_THREADS), lds, (hipStream_t)stream, a);
-    H3D_CHECK_LAUNCH("psroi_kernel");
-    return H3D_OK;
+    if (count) return h3d_launch({"psroi_kernel", false}, psroi_kernel<false>, dim3(grid), dim3(PSROI_THREADS), lds, (hipStream_t)stream, a);
+    return h3d_launch({"psroi_kernel", true}, psroi_kernel<true>, dim3(grid), dim3(PSROI_THREADS), lds, (hipStream_t)stream, a);
 }
 
 static int psroi_check_common(const char *what, int B, int C, int H, int W, int R, int output_dim, int group_size, int P, int part,

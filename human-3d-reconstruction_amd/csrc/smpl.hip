@@ -167,10 +167,8 @@ extern "C" int h3d_smpl_pose(const float *betas, const float *thetas, const floa
     if (!betas || !thetas || !j_template || !j_shapedirs || !parents || !pose_feat || !A || !joints)
         H3D_FAIL(H3D_ERR_ARG, "smpl_pose: null pointer");
     if (P <= 0 || (coefT && Ppad < P)) H3D_FAIL(H3D_ERR_SHAPE, "smpl_pose: P=%d Ppad=%d", P, Ppad);
-    hipLaunchKernelGGL(smpl_pose_kernel<false>, dim3(cdiv(P, 2)), dim3(64), 0, (hipStream_t)stream, betas, thetas, j_template,
-                       j_shapedirs, parents, P, pose_feat, A, joints, coefT, Ppad, SmplHeadsSrc{});
-    H3D_CHECK_LAUNCH("smpl_pose_kernel");
-    return H3D_OK;
+    return h3d_launch({"smpl_pose_kernel", false}, smpl_pose_kernel<false>, dim3(cdiv(P, 2)), dim3(64), 0, (hipStream_t)stream, betas, thetas, j_template,
+                      j_shapedirs, parents, P, pose_feat, A, joints, coefT, Ppad, SmplHeadsSrc{});
 }
 
 extern "C" int h3d_smpl_pose_heads(const float *pose_map, const float *shape_map, const int64_t *inds, int B, int K, int n, int HW,
@@ -184,10 +182,8 @@ extern "C" int h3d_smpl_pose_heads(const float *pose_map, const float *shape_map
     SmplHeadsSrc hs;
     hs.pose_map = pose_map; hs.shape_map = shape_map; hs.inds = inds; hs.n = n; hs.K = K; hs.HW = HW; hs.betas_out = betas_out;
     hs.coefK3 = (bf16_t *)coefK3;
-    hipLaunchKernelGGL(smpl_pose_kernel<true>, dim3(cdiv(Ppad, 2)), dim3(64), 0, (hipStream_t)stream, nullptr, nullptr, j_template, j_shapedirs,
-                       parents, P, pose_feat, A, joints, nullptr, Ppad, hs);
-    H3D_CHECK_LAUNCH("smpl_pose_kernel");
-    return H3D_OK;
+    return h3d_launch({"smpl_pose_kernel", true}, smpl_pose_kernel<true>, dim3(cdiv(Ppad, 2)), dim3(64), 0, (hipStream_t)stream, nullptr, nullptr, j_template,
+                      j_shapedirs, parents, P, pose_feat, A, joints, nullptr, Ppad, hs);
 }
 
 // Block = 256 lanes = 256 vertices x PT persons.  The blend-shape contraction
@@ -455,10 +451,8 @@ extern "C" int h3d_smpl_verts2(const float *coefT, const float *A, const float *
         H3D_FAIL(H3D_ERR_SHAPE, "smpl_verts2: P=%d (pad %d, multiple of %d) V=%d (pad %d, multiple of %d) nnz=%d (<= 4)", P, Ppad,
                  SV_PB, V, Vpad, SV_VT, nnz);
     dim3 grid(Vpad / SV_VT, Ppad / SV_PB);
-    hipLaunchKernelGGL(smpl_verts2_kernel, grid, dim3(256), 0, (hipStream_t)stream, coefT, A, v_template, shapedirsT, posedirsT,
-                       lbs_idx, lbs_w, nnz, P, Ppad, V, Vpad, verts);
-    H3D_CHECK_LAUNCH("smpl_verts2_kernel");
-    return H3D_OK;
+    return h3d_launch({"smpl_verts2_kernel"}, smpl_verts2_kernel, grid, dim3(256), 0, (hipStream_t)stream, coefT, A, v_template, shapedirsT, posedirsT,
+                      lbs_idx, lbs_w, nnz, P, Ppad, V, Vpad, verts);
 #endif
 }
 
@@ -470,19 +464,11 @@ extern "C" int h3d_smpl_verts(const float *betas, const float *pose_feat, const 
         H3D_FAIL(H3D_ERR_ARG, "smpl_verts: null pointer");
     if (P <= 0 || V <= 0 || Vpad < V || nnz <= 0 || nnz > SMPL_J) H3D_FAIL(H3D_ERR_SHAPE, "smpl_verts: P=%d V=%d nnz=%d", P, V, nnz);
     dim3 grid(cdiv(V, 256), 1);
-    if (P >= 64) {
-        constexpr int PT = 32;
+    return h3d_by_values([&](auto PT) {
         grid.y = cdiv(P, PT);
-        hipLaunchKernelGGL(smpl_verts_kernel<PT>, grid, dim3(256), 0, (hipStream_t)stream, betas, pose_feat, A, v_template,
-                           shapedirsT, posedirsT, lbs_idx, lbs_w, nnz, P, V, Vpad, verts);
-    } else {
-        constexpr int PT = 8;
-        grid.y = cdiv(P, PT);
-        hipLaunchKernelGGL(smpl_verts_kernel<PT>, grid, dim3(256), 0, (hipStream_t)stream, betas, pose_feat, A, v_template,
-                           shapedirsT, posedirsT, lbs_idx, lbs_w, nnz, P, V, Vpad, verts);
-    }
-    H3D_CHECK_LAUNCH("smpl_verts_kernel");
-    return H3D_OK;
+        return h3d_launch({"smpl_verts_kernel", PT}, smpl_verts_kernel<PT>, grid, dim3(256), 0, (hipStream_t)stream, betas, pose_feat, A, v_template,
+                          shapedirsT, posedirsT, lbs_idx, lbs_w, nnz, P, V, Vpad, verts);
+    }, h3d_vals<32, 8>{}, P >= 64 ? 32 : 8);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -676,10 +662,8 @@ extern "C" int h3d_smpl_coef_pack(const float *betas, const float *pose_feat, in
     if (!betas || !pose_feat || !coefK3) H3D_FAIL(H3D_ERR_ARG, "smpl_coef_pack: null pointer");
     if (P <= 0 || Ppad < P || Ppad % S3_PPAD) H3D_FAIL(H3D_ERR_SHAPE, "smpl_coef_pack: P=%d Ppad=%d (multiple of %d)", P, Ppad, S3_PPAD);
     const size_t n = (size_t)Ppad * S3_KP;
-    hipLaunchKernelGGL(smpl_coef_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, betas, pose_feat, P,
-                       Ppad, (bf16_t *)coefK3);
-    H3D_CHECK_LAUNCH("smpl_coef_pack_kernel");
-    return H3D_OK;
+    return h3d_launch({"smpl_coef_pack_kernel"}, smpl_coef_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, betas, pose_feat,
+                      P, Ppad, (bf16_t *)coefK3);
 }
 
 static int smpl_verts3_impl(bool six, const void *coefK3, const float *A, const float *v_template, const void *dirsK3,
@@ -699,14 +683,10 @@ static int smpl_verts3_impl(bool six, const void *coefK3, const float *A, const 
     if ((size_t)3 * Vpad * S3_GROW >= 0x7ffffff0ull || (size_t)Ppad * S3_GROW >= 0x7ffffff0ull)
         H3D_FAIL(H3D_ERR_SHAPE, "smpl_verts3: operand of 2 GiB or more");
     dim3 grid(Vpad / S3_VT, cdiv(Ppad, S3_PB));      // (coefficient rows past Ppad are outside the buffer: zeros)
-    if (six)
-        hipLaunchKernelGGL(smpl_verts3_kernel<true>, grid, dim3(64 * S3_NW), 0, (hipStream_t)stream, (const bf16_t *)coefK3, A, v_template,
-                           (const bf16_t *)dirsK3, lbs_idx, lbs_w, nnz | nnz_flags, P, Ppad, V, Vpad, verts);
-    else
-        hipLaunchKernelGGL(smpl_verts3_kernel<false>, grid, dim3(64 * S3_NW), 0, (hipStream_t)stream, (const bf16_t *)coefK3, A, v_template,
-                           (const bf16_t *)dirsK3, lbs_idx, lbs_w, nnz | nnz_flags, P, Ppad, V, Vpad, verts);
-    H3D_CHECK_LAUNCH("smpl_verts3_kernel");
-    return H3D_OK;
+    return h3d_by_values([&](auto SIX) {
+        return h3d_launch({"smpl_verts3_kernel", SIX}, smpl_verts3_kernel<SIX>, grid, dim3(64 * S3_NW), 0, (hipStream_t)stream, (const bf16_t *)coefK3, A,
+                          v_template, (const bf16_t *)dirsK3, lbs_idx, lbs_w, nnz | nnz_flags, P, Ppad, V, Vpad, verts);
+    }, h3d_vals<false, true>{}, six);
 }
 
 extern "C" int h3d_smpl_verts3(const void *coefK3, const float *A, const float *v_template, const void *dirsK3,

@@ -31,7 +31,6 @@ constexpr int SB_WS = 25;                     // row stride (floats) of the tile
 constexpr int SB_KC = 1536;                   // contraction elements per split of the coefficient kernel (96 MFMA steps)
 constexpr int SB_KP = 224;                    // coefficient rows, padded as the forward pads K
 
-static inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 static inline int sb_groups(int Vpad) { return cdiv(Vpad / S3_VT, SB_NVT); }
 static inline int sb_splits(int Vpad) { return cdiv(3 * Vpad, SB_KC); }
 
@@ -469,15 +468,15 @@ static SbWorkspace sb_layout(int P, int Vpad)
 {
     const size_t Ppad = (size_t)cdiv(P, S3_PPAD) * S3_PPAD;
     SbWorkspace w;
-    size_t o = 0;
-    w.pf = o; o += a256((size_t)4 * P * SMPL_PF);
-    w.A = o; o += a256((size_t)4 * P * SMPL_J * 12);
-    w.joints = o; o += a256((size_t)4 * P * SMPL_J * 3);
-    w.coefK3 = o; o += a256(Ppad * S3_GROW);
-    w.gvp = o; o += a256((size_t)4 * P * 3 * Vpad);
-    w.gApart = o; o += a256((size_t)4 * sb_groups(Vpad) * P * SMPL_J * 12);
-    w.gcpart = o; o += a256((size_t)4 * sb_splits(Vpad) * P * SB_KP);
-    w.total = o;
+    h3d_ws_layout ws;
+    w.pf = ws.take((size_t)4 * P * SMPL_PF);
+    w.A = ws.take((size_t)4 * P * SMPL_J * 12);
+    w.joints = ws.take((size_t)4 * P * SMPL_J * 3);
+    w.coefK3 = ws.take(Ppad * S3_GROW);
+    w.gvp = ws.take((size_t)4 * P * 3 * Vpad);
+    w.gApart = ws.take((size_t)4 * sb_groups(Vpad) * P * SMPL_J * 12);
+    w.gcpart = ws.take((size_t)4 * sb_splits(Vpad) * P * SB_KP);
+    w.total = ws.total;
     return w;
 }
 
@@ -509,14 +508,11 @@ static int sb_vertex_part(const SbWorkspace &w, char *ws, const float *grad_vert
     const int NG = sb_groups(Vpad), NS = sb_splits(Vpad);
     if (hipMemsetAsync(ws + w.gApart, 0, (size_t)4 * NG * P * SMPL_J * 12, st) != hipSuccess)
         H3D_FAIL(H3D_ERR_LAUNCH, "smpl_backward: clearing the transform-gradient partials failed");
-    hipLaunchKernelGGL(smpl_bwd_verts_kernel, dim3(NG, cdiv(Ppad, S3_PB)), dim3(64 * S3_NW), 0, st, (const bf16_t *)(ws + w.coefK3),
+    H3D_TRY(h3d_launch({"smpl_bwd_verts_kernel"}, smpl_bwd_verts_kernel, dim3(NG, cdiv(Ppad, S3_PB)), dim3(64 * S3_NW), 0, st, (const bf16_t *)(ws + w.coefK3),
                        (const float *)(ws + w.A), v_template, (const bf16_t *)dirsK3, lbs_idx, lbs_w, nnz, P, Ppad, V, Vpad, grad_verts,
-                       (float *)(ws + w.gvp), (float *)(ws + w.gApart));
-    H3D_CHECK_LAUNCH("smpl_bwd_verts_kernel");
-    hipLaunchKernelGGL(smpl_bwd_coef_kernel, dim3(cdiv(P, 128), NS), dim3(256), 0, st, (const float *)(ws + w.gvp), (const bf16_t *)dirsV3, P,
-                       3 * Vpad, (float *)(ws + w.gcpart));
-    H3D_CHECK_LAUNCH("smpl_bwd_coef_kernel");
-    return H3D_OK;
+                       (float *)(ws + w.gvp), (float *)(ws + w.gApart)));
+    return h3d_launch({"smpl_bwd_coef_kernel"}, smpl_bwd_coef_kernel, dim3(cdiv(P, 128), NS), dim3(256), 0, st, (const float *)(ws + w.gvp),
+                      (const bf16_t *)dirsV3, P, 3 * Vpad, (float *)(ws + w.gcpart));
 }
 
 extern "C" int h3d_smpl_backward(const float *betas, const float *thetas, const float *grad_verts, const float *grad_joints,
@@ -552,11 +548,9 @@ extern "C" int h3d_smpl_backward(const float *betas, const float *thetas, const 
         rc = sb_vertex_part(w, ws, grad_verts, v_template, dirsK3, dirsV3, lbs_idx, lbs_w, nnz, P, V, Vpad, st);
         if (rc != H3D_OK) return rc;
     }
-    hipLaunchKernelGGL(smpl_bwd_pose_kernel<false>, dim3(cdiv(P, 2)), dim3(64), 0, st, betas, thetas, j_template, j_shapedirs, parents, P,
-                       grad_joints, grad_verts ? (const float *)(ws + w.gApart) : nullptr, sb_groups(Vpad),
-                       grad_verts ? (const float *)(ws + w.gcpart) : nullptr, sb_splits(Vpad), grad_betas, grad_thetas, SmplBwdHeads{});
-    H3D_CHECK_LAUNCH("smpl_bwd_pose_kernel");
-    return H3D_OK;
+    return h3d_launch({"smpl_bwd_pose_kernel", false}, smpl_bwd_pose_kernel<false>, dim3(cdiv(P, 2)), dim3(64), 0, st, betas, thetas, j_template, j_shapedirs,
+                      parents, P, grad_joints, grad_verts ? (const float *)(ws + w.gApart) : nullptr, sb_groups(Vpad),
+                      grad_verts ? (const float *)(ws + w.gcpart) : nullptr, sb_splits(Vpad), grad_betas, grad_thetas, SmplBwdHeads{});
 }
 
 extern "C" int h3d_smpl_heads_backward(const float *pose_map, const float *shape_map, const int64_t *inds, int B, int K, int n, int HW,
@@ -595,9 +589,7 @@ extern "C" int h3d_smpl_heads_backward(const float *pose_map, const float *shape
     SmplBwdHeads hs;
     hs.pose_map = pose_map; hs.shape_map = shape_map; hs.inds = inds; hs.n = n; hs.K = K; hs.HW = HW;
     hs.gpose = grad_pose_map; hs.gshape = grad_shape_map;
-    hipLaunchKernelGGL(smpl_bwd_pose_kernel<true>, dim3(cdiv(P, 2)), dim3(64), 0, st, nullptr, nullptr, j_template, j_shapedirs, parents, P,
-                       grad_joints, grad_verts ? (const float *)(ws + w.gApart) : nullptr, sb_groups(Vpad),
-                       grad_verts ? (const float *)(ws + w.gcpart) : nullptr, sb_splits(Vpad), nullptr, nullptr, hs);
-    H3D_CHECK_LAUNCH("smpl_bwd_pose_kernel");
-    return H3D_OK;
+    return h3d_launch({"smpl_bwd_pose_kernel", true}, smpl_bwd_pose_kernel<true>, dim3(cdiv(P, 2)), dim3(64), 0, st, nullptr, nullptr, j_template, j_shapedirs,
+                      parents, P, grad_joints, grad_verts ? (const float *)(ws + w.gApart) : nullptr, sb_groups(Vpad),
+                      grad_verts ? (const float *)(ws + w.gcpart) : nullptr, sb_splits(Vpad), nullptr, nullptr, hs);
 }

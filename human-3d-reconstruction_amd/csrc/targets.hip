@@ -337,14 +337,13 @@ int tgt_check(const char *who, const void *boxes, const void *second, const void
     return H3D_OK;
 }
 
-int tgt_launch(const char *who, bool pose, const TgtArgs &a, const int32_t *rot_flag, float *hm, float *hm_hp, void *stream)
+int tgt_launch(bool pose, const TgtArgs &a, const int32_t *rot_flag, float *hm, float *hm_hp, void *stream)
 {
     hipStream_t st = (hipStream_t)stream;
     const long waves = (long)a.B * a.max_objs;
     const dim3 grid((unsigned)((waves + 3) / 4));
-    if (pose) hipLaunchKernelGGL(targets_objects_kernel<true>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(targets_objects_kernel<false>, grid, dim3(256), 0, st, a);
-    H3D_CHECK_LAUNCH(who);
+    if (pose) H3D_TRY(h3d_launch({"targets_objects_kernel", true}, targets_objects_kernel<true>, grid, dim3(256), 0, st, a));
+    else H3D_TRY(h3d_launch({"targets_objects_kernel", false}, targets_objects_kernel<false>, grid, dim3(256), 0, st, a));
     if (!hm && !hm_hp) return H3D_OK;
     // a map whose first pixel sits `al` elements behind a 16-byte boundary takes ceil((HW + al) / 1024) workgroups; with HW % 4 != 0 the
     // maps of a tensor differ in it
@@ -353,9 +352,7 @@ int tgt_launch(const char *who, bool pose, const TgtArgs &a, const int32_t *rot_
     if (HW % 4 == 0) al = max(hm ? (int)(((uintptr_t)hm >> 2) & 3) : 0, hm_hp ? (int)(((uintptr_t)hm_hp >> 2) & 3) : 0);
     TgtRenderArgs r = {hm, hm_hp, a.list, rot_flag, a.C, a.J, a.H, a.W, a.max_objs};
     const dim3 rgrid((unsigned)((HW + al + TGT_CHUNK - 1) / TGT_CHUNK), (unsigned)(a.C + a.J), (unsigned)a.B);
-    hipLaunchKernelGGL(targets_render_kernel, rgrid, dim3(256), 0, st, r);
-    H3D_CHECK_LAUNCH(who);
-    return H3D_OK;
+    return h3d_launch({"targets_render_kernel"}, targets_render_kernel, rgrid, dim3(256), 0, st, r);
 }
 
 }  // namespace
@@ -392,7 +389,7 @@ extern "C" int h3d_multi_pose_targets(const float *boxes, const float *keypoints
     a.wh = wh, a.reg = reg, a.ind = ind, a.reg_mask = reg_mask, a.kps = kps, a.kps_mask = kps_mask, a.hp_offset = hp_offset;
     a.hp_ind = hp_ind, a.hp_mask = hp_mask, a.gt_det = gt_det, a.gt_count = gt_count;
     a.list = (hm || hm_hp) ? (int4 *)workspace : nullptr;
-    return tgt_launch(who, true, a, rot_flag, hm, hm_hp, stream);
+    return tgt_launch(true, a, rot_flag, hm, hm_hp, stream);
 }
 
 extern "C" int h3d_ctdet_targets(const float *boxes, const int32_t *cls, const int32_t *num, const double *trans, const int32_t *flipped,
@@ -413,5 +410,5 @@ extern "C" int h3d_ctdet_targets(const float *boxes, const int32_t *cls, const i
     a.wh = wh, a.reg = reg, a.ind = ind, a.reg_mask = reg_mask, a.cat_wh = cat_spec_wh, a.cat_mask = cat_spec_mask;
     a.gt_det = gt_det, a.gt_count = gt_count;
     a.list = hm ? (int4 *)workspace : nullptr;
-    return tgt_launch(who, false, a, nullptr, hm, nullptr, stream);
+    return tgt_launch(false, a, nullptr, hm, nullptr, stream);
 }

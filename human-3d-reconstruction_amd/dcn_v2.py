@@ -11,7 +11,6 @@ raises; parameters may require grad (the nn.Parameter default), results are comp
 Training is opt-in: `dcn_v2_backward` (the `_ext` entry point, DCNv2/src/dcn_v2.h:41-74; kernels: csrc/dcn_bwd.hip), the autograd
 function `_DCNv2` / `dcn_v2_conv_autograd` (dcn_v2.py:16-51) and the modules `TrainableDCNv2` / `TrainableDCN` (same constructors and
 state_dict keys as `DCNv2` / `DCN`; their forward builds a graph).  dcn_v2_psroi_pooling_backward is not implemented."""
-import ctypes
 import math
 
 import os
@@ -67,6 +66,30 @@ def _packed_weights(weight, bias, dtype):
     return ent[0]
 
 
+def _dcn_operands(what, input, weight, bias, offset, mask, geo):
+    """The shape checks dcn_v2_forward and dcn_v2_backward share (the reference's messages, dcn_v2_cuda.cu:60-66) -> (B, C, H, W, Cout, Ho, Wo)."""
+    kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group = geo
+    if input.dim() != 4 or weight.dim() != 4:
+        raise RuntimeError("%s: input must be [B,C,H,W] and weight [Cout,C,kh,kw]" % what)
+    B, C, H, W = input.shape
+    Cout, Ck, kh_, kw_ = weight.shape
+    if kh_ != kernel_h or kw_ != kernel_w:
+        raise RuntimeError("Input shape and kernel shape wont match: (%d x %d vs %d x %d)."
+                           % (kernel_h, kernel_w, kh_, kw_))
+    if C != Ck:
+        raise RuntimeError("Input shape and kernel channels wont match: (%d vs %d)." % (C, Ck))
+    Ho = (H + 2 * pad_h - (dilation_h * (kernel_h - 1) + 1)) // stride_h + 1
+    Wo = (W + 2 * pad_w - (dilation_w * (kernel_w - 1) + 1)) // stride_w + 1
+    if tuple(offset.shape) != (B, 2 * deformable_group * kernel_h * kernel_w, Ho, Wo):
+        raise RuntimeError("offset shape %s does not match [B, 2*dg*kh*kw, Ho, Wo] = %s"
+                           % (tuple(offset.shape), (B, 2 * deformable_group * kernel_h * kernel_w, Ho, Wo)))
+    if tuple(mask.shape) != (B, deformable_group * kernel_h * kernel_w, Ho, Wo):
+        raise RuntimeError("mask shape %s does not match [B, dg*kh*kw, Ho, Wo]" % (tuple(mask.shape),))
+    if bias.numel() != Cout:
+        raise RuntimeError("bias has %d elements, expected %d" % (bias.numel(), Cout))
+    return B, C, H, W, Cout, Ho, Wo
+
+
 def dcn_v2_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride_h, stride_w,
                    pad_h, pad_w, dilation_h, dilation_w, deformable_group):
     """Positional twin of `_ext.dcn_v2_forward` (dcn_v2.py:25-31 call site): fp32 contiguous NCHW CUDA tensors in, a new
@@ -90,22 +113,8 @@ def dcn_v2_forward(input, weight, bias, offset, mask, kernel_h, kernel_w, stride
     if not nhwc:
         input = input.contiguous()
     weight, bias, offset, mask = [t.contiguous() for t in (weight, bias, offset, mask)]
-    B, C, H, W = input.shape
-    Cout, Ck, kh_, kw_ = weight.shape
-    if kh_ != kernel_h or kw_ != kernel_w:
-        raise RuntimeError("Input shape and kernel shape wont match: (%d x %d vs %d x %d)."
-                           % (kernel_h, kernel_w, kh_, kw_))
-    if C != Ck:
-        raise RuntimeError("Input shape and kernel channels wont match: (%d vs %d)." % (C, Ck))
-    Ho = (H + 2 * pad_h - (dilation_h * (kernel_h - 1) + 1)) // stride_h + 1
-    Wo = (W + 2 * pad_w - (dilation_w * (kernel_w - 1) + 1)) // stride_w + 1
-    if tuple(offset.shape) != (B, 2 * deformable_group * kernel_h * kernel_w, Ho, Wo):
-        raise RuntimeError("offset shape %s does not match [B, 2*dg*kh*kw, Ho, Wo] = %s"
-                           % (tuple(offset.shape), (B, 2 * deformable_group * kernel_h * kernel_w, Ho, Wo)))
-    if tuple(mask.shape) != (B, deformable_group * kernel_h * kernel_w, Ho, Wo):
-        raise RuntimeError("mask shape %s does not match [B, dg*kh*kw, Ho, Wo]" % (tuple(mask.shape),))
-    if bias.numel() != Cout:
-        raise RuntimeError("bias has %d elements, expected %d" % (bias.numel(), Cout))
+    B, C, H, W, Cout, Ho, Wo = _dcn_operands("dcn_v2_forward", input, weight, bias, offset, mask,
+                                             (kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group))
     fast = ((kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group)
             == (3, 3, 1, 1, 1, 1, 1, 1, 1) and C % 16 == 0 and H <= 32767 and W <= 32767)
     L = _lib.lib()
@@ -325,36 +334,18 @@ def _dcn_v2_backward(input, weight, bias, offset, mask, grad_output, kernel_h, k
         if t.dtype != torch.float32:
             raise RuntimeError("dcn_v2_backward: expected float32 tensors (reference uses .data<float>())")
     input, weight, bias, offset, mask, grad_output = [t.contiguous() for t in (input, weight, bias, offset, mask, grad_output)]
-    if input.dim() != 4 or weight.dim() != 4:
-        raise RuntimeError("dcn_v2_backward: input must be [B,C,H,W] and weight [Cout,C,kh,kw]")
-    B, C, H, W = input.shape
-    Cout, Ck, kh_, kw_ = weight.shape
-    if kh_ != kernel_h or kw_ != kernel_w:
-        raise RuntimeError("Input shape and kernel shape wont match: (%d x %d vs %d x %d)."
-                           % (kernel_h, kernel_w, kh_, kw_))
-    if C != Ck:
-        raise RuntimeError("Input shape and kernel channels wont match: (%d vs %d)." % (C, Ck))
-    Ho = (H + 2 * pad_h - (dilation_h * (kernel_h - 1) + 1)) // stride_h + 1
-    Wo = (W + 2 * pad_w - (dilation_w * (kernel_w - 1) + 1)) // stride_w + 1
-    if tuple(offset.shape) != (B, 2 * deformable_group * kernel_h * kernel_w, Ho, Wo):
-        raise RuntimeError("offset shape %s does not match [B, 2*dg*kh*kw, Ho, Wo] = %s"
-                           % (tuple(offset.shape), (B, 2 * deformable_group * kernel_h * kernel_w, Ho, Wo)))
-    if tuple(mask.shape) != (B, deformable_group * kernel_h * kernel_w, Ho, Wo):
-        raise RuntimeError("mask shape %s does not match [B, dg*kh*kw, Ho, Wo]" % (tuple(mask.shape),))
-    if bias.numel() != Cout:
-        raise RuntimeError("bias has %d elements, expected %d" % (bias.numel(), Cout))
+    B, C, H, W, Cout, Ho, Wo = _dcn_operands("dcn_v2_backward", input, weight, bias, offset, mask,
+                                             (kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group))
     if tuple(grad_output.shape) != (B, Cout, Ho, Wo):
         raise RuntimeError("grad_output shape %s does not match [B, Cout, Ho, Wo] = %s" % (tuple(grad_output.shape), (B, Cout, Ho, Wo)))
     geo = (B, C, H, W, Cout, kernel_h, kernel_w, stride_h, stride_w, pad_h, pad_w, dilation_h, dilation_w, deformable_group)
     L = _lib.lib()
     with torch.cuda.device(input.device):
-        nws = ctypes.c_size_t(0)
-        _lib.check(L.h3d_dcn_v2_backward_workspace_bytes(*geo, ctypes.byref(nws)), "dcn_v2_backward")
-        ws = torch.empty(max(int(nws.value), 1), dtype=torch.uint8, device=input.device)
+        ws = _lib.workspace(L.h3d_dcn_v2_backward_workspace_bytes, *geo, device=input.device, min_bytes=1, what="dcn_v2_backward")
         outs = [torch.empty_like(t) if n else None for t, n in zip((input, offset, mask, weight, bias), need)]
         fn = L.h3d_dcn_v2_backward_general if general else L.h3d_dcn_v2_backward
         rc = fn(*[_lib.ptr(t) for t in (input, weight, bias, offset, mask, grad_output)], *[_lib.ptr(t) for t in outs], *geo,
-                _lib.ptr(ws), int(nws.value), _lib.stream_ptr())
+                _lib.ptr(ws), ws.numel(), _lib.stream_ptr())
     _lib.check(rc, "dcn_v2_backward")
     return tuple(outs)
 

@@ -24,11 +24,8 @@ def _workspace(dev, B, H, W, hc, chans):
     key = (str(dev), B, H, W, hc, tuple(chans))
     ws = _WORKSPACES.get(key)
     if ws is None:
-        n = ctypes.c_size_t(0)
         carr = (ctypes.c_int * max(len(chans), 1))(*chans)
-        _lib.check(_lib.lib().h3d_heads_backward_workspace_bytes(B, H, W, hc, len(chans), carr, ctypes.byref(n)),
-                   "h3d_heads_backward_workspace_bytes")
-        ws = torch.empty(max(n.value, 256), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(_lib.lib().h3d_heads_backward_workspace_bytes, B, H, W, hc, len(chans), carr, device=dev, min_bytes=256)
         _WORKSPACES[key] = ws
     return ws
 

@@ -114,9 +114,7 @@ def forward_terms(terms):
     dev = terms[0].x.device if terms else torch.device("cuda")
     L = _lib.lib()
     arr = _term_array(terms)
-    n = ctypes.c_size_t(0)
-    _lib.check(L.h3d_loss_workspace_bytes(arr, len(terms), ctypes.byref(n)), "h3d_loss_workspace_bytes")
-    ws = torch.empty(max(n.value, 16), dtype=torch.uint8, device=dev)
+    ws = _lib.workspace(L.h3d_loss_workspace_bytes, arr, len(terms), device=dev, min_bytes=16)
     stats = torch.empty(4 * len(terms) + 1, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(L.h3d_loss_forward(arr, len(terms), _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "h3d_loss_forward")

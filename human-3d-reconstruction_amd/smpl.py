@@ -165,7 +165,6 @@ def lbs_backward(model, betas, thetas, grad_verts=None, grad_joints=None):
     gradients grad_verts [P,V,3] and / or grad_joints [P,24,3] (None = absent) -> (grad_betas [P,10], grad_thetas [P,72]), fp32.
     Everything is recomputed from betas / thetas (h3d_smpl_backward, include/h3d.h section 4b); the sums run in a fixed order, so two
     calls give the same bits.  Needs <= 4 skinning weights per vertex."""
-    import ctypes
     import torch
     from . import _lib
     _lib.require_cuda(betas, thetas, grad_verts, grad_joints)
@@ -185,22 +184,19 @@ def lbs_backward(model, betas, thetas, grad_verts=None, grad_joints=None):
     gb = torch.empty(P, NUM_BETAS, dtype=torch.float32, device=dev)
     gt = torch.empty(P, 72, dtype=torch.float32, device=dev)
     L = _lib.lib()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.h3d_smpl_backward_workspace_bytes(P, d["V"], d["Vpad"], d["nnz"], int(gv is not None), ctypes.byref(nbytes)),
-               "smpl_backward_workspace_bytes")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if nbytes.value else None
+    ws = _lib.workspace(L.h3d_smpl_backward_workspace_bytes, P, d["V"], d["Vpad"], d["nnz"], int(gv is not None), device=dev,
+                        what="smpl_backward_workspace_bytes")
     with torch.cuda.device(dev):
         st = _lib.stream_ptr()              # the current stream of `dev`, as the forward
         _lib.check(L.h3d_smpl_backward(_lib.ptr(betas), _lib.ptr(thetas), _lib.ptr(gv), _lib.ptr(gj), _lib.ptr(d["j_template"]),
                                        _lib.ptr(d["j_shapedirs"]), _lib.ptr(d["parents"]), _lib.ptr(d["v_template"]), _lib.ptr(d["dirsK3"]),
                                        _lib.ptr(d["dirsV3"]), _lib.ptr(d["lbs_idx"]), _lib.ptr(d["lbs_w"]), d["nnz"], P, d["V"], d["Vpad"],
-                                       _lib.ptr(gb), _lib.ptr(gt), _lib.ptr(ws), nbytes.value, st), "smpl_backward")
+                                       _lib.ptr(gb), _lib.ptr(gt), _lib.ptr(ws), ws.numel() if ws is not None else 0, st), "smpl_backward")
     return gb, gt
 
 
 def _heads_backward(model, pose_map, shape_map, inds, n, grad_verts, grad_joints):
     """h3d_smpl_heads_backward: -> (grad_pose_map, grad_shape_map), shaped like the maps."""
-    import ctypes
     import torch
     from . import _lib
     dev = pose_map.device
@@ -213,17 +209,15 @@ def _heads_backward(model, pose_map, shape_map, inds, n, grad_verts, grad_joints
     gp = torch.empty_like(pose_map)
     gs = torch.empty_like(shape_map)
     L = _lib.lib()
-    nbytes = ctypes.c_size_t(0)
-    _lib.check(L.h3d_smpl_backward_workspace_bytes(P, d["V"], d["Vpad"], d["nnz"], int(gv is not None), ctypes.byref(nbytes)),
-               "smpl_backward_workspace_bytes")
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev) if nbytes.value else None
+    ws = _lib.workspace(L.h3d_smpl_backward_workspace_bytes, P, d["V"], d["Vpad"], d["nnz"], int(gv is not None), device=dev,
+                        what="smpl_backward_workspace_bytes")
     with torch.cuda.device(dev):
         st = _lib.stream_ptr()
         _lib.check(L.h3d_smpl_heads_backward(_lib.ptr(pose_map), _lib.ptr(shape_map), _lib.ptr(inds), B, K, n, HW, _lib.ptr(gv), _lib.ptr(gj),
                                              _lib.ptr(d["j_template"]), _lib.ptr(d["j_shapedirs"]), _lib.ptr(d["parents"]),
                                              _lib.ptr(d["v_template"]), _lib.ptr(d["dirsK3"]), _lib.ptr(d["dirsV3"]), _lib.ptr(d["lbs_idx"]),
                                              _lib.ptr(d["lbs_w"]), d["nnz"], d["V"], d["Vpad"], _lib.ptr(gp), _lib.ptr(gs), _lib.ptr(ws),
-                                             nbytes.value, st), "smpl_heads_backward")
+                                             ws.numel() if ws is not None else 0, st), "smpl_heads_backward")
     return gp, gs
 
 

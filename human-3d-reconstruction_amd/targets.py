@@ -10,7 +10,6 @@ libh3d_hip.so (csrc/targets.hip, include/h3d.h section 6) in two launches.
 The dicts feed h3d_amd.losses.loss_multi_pose / loss_obj_detection unchanged.  Out of scope (ValueError here, H3D_ERR_UNSUPPORTED from the
 ABI): mse_loss (draw_msra_gaussian), dense_hp and dense_wh (draw_dense_reg depends on the object order), and the train branch of
 _get_input (random crop, colour augmentation): c, s, rot, flipped are inputs."""
-import ctypes
 
 import numpy as np
 import torch
@@ -82,9 +81,7 @@ def _dev(x, dtype, device):
 
 
 def _workspace(B, max_objs, J, device):
-    n = ctypes.c_size_t(0)
-    _lib.check(_lib.lib().h3d_targets_workspace_bytes(B, max_objs, J, ctypes.byref(n)), "h3d_targets_workspace_bytes")
-    return torch.empty(max(n.value, 16), dtype=torch.uint8, device=device)
+    return _lib.workspace(_lib.lib().h3d_targets_workspace_bytes, B, max_objs, J, device=device, min_bytes=16)
 
 
 def pose_output_specs(B, max_objs, J, H, W):

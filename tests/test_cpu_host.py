@@ -44,6 +44,51 @@ def test_abi4_operator_workspaces_hold_the_activation_maxima():
     assert L.h3d_dcn_nchw_to_nhwc_scaled(None, None, 1, 16, 4, 4, None, None) == -5 and b"null pointer" in L.h3d_last_error()
 
 
+def _ctype_of(param):
+    """ctypes classes a C parameter declaration of include/h3d.h may be bound as."""
+    if "*" in param:
+        if re.match(r"(const )?size_t \*", param):
+            return (ctypes.POINTER(ctypes.c_size_t),)
+        return (ctypes.c_void_p, ctypes.c_char_p, ctypes._Pointer)
+    return {"int": (ctypes.c_int,), "int32_t": (ctypes.c_int,), "size_t": (ctypes.c_size_t,), "float": (ctypes.c_float,)}[param.rsplit(" ", 1)[0]]
+
+
+def test_every_ctypes_signature_matches_its_declaration():
+    L = _lib.lib()
+    hdr = re.sub(r"//[^\n]*|/\*.*?\*/", "", open(os.path.join(ROOT, "include", "h3d.h")).read(), flags=re.S)
+    decls = {name: (ret, [] if params.strip() == "void" else [" ".join(p.split()) for p in params.split(",")])
+             for ret, name, params in re.findall(r"^(int|size_t|const char \*) ?(h3d_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr, flags=re.M)}
+    assert set(decls) == set(re.findall(r"\b(h3d_[a-z0-9_]+)\s*\(", hdr)) and len(decls) == len(_lib.SIGNATURES) + 6
+    bound = dict(_lib.SIGNATURES)
+    for name, (ret, _) in decls.items():
+        if ret == "size_t":
+            fn = getattr(L, name)
+            assert name not in bound and fn.restype is ctypes.c_size_t, name
+            bound[name] = fn.argtypes
+    for name, args in bound.items():
+        params = decls[name][1]
+        assert len(args) == len(params), (name, len(args), len(params))
+        for k, (a, p) in enumerate(zip(args, params)):
+            assert a in _ctype_of(p) or issubclass(a, ctypes._Pointer) and ctypes._Pointer in _ctype_of(p), (name, k, p, a)
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    # tests/golden/workspace_bytes.json: written by tools/gen_workspace_golden.py (which holds the shapes) before the layouts moved
+    # onto h3d_ws_layout; region order, sizes and alignment of every workspace are part of what a caller may have sized buffers by
+    import importlib.util
+    import json
+    spec = importlib.util.spec_from_file_location("gen_workspace_golden", os.path.join(ROOT, "tools", "gen_workspace_golden.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "workspace_bytes.json")))
+    got = json.loads(json.dumps(gen.table()))
+    assert set(got) == set(want) and all(len(rows) >= 12 for rows in want.values())
+    for name in want:
+        for g, w in zip(got[name], want[name]):
+            assert g == w, (name, g, w)
+        assert len(got[name]) == len(want[name]), name
+
+
 def test_op_struct_matches_header_layout():
     # 2 int32, 5 pointers, 18 int32 (ABI 2: + wexp, wexp2) -> 8 + 40 + 72 = 120 bytes on LP64
     assert ctypes.sizeof(_lib.H3dOp) == 120 and _lib.H3dOp.wexp.offset == 112
