@@ -16,9 +16,11 @@ Reference-named entry points (same names / argument meaning as the reference's s
         trains.trainer.{loss_multi_pose,loss_obj_detection} -> h3d_amd.losses.*
     datasets.coco_hp.COCOHP.{_get_label,_get_dataset}, the label block of datasets.coco.COCO.__getitem__,
         utils.image.get_affine_transform -> h3d_amd.targets.{multi_pose_targets,ctdet_targets,get_affine_transform}
+    datasets.coco_hp.COCOHP.{_get_input (train branch),__getitem__}, datasets.coco.COCO.__getitem__ (split == 'train'),
+        utils.image.color_aug -> h3d_amd.train_input.{draw_params,train_input,multi_pose_train_batch,ctdet_train_batch}
 Training the heads `Conv3x3 + ReLU + Conv1x1` (models.model.DLASeg.__init__ / forward) on the frozen backbone:
         h3d_amd.heads.{heads_autograd,TrainableHeads}
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth", "arch", "model", "engine", "weights", "plan", "dcn_calibrate", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets", "heads"]
+__all__ = ["synth", "arch", "model", "engine", "weights", "plan", "dcn_calibrate", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets", "heads", "train_input"]

@@ -110,6 +110,18 @@ class H3dUpdcnDesc(ctypes.Structure):
     _fields_ = [("skip", c_vp), ("w_up", c_vp), ("w_off", c_vp), ("skip_cs", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+TRAIN_BRIGHTNESS, TRAIN_CONTRAST, TRAIN_SATURATION = 0, 1, 2
+TRAIN_INPUT_NO_COLOR_AUG = 1
+
+
+class H3dTrainImage(ctypes.Structure):
+    """Mirror of `struct h3d_train_image` in include/h3d.h (section 3b): 136 bytes, no padding."""
+    _fields_ = [("minv", ctypes.c_double * 6), ("light", ctypes.c_double * 3), ("offset", ctypes.c_int64),
+                ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("row_bytes", ctypes.c_int32), ("flipped", ctypes.c_int32),
+                ("order", ctypes.c_int32 * 3), ("alpha", ctypes.c_float * 3), ("one_minus_alpha", ctypes.c_float * 3),
+                ("reserved", ctypes.c_int32)]
+
+
 # name -> argtypes (restype is int unless noted); also the export list the CPU test checks
 SIGNATURES = {
     "h3d_dcn_v2_forward": [c_vp] * 6 + [c_i] * 14 + [c_vp],
@@ -133,6 +145,9 @@ SIGNATURES = {
     "h3d_smpl_verts3": [c_vp] * 6 + [c_i] * 5 + [c_vp, c_vp],
     "h3d_smpl_verts3_exact": [c_vp] * 6 + [c_i] * 5 + [c_vp, c_vp],
     "h3d_preprocess": [c_vp, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_i, c_i, c_vp, c_vp],
+    # training input (include/h3d.h section 3b; h3d_amd/train_input.py)
+    "h3d_train_input_workspace_bytes": [c_i] * 4 + [ctypes.POINTER(ctypes.c_size_t)],
+    "h3d_train_input": [c_vp, ctypes.c_size_t, c_vp, c_vp, c_i, c_vp, c_vp, c_i, c_i, c_i, c_vp, ctypes.c_size_t, c_vp, c_vp, c_vp],
     "h3d_run_ops": [ctypes.POINTER(H3dOp), c_i, c_vp],
     "h3d_run_ops_timed": [ctypes.POINTER(H3dOp), c_i, c_vp, c_vp],
     "h3d_op_kernel_name": [ctypes.POINTER(H3dOp), ctypes.c_char_p, c_i],

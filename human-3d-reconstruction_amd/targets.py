@@ -8,8 +8,9 @@ libh3d_hip.so (csrc/targets.hip, include/h3d.h section 6) in two launches.
     ctdet_targets(boxes, cls, num, c, s, ...)                  -> the dict COCO.__getitem__ returns (batched, minus 'input')
 
 The dicts feed h3d_amd.losses.loss_multi_pose / loss_obj_detection unchanged.  Out of scope (ValueError here, H3D_ERR_UNSUPPORTED from the
-ABI): mse_loss (draw_msra_gaussian), dense_hp and dense_wh (draw_dense_reg depends on the object order), and the train branch of
-_get_input (random crop, colour augmentation): c, s, rot, flipped are inputs."""
+ABI): mse_loss (draw_msra_gaussian), dense_hp and dense_wh (draw_dense_reg depends on the object order).  c, s, rot, flipped are inputs
+here: the train branch of _get_input that draws them and builds 'input' (random crop, colour augmentation) is h3d_amd/train_input.py,
+whose multi_pose_train_batch / ctdet_train_batch return these dicts with 'input'."""
 
 import numpy as np
 import torch

@@ -583,6 +583,38 @@ int h3d_ctdet_assemble(const float *c_score, const int64_t *c_ind, const int32_t
 int h3d_preprocess(const uint8_t *images, int B, int h, int w, int row_bytes, const double *minv,
                    const float *mean, const float *stdv, int res_h, int res_w, float *out, void *stream);
 
+/* ---- 3b. Training input: the train branch of the same loaders (csrc/augment.hip; h3d_amd/train_input.py) -------------------------
+ * coco_hp.py:151-212 / coco.py:156-198 with split == 'train' and color_aug (utils/image.py:200-232): random crop, rotation, mirror,
+ * colour augmentation, standardise, for B frames that may differ in size.  The random draws are the host's; per image the kernels get: */
+struct h3d_train_image {
+    double minv[6];            /* the INVERSE (dst -> src) 2x3 map of get_affine_transform(c, s, rot, [res_w, res_h]), as h3d_preprocess takes it;
+                                  for a mirrored image c[0] is already w - c[0] - 1, as in the reference                                       */
+    double light[3];           /* lighting_: np.dot(eig_vec, eig_val * alpha) in float64, added per channel (B, G, R) in double             */
+    int64_t offset;            /* byte offset of the frame's first pixel in `images`                                                          */
+    int32_t h, w, row_bytes;   /* 1 <= h, w <= 32767; row_bytes >= 3 w                                                                         */
+    int32_t flipped;           /* 0 | 1: read source column w-1-x (the reference's img[:, ::-1, :])                                          */
+    int32_t order[3];          /* the colour operations in their drawn order: a permutation of H3D_TRAIN_BRIGHTNESS / _CONTRAST / _SATURATION */
+    float alpha[3];            /* per step of `order`: (float32)(1 + uniform(-0.4, 0.4)) ...                                                  */
+    float one_minus_alpha[3];  /* ... and (float32)(1 - alpha), the subtraction in double                                                     */
+    int32_t reserved;          /* 0                                                                                                           */
+};                             /* 136 bytes, no padding                                                                                       */
+#define H3D_TRAIN_BRIGHTNESS 0
+#define H3D_TRAIN_CONTRAST 1
+#define H3D_TRAIN_SATURATION 2
+#define H3D_TRAIN_INPUT_NO_COLOR_AUG 1       /* options: opt.no_color_aug -- one launch, no workspace, order / alpha / light unread */
+/*    images: one buffer of images_bytes bytes that holds every frame (BGR uint8 rows).  `desc` is the descriptor array in HOST memory --
+ *    every per-image check below reads it, before the first HIP call -- and `desc_dev` the same B descriptors in device memory, which the
+ *    kernels read.  mean / stdv [3] and out [B,3,res_h,res_w] fp32 on the device; gs_mean_out [B] fp32 or NULL: the grey mean contrast_
+ *    blends with (written only with colour augmentation).  workspace: h3d_train_input_workspace_bytes (0 with NO_COLOR_AUG), 256-byte
+ *    aligned.  Two launches (warp + fp64 grey sum; colour + standardise), one with NO_COLOR_AUG; the output is bit-identical from run to run.
+ *    B, res_h, res_w, an image's h or w <= 0 or > 32767, row_bytes < 3 w, a frame that leaves the buffer: H3D_ERR_SHAPE.  NULL or
+ *    misaligned pointers, unknown option bits, flipped outside 0 | 1, an order that is no permutation, a NULL or short workspace
+ *    ("workspace" in the message): H3D_ERR_ARG. */
+int h3d_train_input_workspace_bytes(int B, int res_h, int res_w, int options, size_t *bytes);
+int h3d_train_input(const uint8_t *images, size_t images_bytes, const struct h3d_train_image *desc,
+                    const struct h3d_train_image *desc_dev, int B, const float *mean, const float *stdv, int res_h, int res_w,
+                    int options, void *workspace, size_t workspace_bytes, float *out, float *gs_mean_out, void *stream);
+
 /* multi_pose_post_process (utils/post_process.py:41-52 + utils/image.py:19-68, inv affine with
  * rot = 0): dets [B,K,40] (output-res px) + c [B,2], s [B] -> out [B,K,39] image px.
  * J = 0 is the transform of ctdet_post_process (utils/post_process.py:24-38): dets [B,K,6] -> out [B,K,5] (box, score). */
