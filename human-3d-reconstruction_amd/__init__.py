@@ -20,7 +20,9 @@ Reference-named entry points (same names / argument meaning as the reference's s
         utils.image.color_aug -> h3d_amd.train_input.{draw_params,train_input,multi_pose_train_batch,ctdet_train_batch}
 Training the heads `Conv3x3 + ReLU + Conv1x1` (models.model.DLASeg.__init__ / forward) on the frozen backbone:
         h3d_amd.heads.{heads_autograd,TrainableHeads}
+    torch.optim.Adam as trains.trainer.HMRTrainer uses it, HMRModelWithLoss / run_epoch / the lr_step drop, save_model / load_model
+        with the optimiser state -> h3d_amd.optim.Adam, h3d_amd.trainer.HeadsTrainer, h3d_amd.checkpoint.{save_model,load_model}
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth", "arch", "model", "engine", "weights", "plan", "dcn_calibrate", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets", "heads", "train_input"]
+__all__ = ["synth", "arch", "model", "engine", "weights", "plan", "dcn_calibrate", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets", "heads", "train_input", "optim", "trainer", "checkpoint"]

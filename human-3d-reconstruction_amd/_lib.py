@@ -122,6 +122,16 @@ class H3dTrainImage(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+ADAM_CAPACITY, ADAM_CHUNK = 48, 2048        # H3D_ADAM_CAPACITY / H3D_ADAM_CHUNK: tensors per launch, elements per workgroup
+
+
+class H3dAdamTensor(ctypes.Structure):
+    """Mirror of `struct h3d_adam_tensor` in include/h3d.h (section 7): 72 bytes."""
+    _fields_ = [("param", c_vp), ("grad", c_vp), ("exp_avg", c_vp), ("exp_avg_sq", c_vp), ("n", ctypes.c_int64),
+                ("one_minus_b1", ctypes.c_float), ("b2", ctypes.c_float), ("one_minus_b2", ctypes.c_float), ("bc2_sqrt", ctypes.c_float),
+                ("eps", ctypes.c_float), ("neg_step_size", ctypes.c_float), ("weight_decay", ctypes.c_float)]
+
+
 # name -> argtypes (restype is int unless noted); also the export list the CPU test checks
 SIGNATURES = {
     "h3d_dcn_v2_forward": [c_vp] * 6 + [c_i] * 14 + [c_vp],
@@ -181,6 +191,8 @@ SIGNATURES = {
     "h3d_targets_workspace_bytes": [c_i] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
     "h3d_multi_pose_targets": [c_vp] * 8 + [c_i] * 7 + [c_vp] * 13 + [c_i, c_vp, ctypes.c_size_t, c_vp],
     "h3d_ctdet_targets": [c_vp] * 6 + [c_i] * 6 + [c_vp] * 9 + [c_i, c_vp, ctypes.c_size_t, c_vp],
+    # optimiser (include/h3d.h section 7; h3d_amd/optim.py)
+    "h3d_adam_step": [ctypes.POINTER(H3dAdamTensor), c_i, c_vp],
 }
 
 _lib = None

@@ -1,0 +1,118 @@
+"""The training side of the reference's HMRTrainer (trains/trainer.py:140-323) for what trains here: the output heads on the frozen
+backbone (heads.TrainableHeads), the fused losses (losses.loss_multi_pose / loss_obj_detection) and the one-launch Adam step
+(optim.Adam).  Printing, `debug`, the logger and the data loaders are the caller's."""
+import time
+
+import torch
+
+from . import checkpoint, losses, optim
+from .heads import TrainableHeads
+
+
+def _opt(opt, name, default):
+    return getattr(opt, name, default)
+
+
+class ModelWithLoss(torch.nn.Module):
+    """HMRModelWithLoss (trainer.py:140-149)."""
+
+    def __init__(self, model, loss):
+        super().__init__()
+        self.model = model
+        self.loss = loss
+
+    def forward(self, batch):
+        outputs = self.model(batch["input"])
+        loss, loss_stats = self.loss(outputs, batch)
+        return outputs[-1], loss, loss_stats
+
+
+class AverageMeter:
+    """utils/utils.py: the running average weighted by n."""
+
+    def __init__(self):
+        self.val = self.avg = self.sum = self.count = 0
+
+    def update(self, val, n=1):
+        self.val = val
+        self.sum += val * n
+        self.count += n
+        if self.count > 0:
+            self.avg = self.sum / self.count
+
+
+class HeadsTrainer:
+    """opt: task ('multi_pose' | 'ctdet'), lr (opts.py:78, 1.25e-4), lr_step (opts.py:79, [90, 120]), num_iters (opts.py:83, -1 = the
+    whole loader), device, and what the task's loss reads.  model: a model.dla_net(...) in 'f32' or 'f16x3' on the device."""
+
+    def __init__(self, opt, model):
+        self.opt = opt
+        self.model = model
+        self.heads = TrainableHeads(model)
+        task = _opt(opt, "task", "multi_pose")
+        if task == "multi_pose":
+            self.loss = losses.loss_multi_pose(opt)
+        elif task == "ctdet":
+            self.loss = losses.loss_obj_detection(opt)
+        else:
+            raise ValueError("HeadsTrainer: task %r not defined" % (task,))
+        self.loss_stats = list(self.loss.KEYS)
+        self.model_with_loss = ModelWithLoss(self.heads, self.loss)
+        self.lr = _opt(opt, "lr", 1.25e-4)
+        self.lr_step = list(_opt(opt, "lr_step", [90, 120]))
+        self.optimizer = optim.Adam(self.heads.parameters(), self.lr)
+
+    def train_step(self, batch):
+        """forward, loss.mean(), zero_grad(), backward(), step() (trainer.py:262-267) -> (output, loss, loss_stats)."""
+        output, loss, loss_stats = self.model_with_loss(batch)
+        loss = loss.mean()
+        self.optimizer.zero_grad()
+        loss.backward()
+        self.optimizer.step()
+        return output, loss, loss_stats
+
+    def run_epoch(self, phase, epoch, data_loader):
+        """trainer.py:231-301 without the printing: -> ({loss key: average weighted by batch size, 'time': minutes}, results)."""
+        train = phase == "train"
+        self.model_with_loss.train(train)
+        opt = self.opt
+        results = {}
+        avg_loss_stats = {k: AverageMeter() for k in self.loss_stats}
+        num_iters = _opt(opt, "num_iters", -1)
+        if num_iters < 0:
+            num_iters = len(data_loader)
+        device = _opt(opt, "device", None)
+        start = time.time()
+        for iter_id, batch in enumerate(data_loader):
+            if iter_id >= num_iters:
+                break
+            if device is not None:
+                batch = {k: (v.to(device=device, non_blocking=True) if k != "meta" and torch.is_tensor(v) else v) for k, v in batch.items()}
+            if train:
+                output, loss, loss_stats = self.train_step(batch)
+            else:
+                with torch.no_grad():
+                    output, loss, loss_stats = self.model_with_loss(batch)
+            for k in avg_loss_stats:
+                avg_loss_stats[k].update(loss_stats[k].mean().item(), batch["input"].size(0))
+            del output, loss, loss_stats
+        ret = {k: v.avg for k, v in avg_loss_stats.items()}
+        ret["time"] = (time.time() - start) / 60.0
+        return ret, results
+
+    def end_epoch(self, epoch):
+        """The learning-rate drop of trainer.py:316-320; -> the new rate, or None when `epoch` is no step."""
+        if epoch not in self.lr_step:
+            return None
+        lr = self.lr * (0.1 ** (self.lr_step.index(epoch) + 1))
+        for param_group in self.optimizer.param_groups:
+            param_group["lr"] = lr
+        return lr
+
+    def save_model(self, path, epoch):
+        checkpoint.save_model(path, epoch, self.heads, self.optimizer)
+
+    def load_model(self, model_path, resume=False):
+        """-> start_epoch (trainer.py:167-169)."""
+        _, _, start_epoch = checkpoint.load_model(self.heads, model_path, self.optimizer, resume, self.lr, self.lr_step)
+        return start_epoch

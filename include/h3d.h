@@ -820,6 +820,37 @@ int h3d_ctdet_targets(const float *boxes, const int32_t *cls, const int32_t *num
                       float *reg, int64_t *ind, uint8_t *reg_mask, float *cat_spec_wh, uint8_t *cat_spec_mask, float *gt_det,
                       int32_t *gt_count, int options, void *workspace, size_t workspace_bytes, void *stream);
 
+/* =====================================================================================
+ * 7. Optimiser (csrc/optim.hip): multi-tensor Adam, the step of torch.optim.Adam(model.parameters(), opt.lr) (trains/trainer.py:166,
+ *    264-267) for a whole parameter list in one launch.  fp32 storage and arithmetic; asynchronous on `stream`, no allocation, no
+ *    workspace, no table upload: the descriptors travel as the kernel argument, H3D_ADAM_CAPACITY tensors per launch (a longer list
+ *    takes ceil(T / H3D_ADAM_CAPACITY) launches; tensors with n == 0 take no slot).  Per element, every step ONE IEEE-754 binary32
+ *    operation, round to nearest, no contraction, sqrt and / correctly rounded, denormals kept:
+ *        g   = grad                      (weight_decay != 0:  g = grad + weight_decay * p)
+ *        m   = m + one_minus_b1 * (g - m)
+ *        v   = v * b2;   v = v + (one_minus_b2 * g) * g
+ *        den = sqrt(v) / bc2_sqrt + eps
+ *        p   = p + neg_step_size * (m / den)
+ *    with the scalars torch's single-tensor path forms on the host in double and rounds to float once: bc2_sqrt = sqrt(1 - b2^t),
+ *    neg_step_size = -(lr / (1 - b1^t)), t = the tensor's own step count.  `tensors` is HOST memory (read before the call returns); its
+ *    pointers are device memory, 4-byte aligned: 16-byte accesses are used where the four bases of a tensor share their offset inside
+ *    16 bytes, and the result of an element does not depend on the access it takes.  A workgroup steps H3D_ADAM_CHUNK elements.
+ *    Checked before the first HIP call: n_tensors < 0 or n < 0: H3D_ERR_SHAPE; NULL `tensors`, a NULL pointer in a tensor with n > 0,
+ *    a base off a 4-byte boundary, a non-finite scalar, b2 outside [0,1), eps < 0, bc2_sqrt <= 0: H3D_ERR_ARG.  n_tensors == 0 and
+ *    tensors with n == 0 launch nothing.  The buffers of one call must not overlap.
+ * ===================================================================================== */
+#define H3D_ADAM_CAPACITY 48
+#define H3D_ADAM_CHUNK 2048
+typedef struct h3d_adam_tensor {
+    float *param;
+    const float *grad;
+    float *exp_avg;
+    float *exp_avg_sq;
+    int64_t n;
+    float one_minus_b1, b2, one_minus_b2, bc2_sqrt, eps, neg_step_size, weight_decay;
+} h3d_adam_tensor;
+int h3d_adam_step(const h3d_adam_tensor *tensors /* host memory */, int n_tensors, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
