@@ -122,6 +122,7 @@ class H3dTrainImage(ctypes.Structure):
                 ("reserved", ctypes.c_int32)]
 
 
+SMPL_KP_MAX_K, SMPL_KP_MAX_NV = 32, 16              # H3D_SMPL_KP_MAX_K / H3D_SMPL_KP_MAX_NV
 ADAM_CAPACITY, ADAM_CHUNK = 48, 2048        # H3D_ADAM_CAPACITY / H3D_ADAM_CHUNK: tensors per launch, elements per workgroup
 
 
@@ -184,6 +185,10 @@ SIGNATURES = {
     "h3d_smpl_backward_workspace_bytes": [c_i] * 5 + [ctypes.POINTER(ctypes.c_size_t)],
     "h3d_smpl_backward": [c_vp] * 12 + [c_i] * 4 + [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
     "h3d_smpl_heads_backward": [c_vp] * 3 + [c_i] * 4 + [c_vp] * 10 + [c_i] * 3 + [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
+    # SMPL keypoint reprojection loss (include/h3d.h section 4c; h3d_amd/smpl_loss.py)
+    "h3d_smpl_kp_loss_workspace_bytes": [c_i, c_i, ctypes.POINTER(ctypes.c_size_t)],
+    "h3d_smpl_kp_loss_forward": [c_vp] * 6 + [c_i] + [c_vp] * 3 + [c_i] * 7 + [c_vp] * 4 + [ctypes.c_size_t, c_vp],
+    "h3d_smpl_kp_loss_backward": [c_vp] * 6 + [c_i] + [c_vp] * 7 + [c_i] * 7 + [c_vp] * 4,
     # heads backward (include/h3d.h section 2b; h3d_amd/heads.py holds the mirror of `struct h3d_heads_bwd_head`)
     "h3d_heads_backward_workspace_bytes": [c_i] * 5 + [c_vp, ctypes.POINTER(ctypes.c_size_t)],
     "h3d_heads_backward": [c_vp] + [c_i] * 6 + [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],

@@ -43,14 +43,23 @@ class AverageMeter:
 
 class HeadsTrainer:
     """opt: task ('multi_pose' | 'ctdet'), lr (opts.py:78, 1.25e-4), lr_step (opts.py:79, [90, 120]), num_iters (opts.py:83, -1 = the
-    whole loader), device, and what the task's loss reads.  model: a model.dla_net(...) in 'f32' or 'f16x3' on the device."""
+    whole loader), device, and what the task's loss reads.  model: a model.dla_net(...) in 'f32' or 'f16x3' on the device.
+    smpl_model (smpl.SMPLModel) and kp_regressor (smpl_loss.KeypointRegressor), both given and opt.smpl_kp_weight > 0 (multi_pose only):
+    the loss is smpl_loss.loss_multi_pose_smpl, which adds the keypoint reprojection loss on the SMPL output and so trains the `pose`,
+    `shape` and `cam` (3 channels) heads the model must then have; otherwise nothing changes."""
 
-    def __init__(self, opt, model):
+    def __init__(self, opt, model, smpl_model=None, kp_regressor=None):
         self.opt = opt
         self.model = model
         self.heads = TrainableHeads(model)
         task = _opt(opt, "task", "multi_pose")
-        if task == "multi_pose":
+        if task == "multi_pose" and smpl_model is not None and kp_regressor is not None and _opt(opt, "smpl_kp_weight", 0) > 0:
+            from . import smpl_loss
+            want = {"pose": 72, "shape": 10, "cam": 3}
+            if any(model.heads.get(h) != c for h, c in want.items()):
+                raise ValueError("HeadsTrainer: the keypoint reprojection loss needs the heads %s, the model has %s" % (want, dict(model.heads)))
+            self.loss = smpl_loss.loss_multi_pose_smpl(opt, smpl_model, kp_regressor)
+        elif task == "multi_pose":
             self.loss = losses.loss_multi_pose(opt)
         elif task == "ctdet":
             self.loss = losses.loss_obj_detection(opt)

@@ -714,6 +714,51 @@ int h3d_smpl_heads_backward(const float *pose_map, const float *shape_map, const
                             float *grad_shape_map, void *workspace, size_t workspace_bytes, void *stream);
 
 /* =====================================================================================
+ * 4c. SMPL keypoint reprojection loss (csrc/smpl_loss.hip; no reference code: the project's own definition).
+ *    Per person slot p = b n + m (image b < B, the first n <= max_objs slots of its label rows), keypoint k < K, c in {x, y}:
+ *      kp3d[p,k]   = sum_j JW[k,j] joints[p,j] + sum_{i<NV} VW[k,i] verts[p, VI[k,i]]     (j ascending, then i ascending; fp32, every
+ *                                                                                          product and sum rounded on its own)
+ *      (s, tx, ty) = cam_map[b, 0..2, ind[b,m]]                                            (NCHW [B,3,HW] read in place, raw values)
+ *      pred[p,k,c] = s kp3d[p,k,c] + t_c
+ *      l = sum m |pred - hps[b,m,2k+c]|,  num = sum m,  m = hps_mask[b,m,2k+c],  loss = l / (num + 1e-4)    (RegWeightedL1Loss's convention)
+ *    joints [P,24,3], verts [P,V,3] (NULL with NV == 0), ind [B,max_objs] int64, hps [B,max_objs,2K], hps_mask [B,max_objs,2K] of
+ *    mask_type H3D_LOSS_MASK_U8 | H3D_LOSS_MASK_F32; the regressor: joint_w [K,24], vert_idx i32 [K,NV], vert_w [K,NV].
+ *    Outputs of the forward: kp3d [P,K,3], pred [P,K,2], stats [3] = {loss, l, num}.
+ *    DECIDED HERE (as in section 5): a slot whose ind lies outside [0,HW) adds nothing to l, num or any gradient; its pred is stored as 0,
+ *    its kp3d as for any slot.  A vert_idx entry outside [0,V) is skipped by the kernels (the Python constructor refuses it).
+ *    - Forward: two launches, asynchronous on `stream`, no allocation.  One wave per slot; fp32 per lane -> wave shuffles -> LDS -> one
+ *      plain-stored partial per workgroup, summed in a fixed order in fp64 by the finish launch: no float atomics, bit-identical from run
+ *      to run.  num == 0 gives loss 0.
+ *    - Backward: g = coef sign(pred - hps) m with coef = grad_out[0] / (num + 1e-4) formed in fp64 and rounded once (grad_out and stats in
+ *      device memory; sign(0) = 0, torch's L1 subgradient), g_s = sum_{k,c} g kp3d_c, g_t_c = sum_k g, g_kp3d[p,k] = (s g_x, s g_y, 0);
+ *      grad_joints [P,24,3] = sum_k JW[k,j] g_kp3d[p,k] (k ascending; every element stored), grad_verts [P,V,3] = sum over the inverted
+ *      table (below) and 0 elsewhere, grad_cam_map [B,3,HW] = g_s, g_t added at the slot's pixel and 0 elsewhere.  Any of the three may be
+ *      NULL (skipped).  Two launches: a zero fill of grad_cam_map and grad_verts, then the scatter; the camera values are added with float
+ *      atomic adds because two slots may share a pixel -- the order of those adds varies (last bits of a shared pixel), everything else is
+ *      bit-identical from run to run.  kp3d and pred are what the forward wrote.
+ *    - The inverted table (built by the host, h3d_amd/smpl_loss.py): inv_vertex i32 [n_touched] = the vertices with a non-zero weight,
+ *      ascending; inv_start i32 [n_touched + 1]; inv_k i32 / inv_w f32 [inv_start[n_touched]] = per touched vertex its (k, VW[k,i]) in
+ *      (k, i) order.  n_touched <= K * H3D_SMPL_KP_MAX_NV.
+ *    - Limits the kernels are built for: K <= H3D_SMPL_KP_MAX_K (one lane per (k, c) of a wave in the backward), NV <= H3D_SMPL_KP_MAX_NV.
+ *      Beyond them: H3D_ERR_UNSUPPORTED.  B, max_objs, n, HW, K <= 0, n > max_objs, NV < 0, V <= 0 where vertices are used, more than
+ *      2^31 / 96 person slots: H3D_ERR_SHAPE.  NULL operands, a bad mask_type, a NULL, short or not 8-byte aligned workspace
+ *      ("workspace" in the message): H3D_ERR_ARG.  Every check runs before the first HIP call.
+ *    Workspace: a256(8 ceil(B n / 4)) bytes, one {l, num} partial per workgroup of four slots.
+ * ===================================================================================== */
+#define H3D_SMPL_KP_MAX_K 32
+#define H3D_SMPL_KP_MAX_NV 16
+int h3d_smpl_kp_loss_workspace_bytes(int B, int n, size_t *bytes);
+int h3d_smpl_kp_loss_forward(const float *joints, const float *verts, const float *cam_map, const int64_t *ind, const float *hps,
+                             const void *hps_mask, int mask_type, const float *joint_w, const int32_t *vert_idx, const float *vert_w,
+                             int B, int max_objs, int n, int HW, int K, int NV, int V, float *kp3d, float *pred, float *stats,
+                             void *workspace, size_t workspace_bytes, void *stream);
+int h3d_smpl_kp_loss_backward(const float *kp3d, const float *pred, const float *cam_map, const int64_t *ind, const float *hps,
+                              const void *hps_mask, int mask_type, const float *stats, const float *grad_out, const float *joint_w,
+                              const int32_t *inv_vertex, const int32_t *inv_start, const int32_t *inv_k, const float *inv_w, int n_touched,
+                              int B, int max_objs, int n, int HW, int K, int V, float *grad_joints, float *grad_verts, float *grad_cam_map,
+                              void *stream);
+
+/* =====================================================================================
  * 5. Losses (losses.py, trains/trainer.py:29-137): the focal term of `_neg_loss` (losses.py:42-67) and the four gathered regression
  *    terms, forward and backward, in descriptor form: one h3d_loss_term per term, ALL terms of a call in one partial-sum launch plus
  *    one finish launch (csrc/loss.hip).  No host synchronisation: where the reference branches on the host (`if num_pos == 0`) the
