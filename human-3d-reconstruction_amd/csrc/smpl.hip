@@ -9,23 +9,21 @@
 //                      tile kept in registers (PT persons per lane), then 4-sparse LBS.
 //                      Model tensors are stored K-major ([k][V*3]) so lanes (= vertices) read
 //                      consecutive addresses for every k.
+// Shared with the backward (smpl_bwd.hip), each piece in one place: the pose stage itself (lane mapping, parameter loads from rows or
+// head maps, rest joint, Rodrigues, chain) is smpl_pose.h, templated on the scalar type; the generation-3 vertex tile (contraction,
+// then accumulator zeroing, vertex fetch, accumulator transposition and blended transform of the skinning rounds) is smpl_tile.h.
 #include "common.h"
-#include "smpl_tile.h"      // SMPL_J / SMPL_NB / SMPL_PF, the generation-3 tile constants, staging and MFMA stream, split3
+#include "smpl_tile.h"      // SMPL_J / SMPL_NB / SMPL_PF, the generation-3 tile: constants, staging, MFMA stream, skinning steps, split3
+#include "smpl_pose.h"
 #include <type_traits>
 
-// One lane per (person, joint): a wave holds two persons (lanes 32q + j, j < 24).  Rodrigues, the rest joints and
-// the outputs are joint-parallel; the kinematic chain walks the joints in their (topological) order and lane j
-// fetches its parent's transform by a shuffle -- 23 short steps instead of a 24-joint serial program per lane with
-// its 24 x 12 transform table in scratch memory (0.13 ms -> 0.02 ms at 6400 persons).
-// HEADS (round 4: the detector's tail as fewer launches): the parameters are read where the network left them -- person p is
-// detection q = p % n of image b = p / n, its betas / thetas are the `shape` / `pose` head maps [B,10|72,HW] at pixel inds[b*K + q]
-// (what `_transpose_and_gather_feat`, utils.py:23-27, would have copied out in two launches) -- and the generation-3 coefficient
+// smpl_pose_kernel: the pose stage of smpl_pose.h in fp32 (lane mapping, parameter loads, rest joint, Rodrigues, local transform, chain)
+// plus what it stores.  Rodrigues, the rest joints and the outputs are joint-parallel; the chain walks the joints in their order.
+// HEADS (round 4: the detector's tail as fewer launches): the parameters are read where the network left them (SmplHeadMaps: what
+// `_transpose_and_gather_feat`, utils.py:23-27, would have copied out in two launches) -- and the generation-3 coefficient
 // operand coefK3 [Ppad][14][3][16] (h3d_smpl_coef_pack's output: the h / m / l bf16 terms of [beta | pose_feat | 0], zero rows for
 // p >= P) is written by the lanes that hold the values.  Same arithmetic on the same values: bit-identical to the three launches.
-struct SmplHeadsSrc {
-    const float *pose_map, *shape_map;
-    const int64_t *inds;
-    int n, K, HW;
+struct SmplHeadsSrc : SmplHeadMaps {
     float *betas_out;        // [P,10] (API output; may be NULL)
     bf16_t *coefK3;          // [Ppad][14][3][16]
 };
@@ -38,23 +36,15 @@ __global__ __launch_bounds__(64) void smpl_pose_kernel(const float *__restrict__
                                                        float *__restrict__ pose_feat, float *__restrict__ A,
                                                        float *__restrict__ joints, float *__restrict__ coefT, int Ppad, SmplHeadsSrc hs)
 {
-    const int l = threadIdx.x, j = l & 31, half = l >> 5;
-    const int p = blockIdx.x * 2 + half;
-    const bool act = p < P && j < SMPL_J;
-    const int pc = p < P ? p : P - 1, jc = j < SMPL_J ? j : 0;       // clamped: every lane computes, only `act` lanes store
+    const SmplLane ln = smpl_lane(P);
+    const int j = ln.j, p = ln.p, jc = ln.jc;
+    const bool act = ln.act;
     float beta[SMPL_NB];
-    [[maybe_unused]] size_t hb = 0;
-    [[maybe_unused]] int hpix = 0;
+    [[maybe_unused]] SmplHeadPix hp;
+    if constexpr (HEADS) hp = smpl_head_pix(hs, ln.pc);
+    smpl_load_beta<HEADS>(beta, betas, hs, hp, ln.pc);
     if constexpr (HEADS) {
-        hb = (size_t)(pc / hs.n);
-        const int64_t pix = hs.inds[hb * hs.K + (pc - (int)hb * hs.n)];
-        hpix = (int)(pix < 0 ? 0 : pix >= hs.HW ? hs.HW - 1 : pix);
-#pragma unroll
-        for (int k = 0; k < SMPL_NB; ++k) beta[k] = hs.shape_map[(hb * SMPL_NB + k) * hs.HW + hpix];
         if (hs.betas_out && p < P && j < SMPL_NB) hs.betas_out[(size_t)p * SMPL_NB + j] = beta[j];
-    } else {
-#pragma unroll
-    for (int k = 0; k < SMPL_NB; ++k) beta[k] = betas[(size_t)pc * SMPL_NB + k];
     }
     if (coefT && p < P && j < SMPL_NB) coefT[(size_t)j * Ppad + p] = beta[j];     // k-major [beta | pose_feat] (gen 2 kernel)
     [[maybe_unused]] auto put_coef = [&](int k, float v) {          // coefK3[p][k >> 4][term][k & 15], zero rows for p >= P
@@ -69,40 +59,11 @@ __global__ __launch_bounds__(64) void smpl_pose_kernel(const float *__restrict__
             if (j >= SMPL_J && j < SMPL_J + 7) put_coef(SMPL_NB + SMPL_PF + (j - SMPL_J), 0.f);      // K padding 217..223
         }
     }
-    // rest joint of (p, j)
-    float jr[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float s = j_template[jc * 3 + c];
-#pragma unroll
-        for (int k = 0; k < SMPL_NB; ++k) s = fmaf(j_shapedirs[(jc * 3 + c) * SMPL_NB + k], beta[k], s);
-        jr[c] = s;
-    }
-    // Rodrigues with the smplx convention: angle = ||theta + 1e-8||, axis = theta / angle
-    float tx, ty, tz;
-    if constexpr (HEADS) {
-        const float *tp = hs.pose_map + (hb * 72 + jc * 3) * hs.HW + hpix;
-        tx = tp[0]; ty = tp[hs.HW]; tz = tp[2 * (size_t)hs.HW];
-    } else {
-        tx = thetas[(size_t)pc * 72 + jc * 3]; ty = thetas[(size_t)pc * 72 + jc * 3 + 1]; tz = thetas[(size_t)pc * 72 + jc * 3 + 2];
-    }
-    const float ex = tx + 1e-8f, ey = ty + 1e-8f, ez = tz + 1e-8f;
-    const float angle = sqrtf(ex * ex + ey * ey + ez * ez);
-    const float inv = 1.f / angle;
-    const float x = tx * inv, y = ty * inv, z = tz * inv;
-    float sn, cs;
-    sincosf(angle, &sn, &cs);
-    const float oc = 1.f - cs;
-    float R[9];          // R = I + sin K + (1-cos) K^2,  K = skew(x,y,z)
-    R[0] = 1.f + oc * (-(y * y) - z * z);
-    R[1] = -sn * z + oc * (x * y);
-    R[2] = sn * y + oc * (x * z);
-    R[3] = sn * z + oc * (x * y);
-    R[4] = 1.f + oc * (-(x * x) - z * z);
-    R[5] = -sn * x + oc * (y * z);
-    R[6] = -sn * y + oc * (x * z);
-    R[7] = sn * x + oc * (y * z);
-    R[8] = 1.f + oc * (-(x * x) - y * y);
+    float jr[3], th[3];
+    smpl_rest_joint(jr, j_template, j_shapedirs, beta, jc);
+    smpl_load_theta<HEADS>(th, thetas, hs, hp, ln.pc, jc);
+    const SmplRot<float> rot = smpl_rodrigues(th[0], th[1], th[2]);
+    const float (&R)[9] = rot.R;
     if (act && j > 0) {
         float *pf = pose_feat + (size_t)p * SMPL_PF + (j - 1) * 9;
 #pragma unroll
@@ -118,35 +79,11 @@ __global__ __launch_bounds__(64) void smpl_pose_kernel(const float *__restrict__
             for (int i = 0; i < 9; ++i) put_coef(SMPL_NB + (j - 1) * 9 + i, R[i] - ((i == 0 || i == 4 || i == 8) ? 1.f : 0.f));
         }
     }
-    // local transform L = [R | jr - jr(parent)] (root: [R | jr]); G starts as L and becomes G(parent) . L
     const int par = parents[jc];
-    const int plane = half * 32 + (par < 0 ? 0 : par);
-    float G[12];
-    {
-        const float px = __shfl(jr[0], plane), py = __shfl(jr[1], plane), pz = __shfl(jr[2], plane);
-        const float rel[3] = {par < 0 ? jr[0] : jr[0] - px, par < 0 ? jr[1] : jr[1] - py, par < 0 ? jr[2] : jr[2] - pz};
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { G[a * 4] = R[a * 3]; G[a * 4 + 1] = R[a * 3 + 1]; G[a * 4 + 2] = R[a * 3 + 2]; G[a * 4 + 3] = rel[a]; }
-    }
-    for (int step = 1; step < SMPL_J; ++step) {          // joints are stored parents-first (SMPL's kintree order)
-        float Gp[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) Gp[i] = __shfl(G[i], plane);          // my parent's (already global) transform
-        if (j == step) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const float g0 = Gp[a * 4], g1 = Gp[a * 4 + 1], g2 = Gp[a * 4 + 2], g3 = Gp[a * 4 + 3];
-                const float l0 = G[0], l1 = G[1], l2 = G[2], l3 = G[3], l4 = G[4], l5 = G[5], l6 = G[6], l7 = G[7], l8 = G[8],
-                            l9 = G[9], l10 = G[10], l11 = G[11];
-                Gp[a * 4] = g0 * l0 + g1 * l4 + g2 * l8;
-                Gp[a * 4 + 1] = g0 * l1 + g1 * l5 + g2 * l9;
-                Gp[a * 4 + 2] = g0 * l2 + g1 * l6 + g2 * l10;
-                Gp[a * 4 + 3] = g0 * l3 + g1 * l7 + g2 * l11 + g3;
-            }
-#pragma unroll
-            for (int i = 0; i < 12; ++i) G[i] = Gp[i];
-        }
-    }
+    const int plane = ln.half * 32 + (par < 0 ? 0 : par);
+    float rel[3], G[12];
+    smpl_local(rel, G, R, jr, par, plane);
+    smpl_chain(G, j, plane);
     if (act) {
         float *Ao = A + ((size_t)p * SMPL_J + j) * 12;
         float *jo = joints + ((size_t)p * SMPL_J + j) * 3;
@@ -524,12 +461,7 @@ __global__ __launch_bounds__(64 * S3_NW) void smpl_verts3_kernel(const bf16_t *_
     const int dbytes = 3 * Vpad * S3_GROW, cbytes = Ppad * S3_GROW;
 
     f32x16 acc[3][2];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[c][t][i] = 0.f;
+    s3_zero(acc);
 
     // the 3x4 transforms of a skinning round (8 persons per wave: [8][288] floats = 576 float4, 9 per lane) are fetched
     // into registers one round ahead -- round 0 before the contraction -- so no round waits on global memory
@@ -548,15 +480,8 @@ __global__ __launch_bounds__(64 * S3_NW) void smpl_verts3_kernel(const bf16_t *_
     load_A(0);
     // this lane's vertex in the skinning phase: template position and (<= 4) joint indices / weights, also fetched early
     const int v = v0 + l;
-    const int vc = v < V ? v : V - 1;
-    int jidx[4];
-    float jw[4];
-#pragma unroll
-    for (int sI = 0; sI < 4; ++sI) {
-        jidx[sI] = sI < nnz ? lbs_idx[(size_t)vc * nnz + sI] : 0;
-        jw[sI] = sI < nnz ? lbs_w[(size_t)vc * nnz + sI] : 0.f;
-    }
-    const float t0 = v_template[vc], t1 = v_template[Vpad + vc], t2 = v_template[2 * Vpad + vc];
+    S3Vertex vx;
+    s3_vertex(vx, v < V ? v : V - 1, nnz, lbs_idx, lbs_w, v_template, Vpad);
     s3_issue((const char *)dirsK3, dbytes, (const char *)coefK3, cbytes, smem, aoff, boff, wv, 0);
     const int fa_off = r * S3_ROWB + h * 16;                                   // + (c * 64 + t * 32) rows, + part * 32
     const int fb_off = S3_APIECES * 1024 + (wv * 32 + r) * S3_ROWB + h * 16;
@@ -589,18 +514,7 @@ __global__ __launch_bounds__(64 * S3_NW) void smpl_verts3_kernel(const bf16_t *_
         // under another's blend (vector ALU)
         __builtin_amdgcn_wave_barrier();
         // (a) my accumulators of persons [8 rnd, 8 rnd + 8): C layout row = vertex, column = person
-        if ((r / S3_RP) == rnd) {
-            const int pl = r % S3_RP;
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-#pragma unroll
-                for (int t = 0; t < 2; ++t)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const int vl = t * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                        *reinterpret_cast<float *>(sT + pl * S3_TSTRIDE + (vl * 3 + c) * 4) = acc[c][t][i];
-                    }
-        }
+        s3_transpose_round<S3_RP, S3_TSTRIDE>(acc, sT, rnd, r, h);
         // (b) the 3x4 transforms of those 8 persons (prefetched), then the next round's go in flight
 #pragma unroll
         for (int k = 0; k < NA4; ++k) {
@@ -615,24 +529,17 @@ __global__ __launch_bounds__(64 * S3_NW) void smpl_verts3_kernel(const bf16_t *_
         for (int q = 0; q < S3_RP; ++q) {
             const int p = p0 + wv * 32 + rnd * S3_RP + q;
             float T[12];
-#pragma unroll
-            for (int i = 0; i < 12; ++i) T[i] = 0.f;
-#pragma unroll
-            for (int sI = 0; sI < 4; ++sI) {
-                const float *Ap = sA + q * SMPL_J * 12 + jidx[sI] * 12;
-#pragma unroll
-                for (int i4 = 0; i4 < 3; ++i4) {
-                    const f32x4 a4 = *reinterpret_cast<const f32x4 *>(Ap + 4 * i4);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) T[4 * i4 + e] = fmaf(jw[sI], a4[e], T[4 * i4 + e]);
-                }
-            }
+            s3_blend(T, sA + q * SMPL_J * 12, vx);
             const float *xyz = reinterpret_cast<const float *>(sT + q * S3_TSTRIDE + l * 12);
-            const float x = t0 + xyz[0], y = t1 + xyz[1], z = t2 + xyz[2];
+            const float x = vx.t0 + xyz[0], y = vx.t1 + xyz[1], z = vx.t2 + xyz[2];
             if (v < V && p < P) {
+#pragma clang fp contract(off)
+                // T [x y z 1] with every rounding written out.  Which product of a row is rounded on its own was the compiler's
+                // choice, row by row, and the stored outputs and the tests hold these bits: written as T[0] * x + T[1] * y + ..., the
+                // choice moves with how the code around it is vectorised
                 typedef __attribute__((ext_vector_type(3))) float f32x3;     // one 12-byte store per lane
-                const f32x3 o3 = {T[0] * x + T[1] * y + T[2] * z + T[3], T[4] * x + T[5] * y + T[6] * z + T[7],
-                                  T[8] * x + T[9] * y + T[10] * z + T[11]};
+                const f32x3 o3 = {fmaf(T[2], z, fmaf(T[0], x, T[1] * y)) + T[3], fmaf(T[6], z, fmaf(T[5], y, T[4] * x)) + T[7],
+                                  (fmaf(T[8], x, T[9] * y) + T[10] * z) + T[11]};
                 __builtin_memcpy(verts + ((size_t)p * V + v) * 3, &o3, 12);
             }
         }

@@ -3,8 +3,9 @@
 //     coef = [beta | vec(R[1:] - I)]      v_p = v_template + D . coef      A_j from the kinematic chain
 //     T_v = sum_j w_vj A_j                verts_v = T_v [v_p; 1]           joints_j = G_j.t
 // Three launches, everything recomputed from betas / thetas (h3d_smpl_pose + h3d_smpl_coef_pack into the workspace first):
-//   smpl_bwd_verts_kernel  64 vertices x 256 persons per step, as smpl_verts3_kernel: v_p by the forward's six-product contraction
-//                          (smpl_tile.h, shared, not copied), then with lane = vertex g_vp = T_R^T gV -> workspace [P][3][Vpad] and
+//   smpl_bwd_verts_kernel  64 vertices x 256 persons per step, as smpl_verts3_kernel: v_p by the forward's six-product contraction, its
+//                          vertex fetch, accumulator transposition and blended transform T (all smpl_tile.h, shared, not copied; the
+//                          clamp of the joint indices is this kernel's own), then with lane = vertex g_vp = T_R^T gV -> [P][3][Vpad] and
 //                          this tile's part of gA[p][j] = sum_v w_vj gV_v (x) [v_p; 1] (24 x 12 per person), summed over the tile's
 //                          vertices in vertex order.  A workgroup walks SB_NVT consecutive vertex tiles and adds each into ONE partial
 //                          per (tile group, person): plain loads and stores of a slot no other workgroup touches.
@@ -14,12 +15,15 @@
 //                          into splits of SB_KC; one plain-stored partial per (split, person).
 //   smpl_bwd_pose_kernel   the mirror of smpl_pose_kernel, one lane per (person, joint), two persons per wave, in fp64 (the stage is a
 //                          few microseconds, and fp64 removes the cancellations of sin(a)/a and (1 - cos a)/a^2 near the rest pose):
-//                          sums the partials of the two kernels above in their stored order, walks the chain children first (lane
-//                          `step` hands its contribution to its parent by a shuffle, steps 23 .. 1: a fixed order), applies the
+//                          its forward is smpl_pose.h with T = double, the code smpl_pose_kernel runs with T = float (shared, not
+//                          copied); then it sums the partials of the two kernels above in their stored order, walks the chain children
+//                          first (lane `step` hands its contribution to its parent by a shuffle, steps 23 .. 1: a fixed order), applies the
 //                          rest-joint gradient to grad_betas and the Rodrigues backward to grad_thetas.
 // No float atomics except the heads variant's scatter into the zero-filled maps (two detections may share a pixel).
+// Host side: the two entry points keep their own checks, zero fills and early returns; their launches are sb_run.
 #include "common.h"
 #include "smpl_tile.h"
+#include "smpl_pose.h"
 
 constexpr int SB_NVT = 4;                     // vertex tiles (of 64) one workgroup folds into one gA partial
 constexpr int SB_RP = 4;                      // persons per skinning round and wave
@@ -62,29 +66,19 @@ __global__ __launch_bounds__(64 * S3_NW) void smpl_bwd_verts_kernel(const bf16_t
         const int v0 = vt * S3_VT;
         s3_dir_offsets<true>(aoff, wv, l, v0, Vpad);
         f32x16 acc[3][2];
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[c][t][i] = 0.f;
-        // this lane's vertex in the skinning phase (rows past V compute a duplicate of V - 1 with a zero upstream gradient)
+        s3_zero(acc);
+        // this lane's vertex in the skinning phase (rows past V compute a duplicate of V - 1 with a zero upstream gradient); the joint
+        // indices also address s_W and gApart here, so they are clamped
         const int v = v0 + l;
-        const int vc = v < V ? v : V - 1;
-        int jidx[4];
-        float jw[4];
+        S3Vertex vx;
+        s3_vertex(vx, v < V ? v : V - 1, nnz, lbs_idx, lbs_w, v_template, Vpad);
 #pragma unroll
-        for (int sI = 0; sI < 4; ++sI) {
-            int ji = sI < nnz ? lbs_idx[(size_t)vc * nnz + sI] : 0;
-            jidx[sI] = ji < 0 ? 0 : ji >= SMPL_J ? SMPL_J - 1 : ji;
-            jw[sI] = sI < nnz ? lbs_w[(size_t)vc * nnz + sI] : 0.f;
-        }
-        const float t0 = v_template[vc], t1 = v_template[Vpad + vc], t2 = v_template[2 * Vpad + vc];
+        for (int sI = 0; sI < 4; ++sI) vx.jidx[sI] = vx.jidx[sI] < 0 ? 0 : vx.jidx[sI] >= SMPL_J ? SMPL_J - 1 : vx.jidx[sI];
         if (wv == 0) {                         // the tile's skinning weights as a dense [64][24] block: row l is private to lane l
             for (int j = 0; j < SMPL_J; ++j) s_W[l * SB_WS + j] = 0.f;
 #pragma unroll
             for (int sI = 0; sI < 4; ++sI)
-                if (jw[sI] != 0.f) s_W[l * SB_WS + jidx[sI]] += jw[sI];
+                if (vx.jw[sI] != 0.f) s_W[l * SB_WS + vx.jidx[sI]] += vx.jw[sI];
         }
         s3_issue((const char *)dirsK3, dbytes, (const char *)coefK3, cbytes, smem, aoff, boff, wv, 0);
         s3_contract<true, 0>(acc, smem, (const char *)dirsK3, dbytes, (const char *)coefK3, cbytes, aoff, boff, wv, fa_off, fb_off);
@@ -103,18 +97,7 @@ __global__ __launch_bounds__(64 * S3_NW) void smpl_bwd_verts_kernel(const bf16_t
         for (int rnd = 0; rnd < 32 / SB_RP; ++rnd) {
             // sT / sG / sA are private to the wave and LDS executes a wave's instructions in order (as in smpl_verts3_kernel)
             __builtin_amdgcn_wave_barrier();
-            if ((r / SB_RP) == rnd) {          // (a) the displacements of persons [4 rnd, 4 rnd + 4): C layout row = vertex, column = person
-                const int pl = r % SB_RP;
-#pragma unroll
-                for (int c = 0; c < 3; ++c)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t)
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            const int vl = t * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
-                            *reinterpret_cast<float *>(sT + pl * SB_TSTRIDE + (vl * 3 + c) * 4) = acc[c][t][i];
-                        }
-            }
+            s3_transpose_round<SB_RP, SB_TSTRIDE>(acc, sT, rnd, r, h);          // (a) the displacements of persons [4 rnd, 4 rnd + 4)
             for (int i = l; i < SB_RP * SMPL_J * 3; i += 64) {          // (b) their 3x4 transforms
                 const int q = i / (SMPL_J * 3), rr = i - q * (SMPL_J * 3);
                 const int p = p0 + wv * 32 + rnd * SB_RP + q;
@@ -127,21 +110,10 @@ __global__ __launch_bounds__(64 * S3_NW) void smpl_bwd_verts_kernel(const bf16_t
             for (int q = 0; q < SB_RP; ++q) {   // (c) lane = vertex: g_vp = T_R^T gV; v_p and gV go back to LDS for the reduction
                 const int p = p0 + wv * 32 + rnd * SB_RP + q;
                 float T[12];
-#pragma unroll
-                for (int i = 0; i < 12; ++i) T[i] = 0.f;
-#pragma unroll
-                for (int sI = 0; sI < 4; ++sI) {
-                    const float *Ap = sA + q * SMPL_J * 12 + jidx[sI] * 12;
-#pragma unroll
-                    for (int i4 = 0; i4 < 3; ++i4) {
-                        const f32x4 a4 = *reinterpret_cast<const f32x4 *>(Ap + 4 * i4);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) T[4 * i4 + e] = fmaf(jw[sI], a4[e], T[4 * i4 + e]);
-                    }
-                }
+                s3_blend(T, sA + q * SMPL_J * 12, vx);
                 float *xyz = reinterpret_cast<float *>(sT + q * SB_TSTRIDE + l * 12);
                 float *gq = reinterpret_cast<float *>(sG + q * SB_TSTRIDE + l * 12);
-                const float x = t0 + xyz[0], y = t1 + xyz[1], z = t2 + xyz[2];
+                const float x = vx.t0 + xyz[0], y = vx.t1 + xyz[1], z = vx.t2 + xyz[2];
                 float gx = 0.f, gy = 0.f, gz = 0.f;
                 if (v < V && p < P) {
                     const float *gv = grad_verts + ((size_t)p * V + v) * 3;
@@ -151,9 +123,10 @@ __global__ __launch_bounds__(64 * S3_NW) void smpl_bwd_verts_kernel(const bf16_t
                 gq[0] = gx; gq[1] = gy; gq[2] = gz;
                 if (p < P) {
                     float *o = gvp + (size_t)p * 3 * Vpad + v;          // v < Vpad; rows past V receive zeros
-                    o[0] = T[0] * gx + T[4] * gy + T[8] * gz;
-                    o[Vpad] = T[1] * gx + T[5] * gy + T[9] * gz;
-                    o[2 * (size_t)Vpad] = T[2] * gx + T[6] * gy + T[10] * gz;
+                    // (the roundings written out: as a * gx + b * gy + c * gz the contraction moves with the code around it)
+                    o[0] = fmaf(T[8], gz, fmaf(T[0], gx, T[4] * gy));
+                    o[Vpad] = fmaf(T[9], gz, fmaf(T[1], gx, T[5] * gy));
+                    o[2 * (size_t)Vpad] = fmaf(T[10], gz, fmaf(T[2], gx, T[6] * gy));
                 }
             }
             __builtin_amdgcn_wave_barrier();
@@ -168,11 +141,11 @@ __global__ __launch_bounds__(64 * S3_NW) void smpl_bwd_verts_kernel(const bf16_t
                 float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
 #pragma unroll 4
                 for (int vv = 0; vv < S3_VT; ++vv) {
-                    const float g = s_W[vv * SB_WS + j] * gq[vv * 3];
+                    const float w = s_W[vv * SB_WS + j], g = w * gq[vv * 3];
                     s0 = fmaf(g, xq[vv * 3], s0);
                     s1 = fmaf(g, xq[vv * 3 + 1], s1);
                     s2 = fmaf(g, xq[vv * 3 + 2], s2);
-                    s3 += g;
+                    s3 = fmaf(w, gq[vv * 3], s3);          // not s3 + g: one rounding, as the sum always had
                 }
                 if (p < P) {
                     float *o = gApart + ((size_t)blockIdx.x * P + p) * (SMPL_J * 12) + j * 12 + a * 4;
@@ -248,10 +221,7 @@ __global__ __launch_bounds__(256) void smpl_bwd_coef_kernel(const float *__restr
     }
 }
 
-struct SmplBwdHeads {
-    const float *pose_map, *shape_map;
-    const int64_t *inds;
-    int n, K, HW;
+struct SmplBwdHeads : SmplHeadMaps {
     float *gpose, *gshape;                    // [B,72,HW], [B,10,HW], zero-filled by the launcher; either may be NULL
 };
 
@@ -263,82 +233,27 @@ __global__ __launch_bounds__(64) void smpl_bwd_pose_kernel(const float *__restri
                                                            const float *__restrict__ gcpart, int NS, float *__restrict__ grad_betas,
                                                            float *__restrict__ grad_thetas, SmplBwdHeads hs)
 {
-    const int l = threadIdx.x, j = l & 31, half = l >> 5;
-    const int p = blockIdx.x * 2 + half;
-    const bool act = p < P && j < SMPL_J;
-    const int pc = p < P ? p : P - 1, jc = j < SMPL_J ? j : 0;
-    // ---- the forward of smpl_pose_kernel, in fp64 ----
-    double beta[SMPL_NB];
-    [[maybe_unused]] size_t hb = 0;
-    [[maybe_unused]] int hpix = 0;
-    float tx32, ty32, tz32;
-    if constexpr (HEADS) {
-        hb = (size_t)(pc / hs.n);
-        const int64_t pix = hs.inds[hb * hs.K + (pc - (int)hb * hs.n)];
-        hpix = (int)(pix < 0 ? 0 : pix >= hs.HW ? hs.HW - 1 : pix);
-#pragma unroll
-        for (int k = 0; k < SMPL_NB; ++k) beta[k] = hs.shape_map[(hb * SMPL_NB + k) * hs.HW + hpix];
-        const float *tp = hs.pose_map + (hb * 72 + jc * 3) * hs.HW + hpix;
-        tx32 = tp[0]; ty32 = tp[hs.HW]; tz32 = tp[2 * (size_t)hs.HW];
-    } else {
-#pragma unroll
-        for (int k = 0; k < SMPL_NB; ++k) beta[k] = betas[(size_t)pc * SMPL_NB + k];
-        tx32 = thetas[(size_t)pc * 72 + jc * 3]; ty32 = thetas[(size_t)pc * 72 + jc * 3 + 1]; tz32 = thetas[(size_t)pc * 72 + jc * 3 + 2];
-    }
-    double jr[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        double s = j_template[jc * 3 + c];
-#pragma unroll
-        for (int k = 0; k < SMPL_NB; ++k) s += (double)j_shapedirs[(jc * 3 + c) * SMPL_NB + k] * beta[k];
-        jr[c] = s;
-    }
-    // Rodrigues, smplx convention: angle = ||theta + 1e-8||, axis = theta / angle; 1 - cos a as 2 sin^2(a / 2)
-    const double tx = tx32, ty = ty32, tz = tz32;
-    const double ex = tx + 1e-8, ey = ty + 1e-8, ez = tz + 1e-8;
-    const double angle = sqrt(ex * ex + ey * ey + ez * ez);
-    const double inv = 1.0 / angle;
-    const double x = tx * inv, y = ty * inv, z = tz * inv;
-    const double sn = sin(angle), cs = cos(angle), sh = sin(0.5 * angle);
-    const double oc = 2.0 * sh * sh;
-    double R[9];
-    R[0] = 1.0 + oc * (-(y * y) - z * z);
-    R[1] = -sn * z + oc * (x * y);
-    R[2] = sn * y + oc * (x * z);
-    R[3] = sn * z + oc * (x * y);
-    R[4] = 1.0 + oc * (-(x * x) - z * z);
-    R[5] = -sn * x + oc * (y * z);
-    R[6] = -sn * y + oc * (x * z);
-    R[7] = sn * x + oc * (y * z);
-    R[8] = 1.0 + oc * (-(x * x) - y * y);
+    const SmplLane ln = smpl_lane(P);
+    const int j = ln.j, half = ln.half, p = ln.p, pc = ln.pc, jc = ln.jc;
+    const bool act = ln.act;
+    // ---- the forward of smpl_pose_kernel (smpl_pose.h), in fp64 ----
+    double beta[SMPL_NB], jr[3];
+    float th[3];
+    [[maybe_unused]] SmplHeadPix hp;
+    if constexpr (HEADS) hp = smpl_head_pix(hs, pc);
+    [[maybe_unused]] const size_t hb = hp.hb;
+    [[maybe_unused]] const int hpix = hp.hpix;
+    smpl_load_beta<HEADS>(beta, betas, hs, hp, pc);
+    smpl_load_theta<HEADS>(th, thetas, hs, hp, pc, jc);
+    smpl_rest_joint(jr, j_template, j_shapedirs, beta, jc);
+    const SmplRot<double> rot = smpl_rodrigues<double>(th[0], th[1], th[2]);
+    const double x = rot.x, y = rot.y, z = rot.z, inv = rot.inv, ex = rot.ex, ey = rot.ey, ez = rot.ez, sn = rot.sn, cs = rot.cs, oc = rot.oc;
+    const double (&R)[9] = rot.R;
     const int par = parents[jc];
     const int plane = half * 32 + (par < 0 ? 0 : par);
-    double rel[3];
-    {
-        const double px = __shfl(jr[0], plane), py = __shfl(jr[1], plane), pz = __shfl(jr[2], plane);
-        rel[0] = par < 0 ? jr[0] : jr[0] - px; rel[1] = par < 0 ? jr[1] : jr[1] - py; rel[2] = par < 0 ? jr[2] : jr[2] - pz;
-    }
-    double G[12];                              // global transform rows [R | t]
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { G[a * 4] = R[a * 3]; G[a * 4 + 1] = R[a * 3 + 1]; G[a * 4 + 2] = R[a * 3 + 2]; G[a * 4 + 3] = rel[a]; }
-    for (int step = 1; step < SMPL_J; ++step) {
-        double Gp[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) Gp[i] = __shfl(G[i], plane);
-        if (j == step) {
-            double N[12];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const double g0 = Gp[a * 4], g1 = Gp[a * 4 + 1], g2 = Gp[a * 4 + 2], g3 = Gp[a * 4 + 3];
-                N[a * 4] = g0 * G[0] + g1 * G[4] + g2 * G[8];
-                N[a * 4 + 1] = g0 * G[1] + g1 * G[5] + g2 * G[9];
-                N[a * 4 + 2] = g0 * G[2] + g1 * G[6] + g2 * G[10];
-                N[a * 4 + 3] = g0 * G[3] + g1 * G[7] + g2 * G[11] + g3;
-            }
-#pragma unroll
-            for (int i = 0; i < 12; ++i) G[i] = N[i];
-        }
-    }
+    double rel[3], G[12];                      // G: global transform rows [R | t]
+    smpl_local(rel, G, R, jr, par, plane);
+    smpl_chain(G, j, plane);
     // ---- upstream: gA (the vertex kernel's partials, tile groups in order), grad_joints ----
     double gA[12];
 #pragma unroll
@@ -500,19 +415,49 @@ extern "C" int h3d_smpl_backward_workspace_bytes(int P, int V, int Vpad, int nnz
     return H3D_OK;
 }
 
-// the two hot kernels on a workspace whose pf / A / coefK3 are filled
-static int sb_vertex_part(const SbWorkspace &w, char *ws, const float *grad_verts, const float *v_template, const void *dirsK3,
-                          const void *dirsV3, const int32_t *lbs_idx, const float *lbs_w, int nnz, int P, int V, int Vpad, hipStream_t st)
+// what an upstream grad_verts needs: the model tensors of the vertex kernels and the workspace
+static int sb_check_verts_args(const char *what, const SbWorkspace &w, const float *grad_verts, const float *v_template, const void *dirsK3,
+                               const void *dirsV3, const int32_t *lbs_idx, const float *lbs_w, const void *workspace, size_t workspace_bytes)
 {
-    const int Ppad = cdiv(P, S3_PPAD) * S3_PPAD;
-    const int NG = sb_groups(Vpad), NS = sb_splits(Vpad);
-    if (hipMemsetAsync(ws + w.gApart, 0, (size_t)4 * NG * P * SMPL_J * 12, st) != hipSuccess)
-        H3D_FAIL(H3D_ERR_LAUNCH, "smpl_backward: clearing the transform-gradient partials failed");
-    H3D_TRY(h3d_launch({"smpl_bwd_verts_kernel"}, smpl_bwd_verts_kernel, dim3(NG, cdiv(Ppad, S3_PB)), dim3(64 * S3_NW), 0, st, (const bf16_t *)(ws + w.coefK3),
-                       (const float *)(ws + w.A), v_template, (const bf16_t *)dirsK3, lbs_idx, lbs_w, nnz, P, Ppad, V, Vpad, grad_verts,
-                       (float *)(ws + w.gvp), (float *)(ws + w.gApart)));
-    return h3d_launch({"smpl_bwd_coef_kernel"}, smpl_bwd_coef_kernel, dim3(cdiv(P, 128), NS), dim3(256), 0, st, (const float *)(ws + w.gvp),
-                      (const bf16_t *)dirsV3, P, 3 * Vpad, (float *)(ws + w.gcpart));
+    if (grad_verts && (!v_template || !dirsK3 || !dirsV3 || !lbs_idx || !lbs_w))
+        H3D_FAIL(H3D_ERR_ARG, "%s: null model pointer with grad_verts given", what);
+    if (grad_verts && (!workspace || workspace_bytes < w.total))
+        H3D_FAIL(H3D_ERR_ARG, "%s: workspace of %zu bytes needed, %zu given", what, w.total, workspace ? workspace_bytes : (size_t)0);
+    return H3D_OK;
+}
+
+// The launches of both entry points, past their checks and early returns; HEADS: the parameters come from the head maps of `hs` (betas,
+// thetas, grad_betas, grad_thetas NULL), the gradients go to its maps.  With grad_verts the forward pose stage of that flavour fills
+// pf / A / coefK3 of the workspace and the two hot kernels leave their partials there; the pose kernel then reads them.
+template <bool HEADS>
+static int sb_run(const float *betas, const float *thetas, const SmplBwdHeads &hs, const float *grad_verts, const float *grad_joints,
+                  const float *j_template, const float *j_shapedirs, const int32_t *parents, const float *v_template, const void *dirsK3,
+                  const void *dirsV3, const int32_t *lbs_idx, const float *lbs_w, int nnz, int P, int V, int Vpad, float *grad_betas,
+                  float *grad_thetas, const SbWorkspace &w, void *workspace, void *stream)
+{
+    char *ws = (char *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    const int NG = sb_groups(Vpad), NS = sb_splits(Vpad), Ppad = cdiv(P, S3_PPAD) * S3_PPAD;
+    if (grad_verts) {
+        float *pf = (float *)(ws + w.pf), *A = (float *)(ws + w.A), *joints = (float *)(ws + w.joints);
+        if constexpr (HEADS) {
+            H3D_TRY(h3d_smpl_pose_heads(hs.pose_map, hs.shape_map, hs.inds, P / hs.n, hs.K, hs.n, hs.HW, j_template, j_shapedirs, parents, nullptr,
+                                        pf, A, joints, ws + w.coefK3, Ppad, stream));
+        } else {
+            H3D_TRY(h3d_smpl_pose(betas, thetas, j_template, j_shapedirs, parents, P, pf, A, joints, nullptr, Ppad, stream));
+            H3D_TRY(h3d_smpl_coef_pack(betas, pf, P, Ppad, ws + w.coefK3, stream));
+        }
+        if (hipMemsetAsync(ws + w.gApart, 0, (size_t)4 * NG * P * SMPL_J * 12, st) != hipSuccess)
+            H3D_FAIL(H3D_ERR_LAUNCH, "smpl_backward: clearing the transform-gradient partials failed");
+        H3D_TRY(h3d_launch({"smpl_bwd_verts_kernel"}, smpl_bwd_verts_kernel, dim3(NG, cdiv(Ppad, S3_PB)), dim3(64 * S3_NW), 0, st, (const bf16_t *)(ws + w.coefK3),
+                           (const float *)A, v_template, (const bf16_t *)dirsK3, lbs_idx, lbs_w, nnz, P, Ppad, V, Vpad, grad_verts,
+                           (float *)(ws + w.gvp), (float *)(ws + w.gApart)));
+        H3D_TRY(h3d_launch({"smpl_bwd_coef_kernel"}, smpl_bwd_coef_kernel, dim3(cdiv(P, 128), NS), dim3(256), 0, st, (const float *)(ws + w.gvp),
+                           (const bf16_t *)dirsV3, P, 3 * Vpad, (float *)(ws + w.gcpart)));
+    }
+    return h3d_launch({"smpl_bwd_pose_kernel", HEADS}, smpl_bwd_pose_kernel<HEADS>, dim3(cdiv(P, 2)), dim3(64), 0, st, betas, thetas, j_template, j_shapedirs,
+                      parents, P, grad_joints, grad_verts ? (const float *)(ws + w.gApart) : nullptr, NG,
+                      grad_verts ? (const float *)(ws + w.gcpart) : nullptr, NS, grad_betas, grad_thetas, hs);
 }
 
 extern "C" int h3d_smpl_backward(const float *betas, const float *thetas, const float *grad_verts, const float *grad_joints,
@@ -520,37 +465,21 @@ extern "C" int h3d_smpl_backward(const float *betas, const float *thetas, const 
                                  const void *dirsK3, const void *dirsV3, const int32_t *lbs_idx, const float *lbs_w, int nnz, int P, int V,
                                  int Vpad, float *grad_betas, float *grad_thetas, void *workspace, size_t workspace_bytes, void *stream)
 {
-    int rc = sb_check_shape("smpl_backward", P, V, Vpad, nnz);
-    if (rc != H3D_OK) return rc;
+    H3D_TRY(sb_check_shape("smpl_backward", P, V, Vpad, nnz));
     if (P == 0) return H3D_OK;
     if (!betas || !thetas || !j_template || !j_shapedirs || !parents) H3D_FAIL(H3D_ERR_ARG, "smpl_backward: null pointer");
-    if (grad_verts && (!v_template || !dirsK3 || !dirsV3 || !lbs_idx || !lbs_w))
-        H3D_FAIL(H3D_ERR_ARG, "smpl_backward: null model pointer with grad_verts given");
     const SbWorkspace w = sb_layout(P, Vpad);
-    if (grad_verts && (!workspace || workspace_bytes < w.total))
-        H3D_FAIL(H3D_ERR_ARG, "smpl_backward: workspace of %zu bytes needed, %zu given", w.total, workspace ? workspace_bytes : (size_t)0);
-    hipStream_t st = (hipStream_t)stream;
+    H3D_TRY(sb_check_verts_args("smpl_backward", w, grad_verts, v_template, dirsK3, dirsV3, lbs_idx, lbs_w, workspace, workspace_bytes));
     if (!grad_verts && !grad_joints) {
+        hipStream_t st = (hipStream_t)stream;
         if ((grad_betas && hipMemsetAsync(grad_betas, 0, (size_t)4 * P * SMPL_NB, st) != hipSuccess) ||
             (grad_thetas && hipMemsetAsync(grad_thetas, 0, (size_t)4 * P * 72, st) != hipSuccess))
             H3D_FAIL(H3D_ERR_LAUNCH, "smpl_backward: zero fill failed");
         return H3D_OK;
     }
     if (!grad_betas && !grad_thetas) return H3D_OK;
-    char *ws = (char *)workspace;
-    if (grad_verts) {
-        const int Ppad = cdiv(P, S3_PPAD) * S3_PPAD;
-        rc = h3d_smpl_pose(betas, thetas, j_template, j_shapedirs, parents, P, (float *)(ws + w.pf), (float *)(ws + w.A),
-                           (float *)(ws + w.joints), nullptr, Ppad, stream);
-        if (rc != H3D_OK) return rc;
-        rc = h3d_smpl_coef_pack(betas, (const float *)(ws + w.pf), P, Ppad, ws + w.coefK3, stream);
-        if (rc != H3D_OK) return rc;
-        rc = sb_vertex_part(w, ws, grad_verts, v_template, dirsK3, dirsV3, lbs_idx, lbs_w, nnz, P, V, Vpad, st);
-        if (rc != H3D_OK) return rc;
-    }
-    return h3d_launch({"smpl_bwd_pose_kernel", false}, smpl_bwd_pose_kernel<false>, dim3(cdiv(P, 2)), dim3(64), 0, st, betas, thetas, j_template, j_shapedirs,
-                      parents, P, grad_joints, grad_verts ? (const float *)(ws + w.gApart) : nullptr, sb_groups(Vpad),
-                      grad_verts ? (const float *)(ws + w.gcpart) : nullptr, sb_splits(Vpad), grad_betas, grad_thetas, SmplBwdHeads{});
+    return sb_run<false>(betas, thetas, SmplBwdHeads{}, grad_verts, grad_joints, j_template, j_shapedirs, parents, v_template, dirsK3, dirsV3, lbs_idx,
+                         lbs_w, nnz, P, V, Vpad, grad_betas, grad_thetas, w, workspace, stream);
 }
 
 extern "C" int h3d_smpl_heads_backward(const float *pose_map, const float *shape_map, const int64_t *inds, int B, int K, int n, int HW,
@@ -562,8 +491,7 @@ extern "C" int h3d_smpl_heads_backward(const float *pose_map, const float *shape
     if (B < 0 || K < 0 || n < 0 || n > K || HW < 0 || (B > 0 && n > 0 && HW == 0) || (long long)B * n > 0x7fffffffLL)
         H3D_FAIL(H3D_ERR_SHAPE, "smpl_heads_backward: B=%d K=%d n=%d HW=%d", B, K, n, HW);
     const int P = B * n;
-    int rc = sb_check_shape("smpl_heads_backward", P, V, Vpad, nnz);
-    if (rc != H3D_OK) return rc;
+    H3D_TRY(sb_check_shape("smpl_heads_backward", P, V, Vpad, nnz));
     hipStream_t st = (hipStream_t)stream;
     // the maps are zero-filled whatever follows: persons add at their pixels
     if ((grad_pose_map && B > 0 && HW > 0 && hipMemsetAsync(grad_pose_map, 0, (size_t)4 * B * 72 * HW, st) != hipSuccess) ||
@@ -571,25 +499,12 @@ extern "C" int h3d_smpl_heads_backward(const float *pose_map, const float *shape
         H3D_FAIL(H3D_ERR_LAUNCH, "smpl_heads_backward: zero fill failed");
     if (P == 0) return H3D_OK;
     if (!pose_map || !shape_map || !inds || !j_template || !j_shapedirs || !parents) H3D_FAIL(H3D_ERR_ARG, "smpl_heads_backward: null pointer");
-    if (grad_verts && (!v_template || !dirsK3 || !dirsV3 || !lbs_idx || !lbs_w))
-        H3D_FAIL(H3D_ERR_ARG, "smpl_heads_backward: null model pointer with grad_verts given");
     const SbWorkspace w = sb_layout(P, Vpad);
-    if (grad_verts && (!workspace || workspace_bytes < w.total))
-        H3D_FAIL(H3D_ERR_ARG, "smpl_heads_backward: workspace of %zu bytes needed, %zu given", w.total, workspace ? workspace_bytes : (size_t)0);
+    H3D_TRY(sb_check_verts_args("smpl_heads_backward", w, grad_verts, v_template, dirsK3, dirsV3, lbs_idx, lbs_w, workspace, workspace_bytes));
     if ((!grad_verts && !grad_joints) || (!grad_pose_map && !grad_shape_map)) return H3D_OK;
-    char *ws = (char *)workspace;
-    if (grad_verts) {
-        const int Ppad = cdiv(P, S3_PPAD) * S3_PPAD;
-        rc = h3d_smpl_pose_heads(pose_map, shape_map, inds, B, K, n, HW, j_template, j_shapedirs, parents, nullptr, (float *)(ws + w.pf),
-                                 (float *)(ws + w.A), (float *)(ws + w.joints), ws + w.coefK3, Ppad, stream);
-        if (rc != H3D_OK) return rc;
-        rc = sb_vertex_part(w, ws, grad_verts, v_template, dirsK3, dirsV3, lbs_idx, lbs_w, nnz, P, V, Vpad, st);
-        if (rc != H3D_OK) return rc;
-    }
     SmplBwdHeads hs;
     hs.pose_map = pose_map; hs.shape_map = shape_map; hs.inds = inds; hs.n = n; hs.K = K; hs.HW = HW;
     hs.gpose = grad_pose_map; hs.gshape = grad_shape_map;
-    return h3d_launch({"smpl_bwd_pose_kernel", true}, smpl_bwd_pose_kernel<true>, dim3(cdiv(P, 2)), dim3(64), 0, st, nullptr, nullptr, j_template, j_shapedirs,
-                      parents, P, grad_joints, grad_verts ? (const float *)(ws + w.gApart) : nullptr, sb_groups(Vpad),
-                      grad_verts ? (const float *)(ws + w.gcpart) : nullptr, sb_splits(Vpad), nullptr, nullptr, hs);
+    return sb_run<true>(nullptr, nullptr, hs, grad_verts, grad_joints, j_template, j_shapedirs, parents, v_template, dirsK3, dirsV3, lbs_idx, lbs_w,
+                        nnz, P, V, Vpad, nullptr, nullptr, w, workspace, stream);
 }

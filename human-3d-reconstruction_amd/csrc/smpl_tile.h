@@ -1,6 +1,9 @@
 // The generation-3 blend-shape contraction of the SMPL stage, shared by the forward (smpl.hip: smpl_verts3_kernel) and the backward
-// (smpl_bwd.hip: smpl_bwd_verts_kernel, which recomputes v_posed): tile constants, the LDS-DMA staging of the 2-slot ring and the
-// MFMA stream over the three-term bf16 split.  The description of the tiling is in smpl.hip above smpl_verts3_kernel.
+// (smpl_bwd.hip: smpl_bwd_verts_kernel, which recomputes v_posed): tile constants, the LDS-DMA staging of the 2-slot ring, the
+// MFMA stream over the three-term bf16 split, and the steps of the skinning rounds after it that both kernels take: accumulator zeroing,
+// the lane's vertex record (s3_vertex), the accumulator -> LDS transposition of a round (s3_transpose_round) and the blended transform
+// (s3_blend).  The forward's register prefetch of A and each kernel's own outputs stay with the kernels.  The description of the tiling
+// is in smpl.hip above smpl_verts3_kernel; the pose stage the two pose kernels share is smpl_pose.h.
 #pragma once
 #include "common.h"
 
@@ -126,6 +129,70 @@ __device__ __forceinline__ void s3_contract(f32x16 (&acc)[3][2], char *smem, con
                 E::mma(acc[c][0], ah0, bh);
                 E::mma(acc[c][1], ah1, bh);
             }
+        }
+    }
+}
+
+// ---- after the contraction: skinning with lane = vertex, in rounds of RP persons per wave ------------------------------------------
+__device__ __forceinline__ void s3_zero(f32x16 (&acc)[3][2])
+{
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[c][t][i] = 0.f;
+}
+
+// this lane's vertex in the skinning phase: (<= 4) joint indices / weights and the template position
+struct S3Vertex {
+    int jidx[4];
+    float jw[4];
+    float t0, t1, t2;
+};
+__device__ __forceinline__ void s3_vertex(S3Vertex &vx, int vc, int nnz, const int32_t *lbs_idx, const float *lbs_w,
+                                              const float *v_template, int Vpad)
+{
+#pragma unroll
+    for (int sI = 0; sI < 4; ++sI) {
+        vx.jidx[sI] = sI < nnz ? lbs_idx[(size_t)vc * nnz + sI] : 0;
+        vx.jw[sI] = sI < nnz ? lbs_w[(size_t)vc * nnz + sI] : 0.f;
+    }
+    vx.t0 = v_template[vc]; vx.t1 = v_template[Vpad + vc]; vx.t2 = v_template[2 * Vpad + vc];
+}
+
+// The accumulators (C layout: row = vertex, column = person; r = lane & 31, h = lane >> 5) of persons [RP rnd, RP rnd + RP) of this wave
+// -> sT [RP persons][64 v][3] floats, STRIDE bytes per person: lane = person becomes lane = vertex
+template <int RP, int STRIDE>
+__device__ __forceinline__ void s3_transpose_round(const f32x16 (&acc)[3][2], char *sT, int rnd, int r, int h)
+{
+    if ((r / RP) == rnd) {
+        const int pl = r % RP;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int vl = t * 32 + (i & 3) + 8 * (i >> 2) + 4 * h;
+                    *reinterpret_cast<float *>(sT + pl * STRIDE + (vl * 3 + c) * 4) = acc[c][t][i];
+                }
+    }
+}
+
+// T = sum_s jw[s] A[jidx[s]]: the blended 3x4 transform of the lane's vertex for the person whose 24 transforms are at Aq (LDS)
+__device__ __forceinline__ void s3_blend(float (&T)[12], const float *Aq, const S3Vertex &vx)
+{
+#pragma unroll
+    for (int i = 0; i < 12; ++i) T[i] = 0.f;
+#pragma unroll
+    for (int sI = 0; sI < 4; ++sI) {
+        const float *Ap = Aq + vx.jidx[sI] * 12;
+#pragma unroll
+        for (int i4 = 0; i4 < 3; ++i4) {
+            const f32x4 a4 = *reinterpret_cast<const f32x4 *>(Ap + 4 * i4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) T[4 * i4 + e] = fmaf(vx.jw[sI], a4[e], T[4 * i4 + e]);
         }
     }
 }

@@ -11,7 +11,7 @@ head maps): csrc/smpl_bwd.hip, through `lbs_backward` and, when an input require
 """
 import numpy as np
 
-from . import synth
+from . import _lib, synth
 
 NUM_VERTS = 6890
 NUM_JOINTS = 24
@@ -114,20 +114,27 @@ def _device_pack(model, device, nnz=None):
     }
 
 
-def _dirs_k3(model, Vpad, device, KP=224):
-    """[3][Vpad][KP/16][3 terms][16] bf16: x = h + m + l with h = bf16(x), m = bf16(x - h), l = bf16(x - h - m)
-    (round-to-nearest-even; exact to 24 significant bits) -- the operand format of csrc/smpl.hip smpl_verts3."""
+def _bf16_split3(d):
+    """fp32 numpy array -> the bf16 tensors (h, m, lo) of the three-term split: x = h + m + l with h = bf16(x), m = bf16(x - h),
+    l = bf16(x - h - m) (round-to-nearest-even at each step, the differences in fp32; exact to 24 significant bits)."""
     import torch
-    V = model.v_template.shape[0]
-    d = np.zeros((3, Vpad, KP), np.float32)
-    d[:, :V, :NUM_BETAS] = model.shapedirs.transpose(1, 0, 2)                      # [V,3,10] -> [3,V,10]
-    d[:, :V, NUM_BETAS:NUM_BETAS + NUM_POSE_FEAT] = model.posedirs.transpose(1, 0, 2)
     x = torch.from_numpy(d)
     h = x.to(torch.bfloat16)
     r1 = x - h.float()
     m = r1.to(torch.bfloat16)
     lo = (r1 - m.float()).to(torch.bfloat16)
-    out = torch.stack([t.reshape(3, Vpad, KP // 16, 16) for t in (h, m, lo)], dim=3)     # [3][Vpad][14][3][16]
+    return h, m, lo
+
+
+def _dirs_k3(model, Vpad, device, KP=224):
+    """[3][Vpad][KP/16][3 terms][16] bf16: the three-term split (_bf16_split3) of the K-contiguous direction rows -- the operand
+    format of csrc/smpl.hip smpl_verts3."""
+    import torch
+    V = model.v_template.shape[0]
+    d = np.zeros((3, Vpad, KP), np.float32)
+    d[:, :V, :NUM_BETAS] = model.shapedirs.transpose(1, 0, 2)                      # [V,3,10] -> [3,V,10]
+    d[:, :V, NUM_BETAS:NUM_BETAS + NUM_POSE_FEAT] = model.posedirs.transpose(1, 0, 2)
+    out = torch.stack([t.reshape(3, Vpad, KP // 16, 16) for t in _bf16_split3(d)], dim=3)     # [3][Vpad][14][3][16]
     return out.contiguous().to(device)
 
 
@@ -139,12 +146,7 @@ def _dirs_v3(model, Vpad, device, KP=224):
     d = np.zeros((KP, 3, Vpad), np.float32)
     d[:NUM_BETAS, :, :V] = model.shapedirs.transpose(2, 1, 0)                      # [V,3,10] -> [10,3,V]
     d[NUM_BETAS:NUM_BETAS + NUM_POSE_FEAT, :, :V] = model.posedirs.transpose(2, 1, 0)
-    x = torch.from_numpy(d)
-    h = x.to(torch.bfloat16)
-    r1 = x - h.float()
-    m = r1.to(torch.bfloat16)
-    lo = (r1 - m.float()).to(torch.bfloat16)
-    return torch.stack([h, m, lo], dim=0).contiguous().to(device)
+    return torch.stack(_bf16_split3(d), dim=0).contiguous().to(device)
 
 
 def _pack_for(model, dev, backward=False):
@@ -166,7 +168,6 @@ def lbs_backward(model, betas, thetas, grad_verts=None, grad_joints=None):
     Everything is recomputed from betas / thetas (h3d_smpl_backward, include/h3d.h section 4b); the sums run in a fixed order, so two
     calls give the same bits.  Needs <= 4 skinning weights per vertex."""
     import torch
-    from . import _lib
     _lib.require_cuda(betas, thetas, grad_verts, grad_joints)
     dev = betas.device
     d = _pack_for(model, dev, backward=True)
@@ -177,48 +178,49 @@ def lbs_backward(model, betas, thetas, grad_verts=None, grad_joints=None):
     thetas = thetas.detach().contiguous().float().view(P, 72)
     if betas.shape != (P, NUM_BETAS):
         raise RuntimeError("lbs_backward: betas [P,10], thetas [P,72]")
-    gv = None if grad_verts is None else grad_verts.detach().float().contiguous()       # (an expanded upstream becomes dense here)
-    gj = None if grad_joints is None else grad_joints.detach().float().contiguous()
-    if (gv is not None and gv.shape != (P, d["V"], 3)) or (gj is not None and gj.shape != (P, NUM_JOINTS, 3)):
+    if (grad_verts is not None and grad_verts.shape != (P, d["V"], 3)) or (grad_joints is not None and grad_joints.shape != (P, NUM_JOINTS, 3)):
         raise RuntimeError("lbs_backward: grad_verts [P,V,3], grad_joints [P,24,3]")
+    L, gv, gj, ws = _backward_inputs(d, P, dev, grad_verts, grad_joints)
     gb = torch.empty(P, NUM_BETAS, dtype=torch.float32, device=dev)
     gt = torch.empty(P, 72, dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    ws = _lib.workspace(L.h3d_smpl_backward_workspace_bytes, P, d["V"], d["Vpad"], d["nnz"], int(gv is not None), device=dev,
-                        what="smpl_backward_workspace_bytes")
     with torch.cuda.device(dev):
         st = _lib.stream_ptr()              # the current stream of `dev`, as the forward
-        _lib.check(L.h3d_smpl_backward(_lib.ptr(betas), _lib.ptr(thetas), _lib.ptr(gv), _lib.ptr(gj), _lib.ptr(d["j_template"]),
-                                       _lib.ptr(d["j_shapedirs"]), _lib.ptr(d["parents"]), _lib.ptr(d["v_template"]), _lib.ptr(d["dirsK3"]),
-                                       _lib.ptr(d["dirsV3"]), _lib.ptr(d["lbs_idx"]), _lib.ptr(d["lbs_w"]), d["nnz"], P, d["V"], d["Vpad"],
-                                       _lib.ptr(gb), _lib.ptr(gt), _lib.ptr(ws), ws.numel() if ws is not None else 0, st), "smpl_backward")
+        _lib.check(L.h3d_smpl_backward(_lib.ptr(betas), _lib.ptr(thetas), _lib.ptr(gv), _lib.ptr(gj), *_model_ptrs(d), d["nnz"], P, d["V"],
+                                       d["Vpad"], _lib.ptr(gb), _lib.ptr(gt), _lib.ptr(ws), ws.numel() if ws is not None else 0, st), "smpl_backward")
     return gb, gt
 
 
 def _heads_backward(model, pose_map, shape_map, inds, n, grad_verts, grad_joints):
     """h3d_smpl_heads_backward: -> (grad_pose_map, grad_shape_map), shaped like the maps."""
     import torch
-    from . import _lib
     dev = pose_map.device
     d = _pack_for(model, dev, backward=True)
     B, K = inds.shape
     HW = pose_map.shape[2] * pose_map.shape[3]
-    P = B * n
-    gv = None if grad_verts is None else grad_verts.detach().float().contiguous()
-    gj = None if grad_joints is None else grad_joints.detach().float().contiguous()
+    L, gv, gj, ws = _backward_inputs(d, B * n, dev, grad_verts, grad_joints)
     gp = torch.empty_like(pose_map)
     gs = torch.empty_like(shape_map)
-    L = _lib.lib()
-    ws = _lib.workspace(L.h3d_smpl_backward_workspace_bytes, P, d["V"], d["Vpad"], d["nnz"], int(gv is not None), device=dev,
-                        what="smpl_backward_workspace_bytes")
     with torch.cuda.device(dev):
         st = _lib.stream_ptr()
         _lib.check(L.h3d_smpl_heads_backward(_lib.ptr(pose_map), _lib.ptr(shape_map), _lib.ptr(inds), B, K, n, HW, _lib.ptr(gv), _lib.ptr(gj),
-                                             _lib.ptr(d["j_template"]), _lib.ptr(d["j_shapedirs"]), _lib.ptr(d["parents"]),
-                                             _lib.ptr(d["v_template"]), _lib.ptr(d["dirsK3"]), _lib.ptr(d["dirsV3"]), _lib.ptr(d["lbs_idx"]),
-                                             _lib.ptr(d["lbs_w"]), d["nnz"], d["V"], d["Vpad"], _lib.ptr(gp), _lib.ptr(gs), _lib.ptr(ws),
+                                             *_model_ptrs(d), d["nnz"], d["V"], d["Vpad"], _lib.ptr(gp), _lib.ptr(gs), _lib.ptr(ws),
                                              ws.numel() if ws is not None else 0, st), "smpl_heads_backward")
     return gp, gs
+
+
+def _backward_inputs(d, P, dev, grad_verts, grad_joints):
+    """What a call of h3d_smpl_backward / h3d_smpl_heads_backward needs besides the parameters: the library, the upstream gradients as
+    dense fp32 (None = absent) and the workspace (None = none needed)."""
+    gv = None if grad_verts is None else grad_verts.detach().float().contiguous()       # (an expanded upstream becomes dense here)
+    gj = None if grad_joints is None else grad_joints.detach().float().contiguous()
+    L = _lib.lib()
+    ws = _lib.workspace(L.h3d_smpl_backward_workspace_bytes, P, d["V"], d["Vpad"], d["nnz"], int(gv is not None), device=dev,
+                        what="smpl_backward_workspace_bytes")
+    return L, gv, gj, ws
+
+
+def _model_ptrs(d):
+    return [_lib.ptr(d[k]) for k in ("j_template", "j_shapedirs", "parents", "v_template", "dirsK3", "dirsV3", "lbs_idx", "lbs_w")]
 
 
 _functions = None
@@ -283,32 +285,35 @@ def lbs(model, betas, thetas, return_joints=False, kernel="auto"):
     need <= 4 skinning weights per vertex), "gen1" = register kernel, "auto" = gen3 when applicable and P >= 64, "auto_exact" = gen3x."""
     import torch
     if torch.is_grad_enabled() and (betas.requires_grad or thetas.requires_grad):
-        _lib_check_cuda(betas, thetas)
+        _lib.require_cuda(betas, thetas)
         verts, joints = _autograd_functions()[0].apply(model, kernel, betas, thetas)
         return (verts, joints) if return_joints else verts
     return _lbs_forward(model, betas, thetas, return_joints, kernel)
 
 
-def _lib_check_cuda(*tensors):
-    from . import _lib
-    _lib.require_cuda(*tensors)
+def _forward_outputs(d, P, dev):
+    """Uninitialised pose_feat, A, joints, verts of a forward over P persons."""
+    import torch
+    return (torch.empty(P, NUM_POSE_FEAT, dtype=torch.float32, device=dev), torch.empty(P, NUM_JOINTS, 12, dtype=torch.float32, device=dev),
+            torch.empty(P, NUM_JOINTS, 3, dtype=torch.float32, device=dev), torch.empty(P, d["V"], 3, dtype=torch.float32, device=dev))
+
+
+def _verts3(L, d, coefK, A, verts, P, Ppad, exact, st):
+    """The generation-3 vertex launch on a filled coefficient operand and A."""
+    fn = L.h3d_smpl_verts3_exact if exact else L.h3d_smpl_verts3
+    _lib.check(fn(_lib.ptr(coefK), _lib.ptr(A), _lib.ptr(d["v_template"]), _lib.ptr(d["dirsK3"]), _lib.ptr(d["lbs_idx"]), _lib.ptr(d["lbs_w"]),
+                  d["nnz"], P, Ppad, d["V"], d["Vpad"], _lib.ptr(verts), st), "smpl_verts3")
 
 
 def _lbs_forward(model, betas, thetas, return_joints, kernel):
     import torch
-    from . import _lib
     _lib.require_cuda(betas, thetas)
     dev = betas.device
-    if model._dev is None or model._dev["v_template"].device != dev:
-        model._dev = _device_pack(model, dev)
-    d = model._dev
+    d = _pack_for(model, dev)
     betas = betas.contiguous().float()
     thetas = thetas.contiguous().float().view(betas.shape[0], 72)
     P = betas.shape[0]
-    pf = torch.empty(P, NUM_POSE_FEAT, dtype=torch.float32, device=dev)
-    A = torch.empty(P, NUM_JOINTS, 12, dtype=torch.float32, device=dev)
-    joints = torch.empty(P, NUM_JOINTS, 3, dtype=torch.float32, device=dev)
-    verts = torch.empty(P, d["V"], 3, dtype=torch.float32, device=dev)
+    pf, A, joints, verts = _forward_outputs(d, P, dev)
     L = _lib.lib()
     gen3 = kernel in ("gen3", "gen3x") or (kernel in ("auto", "auto_exact") and d["nnz"] <= 4 and P >= 64)
     exact = kernel in ("gen3x", "auto_exact")
@@ -323,10 +328,7 @@ def _lbs_forward(model, betas, thetas, return_joints, kernel):
         if gen3:
             coefK = torch.empty(Ppad, 14, 3, 16, dtype=torch.bfloat16, device=dev)
             _lib.check(L.h3d_smpl_coef_pack(_lib.ptr(betas), _lib.ptr(pf), P, Ppad, _lib.ptr(coefK), st), "smpl_coef_pack")
-            fn = L.h3d_smpl_verts3_exact if exact else L.h3d_smpl_verts3
-            _lib.check(fn(_lib.ptr(coefK), _lib.ptr(A), _lib.ptr(d["v_template"]), _lib.ptr(d["dirsK3"]),
-                          _lib.ptr(d["lbs_idx"]), _lib.ptr(d["lbs_w"]), d["nnz"], P, Ppad, d["V"], d["Vpad"],
-                          _lib.ptr(verts), st), "smpl_verts3")
+            _verts3(L, d, coefK, A, verts, P, Ppad, exact, st)
         elif gen2:
             _lib.check(L.h3d_smpl_verts2(_lib.ptr(coefT), _lib.ptr(A), _lib.ptr(d["v_template"]),
                                          _lib.ptr(d["shapedirsT"]), _lib.ptr(d["posedirsT"]), _lib.ptr(d["lbs_idx"]),
@@ -350,7 +352,7 @@ def lbs_from_heads(model, pose_map, shape_map, inds, n, return_joints=False, exa
     (h3d_smpl_heads_backward: zero off the gathered pixels, detections that share a pixel add up)."""
     import torch
     if torch.is_grad_enabled() and (pose_map.requires_grad or shape_map.requires_grad):
-        _lib_check_cuda(pose_map, shape_map, inds)
+        _lib.require_cuda(pose_map, shape_map, inds)
         verts, joints = _autograd_functions()[1].apply(model, n, exact, inds, pose_map, shape_map)
         return (verts, joints) if return_joints else verts
     return _lbs_from_heads_forward(model, pose_map, shape_map, inds, n, return_joints, exact)
@@ -358,12 +360,9 @@ def lbs_from_heads(model, pose_map, shape_map, inds, n, return_joints=False, exa
 
 def _lbs_from_heads_forward(model, pose_map, shape_map, inds, n, return_joints, exact):
     import torch
-    from . import _lib
     _lib.require_cuda(pose_map, shape_map, inds)
     dev = pose_map.device
-    if model._dev is None or model._dev["v_template"].device != dev:
-        model._dev = _device_pack(model, dev)
-    d = model._dev
+    d = _pack_for(model, dev)
     if d["nnz"] > 4:
         raise RuntimeError("lbs_from_heads: more than 4 skinning weights per vertex (use lbs)")
     if (pose_map.dtype != torch.float32 or shape_map.dtype != torch.float32 or not pose_map.is_contiguous() or not shape_map.is_contiguous()
@@ -375,10 +374,7 @@ def _lbs_from_heads_forward(model, pose_map, shape_map, inds, n, return_joints, 
         raise RuntimeError("lbs_from_heads: pose [B,72,H,W], shape [B,10,H,W], inds [B,K], 0 < n <= K")
     P = B * n
     Ppad = ((P + 127) // 128) * 128
-    pf = torch.empty(P, NUM_POSE_FEAT, dtype=torch.float32, device=dev)
-    A = torch.empty(P, NUM_JOINTS, 12, dtype=torch.float32, device=dev)
-    joints = torch.empty(P, NUM_JOINTS, 3, dtype=torch.float32, device=dev)
-    verts = torch.empty(P, d["V"], 3, dtype=torch.float32, device=dev)
+    pf, A, joints, verts = _forward_outputs(d, P, dev)
     coefK = torch.empty(Ppad, 14, 3, 16, dtype=torch.bfloat16, device=dev)
     L = _lib.lib()
     with torch.cuda.device(dev):
@@ -386,7 +382,5 @@ def _lbs_from_heads_forward(model, pose_map, shape_map, inds, n, return_joints, 
         _lib.check(L.h3d_smpl_pose_heads(_lib.ptr(pose_map), _lib.ptr(shape_map), _lib.ptr(inds), B, K, n, HW, _lib.ptr(d["j_template"]),
                                          _lib.ptr(d["j_shapedirs"]), _lib.ptr(d["parents"]), None, _lib.ptr(pf), _lib.ptr(A), _lib.ptr(joints),
                                          _lib.ptr(coefK), Ppad, st), "smpl_pose_heads")
-        fn = L.h3d_smpl_verts3_exact if exact else L.h3d_smpl_verts3
-        _lib.check(fn(_lib.ptr(coefK), _lib.ptr(A), _lib.ptr(d["v_template"]), _lib.ptr(d["dirsK3"]), _lib.ptr(d["lbs_idx"]), _lib.ptr(d["lbs_w"]),
-                      d["nnz"], P, Ppad, d["V"], d["Vpad"], _lib.ptr(verts), st), "smpl_verts3")
+        _verts3(L, d, coefK, A, verts, P, Ppad, exact, st)
     return (verts, joints) if return_joints else verts
