@@ -123,6 +123,8 @@ class H3dTrainImage(ctypes.Structure):
 
 
 SMPL_KP_MAX_K, SMPL_KP_MAX_NV = 32, 16              # H3D_SMPL_KP_MAX_K / H3D_SMPL_KP_MAX_NV
+RENDER_NEGATE_Z, RENDER_CULL_BACK = 1, 2           # H3D_RENDER_NEGATE_Z / H3D_RENDER_CULL_BACK
+RENDER_MAX_V, RENDER_MAX_SIDE = 13120, 16384        # H3D_RENDER_MAX_V / H3D_RENDER_MAX_SIDE
 ADAM_CAPACITY, ADAM_CHUNK = 48, 2048        # H3D_ADAM_CAPACITY / H3D_ADAM_CHUNK: tensors per launch, elements per workgroup
 
 
@@ -189,6 +191,10 @@ SIGNATURES = {
     "h3d_smpl_kp_loss_workspace_bytes": [c_i, c_i, ctypes.POINTER(ctypes.c_size_t)],
     "h3d_smpl_kp_loss_forward": [c_vp] * 6 + [c_i] + [c_vp] * 3 + [c_i] * 7 + [c_vp] * 4 + [ctypes.c_size_t, c_vp],
     "h3d_smpl_kp_loss_backward": [c_vp] * 6 + [c_i] + [c_vp] * 7 + [c_i] * 7 + [c_vp] * 4,
+    # mesh rendering (include/h3d.h section 4d; h3d_amd/render.py)
+    "h3d_render_workspace_bytes": [c_i] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
+    "h3d_render_rasterize": [c_vp] * 6 + [c_i] * 9 + [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
+    "h3d_render_shade": [c_vp] * 5 + [c_i] * 6 + [ctypes.c_float, ctypes.c_float, c_i, c_i, c_vp, c_vp],
     # heads backward (include/h3d.h section 2b; h3d_amd/heads.py holds the mirror of `struct h3d_heads_bwd_head`)
     "h3d_heads_backward_workspace_bytes": [c_i] * 5 + [c_vp, ctypes.POINTER(ctypes.c_size_t)],
     "h3d_heads_backward": [c_vp] + [c_i] * 6 + [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],

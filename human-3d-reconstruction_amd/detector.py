@@ -51,6 +51,7 @@ class Opt:
         self.flip_idx = [[1, 2], [3, 4], [5, 6], [7, 8], [9, 10], [11, 12], [13, 14], [15, 16]]       # opts.py:250
         self.smpl = False             # north_star extension: pose/shape heads + LBS
         self.smpl_people = None       # meshes per image (None = K)
+        self.smpl_cam = False         # with smpl: a 3-channel `cam` head (s, tx, ty: smpl_loss trains it, render.render_detections reads it)
         self.dtype = "bf16"
         for k, v in kw.items():
             setattr(self, k, v)
@@ -72,6 +73,8 @@ class Opt:
                 heads["hp_offset"] = 2
             if self.smpl:
                 heads.update(SMPL_HEADS)
+                if self.smpl_cam:
+                    heads["cam"] = 3
         else:
             raise ValueError("task not defined!")              # opts.py:260
         self.heads = heads

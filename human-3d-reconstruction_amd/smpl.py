@@ -24,7 +24,7 @@ PARENTS = np.array([-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16
 class SMPLModel:
     """Host container of the SMPL tensors (float32 numpy) + lazily-built device pack."""
 
-    def __init__(self, v_template, shapedirs, posedirs, J_regressor, weights, parents=PARENTS):
+    def __init__(self, v_template, shapedirs, posedirs, J_regressor, weights, parents=PARENTS, faces=None):
         self.v_template = np.ascontiguousarray(v_template, np.float32)      # [V,3]
         self.shapedirs = np.ascontiguousarray(shapedirs, np.float32)        # [V,3,10]
         self.posedirs = np.ascontiguousarray(posedirs, np.float32)          # [V,3,207]
@@ -41,6 +41,13 @@ class SMPLModel:
         if par.shape != (NUM_JOINTS,) or par[0] != -1 or not all(0 <= par[j] < j for j in range(1, NUM_JOINTS)):
             raise ValueError("SMPLModel: parents must be %d entries with parents[0] == -1 and 0 <= parents[j] < j (parents first), got %s"
                              % (NUM_JOINTS, par.tolist()))
+        # the surface (render.MeshRenderer reads it; the skinning stage does not): [F,3] int32 vertex indices, or None
+        self.faces = None
+        if faces is not None:
+            f = np.asarray(faces)
+            if f.dtype.kind not in "iu" or f.ndim != 2 or f.shape[1] != 3 or (f.size and (int(f.min()) < 0 or int(f.max()) >= V)):
+                raise ValueError("SMPLModel: faces must be integers [F,3] in [0, %d), got %s %s" % (V, f.dtype, f.shape))
+            self.faces = np.ascontiguousarray(f, np.int32)
         self._dev = None
 
     @classmethod
@@ -67,13 +74,17 @@ class SMPLModel:
     def from_npz(cls, path):
         d = np.load(path, allow_pickle=False)
         parents = d["parents"] if "parents" in d else PARENTS
+        faces = d["faces"] if "faces" in d else d["f"] if "f" in d else None
         return cls(d["v_template"], d["shapedirs"], d["posedirs"], d["J_regressor"], d["weights"],
-                   parents)
+                   parents, faces=faces)
 
     def numpy_dict(self):
-        return {"v_template": self.v_template, "shapedirs": self.shapedirs,
-                "posedirs": self.posedirs, "J_regressor": self.J_regressor,
-                "weights": self.weights, "parents": self.parents}
+        d = {"v_template": self.v_template, "shapedirs": self.shapedirs,
+             "posedirs": self.posedirs, "J_regressor": self.J_regressor,
+             "weights": self.weights, "parents": self.parents}
+        if self.faces is not None:
+            d["faces"] = self.faces
+        return d
 
 
 # ----------------------------------------------------------------------------------------------

@@ -759,6 +759,73 @@ int h3d_smpl_kp_loss_backward(const float *kp3d, const float *pred, const float 
                               void *stream);
 
 /* =====================================================================================
+ * 4d. Mesh rendering: a z-buffered visibility-buffer rasteriser for batches of posed meshes under section 4c's weak-perspective camera
+ *    (csrc/render.hip; h3d_amd/render.py; no reference code: the project's own definition).
+ *    Inputs: verts [P,V,3] f32 with P = B n (slot p = b n + m belongs to image b), faces [F,3] i32 shared by all slots, cam_map
+ *    [B,3,H,W] f32 and ind [B,max_objs] i64 read in place exactly as section 4c reads them, valid [P] u8 or NULL, dz [P] f32 or NULL
+ *    (NULL = 0), the integer up-sampling factor up >= 1: the target is Hr x Wr = up H x up W pixels.
+ *    Every float step below is ONE IEEE-754 binary32 operation, round to nearest even, no contraction, / and sqrt correctly rounded,
+ *    denormals kept; (float)(integer) rounds to nearest even.
+ *    PROJECTION of vertex (X, Y, Z) of slot p, with (s, tx, ty) = cam_map[b, 0..2, ind[b,m]] and cx = ind % W, cy = ind / W:
+ *        xs = (float)up * (((s * X) + tx) + (float)cx)        ys = (float)up * (((s * Y) + ty) + (float)cy)
+ *        fx = rintf(16 * xs), fy = rintf(16 * ys)              the 1/16-pixel lattice; xi = (int)fx, yi = (int)fy
+ *        d  = Z + dz[p]            with H3D_RENDER_NEGATE_Z:  d = (-Z) + dz[p]            (a smaller d is nearer)
+ *      A vertex is BAD when |fx| <= 2^19, |fy| <= 2^19 or |d| < inf fails (so with any NaN).  Pixel (i, j) of the target is sampled at
+ *      lattice point (16 i, 16 j): no half-pixel shift (CenterNet's map-to-input scaling), so a vertex and the pred of section 4c of the
+ *      same body point coincide.
+ *    SKIPPED SLOTS (write nothing): ind outside [0,HW); valid[p] == 0; s NaN, infinite or <= 0.
+ *    SKIPPED FACES: an index outside [0,V) (never dereferenced); a BAD vertex; o == 0, or H3D_RENDER_CULL_BACK and S < 0, where
+ *        o = (int64)(x1 - x0) * (y2 - y0) - (int64)(y1 - y0) * (x2 - x0)                   (exact: every product is below 2^42)
+ *        S = -o, with H3D_RENDER_NEGATE_Z S = o: the doubled signed area, POSITIVE when the side from which the face's vertices run
+ *        counter-clockwise in the right-handed body frame -- the outside of an outward-oriented mesh -- is turned to the viewer.
+ *    COVERAGE (exact integers): with o < 0 vertices 1 and 2 (and their d) change places, so that A = |o| > 0.  At lattice point (px, py)
+ *        w0 = (x2 - x1) (py - y1) - (y2 - y1) (px - x1)       edge 0 = v1 -> v2
+ *        w1 = (x0 - x2) (py - y2) - (y0 - y2) (px - x2)       edge 1 = v2 -> v0
+ *        w2 = (x1 - x0) (py - y0) - (y1 - y0) (px - x0)       edge 2 = v0 -> v1               (w0 + w1 + w2 = A)
+ *      The pixel is covered when for every edge w > 0, or w == 0 and the edge a -> b is a TOP edge (by == ay and bx > ax) or a LEFT edge
+ *      (by < ay): the top-left rule -- a pixel centre on an edge shared by two faces belongs to exactly one of them, one on the right or
+ *      bottom border of a mesh to none.  Only the pixels of the bounding box [ceil(min x / 16), floor(max x / 16)] x (the same in y),
+ *      clipped to the target, are visited.
+ *    DEPTH at a covered pixel:  depth = d0 + (((float)w1 * (d1 - d0)) + ((float)w2 * (d2 - d0))) / (float)A   (two differences, two
+ *      products, one sum, one division, one sum, in this order; d1 and d2 after the exchange above).  A face of one depth has exactly that
+ *      depth everywhere, and the rounding errors scale with the depth range of the face, not with its distance.  A face whose depth is NaN
+ *      at the pixel does not take it.
+ *    VISIBILITY: one 64-bit key per target pixel, key = hi << 32 | (m F + f) with u = the bits of depth and hi = ~u if u has its sign
+ *      bit set, else u | 0x80000000 (unsigned order = float order, -0 below +0; invertible).  The key buffer starts as all ones (one
+ *      memset) and every covering face takes an unsigned 64-bit atomic minimum: the result is the nearest face, among equal depths the
+ *      smallest id, whatever the arrival order -- bit-identical from run to run.  No float atomics.  n F must be below 2^31.
+ *    OUTPUTS (every byte is written; hand in uninitialised memory): face_id [B,Hr,Wr] i32 = m F + f or -1 (background);
+ *      depth [B,Hr,Wr] f32 = the float recovered from the key, +inf for background; rgb [B,Hr,Wr,3] u8 (the shade entry point) over
+ *      image [B,Hr,Wr,3] u8 or, with image NULL, the colour `background` (0xRRGGBB).
+ *    SHADING of the winning face (f, m) of a pixel, headlight Lambert, from the body coordinates (v0, v1, v2 in the face's own order):
+ *        e1 = v1 - v0, e2 = v2 - v0;  nx = e1y e2z - e1z e2y, ny = e1z e2x - e1x e2z, nz = e1x e2y - e1y e2x      (two products, one difference)
+ *        len = sqrtf((nx nx + ny ny) + nz nz);   I = 0 if len == 0, else ambient + (1 - ambient) * (|nz| / len)
+ *        out_c = sat8(rintf(alpha * (I * (float)colour_c) + (1 - alpha) * (float)image_c))     sat8: NaN and negatives 0, above 255 -> 255
+ *      colour [P,3] u8 or NULL (then default_colour, 0xRRGGBB); a background pixel copies image_c (or the background colour).  A key whose
+ *      id is not below n F, or whose face holds an index outside [0,V), is shaded as background (a key buffer of another mesh cannot
+ *      make the kernel read out of bounds).  The keys are only read: one key buffer serves any number of shade calls.
+ *    Launches: rasterize = one memset, render_raster_kernel (one workgroup per slot: the slot's projected vertices in LDS, 12 bytes each),
+ *      render_resolve_kernel; shade = one render_resolve_kernel launch.  Asynchronous on `stream`, no allocation.
+ *    Workspace: the key buffer, a256(8 B Hr Wr) bytes, 8-byte aligned; rasterize leaves the keys in it for the shade entry point.
+ *    Checked before the first HIP call: NULL verts / faces / cam_map / ind / outputs / keys, a NULL, short or not 8-byte aligned
+ *      workspace ("workspace" in the message), unknown flag bits, alpha or ambient outside [0,1] (or NaN): H3D_ERR_ARG; B, max_objs, n,
+ *      V, F, H, W <= 0, n > max_objs, up < 1, Hr or Wr > H3D_RENDER_MAX_SIDE, B Hr Wr >= 2^31: H3D_ERR_SHAPE; V > H3D_RENDER_MAX_V (the
+ *      largest V, a multiple of 64, whose 12 V bytes of staging fit the 160 KiB of LDS beside the 6 KiB face queue), n F >= 2^31:
+ *      H3D_ERR_UNSUPPORTED.  There is no second path.
+ * ===================================================================================== */
+#define H3D_RENDER_NEGATE_Z 1
+#define H3D_RENDER_CULL_BACK 2
+#define H3D_RENDER_MAX_V 13120
+#define H3D_RENDER_MAX_SIDE 16384
+int h3d_render_workspace_bytes(int B, int Hr, int Wr, size_t *bytes);
+int h3d_render_rasterize(const float *verts, const int32_t *faces, const float *cam_map, const int64_t *ind, const uint8_t *valid,
+                         const float *dz, int B, int max_objs, int n, int V, int F, int H, int W, int up, int flags, int32_t *face_id,
+                         float *depth, void *workspace, size_t workspace_bytes, void *stream);
+int h3d_render_shade(const void *keys, const float *verts, const int32_t *faces, const uint8_t *colour, const uint8_t *image, int B, int n,
+                     int V, int F, int Hr, int Wr, float alpha, float ambient, int default_colour, int background, uint8_t *rgb,
+                     void *stream);
+
+/* =====================================================================================
  * 5. Losses (losses.py, trains/trainer.py:29-137): the focal term of `_neg_loss` (losses.py:42-67) and the four gathered regression
  *    terms, forward and backward, in descriptor form: one h3d_loss_term per term, ALL terms of a call in one partial-sum launch plus
  *    one finish launch (csrc/loss.hip).  No host synchronisation: where the reference branches on the host (`if num_pos == 0`) the
