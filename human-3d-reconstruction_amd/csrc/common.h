@@ -287,15 +287,16 @@ template <> struct ET<f16_t> {
 
 // "f16x3" plans (H3D_F16X3, round 5): fp32 STORAGE everywhere (activations, residuals, head maps: the layout, the launches and the
 // elementwise kernels of the f32 plan), but every contraction runs on the fp16 matrix cores with both fp32 operands split into two
-// fp16 terms, x = hi + lo with hi = fp16(x) and lo = fp16(x - hi) (round to nearest even: |x - hi - lo| <= 2^-24 |x| while lo is a
-// normal fp16, <= 3e-8 absolute below that), and THREE products per fp32 product -- hi.hi + hi.lo + lo.hi, the dropped lo.lo is
+// fp16 terms, x = hi + lo with hi = fp16(x) and lo = fp16(x - hi) (round to nearest even: |x - hi - lo| <= 2^-23 |x| while lo is a
+// normal fp16, <= 2^-25 = 3e-8 ABSOLUTE once it is a subnormal one, i.e. below |x| ~ 2^-2: DESIGN.md 9.4), and THREE products per fp32 product -- hi.hi + hi.lo + lo.hi, the dropped lo.lo is
 // 2^-22 relative -- accumulated in fp32 by the MFMA: 3 x v_mfma_f32_32x32x16_f16 (96 cycles) per 16-channel step instead of
 // 8 x v_mfma_f32_32x32x2_f32 (512 cycles).  This is the parity arithmetic on the 2.5 PFLOP/s matrix cores: the reference computes
 // in fp32 throughout (dcn_v2_cuda.cu:59 `using scalar_t = float`; model.py modules are fp32), and "bit-exact top-k indices" only
 // survives fp32-level head errors.  A fragment is the SAME 32 bytes per lane as ET<float>'s (8 K elements), holding the 8 hi halves
 // in the first 16 bytes and the 8 lo halves in the second: the LDS geometry of every kernel is the f32 one, filters are pre-split
 // by the host (engine.PackedWeights), activations are split by the thread that stages them into LDS.
-// CONTRACT (network plans): |activation| <= 65504 (fp16's range; larger values and NaN saturate, finite) -- three orders of magnitude
+// CONTRACT (network plans): |activation| <= 65504 (fp16's range; larger values and NaN saturate, finite: every kernel computes on the
+// activation CLAMPED to +-65504, whichever staging path reads it -- tests/test_gpu_x3_domain.py) -- three orders of magnitude
 // above anything a DLA-34 / Hourglass / ResNet feature map holds.  The fp32 OPERATOR (csrc/dcn2.hip behind 0x200000, csrc/dcn3.hip's
 // `DCN` module launch) scales its activations by a device-derived power of two first (dcn_act_exp) and does not clamp its samples.
 struct x3_t { float v; };          // element type tag: 4 bytes of fp32 in memory

@@ -161,11 +161,19 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
     // the `DCN` module's launch (H3D_OPF_DCN_FUSED_SCALED_INPUT): x arrives scaled below 2^14 (h3d_dcn_nchw_to_nhwc_scaled), so staging and splitting need no
     // clamp -- and take none, so that a NaN / inf activation stays non-finite through both contractions as it does in the reference
     [[maybe_unused]] const bool xraw = std::is_same_v<T, x3_t> && !WDMA && a.xscaled;
-    [[maybe_unused]] auto prep_mem = [&](const typename X::frag &f) {      // a sample blended from values read straight from memory
-        if constexpr (std::is_same_v<T, x3_t> && !WDMA) {
-            if (xraw) return X::prep(f);
+    // A corner fragment read straight from memory (pass 2).  f16x3 plans clamp it to +-65504 as the staging clamps the apron (X::convert16), so
+    // that a far sample is the SAME blend of clamped values an apron sample is -- clamping the blend instead gave w * 1e5 where the contract
+    // (common.h) says w * 65504, and 65504 for any weight on an infinity (found by tests/test_gpu_x3_domain.py).  The blend of clamped
+    // corners needs no clamp of its own (X::prep).  The `DCN` module's scaled input is clamped nowhere (xraw, above).
+    [[maybe_unused]] auto corner_mem = [&](const char *p) {
+        typename X::frag f = X::global8(p);
+        if constexpr (std::is_same_v<T, x3_t>) {
+            if (!xraw) {
+                f.lo = __builtin_bit_cast(f32x4, X::convert16(__builtin_bit_cast(u32x4, f.lo)));
+                f.hi = __builtin_bit_cast(f32x4, X::convert16(__builtin_bit_cast(u32x4, f.hi)));
+            }
         }
-        return X::prep_raw(f);
+        return f;
     };
     [[maybe_unused]] auto store_w = [&](char *dst_row_tap, int v, u32x4 raw, int which) {      // one 16-byte vector of a staged filter row -> LDS
         if constexpr (std::is_same_v<T, x3_t> && !WDMA) {
@@ -543,14 +551,15 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
             }
         }
     };
-    // f16x3: a patch unit is 4 fp32 channels of the sample, blended in fp32 with the entry's four weights
+    // f16x3: a patch unit is 4 fp32 channels of the sample, blended in fp32 with the entry's four weights from corners CLAMPED as the apron's
+    // are (X::convert16; see corner_mem): the slot is read by X::prep, which does not clamp, and a blend of clamped corners needs none
     auto blend4 = [&](const u32x4 (&c)[4], const typename X::geo &g) -> u32x4 {
         u32x4 o = {0u, 0u, 0u, 0u};
         if constexpr (SS == 4) {
+            auto cl = [](uint32_t v) { return __builtin_amdgcn_fmed3f(__uint_as_float(v), -65504.f, 65504.f); };
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                o[e] = __float_as_uint(__builtin_amdgcn_fmed3f(fmaf(g.w[3], __uint_as_float(c[3][e]), fmaf(g.w[2], __uint_as_float(c[2][e]), fmaf(g.w[1], __uint_as_float(c[1][e]), g.w[0] * __uint_as_float(c[0][e])))),
-                                                               -65504.f, 65504.f));      // (the slot is read by X::prep, which does not clamp)
+                o[e] = __float_as_uint(fmaf(g.w[3], cl(c[3][e]), fmaf(g.w[2], cl(c[2][e]), fmaf(g.w[1], cl(c[1][e]), g.w[0] * cl(c[0][e])))));
         }
         return o;
     };
@@ -881,12 +890,12 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
                         typename X::frag v[4];
                         if constexpr (SS == 4) {
 #pragma unroll
-                            for (int k = 0; k < 4; ++k) { v[k].lo = __builtin_bit_cast(f32x4, pv[j][k][0]); v[k].hi = __builtin_bit_cast(f32x4, pv[j][k][CV - 1]); }
+                            for (int k = 0; k < 4; ++k) { v[k].lo = __builtin_bit_cast(f32x4, X::convert16(pv[j][k][0])); v[k].hi = __builtin_bit_cast(f32x4, X::convert16(pv[j][k][CV - 1])); }      // (clamped: see corner_mem)
                         } else {
 #pragma unroll
                             for (int k = 0; k < 4; ++k) v[k].v = __builtin_bit_cast(half8_t, X::convert16(pv[j][k][0]));
                         }
-                        fbs[j] = prep_mem(X::blend(v, qg[t0 + j]));
+                        fbs[j] = X::prep(X::blend(v, qg[t0 + j]));
                     }
                     if (t0 + TB < 9) fetch(t0 + TB);                               // the next taps fly while these are multiplied
 #pragma unroll
@@ -924,14 +933,14 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
                 for (int kk = 0; kk < CK / 16; ++kk) fb[kk] = X::zero();
                 const bool any = dcn_far_gather<X, C::HH>(fb, live && !((pmask >> tap) & 1), (float)(oy - 1 + ti) + d.d_h, (float)(ox - 1 + tj) + d.d_w, hy0, hx0, a.H, a.W,
                     [&] { return dcn2_sigmoid(d.d_m); },
-                    [&](int kk, int y, int x) { return X::global8(img + ((size_t)(y * a.W + x) * a.in_cs + c0 + kk * 16 + 8 * h) * ES); });
+                    [&](int kk, int y, int x) { return corner_mem(img + ((size_t)(y * a.W + x) * a.in_cs + c0 + kk * 16 + 8 * h) * ES); });
                 if (!__any(any)) continue;
 #pragma unroll
                 for (int kk = 0; kk < CK / 16; ++kk) {
                     typename X::wfrag fa[MT];
 #pragma unroll
                     for (int m = 0; m < MT; ++m) fa[m] = X::lds_w(s_w + aoff + m * 32 * C::WB + (tap * CK + kk * 16) * SS);
-                    const typename X::bfrag pb = prep_mem(fb[kk]);
+                    const typename X::bfrag pb = X::prep(fb[kk]);
 #pragma unroll
                     for (int m = 0; m < MT; ++m) X::mma(acc[m][0], fa[m], pb);
                 }

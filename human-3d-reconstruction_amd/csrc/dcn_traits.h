@@ -195,7 +195,8 @@ template <> struct SE<x3_t> : SE<float> {
     static __device__ __forceinline__ wfrag lds_w(const char *p) { return ET<x3_t>::lds_frag(p); }
     // prep: a sample blended from values that went through convert16 (clamped to the fp16 range while staging: a convex combination
     // times a mask in (0, 1) stays inside it), so the split needs no clamp of its own -- 8 of its 28 vector instructions, nine times per
-    // staged element.  prep_raw: a sample blended from values read straight from memory (pass 2).
+    // staged element.  prep_raw: a sample blended from UNCLAMPED values read straight from memory (pass 2 of csrc/dcn2.hip's operator without
+    // an activation scale; csrc/dcn3.hip clamps such corners as they arrive and uses prep).
     static __device__ __forceinline__ bfrag prep(const frag &f)
     {
         const float x[8] = {f.lo[0], f.lo[1], f.lo[2], f.lo[3], f.hi[0], f.hi[1], f.hi[2], f.hi[3]};
