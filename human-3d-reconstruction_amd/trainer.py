@@ -109,6 +109,43 @@ class HeadsTrainer:
         ret["time"] = (time.time() - start) / 60.0
         return ret, results
 
+    @torch.no_grad()
+    def val(self, data_loader, gt):
+        """The reference's val() (trainer.py:326-328, save_result :456-469, datasets/coco_hp.py:92-138) for multi_pose: the detector path
+        (network with the heads as trained, decode with opt.K, post-process) over the loader, then COCO's keypoint and box evaluation of
+        the collected records on the device (coco_eval) -> (keypoint stats [10], bbox stats [12]); the two coco_eval.EvalResult are kept
+        in self.last_val.  gt: coco_eval.GroundTruth.  A batch: dict(input [B,3,H,W], meta = dict(c [B,2], s [B], index [B] = the
+        images' positions in gt)); images the loader never shows count as images without detections."""
+        from . import coco_eval, decode
+        from .detector import multi_pose_post_process
+        opt = self.opt
+        if _opt(opt, "task", "multi_pose") != "multi_pose":
+            raise ValueError("HeadsTrainer.val: task %r not defined" % (_opt(opt, "task", None),))
+        model = self.model
+        was_training = model.training
+        model.eval()
+        model.set_compute_dtype(model.compute_dtype)        # drops the cached plan: it is rebuilt from the parameters as they are now
+        num_iters = _opt(opt, "num_iters", -1)
+        if num_iters < 0:
+            num_iters = len(data_loader)
+        device = _opt(opt, "device", None)
+        collected = coco_eval.CocoEvaluator(gt, "keypoints")
+        for iter_id, batch in enumerate(data_loader):
+            if iter_id >= num_iters:
+                break
+            x, meta = batch["input"], batch["meta"]
+            if device is not None:
+                x = x.to(device=device, non_blocking=True)
+            out = model(x)[-1]
+            dets = decode.multi_pose_decode_logits(
+                out["hm"], out["wh"], out["hps"], reg=out.get("reg") if _opt(opt, "reg_offset", True) else None,
+                hm_hp=out.get("hm_hp") if _opt(opt, "hm_hp", True) else None,
+                hp_offset=out.get("hp_offset") if _opt(opt, "reg_hp_offset", True) else None, K=_opt(opt, "K", 100))
+            collected.update(meta["index"], multi_pose_post_process(dets, meta["c"], meta["s"], out["hm"].shape[2], out["hm"].shape[3]))
+        model.train(was_training)
+        self.last_val = {"keypoints": collected.compute("keypoints"), "bbox": collected.compute("bbox")}
+        return self.last_val["keypoints"].stats, self.last_val["bbox"].stats
+
     def end_epoch(self, epoch):
         """The learning-rate drop of trainer.py:316-320; -> the new rate, or None when `epoch` is no step."""
         if epoch not in self.lr_step:

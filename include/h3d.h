@@ -963,6 +963,78 @@ typedef struct h3d_adam_tensor {
 } h3d_adam_tensor;
 int h3d_adam_step(const h3d_adam_tensor *tensors /* host memory */, int n_tensors, void *stream);
 
+/* =====================================================================================
+ * 8. Evaluation (csrc/eval.hip; h3d_amd/coco_eval.py): COCO keypoint (OKS) and box AP on the device tensors the
+ *    detectors produce -- what the reference's val() gets from pycocotools' COCOeval (datasets/coco_hp.py:92-138, datasets/coco.py:
+ *    126-135).  Detections are fp32 and widened exactly; ground truth, thresholds and every result are fp64.  Every step is ONE IEEE-754
+ *    binary64 operation, round to nearest, no contraction, in the order written here (tests/coco_eval_ref.py restates it with loops);
+ *    exp is the only operation that is not correctly rounded.  Asynchronous on `stream`, no allocation.
+ *
+ *    h3d_coco_match, one workgroup per image n.  dets [N,D,det_stride] f32: a row is x1, y1, x2, y2, score and, for keypoints, 17 (x, y)
+ *    pairs; det_cls [N,D] i32 or NULL (all class 0); det_num [N] i32 or NULL (all D; clamped to [0,D]); ground truth padded to G per
+ *    image: gt_boxes [N,G,4] (x, y, w, h), gt_keypoints [N,G,17,3] (x, y, v; keypoints only), gt_area, gt_iscrowd (u8), gt_cls [N,G],
+ *    gt_num [N] (clamped to [0,G]).  area_rng [A,2], iou_thrs [T], kp_vars [17] = (2 sigma)^2: device memory, written by the host, so
+ *    that device and host compare against the same doubles.
+ *      records  w = x2 - x1, h = y2 - y1 in fp64; with H3D_COCO_ROUND2 every box value, the score and every keypoint coordinate v becomes
+ *               rint(v * 100) / 100 = float("{:.2f}".format(v)), the reference's export rounding (DOMAIN: finite values, |v| < 2^20;
+ *               rint is half-to-even like the decimal formatting on an exact tie).  area = w * h of the rounded box, for both types.
+ *               Written to dt_box [N,D,4] (x, y, w, h), dt_score, dt_area [N,D], dt_keypoints [N,D,34]; rows d >= det_num are 0.
+ *      ranks    dt_rank [N,D]: the detection's place among those of its image AND class by score descending, stable (ties in index
+ *               order); -1 for d >= det_num.  Detections with rank >= max_det (the largest maxDet) are not matched.
+ *      ignore   gt_ignore [N,A,G] = iscrowd (keypoints: or no joint with v > 0) or area < lo or area > hi; 0 in the padding.
+ *      matrix   row d, column g, 0 in the padding.  Boxes: iw = min(dx + dw, gx + gw) - max(dx, gx), ih likewise; 0 if either is <= 0,
+ *               else I = iw ih, U = dw dh (crowd) or dw dh + gw gh - I, I / U.  Keypoints: k1 = joints with vg > 0; per joint
+ *               dx = xd - xg (k1 > 0) or max(0, x0 - xd) + max(0, xd - x1) with x0 = x - w, x1 = x + w 2 of the ground-truth box
+ *               (k1 = 0), dy likewise; e = (dx dx + dy dy) / vars / (area + 2^-52) / 2; oks = (sum of exp(-e) in joint order over the
+ *               joints with vg > 0, or over all 17 when k1 = 0) / (k1 or 17).  Classes are not looked at here.
+ *      walk     per (area range, threshold t), detections in score order, each against the ground truths of its class, not-ignored
+ *               ones first (stable): best = min(t, 1 - 1e-10), m = none; skip g if matched at this t and not crowd; stop if m is a
+ *               not-ignored one and g is ignored; skip if matrix[d,g] < best; else best = matrix[d,g], m = g (the last of equals
+ *               wins).  dt_match [N,A,T,D] = m (index into the image's ground truths, -1 = none), dt_ignore = gt_ignore of m, or,
+ *               unmatched, area of d outside the range.  Unranked and padding detections: -1 and 0.
+ *    ious [N,D,G] may be NULL; the matrix then lives in LDS when D G 8 <= 96 KiB and in the workspace otherwise (bytes from
+ *    h3d_coco_match_workspace_bytes; with ious given no workspace is used).  LIMITS: D <= H3D_COCO_MAX_D, G <= H3D_COCO_MAX_G,
+ *    A <= H3D_COCO_MAX_A, A T <= H3D_COCO_MAX_LANES: H3D_ERR_UNSUPPORTED beyond them, checked before the first HIP call, nothing is
+ *    written.  Negative sizes, det_stride < 5 (39 for keypoints), max_det < 1, N A T D or N A G >= 2^31: H3D_ERR_SHAPE.  NULL required
+ *    operands, an unknown iou_type or flag, an fp64 pointer off an 8-byte boundary, a NULL or short workspace ("workspace" in the
+ *    message): H3D_ERR_ARG.  N == 0: nothing is launched.
+ *
+ *    h3d_coco_accumulate, one workgroup per (class k, area range a, maxDet m, threshold t).  order [N D] i64: flat indices n D + d of ALL
+ *    detection slots sorted by class, and inside a class by dt_score descending, stable with respect to n D + d (two stable sorts);
+ *    seg_start [K+1] i32: the first position of every class in it (slots that belong to no class of 0 .. K-1 lie outside
+ *    [seg_start[0], seg_start[K])).  Of its class' detections the row keeps those with 0 <= dt_rank < max_dets[m]:
+ *        npig = ground truths of class k with gt_ignore == 0;  npig == 0: precision and recall of the cell are -1
+ *        tp = running count of (matched and not dt_ignore), fp = of (unmatched and not dt_ignore)
+ *        rc = tp / npig;  pr = tp / (fp + tp + 2^-52);  recall = the last rc, 0 without detections
+ *        precision[r] = max { pr[i] : rc[i] >= rec_thrs[r] }, 0 for the empty set
+ *    which is COCOeval's right-to-left envelope followed by searchsorted(rc, recThrs, 'left').  precision [T,R,K,A,M], recall
+ *    [T,K,A,M] fp64.  max_dets [M] is HOST memory (read before the call returns), M <= H3D_COCO_MAX_M; rec_thrs [R] device memory,
+ *    ascending, R <= H3D_COCO_MAX_R.  The workspace (h3d_coco_accumulate_workspace_bytes) holds npig [K,A] i32 at its start.
+ *    A workgroup scans H3D_COCO_SCAN_CHUNK positions per step.  Errors as above.
+ * ===================================================================================== */
+#define H3D_COCO_BBOX 0
+#define H3D_COCO_KEYPOINTS 1
+#define H3D_COCO_ROUND2 1
+#define H3D_COCO_MAX_D 128
+#define H3D_COCO_MAX_G 1024
+#define H3D_COCO_MAX_A 4
+#define H3D_COCO_MAX_LANES 64
+#define H3D_COCO_MAX_M 4
+#define H3D_COCO_MAX_R 128
+#define H3D_COCO_SCAN_CHUNK 1024
+int h3d_coco_match_workspace_bytes(int N, int D, int G, size_t *bytes);
+int h3d_coco_match(const float *dets, int det_stride, const int32_t *det_cls, const int32_t *det_num, const double *gt_boxes,
+                   const double *gt_keypoints, const double *gt_area, const uint8_t *gt_iscrowd, const int32_t *gt_cls,
+                   const int32_t *gt_num, int N, int D, int G, int iou_type, int flags, int max_det, const double *area_rng, int A,
+                   const double *iou_thrs, int T, const double *kp_vars, double *ious, int32_t *dt_match, uint8_t *dt_ignore,
+                   uint8_t *gt_ignore, double *dt_score, int32_t *dt_rank, double *dt_box, double *dt_area, double *dt_keypoints,
+                   void *workspace, size_t workspace_bytes, void *stream);
+int h3d_coco_accumulate_workspace_bytes(int K, int A, size_t *bytes);
+int h3d_coco_accumulate(const int64_t *order, const int32_t *seg_start, const int32_t *dt_rank, const int32_t *dt_match,
+                        const uint8_t *dt_ignore, const uint8_t *gt_ignore, const int32_t *gt_cls, const int32_t *gt_num, int N, int D,
+                        int G, int K, int A, int T, const int32_t *max_dets /* host memory */, int M, const double *rec_thrs, int R,
+                        double *precision, double *recall, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
