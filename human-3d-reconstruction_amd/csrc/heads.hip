@@ -47,6 +47,8 @@ struct HeadsArgs {
     int xcd;   // h3d_tile_id mode
     float s1;                // f16x3 plans: 2^-wexp of the 3x3 filters AND of b1 (h3d_heads_desc.wexp); 1 otherwise
     float s2[HEADS_MAX];     // ... 2^-wexp2 of a head's 1x1 filters
+    const long long *inds;   // sparse launches (h3d_heads_sparse): [B*K] flat output positions y*W + x, image = entry / K
+    int K;
     unsigned long long *stamps;   // profiling builds: per workgroup {kernel start, end, cycles wave 0 spent in the stage barriers, in gemm2, waiting for its own DMA pieces}
 };
 
@@ -55,6 +57,7 @@ struct HeadsCfg {
     static constexpr int TW = 32;
     static constexpr int ES = sizeof(T);
     static constexpr int NT = TH / 8;                 // N-tiles (rows of 32 pixels) per wave, 8 waves
+    static constexpr int NW = 8;                      // waves of the workgroup
     static constexpr int IN_H = TH + 2, IN_W = TW + 2;
     static constexpr int SB = HC_IN * ES + 16;        // halo pixel stride (padded: register-staged once)
     static constexpr int RB = IN_W * SB;              // halo row stride
@@ -70,6 +73,28 @@ struct HeadsCfg {
     static constexpr int LDS = LDS_IN + 2 * SLOT + LDS_W2 + 2 * LDS_BIAS;
     static constexpr int RPI = 1024 / RBW;            // weight rows per LDS-DMA wave-instruction
     static constexpr int VPR = HC_IN * ES / 16;       // 16-byte vectors per halo pixel
+};
+
+// Sparse launches (h3d_heads_sparse): the heads at a LIST of output positions instead of a tile.  A computing wave owns 32 positions,
+// the 32 columns of ONE N-tile (a column of an MFMA result depends on that column's B operand only, so a position's value
+// does not depend on what the other columns hold); each position has its own 3x3 x 64-channel neighbourhood in LDS, laid out as
+// a 3-pixel-wide image of the dense kernel's pixel stride: tap (dy, dx) sits at dy * RB + dx * SB as in the halo tile, and the
+// stage code, gemm2 and the epilogue are the dense kernel's at NT = 1.  Two more waves only help with the LDS-DMA of the
+// filters (an LDS-DMA instruction costs its wave 100-185 issue cycles; a stage is 24 MFMAs per computing wave here).
+template <typename T>
+struct HeadsSparseCfg {
+    using D = HeadsCfg<T, 16>;
+    static_assert(sizeof(T) == 2, "sparse heads: 2-byte plans");
+    static constexpr int ES = D::ES, NT = 1, TW = D::TW;
+    static constexpr int CW = 2, NW = 4;              // computing waves | waves of the workgroup
+    static constexpr int NPOS = 32 * CW;              // positions per workgroup
+    static constexpr int SB = D::SB, RB = 3 * SB, PB = 3 * RB;   // pixel | patch row | patch (position) stride
+    static constexpr int RBW = D::RBW, CPR = D::CPR, SWZ_SHIFT = D::SWZ_SHIFT, TAPS = D::TAPS, TRS = D::TRS, SLOT = D::SLOT;
+    static constexpr int LDS_IN = NPOS * PB;
+    static constexpr int LDS_W2 = D::LDS_W2, LDS_BIAS = D::LDS_BIAS;
+    static constexpr int LDS = LDS_IN + 2 * SLOT + LDS_W2 + 2 * LDS_BIAS;
+    static constexpr int RPI = D::RPI, VPR = D::VPR;
+    static_assert(LDS <= 160 * 1024, "LDS of a CU");
 };
 
 // 16-byte LDS read the compiler's wait-count pass does not see (see heads_kernel's stage): the caller waits.
@@ -185,16 +210,17 @@ __device__ __forceinline__ void gemm2(f32x16 (&acc)[2][NT], f32x16 (&acc2)[M2][N
 // for every piece (global_load_lds): an LDS-DMA instruction costs its wave 100-185 issue cycles as it is, and the address
 // arithmetic in front of each of the 3 + 2 pieces per wave and stage came on top (the weight stream was 10 % of the kernel:
 // ablation in DESIGN.md 2.3).  Plain functions of plain arguments: a lambda capturing a buffer descriptor drops the host stub.
-template <typename T, int TH>
+template <typename T, int TH, int NW = 8>
 __device__ __forceinline__ void heads_dma_w1(const char *w1, int w1_bytes, char *slot, int wv, int l, int soff)
 {
     using C = HeadsCfg<T, TH>;
     constexpr int ES = sizeof(T);
     const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)w1, 0, w1_bytes, 0x00020000);
     constexpr int NI = C::TAPS * HC_SLAB / C::RPI;          // wave-instructions per stage (24 / 16)
+    static_assert(NI % NW == 0, "whole wave-instructions per wave");
 #pragma unroll
-    for (int j = 0; j < NI / 8; ++j) {
-        const int g = j * 8 + wv;                            // 1 KB run index
+    for (int j = 0; j < NI / NW; ++j) {
+        const int g = j * NW + wv;                           // 1 KB run index
         const int row_all = g * C::RPI + l / C::CPR;         // = tap_in_stage * 64 + row
         const int tp = row_all / HC_SLAB, row = row_all - tp * HC_SLAB;
         const int c = (l % C::CPR) ^ ((row >> C::SWZ_SHIFT) & (C::CPR - 1));
@@ -202,7 +228,7 @@ __device__ __forceinline__ void heads_dma_w1(const char *w1, int w1_bytes, char 
                                                  ((row * 9 + tp) * HC_IN) * ES + c * 16, soff, 0, 0);
     }
 }
-template <typename T, int TH>
+template <typename T, int TH, int NW = 8>
 __device__ __forceinline__ void heads_dma_w2(const char *w2, int head_conv, char *s_w2, int wv, int l, int soff)
 {
     using C = HeadsCfg<T, TH>;
@@ -210,8 +236,8 @@ __device__ __forceinline__ void heads_dma_w2(const char *w2, int head_conv, char
     const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)w2, 0, 32 * HC_MT2 * head_conv * ES, 0x00020000);
     constexpr int NI = 32 * HC_MT2 / C::RPI;                 // 12 / 24 wave-instructions
 #pragma unroll
-    for (int j = 0; j < (NI + 7) / 8; ++j) {
-        const int g = j * 8 + wv;
+    for (int j = 0; j < (NI + NW - 1) / NW; ++j) {
+        const int g = j * NW + wv;
         if (g < NI) {
             const int row = g * C::RPI + l / C::CPR;
             const int c = (l % C::CPR) ^ ((row >> C::SWZ_SHIFT) & (C::CPR - 1));
@@ -221,10 +247,12 @@ __device__ __forceinline__ void heads_dma_w2(const char *w2, int head_conv, char
     }
 }
 
-template <typename T, int TH, int M2, bool BIASC, bool MIXED = false>
+// SPARSE: the workgroup's "tile" is 32 * CW entries of the position list a.inds (HeadsSparseCfg); everything per position -- operands,
+// the order of every accumulator's MFMA chain, the epilogue -- is the dense code, so the value is the dense launch's bit for bit.
+template <typename T, int TH, int M2, bool BIASC, bool MIXED = false, bool SPARSE = false>
 __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
 {
-    using C = HeadsCfg<T, TH>;
+    using C = std::conditional_t<SPARSE, HeadsSparseCfg<T>, HeadsCfg<T, TH>>;
     using E = ET<T>;
     constexpr int ES = C::ES;
     constexpr int NT = C::NT;
@@ -237,7 +265,7 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
     const int tid = threadIdx.x;
     const int wv = tid >> 6, l = tid & 63, r = l & 31, h = l >> 5;
     const int tiles = a.tiles_x * a.tiles_y;
-    const int bid = h3d_tile_id(blockIdx.x, gridDim.x, a.xcd);
+    const int bid = SPARSE ? (int)blockIdx.x : h3d_tile_id(blockIdx.x, gridDim.x, a.xcd);
     const int b = bid / tiles;
     const int t = bid - b * tiles;
     const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
@@ -254,18 +282,46 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
     auto issue_w1 = [&](int s) {
         if ((H3D_DBG(a) & 1) && s > 0) return;
         const int hs = s / C::TRS, tr = s - hs * C::TRS;        // hs = head * slabs + slab
-        heads_dma_w1<T, TH>(a.w1, w1_bytes, s_ring + (s & 1) * C::SLOT, wvs, l, ((hs * HC_SLAB * 9 + tr * C::TAPS) * HC_IN) * ES);
+        heads_dma_w1<T, TH, C::NW>(a.w1, w1_bytes, s_ring + (s & 1) * C::SLOT, wvs, l, ((hs * HC_SLAB * 9 + tr * C::TAPS) * HC_IN) * ES);
     };
     // ---- LDS-DMA of the 1x1 slice [96 rows][64 K of this slab] -> s_w2 --------------------------------
     auto issue_w2 = [&](int head, int slab) {
         if (H3D_DBG(a) & 1) return;
-        heads_dma_w2<T, TH>(a.w2[head], a.head_conv, s_w2, wvs, l, slab * HC_SLAB * ES);
+        heads_dma_w2<T, TH, C::NW>(a.w2[head], a.head_conv, s_w2, wvs, l, slab * HC_SLAB * ES);
     };
 
     // ---- prologue: stage 0 weights in flight, halo tile (all 64 channels, zero outside the image) -----
     issue_w1(0);
     heads_issue_bias(a.b1, a.head_conv, a.b2[0], s_bias, __builtin_amdgcn_readfirstlane(wv), l);
-    {
+    // sparse: this lane's position (computing waves; an entry past the list or outside the map stores nothing) and whether the wave computes
+    [[maybe_unused]] int sp_b = 0, sp_y = 0, sp_x = 0;
+    [[maybe_unused]] bool sp_ok = false, idle = false;
+    if constexpr (SPARSE) {
+        idle = wvs >= C::CW;
+        const int p = bid * C::NPOS + wv * 32 + r;
+        if (!idle && p < a.B * a.K) {
+            const long long ind = a.inds[p];
+            if (ind >= 0 && ind < (long long)a.H * a.W) { sp_ok = true; sp_b = p / a.K; sp_y = (int)ind / a.W; sp_x = (int)ind - sp_y * a.W; }
+        }
+        // the 3x3 neighbourhood of every position (all 64 channels, zero outside the image, as the dense halo)
+        constexpr int NPV = C::NPOS * 9 * C::VPR;
+        stage_vectors<NPV, 64 * C::NW>(
+            tid,
+            [&](int i) -> u32x4 {
+                const int v = i % C::VPR, q = i / C::VPR, pix = q % 9, p = bid * C::NPOS + q / 9;
+                if (p >= a.B * a.K) return u32x4{0u, 0u, 0u, 0u};
+                const long long ind = a.inds[p];
+                if (ind < 0 || ind >= (long long)a.H * a.W) return u32x4{0u, 0u, 0u, 0u};
+                const int y = (int)ind / a.W, gy = y - 1 + pix / 3, gx = (int)ind - y * a.W - 1 + pix % 3;
+                if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W)
+                    return *reinterpret_cast<const u32x4 *>(a.in + (((size_t)(p / a.K) * a.H * a.W + (size_t)gy * a.W + gx) * a.in_cs) * ES + v * 16);
+                return u32x4{0u, 0u, 0u, 0u};
+            },
+            [&](int i, u32x4 val) {
+                const int v = i % C::VPR, q = i / C::VPR;
+                *reinterpret_cast<u32x4 *>(s_in + (q / 9) * C::PB + (q % 9) * C::SB + v * 16) = val;
+            });
+    } else {
         const size_t in_img = (size_t)b * a.H * a.W;
         constexpr int NHV = C::IN_H * C::IN_W * C::VPR;
         constexpr int HALF = (NHV + 1) / 2;                 // two batches bound the staging registers
@@ -298,7 +354,10 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
 
     int boff[NT];
 #pragma unroll
-    for (int n = 0; n < NT; ++n) boff[n] = (wv * NT + n) * C::RB + r * C::SB + 8 * h * ES;
+    for (int n = 0; n < NT; ++n) {
+        if constexpr (SPARSE) boff[n] = ((idle ? 0 : wv * 32) + r) * C::PB + 8 * h * ES;
+        else boff[n] = (wv * NT + n) * C::RB + r * C::SB + 8 * h * ES;
+    }
 
 #ifdef H3D_ABLATE
     unsigned long long t_bar = 0, t_g2 = 0, t_dma = 0, t_stage = 0;
@@ -475,7 +534,8 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
 #ifdef H3D_ABLATE
                 const unsigned long long ts0 = __builtin_readcyclecounter();
 #endif
-                if ((H3D_DBG(a) & 4) && wv >= 4) { /* profiling: only the older wave of each SIMD computes (timing only) */ }
+                if (SPARSE && idle) { /* a wave that only moves filters */ }
+                else if ((H3D_DBG(a) & 4) && wv >= 4) { /* profiling: only the older wave of each SIMD computes (timing only) */ }
                 else if ((H3D_DBG(a) & 8) && wv < 4) { /* profiling: only the younger wave computes */ }
                 else if (BIASC && tr == 0) stage(std::true_type{}, slot, tr);
                 else stage(std::false_type{}, slot, tr);
@@ -498,6 +558,7 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
 #ifdef H3D_ABLATE
             const unsigned long long tg0 = __builtin_readcyclecounter();
 #endif
+            if (!(SPARSE && idle))
             gemm2<T, TH, NT, M2H, BIASC>(acc, acc2, s_b + slab * HC_SLAB * 4, s_w2, r, h, sw, a.s1);
 #ifdef H3D_ABLATE
             t_g2 += __builtin_readcyclecounter() - tg0;
@@ -511,9 +572,9 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
         [[maybe_unused]] const float s2 = a.s2[head];
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
-            const int oy = oy0 + wv * NT + n, ox = ox0 + r;
-            if (oy < a.H && ox < a.W) {
-                float *op = out + (((size_t)b * C_head + 4 * h) * a.H + oy) * a.W + ox;
+            const int oy = SPARSE ? sp_y : oy0 + wv * NT + n, ox = SPARSE ? sp_x : ox0 + r, ob = SPARSE ? sp_b : b;
+            if (SPARSE ? sp_ok : oy < a.H && ox < a.W) {
+                float *op = out + (((size_t)ob * C_head + 4 * h) * a.H + oy) * a.W + ox;
 #pragma unroll
                 for (int m2 = 0; m2 < M2H; ++m2) {
 #pragma unroll
@@ -561,7 +622,8 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
 
 static_assert(HEADS_MAX == H3D_HEADS_MAX, "header/kernel mismatch");
 
-int h3d_launch_heads(const h3d_op &op, hipStream_t st)
+// checks of an H3D_OP_HEADS op and its kernel arguments (the dense and the sparse launch)
+static int heads_args(const h3d_op &op, HeadsArgs &a)
 {
     if (!op.in || !op.w || !op.bias || !op.in2) H3D_FAIL(H3D_ERR_ARG, "heads: null pointer");
     const h3d_heads_desc *d = (const h3d_heads_desc *)op.in2;
@@ -572,7 +634,6 @@ int h3d_launch_heads(const h3d_op &op, hipStream_t st)
     if (op.Cout <= 0 || op.Cout % HC_SLAB || op.Cout > 256)
         H3D_FAIL(H3D_ERR_SHAPE, "heads: head_conv %d must be a multiple of %d, at most 256", op.Cout, HC_SLAB);
     if (d->nheads <= 0 || d->nheads > HEADS_MAX) H3D_FAIL(H3D_ERR_SHAPE, "heads: %d heads (max %d)", d->nheads, HEADS_MAX);
-    HeadsArgs a;
     a.in = (const char *)op.in; a.w1 = (const char *)op.w; a.b1 = op.bias;
     a.dbg = op.reserved & H3D_TUNE_HEADS_ABLATE_MASK;
     a.xcd = h3d_xcd_mode();
@@ -581,6 +642,7 @@ int h3d_launch_heads(const h3d_op &op, hipStream_t st)
 #else
     a.stamps = nullptr;
 #endif
+    a.inds = nullptr; a.K = 0;
     a.nheads = d->nheads; a.head_conv = op.Cout; a.B = op.B; a.H = op.H; a.W = op.W; a.in_cs = op.in_cs;
     for (int i = 0; i < d->nheads; ++i) {
         if (!d->head[i].w2 || !d->head[i].b2 || !d->head[i].out) H3D_FAIL(H3D_ERR_ARG, "heads: head %d null pointer", i);
@@ -593,6 +655,15 @@ int h3d_launch_heads(const h3d_op &op, hipStream_t st)
     }
     if (d->wexp < -60 || d->wexp > 60 || (d->wexp && op.dtype != H3D_F16X3)) H3D_FAIL(H3D_ERR_ARG, "heads: wexp %d (an H3D_F16X3 filter exponent)", d->wexp);
     a.s1 = ldexpf(1.f, -d->wexp);
+    return H3D_OK;
+}
+
+int h3d_launch_heads(const h3d_op &op, hipStream_t st)
+{
+    HeadsArgs a;
+    if (const int rc = heads_args(op, a)) return rc;
+    const h3d_heads_desc *d = (const h3d_heads_desc *)op.in2;
+    const int es = h3d_dtype_bytes(op.dtype);
     int m2 = 1, m2min = HC_MT2;
     for (int i = 0; i < d->nheads; ++i) {
         m2 = max(m2, (d->head[i].C + 31) / 32);   // row tiles of the widest head
@@ -615,5 +686,30 @@ int h3d_launch_heads(const h3d_op &op, hipStream_t st)
                 return h3d_launch(name, heads_kernel<T, TH, m2c, bc, mx>, grid, blk, 0, st, a);
             }
         }, h3d_vals<1, 2, 3>{}, m2, h3d_vals<false, true>{}, biasc, std::conditional_t<sizeof(T) == 2, h3d_vals<false, true>, h3d_vals<false>>{}, mixed);
+    });
+}
+
+// The heads of an H3D_OP_HEADS op at the K positions per image listed in `inds` ([B][K] flat y*W + x; an entry outside the map is
+// skipped), written into the heads' dense maps at those positions: bit for bit what the op's dense launch writes there.
+extern "C" int h3d_heads_sparse(const h3d_op *op, const int64_t *inds, int K, void *stream)
+{
+    if (!op || !inds) H3D_FAIL(H3D_ERR_ARG, "heads_sparse: null pointer");
+    if (op->kind != H3D_OP_HEADS) H3D_FAIL(H3D_ERR_ARG, "heads_sparse: op kind %d is not H3D_OP_HEADS", op->kind);
+    if (op->B <= 0 || op->H <= 0 || op->W <= 0 || K <= 0 || (long long)op->B * K > (1 << 24))
+        H3D_FAIL(H3D_ERR_SHAPE, "heads_sparse: B %d, H %d, W %d, K %d", op->B, op->H, op->W, K);
+    if (op->dtype != H3D_BF16 && op->dtype != H3D_F16)
+        H3D_FAIL(H3D_ERR_UNSUPPORTED, "heads_sparse: dtype %d (the 2-byte plans)", op->dtype);
+    if (op->reserved) H3D_FAIL(H3D_ERR_UNSUPPORTED, "heads_sparse: tuning word %#x", (unsigned)op->reserved);
+    HeadsArgs a;
+    if (const int rc = heads_args(*op, a)) return rc;
+    a.inds = (const long long *)inds; a.K = K;
+    a.tiles_x = a.tiles_y = 1;
+    return h3d_by_dtype<bf16_t, f16_t>(op->dtype, "heads_sparse: dtype %d", [&](auto t) {
+        using T = typename decltype(t)::type;
+        using C = HeadsSparseCfg<T>;
+        const dim3 grid(cdiv(op->B * K, C::NPOS)), blk(64 * C::NW);
+        // one instantiation: the body picks the 1 / 2 / 3-tile epilogue width per head
+        const h3d_kname name{"heads_kernel", t, 16, 3, true, h3d_opt(true), h3d_opt(true)};
+        return h3d_launch(name, heads_kernel<T, 16, 3, true, true, true>, grid, blk, 0, (hipStream_t)stream, a);
     });
 }

@@ -124,13 +124,12 @@ def ctdet_decode(heat, wh, reg=None, cat_spec_wh=False, K=100):
     return dets
 
 
-def _multi_pose(heat, wh, kps, reg, hm_hp, hp_offset, K, logits, return_aux=False):
-    heat, wh, kps = _f32c(heat), _f32c(wh), _f32c(kps)
-    reg = None if reg is None else _f32c(reg)
+def _multi_pose_topk(heat, hm_hp, K, logits):
+    """First half of `_multi_pose`: 3x3 NMS + top-K of the centre map and of the key-point maps (the two heads that are read whole).
+    -> the candidates `_multi_pose_assemble` consumes; `inds` [B,K] are the positions at which it reads every other head."""
+    heat = _f32c(heat)
     hm_hp = None if hm_hp is None else _f32c(hm_hp)
-    hp_offset = None if hp_offset is None else _f32c(hp_offset)
     B, C, H, W = heat.shape
-    J = kps.shape[1] // 2
     flags = NMS_SIGMOID if logits else 0
     if hm_hp is not None and hm_hp.shape[0] == B and hm_hp.shape[2:] == heat.shape[2:] and H * W <= MAX_LDS_MAP:
         (s1, i1, y1, x1), (hs, hi, hy, hx) = _map_topk2(heat, hm_hp, K, flags)      # one launch for both tensors
@@ -141,8 +140,20 @@ def _multi_pose(heat, wh, kps, reg, hm_hp, hp_offset, K, logits, return_aux=Fals
             hs, hi, hy, hx = _map_topk(hm_hp, K, flags)
         else:
             hs = hi = hy = hx = None
-            hp_offset = None
-    dets = torch.empty(B, K, 5 + 2 * J + 1, dtype=torch.float32, device=heat.device)
+    return {"scores": s, "inds": i, "clses": c, "ys": y, "xs": x, "hm_score": hs, "hm_inds": hi, "hm_ys": hy, "hm_xs": hx,
+            "shape": (B, H, W), "K": K}
+
+
+def _multi_pose_assemble(top, wh, kps, reg, hp_offset, return_aux=False):
+    """Second half: `wh`, `kps`, `reg` read at top["inds"], `hp_offset` at the key-point peaks -> detections [B,K,40]."""
+    wh, kps = _f32c(wh), _f32c(kps)
+    reg = None if reg is None else _f32c(reg)
+    hp_offset = None if hp_offset is None or top["hm_score"] is None else _f32c(hp_offset)
+    (B, H, W), K = top["shape"], top["K"]
+    J = kps.shape[1] // 2
+    s, i, c, y, x = (top[k] for k in ("scores", "inds", "clses", "ys", "xs"))
+    hs, hi, hy, hx = (top[k] for k in ("hm_score", "hm_inds", "hm_ys", "hm_xs"))
+    dets = torch.empty(B, K, 5 + 2 * J + 1, dtype=torch.float32, device=wh.device)
     _lib.check(_lib.lib().h3d_multi_pose_assemble(
         _lib.ptr(s), _lib.ptr(i), _lib.ptr(c), _lib.ptr(y), _lib.ptr(x),
         _lib.ptr(hs), _lib.ptr(hi), _lib.ptr(hy), _lib.ptr(hx),
@@ -151,6 +162,10 @@ def _multi_pose(heat, wh, kps, reg, hm_hp, hp_offset, K, logits, return_aux=Fals
     if return_aux:     # ("clses" of a one-class map is a view of a shared read-only zero buffer: see _merge)
         return dets, {"scores": s, "inds": i, "clses": c, "ys": y, "xs": x, "hm_score": hs, "hm_inds": hi}
     return dets
+
+
+def _multi_pose(heat, wh, kps, reg, hm_hp, hp_offset, K, logits, return_aux=False):
+    return _multi_pose_assemble(_multi_pose_topk(heat, hm_hp, K, logits), wh, kps, reg, hp_offset, return_aux)
 
 
 def multi_pose_decode(heat, wh, kps, reg=None, hm_hp=None, hp_offset=None, K=100):

@@ -19,6 +19,61 @@ from .utils import _transpose_and_gather_feat
 MULTI_POSE_HEADS = {"hm": 1, "wh": 2, "hps": 34, "reg": 2, "hm_hp": 17, "hp_offset": 2}   # opts.py:248-258
 CTDET_HEADS = {"hm": 80, "wh": 2, "reg": 2}                                                  # opts.py:241-247
 SMPL_HEADS = {"pose": 72, "shape": 10}
+WHOLE_MAP_HEADS = ("hm", "hm_hp", "hp_offset")       # what multi_pose_decode reads as whole maps (3x3 NMS + top-K; hp_offset at up to 17 x K peaks)
+
+
+class LazyHeads(dict):
+    """res["heads"] of a sparse-heads run: every head's dense [B,C,H,W] map, of which the run itself wrote only what it reads --
+    `hm`, `hm_hp`, `hp_offset` whole, every other head at the K detection centres.  The first access through [], get, items, values,
+    iteration, `in` or copy calls `completer` (once), which launches the deferred dense head ops of the run's plan on the
+    current stream; from then on this is a plain dict of complete maps.  keys() and len() touch no map and complete nothing.
+    The maps are the plan's buffers: they belong to the latest run on their slot, as every head tensor of this package does."""
+
+    def __init__(self, maps, completer):
+        super().__init__(maps)
+        self._completer = completer
+
+    @property
+    def complete(self):
+        return self._completer is None
+
+    def rearm(self, completer):
+        """A later run rewrote the maps sparsely (a replay of the hipGraph that holds this dict): incomplete again."""
+        self._completer = completer
+
+    def _complete(self):
+        c = self._completer
+        if c is not None:
+            c()                          # (an error leaves the dict incomplete)
+            self._completer = None
+
+    def __getitem__(self, k):
+        self._complete()
+        return super().__getitem__(k)
+
+    def get(self, k, default=None):
+        self._complete()
+        return super().get(k, default)
+
+    def items(self):
+        self._complete()
+        return super().items()
+
+    def values(self):
+        self._complete()
+        return super().values()
+
+    def __iter__(self):
+        self._complete()
+        return super().__iter__()
+
+    def __contains__(self, k):
+        self._complete()
+        return super().__contains__(k)
+
+    def copy(self):
+        self._complete()
+        return dict(super().items())
 
 
 class Opt:
@@ -92,6 +147,12 @@ class MultiPoseDetector:
         self.model.to(self.device).eval()
         self.smpl_model = smpl_model
         self.fused_tail = True         # False: the decode / SMPL tail as round 3 issued it (A/B and bit-identity tests)
+        # The heads decode and the SMPL stage read at the K detection centres only (wh, hps, reg, pose, shape, cam) are computed THERE only
+        # (csrc/heads.hip h3d_heads_sparse), bit-identical to their dense maps at those positions; res["heads"] completes the maps when
+        # somebody reads them (LazyHeads).  Fused DLA-34 heads, bf16 / f16, no flip_test; False: every head as a dense map, as before.
+        self.sparse_heads = True
+        if opt.arch.replace("-", "_") in ("dla_34", "dla34") and opt.dtype in ("bf16", "f16"):
+            self.model.engine_flags["split_heads"] = tuple(h for h in opt.heads if h in WHOLE_MAP_HEADS)   # (the plan's lowering; `run` decides per call)
         if opt.smpl and smpl_model is None:
             self.smpl_model = _smpl.SMPLModel.synthetic()
 
@@ -107,15 +168,28 @@ class MultiPoseDetector:
         if graph and meta is None:
             return self._run_graph(images, slot)
         opt = self.opt
-        if opt.flip_test:
-            out = self._flip_test_heads(images, slot)
+        plan = None
+        if self.sparse_heads and not opt.flip_test and images.is_cuda and not self.model.training:
+            # backbone + the heads read whole; None: this call has no split plan (another dtype / lowering, sub-batch streams) -> dense
+            plan = self.model.engine(images.device).forward_eager(images, slot)
+        if plan is not None:
+            out = plan.outputs                    # (the deferred heads' maps: valid at `inds` once run_sparse has run)
+            top = decode._multi_pose_topk(out["hm"], out.get("hm_hp") if opt.hm_hp else None, opt.K, logits=True)
+            plan.run_sparse(top["inds"], opt.K)
+            dets, aux = decode._multi_pose_assemble(top, out["wh"], out["hps"], out.get("reg") if opt.reg_offset else None,
+                                                    out.get("hp_offset") if opt.reg_hp_offset else None, return_aux=True)
+            heads = LazyHeads(out, None)
         else:
-            out = self.model(images, slot)[-1]    # (Hourglass returns one dict per stack: inference uses the last)
-        dets, aux = decode.multi_pose_decode_logits(
-            out["hm"], out["wh"], out["hps"], reg=out.get("reg") if opt.reg_offset else None,
-            hm_hp=out.get("hm_hp") if opt.hm_hp else None,
-            hp_offset=out.get("hp_offset") if opt.reg_hp_offset else None, K=opt.K, return_aux=True)
-        res = {"dets": dets, "inds": aux["inds"], "heads": out}
+            if opt.flip_test:
+                out = self._flip_test_heads(images, slot)
+            else:
+                out = self.model(images, slot)[-1]    # (Hourglass returns one dict per stack: inference uses the last)
+            dets, aux = decode.multi_pose_decode_logits(
+                out["hm"], out["wh"], out["hps"], reg=out.get("reg") if opt.reg_offset else None,
+                hm_hp=out.get("hm_hp") if opt.hm_hp else None,
+                hp_offset=out.get("hp_offset") if opt.reg_hp_offset else None, K=opt.K, return_aux=True)
+            heads = out
+        res = {"dets": dets, "inds": aux["inds"], "heads": heads}
         if opt.smpl:
             n = opt.smpl_people or opt.K
             B = aux["inds"].shape[0]
@@ -137,7 +211,25 @@ class MultiPoseDetector:
         if meta is not None:
             res["results"] = multi_pose_post_process(dets, meta["c"], meta["s"], out["hm"].shape[2],
                                                      out["hm"].shape[3])
+        if plan is not None and not torch.cuda.is_current_stream_capturing():
+            heads.rearm(_heads_completer(plan))        # (inside a capture: _run_graph arms it after every replay)
         return res
+
+
+def _heads_completer(plan):
+    """-> the completer of a LazyHeads over `plan`'s maps, armed at the end of a sparse-heads run on the current stream: the deferred
+    dense head ops on whatever stream is current at the first access, behind an event recorded here.  They rewrite the whole maps
+    (the positions the run wrote receive the same bits); the plan's next run waits for them (Plan.pending)."""
+    done = torch.cuda.Event()
+    done.record()
+
+    def complete():
+        cur = torch.cuda.current_stream()
+        cur.wait_event(done)
+        plan.run_deferred()
+        plan.pending = torch.cuda.Event()
+        plan.pending.record(cur)
+    return complete
 
 
 def _run_graph(self, images, slot):
@@ -160,7 +252,14 @@ def _run_graph(self, images, slot):
     g, static_in, res = ent
     if images.data_ptr() != static_in.data_ptr():
         static_in.copy_(images)
+    B, _, H, W = static_in.shape
+    plan = self.model.engine(static_in.device).plans.get((B, H, W) if slot == 0 else (B, H, W, slot))
+    if isinstance(res["heads"], LazyHeads) and plan is not None and plan.pending is not None:
+        torch.cuda.current_stream().wait_event(plan.pending)      # a completion of the previous replay's maps, issued from another stream
+        plan.pending = None
     g.replay()
+    if isinstance(res["heads"], LazyHeads):      # the capture holds the sparse sequence; the maps are completed outside the graph
+        res["heads"].rearm(_heads_completer(plan))
     return res
 
 

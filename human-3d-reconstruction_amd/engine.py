@@ -69,12 +69,34 @@ class DLAEngine:
             return self._forward_split(images, slot)
         plan = self.plan(B, H, W, slot)
         with torch.cuda.device(self.device):
-            if images.dtype == torch.float32 and images.is_contiguous():
-                plan.op_array[0].in_ = images.data_ptr()       # read the caller's batch in place
-            else:
-                plan.images.copy_(images)
-                plan.op_array[0].in_ = plan.images.data_ptr()
+            self._bind(plan, images)
             return plan.run()
+
+    @staticmethod
+    def _bind(plan, images):
+        if images.dtype == torch.float32 and images.is_contiguous():
+            plan.op_array[0].in_ = images.data_ptr()       # read the caller's batch in place
+        else:
+            plan.images.copy_(images)
+            plan.op_array[0].in_ = plan.images.data_ptr()
+
+    def forward_eager(self, images, slot=0):
+        """`split_heads` plans: the backbone and the eager heads only -> the Plan, whose `run_sparse` / `run_deferred` supply the other
+        heads (detector.MultiPoseDetector.run).  None when this call has no such plan (another lowering, sub-batch streams): nothing
+        was launched, call `forward`."""
+        _lib.require_cuda(images)
+        if images.dim() != 4 or images.shape[1] != 3:
+            raise RuntimeError("expected images [B,3,H,W], got %s" % (tuple(images.shape),))
+        B, _, H, W = images.shape
+        if not self.split_heads or self.streams > 1:
+            return None
+        plan = self.plan(B, H, W, slot)
+        if plan.sparse_op is None:
+            return None
+        with torch.cuda.device(self.device):
+            self._bind(plan, images)
+            plan.run_eager()
+        return plan
 
     def _forward_split(self, images, slot=0):
         """Sub-batches on separate HIP streams: the small-grid layers (level4/5, the 16x16 / 32x32 neck

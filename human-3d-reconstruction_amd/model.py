@@ -70,6 +70,7 @@ class DLASeg(nn.Module):
         self.use_dcn = use_dcn
         self.compute_dtype = dtype
         self._engine = None
+        self.engine_flags = {}          # lowering switches (plan.Plan.FLAGS) every engine of this module starts with
         shapes = self._shapes()
         pending_bias = {}
         for key, shape in shapes.items():
@@ -115,6 +116,8 @@ class DLASeg(nn.Module):
         if self._engine is None or self._engine.device != torch.device(device):
             sd = {k: v for k, v in self.state_dict().items()}
             self._engine = DLAEngine(sd, self.heads, self.use_dcn, self.compute_dtype, device, self.head_conv, self.arch_name)
+            for k, v in self.engine_flags.items():
+                setattr(self._engine, k, v)
         return self._engine
 
     def forward(self, x, slot=0):

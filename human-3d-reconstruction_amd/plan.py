@@ -77,6 +77,11 @@ class Plan:
         conv1x1_th16_min_cin=0,   # > 0: 1x1 convs with at least this many input channels (and > 32 outputs) use 16-row tiles
         lower_heads=True,         # False: the plan ends at the 64-channel feature map `Plan.feat` (no heads ops, no head outputs): the
                                   # frozen backbone of h3d_amd.heads.TrainableHeads
+        split_heads=(),           # a tuple of head names (fused heads only): the heads ops come in two parts.  The EAGER part, one launch for
+                                  # these heads (the maps a decode reads whole), ends the prefix `run_eager` executes; the DEFERRED part,
+                                  # the other heads in the default groups, follows it (`run_deferred`).  `run_sparse` evaluates the
+                                  # deferred heads at listed positions only (h3d_heads_sparse).  `run` still runs everything:
+                                  # same instantiations, same per-head arithmetic, the default lowering's maps bit for bit
     )
 
     def __init__(self, pw, B, H, W, **flags):
@@ -103,6 +108,10 @@ class Plan:
         self.outputs = {}
         self.all_outputs = None         # Hourglass: one head dict per stack (outputs = the last one)
         self._out_at = {}               # head -> where its output pointer lives: an op index, or (heads descriptor, slot)
+        self.n_eager = None             # split_heads: ops[:n_eager] = backbone + eager heads, ops[n_eager:] = the deferred heads
+        self.sparse_op = None           # ... and the deferred heads as ONE op outside the array, for h3d_heads_sparse
+        self._sparse_at = {}            # ... head -> (its descriptor, slot)
+        self.pending = None             # an event behind launches another stream issued into this plan's maps (detector.LazyHeads)
         if pw.arch == "hourglass":
             self._lower_hourglass()
         elif pw.arch == "resdcn101":
@@ -125,8 +134,8 @@ class Plan:
         self.outputs[head], self._out_at[head] = o, at
         return View(o, H, W, c, c, 0, 4)
 
-    def _op(self, kind, x=None, out=None, x2=None, **kw):
-        """Append one op and return its index.  The Views give the geometry and the pointers: `x` -> in_, H, W, Cin, in_cs; `out` ->
+    def _op(self, kind, x=None, out=None, x2=None, emit=True, **kw):
+        """Append one op and return its index (emit=False: return the op itself, outside the array).  The Views give the geometry and the pointers: `x` -> in_, H, W, Cin, in_cs; `out` ->
         out, Ho, Wo, Cout, out_cs; `x2` (residual, skip, offsets) -> in2, in2_cs; `kw`: every other field, by its h3d_op name."""
         op = H3dOp()
         op.kind, op.dtype, op.B = kind, _H3D_DT[self.dtype], self.B
@@ -138,6 +147,8 @@ class Plan:
             op.in2, op.in2_cs = x2.ptr, x2.cs
         for k, v in kw.items():
             setattr(op, k, v)
+        if not emit:
+            return op
         self.ops.append(op)
         return len(self.ops) - 1
 
@@ -382,22 +393,39 @@ class Plan:
         if fused:
             # one launch per group of heads with the same number of 32-row output tiles, so the
             # narrow heads do not inherit the register footprint of the 72-channel pose head
-            groups = {}
-            for head, c in self.pw.heads.items():
-                m2 = (c + 31) // 32
-                groups.setdefault(0 if self.mixed_heads else 1 if m2 == 1 else self.wide_heads_m2 or m2, []).append(head)
-            for m2 in sorted(groups):
-                w1, b1, per = self.pw.fused_heads(tuple(groups[m2]))
+            def heads_op(names, emit=True):
+                """One H3D_OP_HEADS over `names`; a head that already has its output (the sparse twin of the deferred ops) writes the same map."""
+                w1, b1, per = self.pw.fused_heads(tuple(names))
                 desc = _lib.H3dHeadsDesc()
                 desc.nheads = len(per)
                 desc.wexp = self.pw.wexp.get(w1.data_ptr(), 0)
                 for i, (head, c, w2, b2) in enumerate(per):
-                    o = self._new_output(head, c, Ho, Wo, (desc, i))
-                    desc.head[i].w2, desc.head[i].b2, desc.head[i].out, desc.head[i].C = w2.data_ptr(), b2.data_ptr(), o.ptr, c
+                    if head in self.outputs:
+                        optr, self._sparse_at[head] = self.outputs[head].data_ptr(), (desc, i)
+                    else:
+                        optr = self._new_output(head, c, Ho, Wo, (desc, i)).ptr
+                    desc.head[i].w2, desc.head[i].b2, desc.head[i].out, desc.head[i].C = w2.data_ptr(), b2.data_ptr(), optr, c
                     desc.head[i].wexp2 = self.pw.wexp.get(w2.data_ptr(), 0)
                 self.keep.append(desc)
-                self._op(_lib.OP_HEADS, feat, in2=ctypes.addressof(desc), w=w1.data_ptr(), bias=b1.data_ptr(),
-                         Ho=Ho, Wo=Wo, Cout=self.pw.head_conv, ksize=3, stride=1)
+                return self._op(_lib.OP_HEADS, feat, in2=ctypes.addressof(desc), w=w1.data_ptr(), bias=b1.data_ptr(),
+                                Ho=Ho, Wo=Wo, Cout=self.pw.head_conv, ksize=3, stride=1, emit=emit)
+
+            eager = tuple(h for h in self.pw.heads if h in tuple(self.split_heads or ()))
+            deferred = tuple(h for h in self.pw.heads if h not in eager)
+            split = bool(eager) and bool(deferred) and self.pw.dtype in LOWP
+            if split:
+                heads_op(eager)
+                self.n_eager = len(self.ops)
+            groups = {}
+            for head, c in self.pw.heads.items():
+                if split and head in eager:
+                    continue
+                m2 = (c + 31) // 32
+                groups.setdefault(0 if self.mixed_heads else 1 if m2 == 1 else self.wide_heads_m2 or m2, []).append(head)
+            for m2 in sorted(groups):
+                heads_op(groups[m2])
+            if split:
+                self.sparse_op = heads_op(deferred, emit=False)
             self.outputs = {h: self.outputs[h] for h in self.pw.heads}      # reference head order
             return
         for head in self.pw.heads:
@@ -499,9 +527,36 @@ class Plan:
                 self.op_array[at].out = views[h].data_ptr()
             else:
                 at[0].head[at[1]].out = views[h].data_ptr()
+            if h in self._sparse_at:
+                at = self._sparse_at[h]
+                at[0].head[at[1]].out = views[h].data_ptr()
         self.outputs = dict(views)
 
-    def run(self):
-        rc = _lib.lib().h3d_run_ops(self.op_array, len(self.ops), _lib.stream_ptr())
-        _lib.check(rc, "h3d_run_ops")
+    def _run_range(self, first, n):
+        if self.pending is not None:        # launches of another stream into this plan's maps come first
+            torch.cuda.current_stream().wait_event(self.pending)
+            self.pending = None
+        if n > 0:
+            ops = self.op_array if first == 0 else ctypes.byref(self.op_array[first])      # (an element is a view of the array's memory)
+            rc = _lib.lib().h3d_run_ops(ops, n, _lib.stream_ptr())
+            _lib.check(rc, "h3d_run_ops")
         return self.outputs
+
+    def run(self):
+        return self._run_range(0, len(self.ops))
+
+    # -- split_heads plans --------------------------------------------------------------------------
+    def run_eager(self):
+        """Backbone + the eager heads.  The deferred heads' maps keep whatever they held."""
+        return self._run_range(0, self.n_eager)
+
+    def run_sparse(self, inds, K):
+        """The deferred heads at inds [B,K] (int64, flat y*W + x of the output map) only, written into their dense maps."""
+        _lib.require_cuda(inds)
+        if inds.dtype != torch.int64 or not inds.is_contiguous() or tuple(inds.shape) != (self.B, K):
+            raise RuntimeError("run_sparse: contiguous int64 inds [%d,%d] expected, got %s %s" % (self.B, K, tuple(inds.shape), inds.dtype))
+        _lib.check(_lib.lib().h3d_heads_sparse(ctypes.byref(self.sparse_op), _lib.ptr(inds), int(K), _lib.stream_ptr()), "h3d_heads_sparse")
+
+    def run_deferred(self):
+        """The deferred heads' dense launches: the whole maps (the positions `run_sparse` wrote receive the same bits)."""
+        return self._run_range(self.n_eager, len(self.ops) - self.n_eager)

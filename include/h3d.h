@@ -473,6 +473,13 @@ int h3d_run_ops_timed(const h3d_op *ops, int n, void *stream, float *ms);
  * (e.g. "conv_kernel<unsigned short, 3, 1, 2, 32, 16>"); nothing is launched. */
 int h3d_op_kernel_name(const h3d_op *op, char *buf, int buflen);
 
+/* The heads of ONE H3D_OP_HEADS op (H3D_BF16 / H3D_F16, reserved = 0) at listed positions only (csrc/heads.hip): inds = [B][K]
+ * flat output positions y*W + x (multi_pose_decode's top-K centres).  Every head of the op's descriptor is evaluated at each
+ * listed position and written into the head's dense NCHW fp32 map there; no other element is written.  The value is bit for bit
+ * what h3d_run_ops writes at that position (same operands, same order of every accumulation).  An entry outside [0, H*W) is
+ * skipped; a position may be listed more than once. */
+int h3d_heads_sparse(const h3d_op *op, const int64_t *inds, int K, void *stream);
+
 /* Layout helpers (host interface keeps the reference's NCHW fp32 tensors at the boundary). */
 int h3d_nchw_f32_to_nhwc(const float *src, void *dst, int dtype, int B, int C, int H, int W,
                          int dst_cs, void *stream);
