@@ -127,6 +127,7 @@ RENDER_NEGATE_Z, RENDER_CULL_BACK = 1, 2           # H3D_RENDER_NEGATE_Z / H3D_R
 RENDER_MAX_V, RENDER_MAX_SIDE = 13120, 16384        # H3D_RENDER_MAX_V / H3D_RENDER_MAX_SIDE
 COCO_BBOX, COCO_KEYPOINTS, COCO_ROUND2 = 0, 1, 1      # H3D_COCO_BBOX / H3D_COCO_KEYPOINTS / H3D_COCO_ROUND2
 COCO_MAX_D, COCO_MAX_G, COCO_SCAN_CHUNK = 128, 1024, 1024       # H3D_COCO_MAX_D / H3D_COCO_MAX_G / H3D_COCO_SCAN_CHUNK
+MESH_EVAL_MAX_SWEEPS = 30                                       # H3D_MESH_EVAL_MAX_SWEEPS
 ADAM_CAPACITY, ADAM_CHUNK = 48, 2048        # H3D_ADAM_CAPACITY / H3D_ADAM_CHUNK: tensors per launch, elements per workgroup
 
 
@@ -212,6 +213,9 @@ SIGNATURES = {
     "h3d_coco_match": [c_vp, c_i] + [c_vp] * 8 + [c_i] * 6 + [c_vp, c_i, c_vp, c_i] + [c_vp] * 11 + [ctypes.c_size_t, c_vp],
     "h3d_coco_accumulate_workspace_bytes": [c_i, c_i, ctypes.POINTER(ctypes.c_size_t)],
     "h3d_coco_accumulate": [c_vp] * 8 + [c_i] * 6 + [ctypes.POINTER(ctypes.c_int32), c_i, c_vp, c_i, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
+    # 3D evaluation (include/h3d.h section 8b; h3d_amd/mesh_eval.py)
+    "h3d_pointset_errors": [c_vp, c_i, c_vp, c_i, c_i, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp],
+    "h3d_metric_means": [c_vp, c_vp, c_i, c_vp, c_vp, c_vp],
 }
 
 _lib = None

@@ -104,6 +104,12 @@ class GroundTruth:
         return GroundTruth(self.boxes[:n], self.keypoints[:n], self.area[:n], self.iscrowd[:n], self.cls[:n], self.num[:n], self.num_classes,
                            self.image_ids[:n], self.cat_ids)
 
+    def select(self, index):
+        """The images at the positions `index`, in that order (mesh_eval.MeshEvaluator matches one batch at a time)."""
+        i = np.asarray(index, np.int64).reshape(-1)
+        return GroundTruth(self.boxes[i], self.keypoints[i], self.area[i], self.iscrowd[i], self.cls[i], self.num[i], self.num_classes,
+                           [self.image_ids[k] for k in i], self.cat_ids)
+
     def to(self, device):
         """The device tensors (made once per device)."""
         import torch

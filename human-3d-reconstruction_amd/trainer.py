@@ -51,6 +51,7 @@ class HeadsTrainer:
     def __init__(self, opt, model, smpl_model=None, kp_regressor=None):
         self.opt = opt
         self.model = model
+        self.smpl_model = smpl_model
         self.heads = TrainableHeads(model)
         task = _opt(opt, "task", "multi_pose")
         if task == "multi_pose" and smpl_model is not None and kp_regressor is not None and _opt(opt, "smpl_kp_weight", 0) > 0:
@@ -110,18 +111,32 @@ class HeadsTrainer:
         return ret, results
 
     @torch.no_grad()
-    def val(self, data_loader, gt):
+    def val(self, data_loader, gt, gt3d=None, smpl_model=None):
         """The reference's val() (trainer.py:326-328, save_result :456-469, datasets/coco_hp.py:92-138) for multi_pose: the detector path
         (network with the heads as trained, decode with opt.K, post-process) over the loader, then COCO's keypoint and box evaluation of
         the collected records on the device (coco_eval) -> (keypoint stats [10], bbox stats [12]); the two coco_eval.EvalResult are kept
         in self.last_val.  gt: coco_eval.GroundTruth.  A batch: dict(input [B,3,H,W], meta = dict(c [B,2], s [B], index [B] = the
-        images' positions in gt)); images the loader never shows count as images without detections."""
+        images' positions in gt)); images the loader never shows count as images without detections.
+        gt3d (mesh_eval.GroundTruth3D, padded like gt) adds the 3D evaluation: the SMPL meshes of all K detection slots (smpl_model, or
+        the one the trainer was built with; the `pose` and `shape` heads at the decode's centres, the exact blend shapes) are compared
+        with the ground-truth person each detection's box matches (mesh_eval.MeshEvaluator), and the mesh_eval.MeshEvalResult (mpjpe,
+        pa_mpjpe, pve, pa_pve, coverage in .extra) is kept in self.last_val['mesh'].  The return value does not change."""
         from . import coco_eval, decode
         from .detector import multi_pose_post_process
         opt = self.opt
         if _opt(opt, "task", "multi_pose") != "multi_pose":
             raise ValueError("HeadsTrainer.val: task %r not defined" % (_opt(opt, "task", None),))
         model = self.model
+        meshes = None
+        if gt3d is not None:
+            from . import mesh_eval, smpl
+            smpl_model = smpl_model if smpl_model is not None else self.smpl_model
+            want = {"pose": 72, "shape": 10}
+            if any(model.heads.get(h) != c for h, c in want.items()):
+                raise ValueError("HeadsTrainer.val: the 3D evaluation needs the heads %s, the model has %s" % (want, dict(model.heads)))
+            if smpl_model is None:
+                raise ValueError("HeadsTrainer.val: the 3D evaluation needs an smpl_model")
+            meshes = mesh_eval.MeshEvaluator(gt, gt3d)
         was_training = model.training
         model.eval()
         model.set_compute_dtype(model.compute_dtype)        # drops the cached plan: it is rebuilt from the parameters as they are now
@@ -137,13 +152,20 @@ class HeadsTrainer:
             if device is not None:
                 x = x.to(device=device, non_blocking=True)
             out = model(x)[-1]
-            dets = decode.multi_pose_decode_logits(
+            dets, aux = decode.multi_pose_decode_logits(
                 out["hm"], out["wh"], out["hps"], reg=out.get("reg") if _opt(opt, "reg_offset", True) else None,
                 hm_hp=out.get("hm_hp") if _opt(opt, "hm_hp", True) else None,
-                hp_offset=out.get("hp_offset") if _opt(opt, "reg_hp_offset", True) else None, K=_opt(opt, "K", 100))
-            collected.update(meta["index"], multi_pose_post_process(dets, meta["c"], meta["s"], out["hm"].shape[2], out["hm"].shape[3]))
+                hp_offset=out.get("hp_offset") if _opt(opt, "reg_hp_offset", True) else None, K=_opt(opt, "K", 100), return_aux=True)
+            results = multi_pose_post_process(dets, meta["c"], meta["s"], out["hm"].shape[2], out["hm"].shape[3])
+            collected.update(meta["index"], results)
+            if meshes is not None:
+                verts, joints = smpl.lbs_from_heads(smpl_model, out["pose"].float().contiguous(), out["shape"].float().contiguous(),
+                                                    aux["inds"], aux["inds"].shape[1], return_joints=True, exact=True)
+                meshes.update(meta["index"], results, joints, verts)
         model.train(was_training)
         self.last_val = {"keypoints": collected.compute("keypoints"), "bbox": collected.compute("bbox")}
+        if meshes is not None:
+            self.last_val["mesh"] = meshes.compute()
         return self.last_val["keypoints"].stats, self.last_val["bbox"].stats
 
     def end_epoch(self, epoch):

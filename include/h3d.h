@@ -1042,6 +1042,68 @@ int h3d_coco_accumulate(const int64_t *order, const int32_t *seg_start, const in
                         int G, int K, int A, int T, const int32_t *max_dets /* host memory */, int M, const double *rec_thrs, int R,
                         double *precision, double *recall, void *workspace, size_t workspace_bytes, void *stream);
 
+/* =====================================================================================
+ * 8b. 3D evaluation (csrc/mesh_eval.hip; h3d_amd/mesh_eval.py; no reference code: the project's own definition):
+ *    MPJPE / PVE (the plain error) and PA-MPJPE / PA-PVE (the error after a similarity Procrustes alignment) of P pairs of point sets.
+ *    Points are fp32 and widened exactly; everything after the loads is fp64, every step ONE IEEE-754 binary64 operation, round to
+ *    nearest, no contraction, in the order written here, parentheses included (tests/mesh_eval_ref.py restates it with loops,
+ *    mesh_eval.evaluate_numpy is the numpy mirror; + - * / and sqrt are correctly rounded, so the kernels are bit-equal to both).
+ *    Asynchronous on `stream`, no allocation, no workspace, no atomics: two calls give the same bits.
+ *
+ *    h3d_pointset_errors, one workgroup per pair k.  pred [Np,n,3], gt [Ng,n,3] f32; pred_idx, gt_idx [P] i32: pair k compares
+ *    pred[pred_idx[k]] with gt[gt_idx[k]] (an index may repeat).  An index < 0 or >= Np (Ng) makes the pair INVALID: nothing of it is
+ *    dereferenced, err, count and transform of the pair are 0.  weight [Ng,n] u8 or NULL (all ones): point i of the pair is valid when
+ *    weight[gt_idx[k], i] != 0; count [P] = the valid points; count == 0: everything of the pair is 0.  Root sources pred_root
+ *    [Np,nr,3], gt_root [Ng,nr,3] f32 (both or neither) and 0 <= root_a, root_b < nr: the origins are o_p = (src[a] + src[b]) * 0.5 per
+ *    coordinate of pred_root[pred_idx[k]], o_g likewise of gt_root[gt_idx[k]] (a == b: that point itself; the weight is not looked at);
+ *    without root sources both are 0.
+ *      SUM      "sum over i of f(i)" below is, for every n: thread t of 256 starts at 0.0 and adds f(i) for the VALID i = t, t + 256, ...
+ *               in ascending order; inside each of the four waves (threads 64 w .. 64 w + 63) v[l] = v[l] + v[l + off] for off = 32, 16,
+ *               8, 4, 2, 1 (lanes l < off; lane 0 holds the wave's sum); the result is ((w0 + w1) + w2) + w3.  A function of n and the
+ *               weights only: never of P, the grid or the batch.
+ *      plain    err[k,0] = SUM |(p - o_p) - (g - o_g)| / count, with |d| = sqrt((d0 d0 + d1 d1) + d2 d2) and count as a double.
+ *      centre   mu_p = SUM p / count, mu_g = SUM g / count (per coordinate); x = p - mu_p, y = g - mu_g.
+ *      moments  in a second pass M[r][c] = SUM y_r x_c, var = SUM ((x0 x0 + x1 x1) + x2 x2).
+ *      special  var == 0 (no extent in the source; count == 1): R = I, s = 1.
+ *      SVD      of M = [c0 c1 c2] V^T by cyclic one-sided Jacobi on the columns of A = M and V = I.  A sweep visits the column pairs
+ *               (p,q) = (0,1), (0,2), (1,2); with dot(u,v) = (u0 v0 + u1 v1) + u2 v2: a = dot(A_p,A_p), b = dot(A_q,A_q), g = dot(A_p,A_q).
+ *               The pair is SKIPPED when |g| <= 2^-50 max(a, b): the rotation left undone is by less than 2^-50.  (The relative test
+ *               |g| <= eps sqrt(a b) never fires against a column that is rounding noise of a larger one -- a coplanar or collinear set
+ *               -- since every rotation renews the noise; this one does, a zero column (a b == 0, so g == 0) included, and forms no
+ *               product a b that could underflow or overflow.  The small columns are left orthogonal to the large ones only to 2^-50 of
+ *               the LARGE norm: U1 is re-orthogonalised below, and of c2 only the norm and one sign are used.)  Otherwise h = b - a,
+ *               g2 = 2 g and
+ *                   |g2| <= |h|:  r = g2 / h,  t = r / (1 + sqrt(1 + r r))
+ *                   else:         z = h / g2,  u = 1 / (|z| + sqrt(1 + z z)),  t = -u if z < 0 else u
+ *               (the smaller root of t^2 + 2 zeta t - 1 = 0 with zeta = h / g2, formed from whichever of zeta and 1 / zeta is at most 1
+ *               in magnitude, so nothing overflows), cs = 1 / sqrt(1 + t t), sn = cs t, and for A and for V, per row:
+ *               new_p = cs old_p - sn old_q, new_q = sn old_p + cs old_q.  The loop ends after the first sweep that skipped all three
+ *               pairs, at the latest after H3D_MESH_EVAL_MAX_SWEEPS sweeps.
+ *      order    nn_j = dot(A_j,A_j); the columns by nn descending through the compare-exchanges (0,1), (1,2), (0,1), each swapping only
+ *               when the later one is strictly larger (a tie keeps the lower original column first); dv = -1 for an odd number of
+ *               swaps else 1: det V (the rotations have determinant 1).  S_j = sqrt(nn_j), c_j and V_j in that order.
+ *      rank 0   S0 == 0 (every target point at its centroid): R = I, s = 0.
+ *      U        U0 = c0 / S0.  U1: if S1 > 0, u = c1 / S1, hh = dot(u,U0), w = u - hh U0, nw = |w|, and U1 = w / nw when nw >= 0.5;
+ *               else (rank 1, a collinear set) k = the coordinate where |U0| is least (the first of equals), w = e_k - U0[k] U0,
+ *               U1 = w / |w|.  U2 = U0 x U1 (U2[0] = U0[1] U1[2] - U0[2] U1[1], cyclic).
+ *      R, s, t  R[r][c] = (U0[r] V0[c] + U1[r] V1[c]) + dv (U2[r] V2[c]): a rotation for every rank, without a direction from a vanishing
+ *               third column.  d = -dv if dot(c2,U2) < 0 else dv;  s = ((S0 + S1) + d S2) / var;
+ *               t[r] = mu_g[r] - s ((R[r][0] mu_p[0] + R[r][1] mu_p[1]) + R[r][2] mu_p[2]).
+ *      aligned  err[k,1] = SUM |q - g| / count with q[r] = s ((R[r][0] p0 + R[r][1] p1) + R[r][2] p2) + t[r], in a third pass.
+ *    err [P,2] f64, count [P] i32, transform [P,13] f64 or NULL: s, R row-major, t.  No NaN or Inf for finite inputs.
+ *    n <= 0, P < 0, Np < 0, Ng < 0, 3 n or 3 nr >= 2^31, one root source without the other, a root index outside [0,nr), a NULL required
+ *    operand, an fp64 pointer off an 8-byte boundary: H3D_ERR_ARG, checked before the first HIP call.  P == 0: nothing is launched.
+ *
+ *    h3d_metric_means, one wave.  err [P,2] f64, count [P] i32 -> means [2] f64 = the means of err[:,0] and err[:,1] over the pairs with
+ *    count > 0, n_pairs [1] i32 = their number (0: both means are 0).  Lane l starts at 0.0 and adds its pairs l, l + 64, ... in
+ *    ascending order, then the wave tree of SUM; the sum is divided by n_pairs as a double.  P == 0 writes zeros.  Errors as above.
+ * ===================================================================================== */
+#define H3D_MESH_EVAL_MAX_SWEEPS 30
+int h3d_pointset_errors(const float *pred, int Np, const float *gt, int Ng, int n, const int32_t *pred_idx, const int32_t *gt_idx, int P,
+                        const uint8_t *weight, const float *pred_root, const float *gt_root, int nr, int root_a, int root_b, double *err,
+                        int32_t *count, double *transform, void *stream);
+int h3d_metric_means(const double *err, const int32_t *count, int P, double *means, int32_t *n_pairs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

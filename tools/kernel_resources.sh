@@ -6,6 +6,7 @@
 #   tools/kernel_resources.sh optim.hip -ffp-contract=off   (the Adam step: DESIGN.md section 21)
 #   tools/kernel_resources.sh smpl_loss.hip -ffp-contract=off   (the keypoint reprojection loss: DESIGN.md section 22)
 #   tools/kernel_resources.sh render.hip -ffp-contract=off      (the mesh rasteriser: DESIGN.md section 23)
+#   tools/kernel_resources.sh mesh_eval.hip -ffp-contract=off   (the 3D evaluation: DESIGN.md section 27)
 # (device-only compile, nothing is written; use it to check that a change did not push a variant over its VGPR cap or into scratch)
 src=$1; shift
 cd "$(dirname "$0")/../human-3d-reconstruction_amd/csrc" || exit 1
