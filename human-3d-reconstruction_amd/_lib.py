@@ -105,6 +105,14 @@ class H3dHeadsDesc(ctypes.Structure):
     _fields_ = [("nheads", ctypes.c_int32), ("wexp", ctypes.c_int32), ("head", _HeadEntry * HEADS_MAX)]
 
 
+HEADS_LISTS_MAX = 4
+
+
+class H3dHeadsList(ctypes.Structure):
+    """Mirror of `struct h3d_heads_list` (one position list of h3d_heads_sparse_lists)."""
+    _fields_ = [("inds", c_vp), ("K", ctypes.c_int32), ("head_mask", ctypes.c_uint32)]
+
+
 class H3dUpdcnDesc(ctypes.Structure):
     """Mirror of `struct h3d_updcn_desc` (host-side descriptor behind H3D_OP_UPDCN_F16)."""
     _fields_ = [("skip", c_vp), ("w_up", c_vp), ("w_off", c_vp), ("skip_cs", ctypes.c_int32), ("reserved", ctypes.c_int32)]
@@ -168,6 +176,7 @@ SIGNATURES = {
     "h3d_run_ops_timed": [ctypes.POINTER(H3dOp), c_i, c_vp, c_vp],
     "h3d_op_kernel_name": [ctypes.POINTER(H3dOp), ctypes.c_char_p, c_i],
     "h3d_heads_sparse": [ctypes.POINTER(H3dOp), c_vp, c_i, c_vp],
+    "h3d_heads_sparse_lists": [ctypes.POINTER(H3dOp), c_i, ctypes.POINTER(H3dHeadsList), c_vp],
     "h3d_nchw_f32_to_nhwc": [c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
     "h3d_nhwc_to_nchw_f32": [c_vp, c_i, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp],
     "h3d_nms_topk": [c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp, c_vp, c_vp, c_vp, c_vp],

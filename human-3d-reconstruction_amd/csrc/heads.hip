@@ -18,6 +18,7 @@
 // so the A-fragment ds_read_b128 stay conflict-free.  The 1x1 slice of a slab arrives the same way.
 // Outputs are written as contiguous NCHW fp32 rows (lane = pixel), the reference's head layout.
 #include "common.h"
+#include <string.h>
 #include <type_traits>
 #include <utility>
 
@@ -25,12 +26,18 @@ constexpr int HEADS_MAX = 16;
 constexpr int HC_IN = 64;     // channels of y (DLA-34 first_level = 2)
 constexpr int HC_SLAB = 64;   // intermediate channels per slab (two 32-row MFMA tiles)
 constexpr int HC_MT2 = 3;     // up to 96 output channels per head
+constexpr int HEADS_LISTS_MAX = 4;   // position lists of one sparse launch (h3d_heads_sparse_lists)
 #ifndef HEADS_PF_WIDE
 #define HEADS_PF_WIDE 0 // the same pipeline in the 2- and 3-tile bodies (wide heads)
 #endif
 #ifndef HEADS_PF
 #define HEADS_PF 2      // measured 0: 1.363, 1: 1.348, 2: 1.335, 3: 1.343 ms (batch 64, the narrow-heads launch)
 #endif
+
+#ifndef HEADS_SPARSE_NW
+#define HEADS_SPARSE_NW 8 // waves of a sparse workgroup, two of which compute: the 24 LDS-DMA instructions of a filter stage are spread over all of them.
+#endif                    // Measured (batch 64, K = 100: 100 six-head + 1700 one-head workgroups in one launch): 4: 217.7, 8: 171.0 us
+static_assert(HEADS_SPARSE_NW == 4 || HEADS_SPARSE_NW == 8, "sparse heads: 24 wave-instructions per stage in whole numbers per wave, at most 512 threads");
 
 struct HeadsArgs {
     const char *in;      // NHWC T feature map
@@ -47,9 +54,13 @@ struct HeadsArgs {
     int xcd;   // h3d_tile_id mode
     float s1;                // f16x3 plans: 2^-wexp of the 3x3 filters AND of b1 (h3d_heads_desc.wexp); 1 otherwise
     float s2[HEADS_MAX];     // ... 2^-wexp2 of a head's 1x1 filters
-    const long long *inds;   // sparse launches (h3d_heads_sparse): [B*K] flat output positions y*W + x, image = entry / K
-    int K;
     unsigned long long *stamps;   // profiling builds: per workgroup {kernel start, end, cycles wave 0 spent in the stage barriers, in gemm2, waiting for its own DMA pieces}
+    // sparse launches (h3d_heads_sparse_lists): position lists in launch order.  List i owns the workgroups [l_wg0[i], l_wg0[i + 1]) and
+    // evaluates the l_nh[i] heads l_head[i][0..) of the op's descriptor, in that order, at l_inds[i]
+    int nlists;
+    const long long *l_inds[HEADS_LISTS_MAX];   // [B*K] flat output positions y*W + x, image = entry / K
+    int l_K[HEADS_LISTS_MAX], l_wg0[HEADS_LISTS_MAX], l_nh[HEADS_LISTS_MAX];
+    int l_head[HEADS_LISTS_MAX][HEADS_MAX];
 };
 
 template <typename T, int TH>
@@ -75,18 +86,19 @@ struct HeadsCfg {
     static constexpr int VPR = HC_IN * ES / 16;       // 16-byte vectors per halo pixel
 };
 
-// Sparse launches (h3d_heads_sparse): the heads at a LIST of output positions instead of a tile.  A computing wave owns 32 positions,
+// Sparse launches (h3d_heads_sparse_lists): the heads at LISTS of output positions instead of a tile; a workgroup's positions come from
+// one list and it runs that list's heads only.  A computing wave owns 32 positions,
 // the 32 columns of ONE N-tile (a column of an MFMA result depends on that column's B operand only, so a position's value
 // does not depend on what the other columns hold); each position has its own 3x3 x 64-channel neighbourhood in LDS, laid out as
 // a 3-pixel-wide image of the dense kernel's pixel stride: tap (dy, dx) sits at dy * RB + dx * SB as in the halo tile, and the
-// stage code, gemm2 and the epilogue are the dense kernel's at NT = 1.  Two more waves only help with the LDS-DMA of the
+// stage code, gemm2 and the epilogue are the dense kernel's at NT = 1.  The other waves only help with the LDS-DMA of the
 // filters (an LDS-DMA instruction costs its wave 100-185 issue cycles; a stage is 24 MFMAs per computing wave here).
 template <typename T>
 struct HeadsSparseCfg {
     using D = HeadsCfg<T, 16>;
     static_assert(sizeof(T) == 2, "sparse heads: 2-byte plans");
     static constexpr int ES = D::ES, NT = 1, TW = D::TW;
-    static constexpr int CW = 2, NW = 4;              // computing waves | waves of the workgroup
+    static constexpr int CW = 2, NW = HEADS_SPARSE_NW;   // computing waves | waves of the workgroup
     static constexpr int NPOS = 32 * CW;              // positions per workgroup
     static constexpr int SB = D::SB, RB = 3 * SB, PB = 3 * RB;   // pixel | patch row | patch (position) stride
     static constexpr int RBW = D::RBW, CPR = D::CPR, SWZ_SHIFT = D::SWZ_SHIFT, TAPS = D::TAPS, TRS = D::TRS, SLOT = D::SLOT;
@@ -247,7 +259,7 @@ __device__ __forceinline__ void heads_dma_w2(const char *w2, int head_conv, char
     }
 }
 
-// SPARSE: the workgroup's "tile" is 32 * CW entries of the position list a.inds (HeadsSparseCfg); everything per position -- operands,
+// SPARSE: the workgroup's "tile" is 32 * CW entries of ONE of the position lists (HeadsSparseCfg); everything per position -- operands,
 // the order of every accumulator's MFMA chain, the epilogue -- is the dense code, so the value is the dense launch's bit for bit.
 template <typename T, int TH, int M2, bool BIASC, bool MIXED = false, bool SPARSE = false>
 __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
@@ -271,7 +283,21 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
     const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
     const int oy0 = ty * TH, ox0 = tx * C::TW;
     const int slabs = a.head_conv / HC_SLAB;
-    const int nstages = a.nheads * slabs * C::TRS;       // tap-row stages of the whole launch
+    // sparse: this workgroup's list (they start on workgroup boundaries), its index among the list's workgroups, the list's heads
+    [[maybe_unused]] int li = 0;
+    if constexpr (SPARSE) {
+#pragma unroll
+        for (int i = 1; i < HEADS_LISTS_MAX; ++i)
+            if (i < a.nlists && bid >= a.l_wg0[i]) li = i;
+    }
+    [[maybe_unused]] const int lb = SPARSE ? bid - a.l_wg0[li] : 0, sp_K = SPARSE ? a.l_K[li] : 0;
+    [[maybe_unused]] const long long *sp_inds = SPARSE ? a.l_inds[li] : nullptr;
+    const int nh = SPARSE ? a.l_nh[li] : a.nheads;       // heads this workgroup runs: the hi-th one is head_at(hi) of the descriptor
+    auto head_at = [&](int hi) -> int {
+        if constexpr (SPARSE) return a.l_head[li][hi];
+        else return hi;
+    };
+    const int nstages = nh * slabs * C::TRS;             // tap-row stages of the workgroup
     const int sw = (r >> C::SWZ_SHIFT) & (C::CPR - 1);   // XOR swizzle of this lane's A-fragment rows
 
     // ---- LDS-DMA of stage s: TAPS taps x 64 rows of W1 for (head, slab) -> ring slot s & 1 -----------
@@ -281,7 +307,9 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
     const int w1_bytes = a.nheads * a.head_conv * 9 * HC_IN * ES;
     auto issue_w1 = [&](int s) {
         if ((H3D_DBG(a) & 1) && s > 0) return;
-        const int hs = s / C::TRS, tr = s - hs * C::TRS;        // hs = head * slabs + slab
+        int hs = s / C::TRS;                                    // hs = head * slabs + slab
+        const int tr = s - hs * C::TRS;
+        if constexpr (SPARSE) { const int hi = hs / slabs; hs += (head_at(hi) - hi) * slabs; }
         heads_dma_w1<T, TH, C::NW>(a.w1, w1_bytes, s_ring + (s & 1) * C::SLOT, wvs, l, ((hs * HC_SLAB * 9 + tr * C::TAPS) * HC_IN) * ES);
     };
     // ---- LDS-DMA of the 1x1 slice [96 rows][64 K of this slab] -> s_w2 --------------------------------
@@ -292,29 +320,29 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
 
     // ---- prologue: stage 0 weights in flight, halo tile (all 64 channels, zero outside the image) -----
     issue_w1(0);
-    heads_issue_bias(a.b1, a.head_conv, a.b2[0], s_bias, __builtin_amdgcn_readfirstlane(wv), l);
+    heads_issue_bias(a.b1 + head_at(0) * a.head_conv, a.head_conv, a.b2[head_at(0)], s_bias, __builtin_amdgcn_readfirstlane(wv), l);
     // sparse: this lane's position (computing waves; an entry past the list or outside the map stores nothing) and whether the wave computes
     [[maybe_unused]] int sp_b = 0, sp_y = 0, sp_x = 0;
     [[maybe_unused]] bool sp_ok = false, idle = false;
     if constexpr (SPARSE) {
         idle = wvs >= C::CW;
-        const int p = bid * C::NPOS + wv * 32 + r;
-        if (!idle && p < a.B * a.K) {
-            const long long ind = a.inds[p];
-            if (ind >= 0 && ind < (long long)a.H * a.W) { sp_ok = true; sp_b = p / a.K; sp_y = (int)ind / a.W; sp_x = (int)ind - sp_y * a.W; }
+        const int p = lb * C::NPOS + wv * 32 + r;
+        if (!idle && p < a.B * sp_K) {
+            const long long ind = sp_inds[p];
+            if (ind >= 0 && ind < (long long)a.H * a.W) { sp_ok = true; sp_b = p / sp_K; sp_y = (int)ind / a.W; sp_x = (int)ind - sp_y * a.W; }
         }
         // the 3x3 neighbourhood of every position (all 64 channels, zero outside the image, as the dense halo)
         constexpr int NPV = C::NPOS * 9 * C::VPR;
         stage_vectors<NPV, 64 * C::NW>(
             tid,
             [&](int i) -> u32x4 {
-                const int v = i % C::VPR, q = i / C::VPR, pix = q % 9, p = bid * C::NPOS + q / 9;
-                if (p >= a.B * a.K) return u32x4{0u, 0u, 0u, 0u};
-                const long long ind = a.inds[p];
+                const int v = i % C::VPR, q = i / C::VPR, pix = q % 9, p = lb * C::NPOS + q / 9;
+                if (p >= a.B * sp_K) return u32x4{0u, 0u, 0u, 0u};
+                const long long ind = sp_inds[p];
                 if (ind < 0 || ind >= (long long)a.H * a.W) return u32x4{0u, 0u, 0u, 0u};
                 const int y = (int)ind / a.W, gy = y - 1 + pix / 3, gx = (int)ind - y * a.W - 1 + pix % 3;
                 if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W)
-                    return *reinterpret_cast<const u32x4 *>(a.in + (((size_t)(p / a.K) * a.H * a.W + (size_t)gy * a.W + gx) * a.in_cs) * ES + v * 16);
+                    return *reinterpret_cast<const u32x4 *>(a.in + (((size_t)(p / sp_K) * a.H * a.W + (size_t)gy * a.W + gx) * a.in_cs) * ES + v * 16);
                 return u32x4{0u, 0u, 0u, 0u};
             },
             [&](int i, u32x4 val) {
@@ -366,9 +394,10 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
     int s = 0;
     // one head: M2H = 32-row tiles of ITS 1x1 output.  MIXED launches (all heads of the model in one launch, so that the halo
     // tile is staged once per workgroup for all of them) instantiate the body for every width up to M2 and pick per head
-    auto head_body = [&](auto m2_tag, int head) {
+    // (hi: the head's place among the heads this workgroup runs, head: its slot in the descriptor; the same number in a dense launch)
+    auto head_body = [&](auto m2_tag, int hi, int head) {
         constexpr int M2H = decltype(m2_tag)::value;
-        const char *s_b = s_bias + (head & 1) * C::LDS_BIAS;
+        const char *s_b = s_bias + (hi & 1) * C::LDS_BIAS;
         f32x16 acc[2][NT], acc2[M2H][NT];
 #pragma unroll
         for (int m = 0; m < 2; ++m)
@@ -527,9 +556,9 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
             for (int tr = 0; tr < C::TRS; ++tr, ++s) {
                 if (s + 1 < nstages) issue_w1(s + 1);          // slot (s+1)&1 was last read in stage s-1
                 if (tr == (C::TRS > 1 ? 1 : 0)) issue_w2(head, slab);   // after the barrier that follows the previous gemm2
-                if (slab == 0 && tr == C::TRS - 1 && head + 1 < a.nheads)   // next head's biases: their slot was last read in the
-                    heads_issue_bias(a.b1 + (head + 1) * a.head_conv, a.head_conv, a.b2[head + 1],   // previous head's epilogue, at least one barrier ago
-                                     s_bias + ((head + 1) & 1) * C::LDS_BIAS, __builtin_amdgcn_readfirstlane(wv), l);
+                if (slab == 0 && tr == C::TRS - 1 && hi + 1 < nh)   // next head's biases: their slot was last read in the
+                    heads_issue_bias(a.b1 + head_at(hi + 1) * a.head_conv, a.head_conv, a.b2[head_at(hi + 1)],   // previous head's epilogue, at least one barrier ago
+                                     s_bias + ((hi + 1) & 1) * C::LDS_BIAS, __builtin_amdgcn_readfirstlane(wv), l);
                 const char *slot = s_ring + (s & 1) * C::SLOT;
 #ifdef H3D_ABLATE
                 const unsigned long long ts0 = __builtin_readcyclecounter();
@@ -594,14 +623,15 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
             }
         }
         };
-    for (int head = 0; head < a.nheads; ++head) {
+    for (int hi = 0; hi < nh; ++hi) {
+        const int head = head_at(hi);
         if constexpr (!MIXED) {
-            head_body(std::integral_constant<int, M2>{}, head);
+            head_body(std::integral_constant<int, M2>{}, hi, head);
         } else {
             const int m2h = __builtin_amdgcn_readfirstlane((a.C[head] + 31) >> 5);
-            if (m2h <= 1) head_body(std::integral_constant<int, 1>{}, head);
-            else if (M2 < 3 || m2h == 2) head_body(std::integral_constant<int, (M2 < 2 ? 1 : 2)>{}, head);
-            else head_body(std::integral_constant<int, M2>{}, head);
+            if (m2h <= 1) head_body(std::integral_constant<int, 1>{}, hi, head);
+            else if (M2 < 3 || m2h == 2) head_body(std::integral_constant<int, (M2 < 2 ? 1 : 2)>{}, hi, head);
+            else head_body(std::integral_constant<int, M2>{}, hi, head);
         }
     }
 #ifdef H3D_ABLATE
@@ -642,7 +672,9 @@ static int heads_args(const h3d_op &op, HeadsArgs &a)
 #else
     a.stamps = nullptr;
 #endif
-    a.inds = nullptr; a.K = 0;
+    a.nlists = 0;
+    memset(a.l_inds, 0, sizeof a.l_inds); memset(a.l_K, 0, sizeof a.l_K); memset(a.l_wg0, 0, sizeof a.l_wg0);
+    memset(a.l_nh, 0, sizeof a.l_nh); memset(a.l_head, 0, sizeof a.l_head);
     a.nheads = d->nheads; a.head_conv = op.Cout; a.B = op.B; a.H = op.H; a.W = op.W; a.in_cs = op.in_cs;
     for (int i = 0; i < d->nheads; ++i) {
         if (!d->head[i].w2 || !d->head[i].b2 || !d->head[i].out) H3D_FAIL(H3D_ERR_ARG, "heads: head %d null pointer", i);
@@ -689,27 +721,68 @@ int h3d_launch_heads(const h3d_op &op, hipStream_t st)
     });
 }
 
-// The heads of an H3D_OP_HEADS op at the K positions per image listed in `inds` ([B][K] flat y*W + x; an entry outside the map is
-// skipped), written into the heads' dense maps at those positions: bit for bit what the op's dense launch writes there.
-extern "C" int h3d_heads_sparse(const h3d_op *op, const int64_t *inds, int K, void *stream)
+static_assert(HEADS_LISTS_MAX == H3D_HEADS_LISTS_MAX, "header/kernel mismatch");
+
+// The heads of an H3D_OP_HEADS op at listed positions, written into the heads' dense maps there: bit for bit what the op's dense
+// launch writes at those positions.  ONE launch for all lists: a list's workgroups (32 * CW positions each) form one run of the grid
+// and loop over that list's heads only; the lists with the most heads -- the longest chain of filter stages -- come first, so that
+// the short workgroups fill the CUs behind them instead of the other way round.
+extern "C" int h3d_heads_sparse_lists(const h3d_op *op, int nlists, const h3d_heads_list *lists, void *stream)
 {
-    if (!op || !inds) H3D_FAIL(H3D_ERR_ARG, "heads_sparse: null pointer");
+    if (!op || !lists) H3D_FAIL(H3D_ERR_ARG, "heads_sparse: null pointer");
     if (op->kind != H3D_OP_HEADS) H3D_FAIL(H3D_ERR_ARG, "heads_sparse: op kind %d is not H3D_OP_HEADS", op->kind);
-    if (op->B <= 0 || op->H <= 0 || op->W <= 0 || K <= 0 || (long long)op->B * K > (1 << 24))
-        H3D_FAIL(H3D_ERR_SHAPE, "heads_sparse: B %d, H %d, W %d, K %d", op->B, op->H, op->W, K);
+    if (nlists <= 0 || nlists > HEADS_LISTS_MAX) H3D_FAIL(H3D_ERR_ARG, "heads_sparse: %d position lists (1..%d)", nlists, HEADS_LISTS_MAX);
+    if (op->B <= 0 || op->H <= 0 || op->W <= 0) H3D_FAIL(H3D_ERR_SHAPE, "heads_sparse: B %d, H %d, W %d", op->B, op->H, op->W);
+    for (int i = 0; i < nlists; ++i) {
+        if (!lists[i].inds) H3D_FAIL(H3D_ERR_ARG, "heads_sparse: list %d null pointer", i);
+        if (lists[i].K <= 0 || (long long)op->B * lists[i].K > (1 << 24))
+            H3D_FAIL(H3D_ERR_SHAPE, "heads_sparse: list %d: B %d, K %d", i, op->B, lists[i].K);
+    }
     if (op->dtype != H3D_BF16 && op->dtype != H3D_F16)
         H3D_FAIL(H3D_ERR_UNSUPPORTED, "heads_sparse: dtype %d (the 2-byte plans)", op->dtype);
     if (op->reserved) H3D_FAIL(H3D_ERR_UNSUPPORTED, "heads_sparse: tuning word %#x", (unsigned)op->reserved);
     HeadsArgs a;
     if (const int rc = heads_args(*op, a)) return rc;
-    a.inds = (const long long *)inds; a.K = K;
+    uint32_t seen = 0;
+    for (int i = 0; i < nlists; ++i) {
+        const uint32_t m = lists[i].head_mask;
+        if (!m || (a.nheads < 32 && m >> a.nheads))
+            H3D_FAIL(H3D_ERR_ARG, "heads_sparse: list %d head mask %#x (bits 0..%d of the op's %d heads, at least one)", i, (unsigned)m, a.nheads - 1, a.nheads);
+        if (m & seen) H3D_FAIL(H3D_ERR_ARG, "heads_sparse: list %d head mask %#x names a head of an earlier list (%#x)", i, (unsigned)m, (unsigned)(m & seen));
+        seen |= m;
+    }
+    // launch order: most heads first (stable)
+    int order[HEADS_LISTS_MAX];
+    for (int i = 0; i < nlists; ++i) order[i] = i;
+    for (int i = 1; i < nlists; ++i)
+        for (int j = i; j > 0 && __builtin_popcount(lists[order[j]].head_mask) > __builtin_popcount(lists[order[j - 1]].head_mask); --j)
+            std::swap(order[j], order[j - 1]);
     a.tiles_x = a.tiles_y = 1;
     return h3d_by_dtype<bf16_t, f16_t>(op->dtype, "heads_sparse: dtype %d", [&](auto t) {
         using T = typename decltype(t)::type;
         using C = HeadsSparseCfg<T>;
-        const dim3 grid(cdiv(op->B * K, C::NPOS)), blk(64 * C::NW);
+        int wgs = 0;
+        a.nlists = nlists;
+        for (int i = 0; i < nlists; ++i) {
+            const h3d_heads_list &ls = lists[order[i]];
+            a.l_inds[i] = (const long long *)ls.inds; a.l_K[i] = ls.K; a.l_wg0[i] = wgs; a.l_nh[i] = 0;
+            for (int h = 0; h < a.nheads; ++h)
+                if (ls.head_mask >> h & 1) a.l_head[i][a.l_nh[i]++] = h;
+            wgs += cdiv(op->B * ls.K, C::NPOS);
+        }
+        const dim3 grid(wgs), blk(64 * C::NW);
         // one instantiation: the body picks the 1 / 2 / 3-tile epilogue width per head
         const h3d_kname name{"heads_kernel", t, 16, 3, true, h3d_opt(true), h3d_opt(true)};
         return h3d_launch(name, heads_kernel<T, 16, 3, true, true, true>, grid, blk, 0, (hipStream_t)stream, a);
     });
+}
+
+// One list, every head of the descriptor (the K top-K centres of multi_pose_decode).
+extern "C" int h3d_heads_sparse(const h3d_op *op, const int64_t *inds, int K, void *stream)
+{
+    if (!op || !inds) H3D_FAIL(H3D_ERR_ARG, "heads_sparse: null pointer");
+    if (op->kind != H3D_OP_HEADS || !op->in2) H3D_FAIL(H3D_ERR_ARG, "heads_sparse: op kind %d is not H3D_OP_HEADS with a descriptor", op->kind);
+    const int n = ((const h3d_heads_desc *)op->in2)->nheads;
+    const h3d_heads_list all = {inds, K, n >= 32 ? ~0u : n > 0 ? (1u << n) - 1 : 1u};     // (a bad head count is heads_args' error)
+    return h3d_heads_sparse_lists(op, 1, &all, stream);
 }

@@ -19,12 +19,14 @@ from .utils import _transpose_and_gather_feat
 MULTI_POSE_HEADS = {"hm": 1, "wh": 2, "hps": 34, "reg": 2, "hm_hp": 17, "hp_offset": 2}   # opts.py:248-258
 CTDET_HEADS = {"hm": 80, "wh": 2, "reg": 2}                                                  # opts.py:241-247
 SMPL_HEADS = {"pose": 72, "shape": 10}
-WHOLE_MAP_HEADS = ("hm", "hm_hp", "hp_offset")       # what multi_pose_decode reads as whole maps (3x3 NMS + top-K; hp_offset at up to 17 x K peaks)
+WHOLE_MAP_HEADS = ("hm", "hm_hp", "hp_offset")       # the heads multi_pose_decode does not read at the K centres: `hm` / `hm_hp` whole (3x3 NMS + top-K),
+PEAK_HEADS = ("hp_offset",)                          # `hp_offset` at the 17 x K key-point peaks of `hm_hp` only (Plan.FLAGS peak_heads)
 
 
 class LazyHeads(dict):
     """res["heads"] of a sparse-heads run: every head's dense [B,C,H,W] map, of which the run itself wrote only what it reads --
-    `hm`, `hm_hp`, `hp_offset` whole, every other head at the K detection centres.  The first access through [], get, items, values,
+    `hm` and `hm_hp` whole, `hp_offset` at the 17 x K key-point peaks (whole where the plan has no peak heads), every other head at the
+    K detection centres.  The first access through [], get, items, values,
     iteration, `in` or copy calls `completer` (once), which launches the deferred dense head ops of the run's plan on the
     current stream; from then on this is a plain dict of complete maps.  keys() and len() touch no map and complete nothing.
     The maps are the plan's buffers: they belong to the latest run on their slot, as every head tensor of this package does."""
@@ -150,9 +152,13 @@ class MultiPoseDetector:
         # The heads decode and the SMPL stage read at the K detection centres only (wh, hps, reg, pose, shape, cam) are computed THERE only
         # (csrc/heads.hip h3d_heads_sparse), bit-identical to their dense maps at those positions; res["heads"] completes the maps when
         # somebody reads them (LazyHeads).  Fused DLA-34 heads, bf16 / f16, no flip_test; False: every head as a dense map, as before.
+        # `hp_offset` is read at the key-point peaks the top-K of `hm_hp` yields and nowhere else: with both heads it is computed at those
+        # 17 x K positions, in the same launch as the centre heads (h3d_heads_sparse_lists).
         self.sparse_heads = True
         if opt.arch.replace("-", "_") in ("dla_34", "dla34") and opt.dtype in ("bf16", "f16"):
             self.model.engine_flags["split_heads"] = tuple(h for h in opt.heads if h in WHOLE_MAP_HEADS)   # (the plan's lowering; `run` decides per call)
+            # (without `hm_hp` there are no peaks and the assemble step does not read `hp_offset`: the run computes it nowhere)
+            self.model.engine_flags["peak_heads"] = tuple(h for h in opt.heads if h in PEAK_HEADS)
         if opt.smpl and smpl_model is None:
             self.smpl_model = _smpl.SMPLModel.synthetic()
 
@@ -175,7 +181,10 @@ class MultiPoseDetector:
         if plan is not None:
             out = plan.outputs                    # (the deferred heads' maps: valid at `inds` once run_sparse has run)
             top = decode._multi_pose_topk(out["hm"], out.get("hm_hp") if opt.hm_hp else None, opt.K, logits=True)
-            plan.run_sparse(top["inds"], opt.K)
+            if plan.sparse_masks[1] and top["hm_inds"] is not None:              # `hp_offset` at the key-point peaks, same launch
+                plan.run_sparse_lists(top["inds"], opt.K, top["hm_inds"].view(top["inds"].shape[0], -1), top["hm_inds"].shape[1] * opt.K)
+            else:
+                plan.run_sparse(top["inds"], opt.K)
             dets, aux = decode._multi_pose_assemble(top, out["wh"], out["hps"], out.get("reg") if opt.reg_offset else None,
                                                     out.get("hp_offset") if opt.reg_hp_offset else None, return_aux=True)
             heads = LazyHeads(out, None)

@@ -80,8 +80,12 @@ class Plan:
         split_heads=(),           # a tuple of head names (fused heads only): the heads ops come in two parts.  The EAGER part, one launch for
                                   # these heads (the maps a decode reads whole), ends the prefix `run_eager` executes; the DEFERRED part,
                                   # the other heads in the default groups, follows it (`run_deferred`).  `run_sparse` evaluates the
-                                  # deferred heads at listed positions only (h3d_heads_sparse).  `run` still runs everything:
+                                  # deferred heads (without the peak_heads) at listed positions only (h3d_heads_sparse).  `run` still runs everything:
                                   # same instantiations, same per-head arithmetic, the default lowering's maps bit for bit
+        peak_heads=(),            # with split_heads: heads (of split_heads or not) that are NOT read whole either, but at a second, longer position
+                                  # list (multi_pose_decode reads `hp_offset` at the 17 x K key-point peaks).  They leave the eager launch
+                                  # for the deferred groups, in their default place, and join the sparse op, where `run_sparse_lists`
+                                  # evaluates them at that second list in the same launch as the centre heads.  Alone: no effect
     )
 
     def __init__(self, pw, B, H, W, **flags):
@@ -111,6 +115,7 @@ class Plan:
         self.n_eager = None             # split_heads: ops[:n_eager] = backbone + eager heads, ops[n_eager:] = the deferred heads
         self.sparse_op = None           # ... and the deferred heads as ONE op outside the array, for h3d_heads_sparse
         self._sparse_at = {}            # ... head -> (its descriptor, slot)
+        self.sparse_masks = (0, 0)      # ... descriptor slots of the heads read at the centres | at the peak list (peak_heads)
         self.pending = None             # an event behind launches another stream issued into this plan's maps (detector.LazyHeads)
         if pw.arch == "hourglass":
             self._lower_hourglass()
@@ -410,7 +415,8 @@ class Plan:
                 return self._op(_lib.OP_HEADS, feat, in2=ctypes.addressof(desc), w=w1.data_ptr(), bias=b1.data_ptr(),
                                 Ho=Ho, Wo=Wo, Cout=self.pw.head_conv, ksize=3, stride=1, emit=emit)
 
-            eager = tuple(h for h in self.pw.heads if h in tuple(self.split_heads or ()))
+            peak = tuple(self.peak_heads or ())
+            eager = tuple(h for h in self.pw.heads if h in tuple(self.split_heads or ()) and h not in peak)
             deferred = tuple(h for h in self.pw.heads if h not in eager)
             split = bool(eager) and bool(deferred) and self.pw.dtype in LOWP
             if split:
@@ -426,6 +432,8 @@ class Plan:
                 heads_op(groups[m2])
             if split:
                 self.sparse_op = heads_op(deferred, emit=False)
+                pk = sum(1 << i for i, h in enumerate(deferred) if h in peak)
+                self.sparse_masks = ((1 << len(deferred)) - 1 - pk, pk)
             self.outputs = {h: self.outputs[h] for h in self.pw.heads}      # reference head order
             return
         for head in self.pw.heads:
@@ -555,7 +563,26 @@ class Plan:
         _lib.require_cuda(inds)
         if inds.dtype != torch.int64 or not inds.is_contiguous() or tuple(inds.shape) != (self.B, K):
             raise RuntimeError("run_sparse: contiguous int64 inds [%d,%d] expected, got %s %s" % (self.B, K, tuple(inds.shape), inds.dtype))
-        _lib.check(_lib.lib().h3d_heads_sparse(ctypes.byref(self.sparse_op), _lib.ptr(inds), int(K), _lib.stream_ptr()), "h3d_heads_sparse")
+        if not self.sparse_masks[1]:
+            _lib.check(_lib.lib().h3d_heads_sparse(ctypes.byref(self.sparse_op), _lib.ptr(inds), int(K), _lib.stream_ptr()), "h3d_heads_sparse")
+        elif self.sparse_masks[0]:
+            self._sparse_lists("run_sparse", (inds, K, self.sparse_masks[0]))
+
+    def _sparse_lists(self, what, *lists):
+        """ONE h3d_heads_sparse_lists launch: (inds [B,K], K, descriptor-slot mask of the heads evaluated there) per list."""
+        arr = (_lib.H3dHeadsList * len(lists))()
+        for e, (inds, K, mask) in zip(arr, lists):
+            _lib.require_cuda(inds)
+            if inds.dtype != torch.int64 or not inds.is_contiguous() or tuple(inds.shape) != (self.B, K):
+                raise RuntimeError("%s: contiguous int64 inds [%d,%d] expected, got %s %s" % (what, self.B, K, tuple(inds.shape), inds.dtype))
+            e.inds, e.K, e.head_mask = inds.data_ptr(), int(K), mask
+        _lib.check(_lib.lib().h3d_heads_sparse_lists(ctypes.byref(self.sparse_op), len(lists), arr, _lib.stream_ptr()), "h3d_heads_sparse_lists")
+
+    def run_sparse_lists(self, inds, K, peak_inds, PK):
+        """`run_sparse` and, in the same launch, the peak heads (`peak_heads`) at peak_inds [B,PK] (int64, flat y*W + x)."""
+        if self.sparse_op is None or not self.sparse_masks[1]:
+            raise RuntimeError("run_sparse_lists: this plan was lowered without peak_heads (dtype %s)" % self.dtype)
+        self._sparse_lists("run_sparse_lists", *([(inds, K, self.sparse_masks[0])] if self.sparse_masks[0] else []), (peak_inds, PK, self.sparse_masks[1]))
 
     def run_deferred(self):
         """The deferred heads' dense launches: the whole maps (the positions `run_sparse` wrote receive the same bits)."""

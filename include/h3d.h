@@ -480,6 +480,23 @@ int h3d_op_kernel_name(const h3d_op *op, char *buf, int buflen);
  * skipped; a position may be listed more than once. */
 int h3d_heads_sparse(const h3d_op *op, const int64_t *inds, int K, void *stream);
 
+/* The same in ONE launch over several position lists, each with its own heads: list i evaluates the heads whose descriptor slot is
+ * set in head_mask at inds [B][K] (h3d_heads_sparse is the one-list, all-heads case).  multi_pose_decode reads `hp_offset` at the
+ * 17 x K key-point peaks and every other gathered head at the K centres: two lists, one launch in the serial tail of the step.
+ * A workgroup takes its positions from one list and runs that list's heads only; the lists with the most heads are scheduled
+ * first.  A position may appear in several lists and more than once in a list (the same bits are stored again); an entry outside
+ * [0, H*W) stores nothing.  A head that no list names is not computed.
+ *    H3D_ERR_ARG: nlists outside 1..H3D_HEADS_LISTS_MAX, a NULL list, an empty mask, a mask bit at or beyond the descriptor's
+ *    nheads, a head named by two lists.  Per list, as h3d_heads_sparse: K <= 0 or B*K > 2^24 is H3D_ERR_SHAPE; a dtype other than
+ *    H3D_BF16 / H3D_F16 or a tuning word in op.reserved is H3D_ERR_UNSUPPORTED. */
+#define H3D_HEADS_LISTS_MAX 4
+typedef struct h3d_heads_list {
+    const int64_t *inds;    /* device, [B][K] */
+    int32_t K;
+    uint32_t head_mask;     /* bit i: head[i] of the op's h3d_heads_desc */
+} h3d_heads_list;
+int h3d_heads_sparse_lists(const h3d_op *op, int nlists, const h3d_heads_list *lists, void *stream);
+
 /* Layout helpers (host interface keeps the reference's NCHW fp32 tensors at the boundary). */
 int h3d_nchw_f32_to_nhwc(const float *src, void *dst, int dtype, int B, int C, int H, int W,
                          int dst_cs, void *stream);
