@@ -22,9 +22,11 @@ Training the heads `Conv3x3 + ReLU + Conv1x1` (models.model.DLASeg.__init__ / fo
         h3d_amd.heads.{heads_autograd,TrainableHeads}
     torch.optim.Adam as trains.trainer.HMRTrainer uses it, HMRModelWithLoss / run_epoch / the lr_step drop, save_model / load_model
         with the optimiser state -> h3d_amd.optim.Adam, h3d_amd.trainer.HeadsTrainer, h3d_amd.checkpoint.{save_model,load_model}
+Training plain convolutions (nn.Conv2d, models.model.BasicBlock / Root with folded BatchNorm) -> h3d_amd.conv.{conv2d_backward,
+        conv2d_autograd,TrainableConv2d,TrainableBasicBlock}
 Without a counterpart in the reference: the 3D evaluation of the SMPL output, MPJPE / PA-MPJPE / PVE / PA-PVE on the device
         -> h3d_amd.mesh_eval.{GroundTruth3D,pointset_errors,metric_means,evaluate_pairs,MeshEvaluator}, HeadsTrainer.val(loader, gt, gt3d, smpl_model)
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth", "arch", "model", "engine", "weights", "plan", "dcn_calibrate", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets", "heads", "train_input", "optim", "trainer", "checkpoint", "mesh_eval"]
+__all__ = ["synth", "arch", "model", "engine", "weights", "plan", "dcn_calibrate", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets", "heads", "train_input", "optim", "trainer", "checkpoint", "mesh_eval", "conv"]

@@ -136,6 +136,7 @@ RENDER_MAX_V, RENDER_MAX_SIDE = 13120, 16384        # H3D_RENDER_MAX_V / H3D_REN
 COCO_BBOX, COCO_KEYPOINTS, COCO_ROUND2 = 0, 1, 1      # H3D_COCO_BBOX / H3D_COCO_KEYPOINTS / H3D_COCO_ROUND2
 COCO_MAX_D, COCO_MAX_G, COCO_SCAN_CHUNK = 128, 1024, 1024       # H3D_COCO_MAX_D / H3D_COCO_MAX_G / H3D_COCO_SCAN_CHUNK
 MESH_EVAL_MAX_SWEEPS = 30                                       # H3D_MESH_EVAL_MAX_SWEEPS
+CONV_BWD_RELU, CONV_BWD_MFMA_CMAX = 1, 2048        # H3D_CONV_BWD_RELU / H3D_CONV_BWD_MFMA_CMAX
 ADAM_CAPACITY, ADAM_CHUNK = 48, 2048        # H3D_ADAM_CAPACITY / H3D_ADAM_CHUNK: tensors per launch, elements per workgroup
 
 
@@ -211,6 +212,10 @@ SIGNATURES = {
     # heads backward (include/h3d.h section 2b; h3d_amd/heads.py holds the mirror of `struct h3d_heads_bwd_head`)
     "h3d_heads_backward_workspace_bytes": [c_i] * 5 + [c_vp, ctypes.POINTER(ctypes.c_size_t)],
     "h3d_heads_backward": [c_vp] + [c_i] * 6 + [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
+    # convolution backward (include/h3d.h section 2c; h3d_amd/conv.py)
+    "h3d_conv2d_backward_workspace_bytes": [c_i] * 14 + [ctypes.POINTER(ctypes.c_size_t)],
+    "h3d_conv2d_backward": [c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_i] + [c_vp] * 4 + [c_i] * 14 + [c_vp, ctypes.c_size_t, c_vp],
+    "h3d_conv2d_backward_general": [c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_i] + [c_vp] * 4 + [c_i] * 14 + [c_vp, ctypes.c_size_t, c_vp],
     # training targets (include/h3d.h section 6; h3d_amd/targets.py)
     "h3d_targets_workspace_bytes": [c_i] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
     "h3d_multi_pose_targets": [c_vp] * 8 + [c_i] * 7 + [c_vp] * 13 + [c_i, c_vp, ctypes.c_size_t, c_vp],

@@ -533,6 +533,44 @@ int h3d_heads_backward(const float *feat, int in_cs, int B, int H, int W, int he
                        float *grad_feat, void *workspace, size_t workspace_bytes, void *stream);
 
 /* =====================================================================================
+ * 2c. Convolution backward (csrc/conv_bwd.hip): the gradients of H3D_OP_CONV's operator, groups = 1,
+ *         y = act(conv2d(x, W, b) + res)                 act = ReLU (H3D_CONV_BWD_RELU) or the identity
+ *    at x, res, W and b (BatchNorm stays folded into W, b: fine-tuning with frozen statistics).  With g = dL/dy:
+ *         gg = g * [y > 0] under ReLU (gradient 0 where y <= 0, torch.relu), else g;      grad_res = gg;   grad_b[o] = sum_px gg[o,px];
+ *         grad_W[o,c,t] = sum_px gg[o,px] x[c, px*s + t*d - p];     grad_x[c,q] = sum_{o,t} W[o,c,t] gg[o,(q + p - t*d)/s].
+ *    fp32 throughout, no float atomics: every output is bit-identical from run to run, whichever other outputs are requested, and is
+ *    overwritten, never accumulated into.
+ *    - x [B,H,W,C at x_cs], y and grad_y [B,Ho,Wo,Cout at y_cs / gy_cs]: fp32 NHWC with a channel stride >= the channels, a multiple
+ *      of 4, 16-byte aligned.  y is the SAVED output and is read only with H3D_CONV_BWD_RELU (may be NULL without).  grad_x [B,H,W,C]
+ *      and grad_res [B,Ho,Wo,Cout]: contiguous NHWC, 16-byte aligned.  weight / grad_weight: the reference's [Cout,C,kh,kw];
+ *      grad_bias [Cout].  Every output pointer may be NULL (all NULL: nothing is launched).
+ *    - h3d_conv2d_backward runs the matrix-core kernels (v_mfma_f32_32x32x2_f32) on 3x3 stride 1 pad 1, 3x3 stride 2 pad 1 and
+ *      1x1 stride 1 pad 0 with dilation 1, C % 16 == 0, Cout % 16 == 0 and C, Cout <= H3D_CONV_BWD_MFMA_CMAX, and the general fp32 FMA
+ *      kernels on everything else; h3d_conv2d_backward_general runs the general kernels on every configuration.
+ *    - non-positive or inconsistent sizes (kernel larger than the padded input, kernel side > 64, a channel stride below the channels or
+ *      no multiple of 4, more than 2^31 / 256 pixels or filter elements): H3D_ERR_SHAPE.  NULL x / weight / grad_y (y with
+ *      H3D_CONV_BWD_RELU), unknown flag bits, a misaligned pointer, a NULL, misaligned or short workspace ("workspace" in the message):
+ *      H3D_ERR_ARG.  Every check runs before the first HIP call.
+ *    - workspace (256-byte aligned): with N = B*Ho*Wo, S = min(256, ceil(N / 512)) pixel splits (split length ceil(N / S) rounded up to 8),
+ *      V = 4 if Cout % 4 == 0 else 1, P = 256 / min(Cout / V, 256) and Sb = ceil(N / (128 P)) chunks of the bias sums, in floats
+ *      N Cout (gg; with H3D_CONV_BWD_RELU only) + kh kw Cout ceil64(C) (the grad_x filter image; matrix-core configurations only)
+ *      + S kh kw Cout C (grad_W partials) + Sb Cout (grad_b partials), each term rounded up to 256 bytes. */
+enum {
+    H3D_CONV_BWD_RELU = 1           /* flags: act = ReLU; y is required */
+};
+#define H3D_CONV_BWD_MFMA_CMAX 2048 /* widest C / Cout of the matrix-core kernels (DLA-34's widest conv input is level5's Root: 1280) */
+int h3d_conv2d_backward_workspace_bytes(int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                                        int flags, size_t *bytes);
+int h3d_conv2d_backward(const float *x, int x_cs, const float *weight, const float *y, int y_cs, const float *grad_y, int gy_cs,
+                        float *grad_x, float *grad_res, float *grad_weight, float *grad_bias, int B, int C, int H, int W, int Cout,
+                        int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int flags, void *workspace, size_t workspace_bytes,
+                        void *stream);
+int h3d_conv2d_backward_general(const float *x, int x_cs, const float *weight, const float *y, int y_cs, const float *grad_y, int gy_cs,
+                                float *grad_x, float *grad_res, float *grad_weight, float *grad_bias, int B, int C, int H, int W, int Cout,
+                                int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int flags, void *workspace,
+                                size_t workspace_bytes, void *stream);
+
+/* =====================================================================================
  * 3. Heat-map decode (decode.py, utils.py).  All tensors contiguous NCHW fp32 as the
  *    reference's heads (model.py:485-489).  Index outputs are int64 like torch.topk's.
  *    Tie rule: equal scores -> lowest flat index first (torch leaves it unspecified).

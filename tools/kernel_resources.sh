@@ -7,6 +7,7 @@
 #   tools/kernel_resources.sh smpl_loss.hip -ffp-contract=off   (the keypoint reprojection loss: DESIGN.md section 22)
 #   tools/kernel_resources.sh render.hip -ffp-contract=off      (the mesh rasteriser: DESIGN.md section 23)
 #   tools/kernel_resources.sh mesh_eval.hip -ffp-contract=off   (the 3D evaluation: DESIGN.md section 27)
+#   tools/kernel_resources.sh conv_bwd.hip          (the convolution backward kernels: DESIGN.md section 28 holds their table)
 # (device-only compile, nothing is written; use it to check that a change did not push a variant over its VGPR cap or into scratch)
 src=$1; shift
 cd "$(dirname "$0")/../human-3d-reconstruction_amd/csrc" || exit 1
