@@ -64,8 +64,10 @@ def grads(c, dtype=torch.float64):
     return g[0], (None if res is None else g[3]), g[1], g[2]
 
 
-def make_case(seed, B, H, W, C, Cout, k=3, stride=1, padding=1, dilation=1, res=False, relu=False):
-    """Gridded (see the module docstring)."""
+def make_case(seed, B, H, W, C, Cout, k=3, stride=1, padding=1, dilation=1, res=False, relu=False, int_gy=False):
+    """Gridded (see the module docstring).  int_gy: grad_y is integers in [-8, 8] instead of random floats -- with the gridded x, w, b and
+    res every gradient is then a sum of multiples of 2^-6 (grad_x), 2^-4 (grad_weight) or 1 (grad_res, grad_bias) far below 2^24 of them:
+    exact in fp32 in any split order, so the kernels are compared with torch.equal (`INT_GY_CASES`)."""
     g = torch.Generator().manual_seed(seed)
     kh, kw = _pair(k)
     Ho, Wo = out_size(H, W, k, stride, padding, dilation)
@@ -73,7 +75,7 @@ def make_case(seed, B, H, W, C, Cout, k=3, stride=1, padding=1, dilation=1, res=
     w = torch.randint(-64, 65, (Cout, C, kh, kw), generator=g).float() / 64.0
     b = (2 * torch.randint(-1024, 1024, (Cout,), generator=g) + 1).float() / 2048.0
     r = torch.randint(-32, 33, (B, Cout, Ho, Wo), generator=g).float() / 16.0 if res else None
-    gy = torch.randn(B, Cout, Ho, Wo, generator=g)
+    gy = torch.randint(-8, 9, (B, Cout, Ho, Wo), generator=g).float() if int_gy else torch.randn(B, Cout, Ho, Wo, generator=g)
     return Case(x, w, b, r, gy, stride, padding, dilation, relu)
 
 
@@ -129,9 +131,26 @@ CASES.update(GENERAL_CASES)
 GENERAL_ON_MFMA = ("s1_2x9x33_48to80_res_relu", "s2_7x9_48to80")
 
 
+# the cases that also run with an integer grad_y, bit for bit against the float64 autograd result
+INT_GY_CASES = ("s1_2x9x33_48to80_res_relu", "s1_1x17x40_32to144_res_relu", "s2_7x9_48to80", "s2_8x10_16to32", "k1_448to64", "split_513",
+                "model_64to64", "g_stem7x7", "g_5x3")
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
     return make_case(**CASES[name])
+
+
+@functools.lru_cache(maxsize=None)
+def int_gy_case(name):
+    return make_case(int_gy=True, **CASES[name])
+
+
+@functools.lru_cache(maxsize=None)
+def int_gy_exact(name):
+    """(grad_x, grad_res or None, grad_weight, grad_bias) of `int_gy_case(name)` from float64 autograd, cast to float32 (no rounding
+    happens: tests/test_oracle_conv_backward.py asserts that float32 autograd gives the same bits).  Computed once."""
+    return tuple(None if t is None else t.float() for t in grads(int_gy_case(name), torch.float64))
 
 
 @functools.lru_cache(maxsize=None)

@@ -7,7 +7,11 @@ so the accumulation is exact in ANY order, and the only rounding left is the one
 kernel stores.  The comparison is then torch.equal(kernel, round(fp64 reference)): a dropped, duplicated or misplaced tap, a wrong halo
 pixel or a channel read from its neighbour changes most of the pixels it touches instead of hiding under a 2^-8 * max|ref| tolerance.
 
-tests/test_oracle_lattice.py pins the conditions above for every case tests/test_gpu_lattice.py runs."""
+tests/test_oracle_lattice.py pins the conditions above for every case tests/test_gpu_lattice.py runs.
+
+The DeformConv also runs on a QUARTER-PIXEL lattice (the last two sections): sampling positions on k/4 and dyadic masks keep the bilinear
+blend exact, for the fused plan kernels (`dcn_frac_operands`) and for the fp32 operator and its backward (`dcn_grid_case`,
+tests/test_gpu_dcn_lattice.py; conditions in tests/test_oracle_dcn_backward.py)."""
 import functools
 
 import numpy as np
@@ -270,3 +274,176 @@ def dcn_pre(x, w, b, wo, bo, acc_dtype=torch.float64):
     o1, o2, mask = torch.chunk(om, 3, dim=1)
     return odcn.dcn_v2_forward(x, w, b, torch.cat((o1, o2), dim=1).contiguous(), torch.sigmoid(mask).contiguous(), 3, 3, 1, 1, 1, 1, 1, 1, 1,
                                acc_dtype=acc_dtype).double()
+
+
+# ---- fused DeformConv on the quarter-pixel lattice --------------------------------------------------------------------------------
+# Sampling positions on k/4 and masks in {0, 1/2, 1}: every bilinear weight (times the mask) is a multiple of 1/32, every product with an
+# integer activation and every partial sum of the blend is exact in fp16 and in fp32 in any order, and the contraction with w in
+# {-1, 0, 1} sums multiples of 1/32 far below 2^24 / 32.  The four-corner blend, the mask folded into the weights, the partial-corner
+# samples at the image border (h_im in (-1, 0) and (H - 1, H)) and the gate exactly at -1 and H are then compared with torch.equal.
+DCN_FRAC_SCALES = (0.25, 0.5, 1.0, 2.0, 4.0)
+DCN_MASK_HALF = 0.0                                 # sigmoid(0) = 1 / (1 + 1) = 0.5 exactly, if the reciprocal of 2 is exact
+DCN_MASK_LEVELS = {"binary": (DCN_MASK_OFF, DCN_MASK_ON), "half": (DCN_MASK_OFF, DCN_MASK_HALF, DCN_MASK_ON)}
+DCN_FRAC_UNIT = 1.0 / 64.0                          # every output is a multiple of this
+DCN_MIN_FRACTIONAL = 0.25                           # share of the offset coordinates off the integers, per coordinate
+DCN_FRAC_DRAW = "8"                                 # suffix of the draw's keys: the first one under which every case meets tests/test_oracle_lattice.py's conditions
+
+
+@functools.lru_cache(maxsize=None)
+def dcn_frac_operands(B, Ci, Co, H, W, mask_levels):
+    """(x, w, b, wo, bo) of a fused DeformConv whose offsets are multiples of 1/4 that differ from pixel to pixel: x, w, bias and the
+    ReLU shift as in `dcn_operands`; offset rows of conv_offset_mask = the centre tap of one input channel times +-{1/4, 1/2, 1, 2, 4}
+    (rows 8 and 9, the centre tap's own offsets: 1/4 only), so a pixel's offset is k/4, k/2, k, 2k or 4k with k that channel's value in
+    -3..3 there -- inside the apron, in patch slots, in pass 2 and outside the image.  Mask rows: zero filters, bias per tap from
+    `mask_levels`: "binary" {+32, -128} (mask 1 or 0), "half" {+32, -128, 0} (mask 1, 0 or 1/2); the centre tap is always on.  The scales
+    and the mask levels are drawn once for all shapes (their keys hold no shape), the channels per Ci."""
+    levels = DCN_MASK_LEVELS[mask_levels]
+    x = lattice_x((B, Ci, H, W), "ldx")
+    w = lattice_w((Co, Ci, 3, 3), "ldw")
+    b = lattice_bias(Co, "ldb")
+    wo = torch.zeros(27, Ci, 3, 3)
+    bo = torch.zeros(27)
+    ch = _ints("lfc" + DCN_FRAC_DRAW, (18,), 0, Ci - 1).long()
+    sc = _ints("lfs" + DCN_FRAC_DRAW, (18,), 0, len(DCN_FRAC_SCALES) - 1).long()
+    sg = _ints("lfg" + DCN_FRAC_DRAW, (18,), 0, 1)
+    for r in range(18):
+        scale = DCN_FRAC_SCALES[0] if r in (8, 9) else DCN_FRAC_SCALES[sc[r]]
+        wo[r, ch[r], 1, 1] = float(scale) * (1.0 if sg[r] else -1.0)
+    lv = _ints("lfm" + DCN_FRAC_DRAW, (9,), 0, 3).long()            # per tap: 0 off, 1 the middle level (on, where there is none), 2 and 3 on
+    for t in range(9):
+        bo[18 + t] = levels[0] if lv[t] == 0 else levels[1] if lv[t] == 1 else levels[-1]
+    bo[18 + 4] = DCN_MASK_ON                        # (the centre tap always)
+    return x, w, b + relu_shift(dcn_pre(x, w, b, wo, bo), DCN_RELU_SHIFT_SIGMAS), wo, bo
+
+
+@functools.lru_cache(maxsize=None)
+def dcn_frac_exact(B, Ci, Co, H, W, mask_levels):
+    """(fp64-accumulated DeformConv + ReLU as fp32, conv_offset_mask output) of `dcn_frac_operands`; computed once per case."""
+    x, w, b, wo, bo = dcn_frac_operands(B, Ci, Co, H, W, mask_levels)
+    return F.relu(dcn_pre(x, w, b, wo, bo)).float(), dcn_offsets(x, wo, bo)
+
+
+def dcn_positions(offset, H, W, k=(3, 3), s=1, p=1, d=1):
+    """(h_im, w_im), each [B, dg * kh * kw, Ho, Wo] in fp64: the sampling positions of DCNv2 (offset channel 2 t is tap t's row offset,
+    2 t + 1 its column offset, group after group)."""
+    B, n2, Ho, Wo = offset.shape
+    K = k[0] * k[1]
+    o = offset.double().reshape(B, n2 // (2 * K), K, 2, Ho, Wo)
+    ti = (torch.arange(K) // k[1]).double().view(1, 1, K, 1, 1) * d
+    tj = (torch.arange(K) % k[1]).double().view(1, 1, K, 1, 1) * d
+    ys = (torch.arange(Ho).double() * s - p).view(1, 1, 1, Ho, 1)
+    xs = (torch.arange(Wo).double() * s - p).view(1, 1, 1, 1, Wo)
+    return (ys + ti + o[:, :, :, 0]).reshape(B, -1, Ho, Wo), (xs + tj + o[:, :, :, 1]).reshape(B, -1, Ho, Wo)
+
+
+DCN_CLASSES = ("h_partial_low", "h_partial_high", "h_on_gate_low", "h_on_gate_high", "w_partial_low", "w_partial_high", "w_on_gate_low",
+               "w_on_gate_high", "far")
+
+
+def dcn_sample_classes(h_im, w_im, H, W):
+    """Number of samples per border class.  partial: the coordinate in (-1, 0) / (size - 1, size), two of the four corners outside the
+    image, the other coordinate inside the gate; on_gate: the coordinate exactly -1 / size (gated off: the reference's `>` and `<`) while
+    the other coordinate is fractional and inside the gate, so that only this comparison gates the sample; far: beyond the gate."""
+    def frac(t):
+        return t != t.floor()
+    h_in, w_in = (h_im > -1) & (h_im < H), (w_im > -1) & (w_im < W)
+    n = lambda m: int(m.sum())
+    return {"h_partial_low": n((h_im > -1) & (h_im < 0) & w_in), "h_partial_high": n((h_im > H - 1) & (h_im < H) & w_in),
+            "h_on_gate_low": n((h_im == -1) & w_in & frac(w_im)), "h_on_gate_high": n((h_im == H) & w_in & frac(w_im)),
+            "w_partial_low": n((w_im > -1) & (w_im < 0) & h_in), "w_partial_high": n((w_im > W - 1) & (w_im < W) & h_in),
+            "w_on_gate_low": n((w_im == -1) & h_in & frac(h_im)), "w_on_gate_high": n((w_im == W) & h_in & frac(h_im)),
+            "far": n((h_im < -1) | (h_im > H) | (w_im < -1) | (w_im > W))}
+
+
+def dcn_fractional_share(offset, k=(3, 3)):
+    """(share of the row offsets, share of the column offsets) that are no integers."""
+    B, n2, Ho, Wo = offset.shape
+    o = offset.double().reshape(B, n2 // 2, 2, Ho, Wo)
+    return float((o[:, :, 0] != o[:, :, 0].round()).double().mean()), float((o[:, :, 1] != o[:, :, 1].round()).double().mean())
+
+
+def dcn_pre_restated(x, w, b, wo, bo, swap_tap=None, keep_tap=None, channels=None):
+    """The fused DeformConv (3 x 3, stride 1, pad 1) before ReLU, restated in fp64 with plain loops over taps and corners -- equal to
+    `dcn_pre` bit for bit on lattice operands -- with one of two defects on request, on input channels [0, channels) (None: all):
+      swap_tap   lh and lw exchanged in the four bilinear weights of that tap;
+      keep_tap   that tap's corner (h_low, w_low) is not zeroed when it lies outside the image: the clamped pixel is read instead."""
+    om = dcn_offsets(x, wo, bo).float().double()
+    B, C, H, W = x.shape
+    Co = w.shape[0]
+    flat = x.double().reshape(B, C, H * W)
+    h_all, w_all = dcn_positions(om[:, :18], H, W)
+    cols = torch.zeros(B, C, 9, H * W, dtype=torch.float64)
+
+    def blend(t, swap, keep):
+        h_im, w_im = h_all[:, t], w_all[:, t]
+        inside = ((h_im > -1) & (w_im > -1) & (h_im < H) & (w_im < W)).double()
+        hl, wl = h_im.floor(), w_im.floor()
+        lh, lw = (w_im - wl, h_im - hl) if swap else (h_im - hl, w_im - wl)
+        m = torch.sigmoid(om[:, 18 + t].float()).double() * inside
+        acc = torch.zeros(B, C, H * W, dtype=torch.float64)
+        for dy, dx, wt in ((0, 0, (1 - lh) * (1 - lw)), (0, 1, (1 - lh) * lw), (1, 0, lh * (1 - lw)), (1, 1, lh * lw)):
+            yy, xx = hl.long() + dy, wl.long() + dx
+            ok = ((yy >= 0) & (yy <= H - 1) & (xx >= 0) & (xx <= W - 1)).double()
+            if keep and (dy, dx) == (0, 0):
+                ok = torch.ones_like(ok)
+            v = torch.gather(flat, 2, (yy.clamp(0, H - 1) * W + xx.clamp(0, W - 1)).view(B, 1, -1).expand(B, C, -1))
+            acc = acc + (wt * ok * m).view(B, 1, -1) * v
+        return acc
+    for t in range(9):
+        cols[:, :, t] = blend(t, False, False)
+        if t in (swap_tap, keep_tap):
+            n = C if channels is None else channels
+            cols[:, :n, t] = blend(t, t == swap_tap, t == keep_tap)[:, :n]
+    return (torch.matmul(w.double().reshape(Co, -1), cols.reshape(B, C * 9, H * W)) + b.double().view(1, Co, 1)).view(B, Co, H, W)
+
+
+
+# ---- the DCNv2 operator and its backward on the same lattice -------------------------------------------------------------------------
+def dcn_grid_case(seed, B, C, Co, H, W, k=(3, 3), s=1, p=1, d=1, dg=1):
+    """(x, w, b, offset, mask, grad_y) for dcn_v2_forward / dcn_v2_backward: x and grad_y integers in [-3, 3], w in {-1, 0, 1}, b integers in
+    [-4, 4], offsets on k/4 (an integer in [-5, 5] plus 0, 1/4, 1/2 or 3/4), a tenth of them pushed past the gate by H + W + 8 (as
+    dcn_backward_ref.make_offsets does), masks on k/8, k = 0..8.  Every bilinear weight, its derivative and every product with the mask is
+    a multiple of 1/128: the output and all five gradients are sums of such multiples far below 2^24 / 128, exact in fp32 in any order --
+    grad_input under float atomics included."""
+    g = torch.Generator().manual_seed(seed)
+    Ho = (H + 2 * p - (d * (k[0] - 1) + 1)) // s + 1
+    Wo = (W + 2 * p - (d * (k[1] - 1) + 1)) // s + 1
+    K = dg * k[0] * k[1]
+    ri = lambda lo, hi, shape: torch.randint(lo, hi + 1, shape, generator=g).float()
+    x = ri(-3, 3, (B, C, H, W))
+    w = ri(-1, 1, (Co, C, k[0], k[1]))
+    b = ri(-4, 4, (Co,))
+    off = ri(-5, 5, (B, 2 * K, Ho, Wo)) + ri(0, 3, (B, 2 * K, Ho, Wo)) / 4.0
+    push = torch.rand(off.shape, generator=g) < 0.1
+    sign = torch.where(torch.rand(off.shape, generator=g) < 0.5, -1.0, 1.0)
+    off = torch.where(push, off + sign * float(H + W + 8), off)
+    m = ri(0, 8, (B, K, Ho, Wo)) / 8.0
+    gy = ri(-3, 3, (B, Co, Ho, Wo))
+    return x, w, b, off, m, gy
+
+
+# name -> (seed, B, C, Co, H, W, k, s, p, d, dg).  The seeds are the first ones from 1 on under which the case holds a sample of every class
+# of `dcn_sample_classes` (tests/test_oracle_dcn_backward.py asserts it).
+DCN_GRID_MFMA = {"m_2x48to7_13x11": (1, 2, 48, 7, 13, 11, (3, 3), 1, 1, 1, 1), "m_64to64_24x40": (1, 1, 64, 64, 24, 40, (3, 3), 1, 1, 1, 1),
+                 "m_512to256_16x16": (1, 1, 512, 256, 16, 16, (3, 3), 1, 1, 1, 1), "m_16to27_20x37": (1, 1, 16, 27, 20, 37, (3, 3), 1, 1, 1, 1)}
+DCN_GRID_GENERAL = {"g_s2": (1, 2, 8, 7, 13, 11, (3, 3), 2, 1, 1, 1), "g_d2_dg2": (1, 2, 8, 7, 13, 11, (3, 3), 1, 2, 2, 2),
+                    "g_dg4": (1, 2, 8, 7, 13, 11, (3, 3), 1, 1, 1, 4), "g_1x1": (5, 2, 5, 3, 9, 7, (1, 1), 1, 0, 1, 1),
+                    "g_3x1_dg3": (1, 1, 6, 67, 15, 17, (3, 1), 1, 1, 1, 3)}
+DCN_GRID_CASES = dict(DCN_GRID_MFMA, **DCN_GRID_GENERAL)
+
+
+@functools.lru_cache(maxsize=None)
+def dcn_grid(name):
+    return dcn_grid_case(*DCN_GRID_CASES[name])
+
+
+@functools.lru_cache(maxsize=None)
+def dcn_grid_exact(name):
+    """(forward, (grad_input, grad_offset, grad_mask, grad_weight, grad_bias)) of a named case from the fp64 oracle, cast to float32 (no
+    rounding happens: tests/test_oracle_dcn_backward.py asserts that the float32 oracle gives the same bits).  Computed once."""
+    import dcn_backward_ref as R
+    x, w, b, off, m, gy = dcn_grid(name)
+    k, s, p, d, dg = DCN_GRID_CASES[name][6:]
+    y = R.forward(*[t.double() for t in (x, w, b, off, m)], k, s, p, d, dg)
+    return y.float(), tuple(t.float() for t in R.oracle_grads(x, w, b, off, m, gy, k, s, p, d, dg))
+

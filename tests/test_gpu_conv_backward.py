@@ -47,6 +47,23 @@ def test_general_kernels_on_matrix_core_configurations(name):
     R.check(name + " general", gpu_grads(c, general=True), g64, e32)
 
 
+@pytest.mark.parametrize("general", [False, True], ids=["auto", "general"])
+@pytest.mark.parametrize("name", R.INT_GY_CASES)
+def test_integer_grad_y_cases_are_bit_equal_to_the_float64_yardstick(name, general):
+    """An integer grad_y on the gridded operands: every gradient is exact in fp32 in any split or summation order
+    (tests/test_oracle_conv_backward.py pins that per case), so all four outputs are compared with torch.equal -- an error confined to the
+    small elements of a tensor cannot hide under the max-norm rule.  auto: the matrix-core kernels where the configuration has them."""
+    c = R.int_gy_case(name)
+    got = gpu_grads(c, general=general)
+    for nm, g, r in zip(R.NAMES, got, R.int_gy_exact(name)):
+        if r is None:               # (no residual in the case: the yardstick has no grad_res)
+            continue
+        g = g.detach().cpu().contiguous()
+        bad = ~(g == r)
+        assert torch.equal(g, r), "%s %s: %d of %d elements differ, first at %s, max |difference| %.3g, max |ref| %.3g" % (
+            name, nm, int(bad.sum()), bad.numel(), tuple(bad.nonzero()[0].tolist()), float((g - r)[bad].abs().max()), float(r.abs().max()))
+
+
 def test_ungridded_random_case_with_a_gate_margin():
     c = R.make_random_case()
     p = c.pre().abs()

@@ -296,6 +296,25 @@ def test_dcn_fused_lattice(case):
     assert_exact(built.run(), L.lowp_round(ref, case[1]), built.name)
 
 
+def _case_id(c):
+    return "%s-%s-%#x-%dx%d-%dx%d-b%d" % (c[0], c[1], c[2], c[4], c[5], c[6], c[7], c[3])
+
+
+@pytest.mark.parametrize("mask_levels", ["binary", "half"])
+@pytest.mark.parametrize("case", dcn_lattice_cases(), ids=_case_id)
+def test_dcn_fused_frac_lattice(case, mask_levels):
+    """The same kernels on the quarter-pixel lattice (lattice_ref.dcn_frac_operands): offsets k/4 and masks 0, 1/2, 1, so the four-corner
+    blend, the mask folded into the weights, the partial corners at the border and the gate exactly at -1 and H are compared bit for bit.
+    "half" needs sigmoid(0) = rcp(2) to be exactly 0.5 on the device, as the integer lattice needs rcp(1) = 1."""
+    kind, dtype, ov, B, Ci, Co, H, W, _ = case
+    x, w, b, wo, bo = L.dcn_frac_operands(B, Ci, Co, H, W, mask_levels)
+    built = dcn_fused_op(kind, x, w, b, wo, bo, dtype, ov)
+    ref, om = L.dcn_frac_exact(B, Ci, Co, H, W, mask_levels)
+    got = built.run()
+    assert_exact(got, L.lowp_round(ref, dtype), "%s, %s masks" % (built.name, mask_levels))
+    assert torch.equal(built.run(), got), built.name
+
+
 # ---- coverage ---------------------------------------------------------------------------------------------------------------------------
 def test_lattice_cases_cover_the_plans():
     """Every conv_kernel< / conv2_kernel< / gemm1_kernel< / dcn3_kernel< instantiation of the batch 64 / 32 / 16 / 8 bf16 plans has a lattice

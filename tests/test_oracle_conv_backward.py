@@ -40,6 +40,36 @@ def test_gridded_cases_have_an_exact_nonzero_pre_activation(name):
     assert bool(((c.b * 2048).round() == c.b * 2048).all()) and bool(((c.b * 2048).abs() % 2 == 1).all())
 
 
+@pytest.mark.parametrize("name", R.INT_GY_CASES)
+def test_integer_grad_y_cases_are_exact_in_fp32(name):
+    """Gridded x, w, b, res and an integer grad_y: float32 autograd gives float64's bits, every gradient lies on its grid, and the sum of
+    the absolute values of its terms (the same autograd run on |w|, |x|, |grad_y| with the gate of the real case) stays below 2^24 units,
+    so no split or summation order can round."""
+    c = R.int_gy_case(name)
+    base = R.case(name)
+    assert all(torch.equal(a, b) for a, b in ((c.x, base.x), (c.w, base.w), (c.b, base.b))) and (c.res is None or torch.equal(c.res, base.res))
+    assert torch.equal(c.gy, c.gy.round()) and float(c.gy.min()) == -8 and float(c.gy.max()) == 8
+    g64, g32 = R.grads(c, torch.float64), R.grads(c, torch.float32)
+    gate = (c.y(torch.float64) > 0).double() if c.relu else torch.ones_like(c.gy, dtype=torch.float64)
+    gg = c.gy.double().abs() * gate
+    lin = R.Case(c.x.abs(), c.w.abs(), torch.zeros_like(c.b), None, gg.float(), c.stride, c.padding, c.dilation, False)
+    bound = R.grads(lin, torch.float64)
+    for nm, a, r, unit, bd in zip(R.NAMES, g32, g64, (64.0, 1.0, 16.0, 1.0), (bound[0], gg, bound[2], bound[3])):
+        assert (a is None) == (r is None), nm
+        if r is None:
+            continue
+        assert torch.equal(a.double(), r), nm
+        assert torch.equal(r * unit, (r * unit).round()) and float(r.abs().max()) > 0, nm
+        assert bool((bd >= r.abs()).all()) and float(bd.max()) * unit < 2.0 ** 24, (nm, float(bd.max()) * unit)
+    assert all((a is None and r is None) or torch.equal(a.double(), r) for a, r in zip(R.int_gy_exact(name), g64))
+
+
+def test_integer_grad_y_case_list():
+    assert R.INT_GY_CASES == ("s1_2x9x33_48to80_res_relu", "s1_1x17x40_32to144_res_relu", "s2_7x9_48to80", "s2_8x10_16to32", "k1_448to64",
+                              "split_513", "model_64to64", "g_stem7x7", "g_5x3")
+    assert all(n in R.CASES for n in R.INT_GY_CASES) and {"g_stem7x7", "g_5x3"} <= set(R.GENERAL_CASES)
+
+
 def test_random_case_has_a_gate_margin():
     p = R.make_random_case().pre().abs()
     assert float(p.min()) >= 1e-3 * float(p.max()) > 0

@@ -1,13 +1,17 @@
 """CPU (-m "not gpu"): the oracle of dcn_v2_backward (tests/dcn_backward_ref.py: autograd over oracle/dcn.py) pinned by gradcheck and by
-hand-derived known answers that do not depend on it; the C ABI declares and binds the new entry points."""
+hand-derived known answers that do not depend on it; the C ABI declares and binds the new entry points; and the conditions under which
+tests/test_gpu_dcn_lattice.py compares the operator and its backward with torch.equal on the quarter-pixel lattice (lattice_ref.dcn_grid_case)."""
 import os
 import re
 
+import pytest
 import torch
 import torch.nn.functional as F
 
 import dcn_backward_ref as R
+import lattice_ref as LR
 from h3d_amd import _lib
+from oracle import dcn as odcn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -94,3 +98,51 @@ def test_header_declares_and_binding_binds_dcn_v2_backward():
     assert L.h3d_dcn_v2_backward_workspace_bytes(2, 64, 16, 16, 64, 3, 3, 1, 1, 1, 1, 1, 1, 3, ctypes.byref(n)) == -1
     assert b"deformable_group" in L.h3d_last_error()
     assert L.h3d_dcn_v2_backward(*([None] * 11), 1, 16, 4, 4, 16, 3, 3, 1, 1, 1, 1, 1, 1, 1, None, 0, None) == -5
+
+
+# ---- the quarter-pixel lattice cases of tests/test_gpu_dcn_lattice.py ---------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(LR.DCN_GRID_CASES))
+def test_grid_cases_are_exact_in_fp32_and_hold_every_border_class(name):
+    seed, B, C, Co, H, W, k, s, p, d, dg = LR.DCN_GRID_CASES[name]
+    x, w, b, off, m, gy = LR.dcn_grid(name)
+    for t, lo, hi in ((x, -3, 3), (gy, -3, 3), (w, -1, 1), (b, -4, 4)):
+        assert torch.equal(t, t.round()) and lo <= float(t.min()) and float(t.max()) <= hi
+    assert torch.equal(off * 4, (off * 4).round()) and torch.equal(m * 8, (m * 8).round()) and set((m * 8).unique().tolist()) == set(range(9))
+    near = off.abs() < H + W                                                 # (the tenth that was pushed past the gate lies beyond)
+    assert 0.05 <= float((~near).float().mean()) <= 0.15 and float(off[near].abs().max()) <= 5.75
+    fh, fw = LR.dcn_fractional_share(off)
+    assert fh >= LR.DCN_MIN_FRACTIONAL and fw >= LR.DCN_MIN_FRACTIONAL, (fh, fw)
+    classes = LR.dcn_sample_classes(*LR.dcn_positions(off, H, W, k, s, p, d), H, W)
+    assert min(classes.values()) >= 1, classes
+    # forward and all five gradients: the float32 oracle gives the float64 oracle's bits, on a grid of 1/128
+    y64 = R.forward(*[t.double() for t in (x, w, b, off, m)], k, s, p, d, dg)
+    assert torch.equal(R.forward(x, w, b, off, m, k, s, p, d, dg).double(), y64) and torch.equal(y64 * 128, (y64 * 128).round())
+    g64 = R.oracle_grads(x, w, b, off, m, gy, k, s, p, d, dg, torch.float64)
+    g32 = R.oracle_grads(x, w, b, off, m, gy, k, s, p, d, dg, torch.float32)
+    for nm, a, r in zip(R.NAMES, g32, g64):
+        assert torch.equal(a.double(), r), nm
+        assert torch.equal(r * 128, (r * 128).round()) and float(r.abs().max()) > 0, nm
+    y, g = LR.dcn_grid_exact(name)
+    assert torch.equal(y.double(), y64) and all(torch.equal(a.double(), r) for a, r in zip(g, g64))
+    # partial sums in ANY order stay exact: the sum of the absolute values of a tensor's terms, in units of its grid, is below 2^24.  For
+    # the forward, grad_input, grad_mask, grad_weight and grad_bias that sum is the same oracle on |x|, |w|, |grad_y| (a blend of |x| is at
+    # least |the blend of x|).  grad_offset (grid 1/32: corner differences times lw / lh on 1/4, times the mask on 1/8) has no such
+    # substitute; its own values leave a factor of 64 below 2^24 for partial sums that exceed the final sum.
+    ax, aw, ag = x.abs(), w.abs(), gy.abs()
+    ya = odcn.dcn_v2_forward_absbound(x, w, off, m, k[0], k[1], s, s, p, p, d, d, dg) + b.abs().double().view(1, -1, 1, 1)
+    assert float(ya.max()) * 128 < 2.0 ** 24
+    ga = R.oracle_grads(ax, aw, b, off, m, ag, k, s, p, d, dg, torch.float64)
+    for i, unit in ((0, 128.0), (2, 16.0), (3, 128.0), (4, 1.0)):            # (grad_mask holds no mask factor: bilinear weights on 1/16)
+        assert torch.equal(g64[i] * unit, (g64[i] * unit).round()), R.NAMES[i]
+        assert bool((ga[i] >= g64[i].abs()).all()) and float(ga[i].max()) * unit < 2.0 ** 24, (R.NAMES[i], float(ga[i].max()) * unit)
+    assert torch.equal(g64[1] * 32, (g64[1] * 32).round()) and float(g64[1].abs().max()) * 32 * 64 < 2.0 ** 24
+
+
+def test_grid_case_list_is_what_the_gpu_file_runs():
+    assert sorted(LR.DCN_GRID_MFMA) == ["m_16to27_20x37", "m_2x48to7_13x11", "m_512to256_16x16", "m_64to64_24x40"]
+    for c in LR.DCN_GRID_MFMA.values():
+        assert c[6:] == ((3, 3), 1, 1, 1, 1) and c[2] % 16 == 0                  # the matrix-core kernels' configuration
+    assert {c[6:] for c in LR.DCN_GRID_GENERAL.values()} == {((3, 3), 2, 1, 1, 1), ((3, 3), 1, 2, 2, 2), ((3, 3), 1, 1, 1, 4), ((1, 1), 1, 0, 1, 1),
+                                                             ((3, 1), 1, 1, 1, 3)}
+    a, b = LR.dcn_grid_case(*LR.DCN_GRID_CASES["g_s2"]), LR.dcn_grid_case(*LR.DCN_GRID_CASES["g_s2"])
+    assert all(torch.equal(s, t) for s, t in zip(a, b))

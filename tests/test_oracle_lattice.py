@@ -11,6 +11,11 @@ The stems and the up-sample + add run on DYADIC operands by design (image on k/2
 weights on k/8): their outputs are rounded in every 2-byte case, so for them the grid conditions (exact fp32 sums in units of 2^-8 ...)
 are pinned instead of the integer range cap.
 
+The fused DeformConv also runs on a QUARTER-PIXEL lattice (offsets k/4, masks 0, 1/2, 1: `test_dcn_frac_*`): the same conditions, plus
+the share of fractional offsets, a census of the border classes (partial corners, a coordinate exactly on the gate, beyond the gate) and
+the 2-byte plans' fp16 blend being exact; `test_exchanged_lh_lw_*` / `test_kept_border_corner_*` measure two blend defects against the
+tolerance of tests/test_gpu_variants.py.
+
 `test_one_dropped_tap_*` records why the lattice files exist: one zeroed filter tap changes most of that filter's rounded lattice
 outputs, and stays below the existing bf16 tolerance under the suite's uniform operand recipe."""
 import numpy as np
@@ -154,6 +159,61 @@ def test_dcn_cases_have_integer_offsets_binary_masks_and_exact_sums(key):
     assert torch.equal(wf, w) and torch.equal(bf, b)
 
 
+# ---- fused DeformConv on the quarter-pixel lattice -------------------------------------------------------------------------------------------
+MASK_LEVELS = ("binary", "half")
+
+
+@pytest.mark.parametrize("mask_levels", MASK_LEVELS)
+@pytest.mark.parametrize("key", _dcn_keys(), ids=lambda k: "%dx%d-%dx%d-b%d" % (k[1], k[2], k[3], k[4], k[0]))
+def test_dcn_frac_cases_meet_the_conditions_of_a_zero_tolerance(key, mask_levels):
+    B, Ci, Co, H, W = key
+    x, w, b, wo, bo = L.dcn_frac_operands(B, Ci, Co, H, W, mask_levels)
+    x0, w0, _, _, _ = L.dcn_operands(*key)
+    assert torch.equal(x, x0) and torch.equal(w, w0) and torch.equal(b, b.round())
+    om = L.dcn_offsets(x, wo, bo)
+    off, mask = om[:, :18], torch.sigmoid(om[:, 18:].float())
+    # offsets: multiples of 1/4 that differ per pixel; every scale is there (inside the apron ... outside the image); the centre tap moves by < 1
+    assert torch.equal(off * 4, (off * 4).round()) and float(off.std(dim=(0, 2, 3)).min()) > 0.0
+    assert set(off.abs().amax(dim=(0, 2, 3)).tolist()) == {3.0 * s for s in L.DCN_FRAC_SCALES}
+    assert float(off[:, 8:10].abs().max()) == 0.75
+    fh, fw = L.dcn_fractional_share(off)
+    assert fh >= L.DCN_MIN_FRACTIONAL and fw >= L.DCN_MIN_FRACTIONAL, (fh, fw)
+    # masks: exactly the levels asked for, all of them present, the centre tap on
+    want = {0.0, 1.0} if mask_levels == "binary" else {0.0, 0.5, 1.0}
+    assert set(mask.unique().tolist()) == want and float(mask[:, 4].min()) == 1.0
+    # every border class has a sample
+    h_im, w_im = L.dcn_positions(off, H, W)
+    classes = L.dcn_sample_classes(h_im, w_im, H, W)
+    assert list(classes) == list(L.DCN_CLASSES) and min(classes.values()) >= 1, classes
+    # the fp32 contraction is the fp64 one; outputs on the 1/64 grid, below 2^24 units in any order; the 2-byte plans' fp16 blend is exact
+    pre = L.dcn_pre(x, w, b, wo, bo)
+    assert torch.equal(L.dcn_pre(x, w, b, wo, bo, acc_dtype=None), pre)
+    units = pre / L.DCN_FRAC_UNIT
+    assert torch.equal(units, units.round()) and (3.0 * 9 * Ci + float(b.abs().max())) / L.DCN_FRAC_UNIT < LIMIT
+    from oracle import dcn as odcn
+    blend16 = odcn.dcn_v2_forward(x, w, b, off.float().contiguous(), mask.contiguous(), 3, 3, 1, 1, 1, 1, 1, 1, 1, acc_dtype=torch.float64, blend="f16")
+    assert torch.equal(blend16.double(), pre)
+    for d, r in L.EXACT_RANGE.items():          # beyond r the 2-byte grid is coarser than 1: still one rounding, but it hides more
+        assert float((pre.abs() > r).double().mean()) <= L.MAX_OUTSIDE, (key, d)
+    assert L.RELU_CLIP[0] <= L.clipped_share(pre) <= L.RELU_CLIP[1], L.clipped_share(pre)
+    ref, om2 = L.dcn_frac_exact(B, Ci, Co, H, W, mask_levels)
+    assert torch.equal(ref.double(), F.relu(pre)) and torch.equal(om2, om)
+    # the rounding into the storage type is a real one: some outputs are no bf16 numbers
+    assert bool((L.lowp_round(ref, "bf16") != ref).any())
+
+
+def test_dcn_frac_draws_are_deterministic_and_shared_between_the_mask_levels():
+    a, b_ = L.dcn_frac_operands(1, 64, 64, 13, 21, "binary"), L.dcn_frac_operands(1, 64, 64, 13, 21, "half")
+    L.dcn_frac_operands.cache_clear()
+    again = L.dcn_frac_operands(1, 64, 64, 13, 21, "binary")
+    assert all(torch.equal(s, t) for s, t in zip(a, again))
+    assert torch.equal(a[3], b_[3]) and torch.equal(a[4][:18], b_[4][:18])          # the same offsets under both mask levels
+    half = b_[4][18:] == L.DCN_MASK_HALF
+    assert 2 <= int(half.sum()) and torch.equal(a[4][18:][half], torch.full((int(half.sum()),), L.DCN_MASK_ON))
+    assert torch.equal(a[4][18:][~half], b_[4][18:][~half]) and int((a[4][18:] == L.DCN_MASK_OFF).sum()) >= 1
+    assert _x3_lo_is_zero(a[3].permute(0, 2, 3, 1).reshape(27, 9, 64))               # offset filters +-1/4 ... 4: no lo half in the f16x3 split
+
+
 # ---- packed operands -----------------------------------------------------------------------------------------------------------------------
 def _x3_lo_is_zero(w):
     K = w.shape[-1]
@@ -245,3 +305,49 @@ def test_one_dropped_tap_in_the_deformconv():
     ref = F.relu(L.dcn_pre(xu, wu, bu, wou, bou))
     err = float((F.relu(L.dcn_pre(xu, _drop(wu, 0, 0), bu, wou, bou)) - ref).abs().max())
     assert 0.0 < err <= 1.2e-2 * max(1.0, float(ref.abs().max())), err
+
+
+# ---- why: two defects of the bilinear blend --------------------------------------------------------------------------------------------------
+FRAC_SMALLEST, FRAC_LONGEST = (1, 128, 128, 7, 5), (1, 512, 256, 16, 16)
+DEFECT_TAP = 0                      # the first tap: its samples reach the top and the left border
+VARIANTS_BF16_TOL = 1.2e-2          # tests/test_gpu_variants.test_dcn_fused_variant_matches_oracle, relative to max |ref|
+
+
+def _defect_figures(defect):
+    """(outputs changed on the smallest case by the one-channel defect, by the all-channel one, max error / max |ref| on the longest case for
+    the one-channel defect, for the all-channel one), all after ReLU; the counts after the rounding to bf16."""
+    assert FRAC_SMALLEST in _dcn_keys() and FRAC_LONGEST in _dcn_keys()
+    out = []
+    x, w, b, wo, bo = L.dcn_frac_operands(*FRAC_SMALLEST, "half")
+    assert torch.equal(L.dcn_pre_restated(x, w, b, wo, bo), L.dcn_pre(x, w, b, wo, bo))          # the restatement itself is exact
+    good = L.lowp_round(F.relu(L.dcn_pre(x, w, b, wo, bo)), "bf16")
+    for channels in (1, None):
+        bad = L.lowp_round(F.relu(L.dcn_pre_restated(x, w, b, wo, bo, channels=channels, **{defect: DEFECT_TAP})), "bf16")
+        out.append(int((bad != good).sum()))
+    x, w, b, wo, bo = L.dcn_frac_operands(*FRAC_LONGEST, "half")
+    ref = F.relu(L.dcn_pre(x, w, b, wo, bo))
+    for channels in (1, None):
+        bad = F.relu(L.dcn_pre_restated(x, w, b, wo, bo, channels=channels, **{defect: DEFECT_TAP}))
+        out.append(float((bad - ref).abs().max()) / float(ref.abs().max()))
+    print("%s on tap %d: changes %d (one channel) / %d (all channels) of %d outputs at %s; max error / max |ref| at %s: %.3g / %.3g"
+          % (defect, DEFECT_TAP, out[0], out[1], good.numel(), FRAC_SMALLEST, FRAC_LONGEST, out[2], out[3]))
+    return out
+
+
+def test_exchanged_lh_lw_on_one_tap_changes_the_exact_result_and_one_channel_of_it_hides_under_the_tolerance():
+    """lh and lw exchanged in one tap's bilinear weights.  In ONE input channel (one lane's element of a fragment) it changes at least 32
+    outputs of the smallest case and stays under 1.2e-2 max |ref| on the longest contraction: the tolerance test cannot see it.  In all
+    channels of the tap it moves outputs by a quarter of max |ref|: that one the tolerance test does see."""
+    one, every, rel_one, rel_every = _defect_figures("swap_tap")
+    assert one >= 32 and every >= 256, (one, every)
+    assert 0.0 < rel_one <= VARIANTS_BF16_TOL, rel_one
+    assert rel_every > VARIANTS_BF16_TOL, rel_every
+
+
+def test_kept_border_corner_on_one_tap_changes_the_exact_result_and_one_channel_of_it_hides_under_the_tolerance():
+    """A corner outside the image that is read (clamped) instead of zeroed: touches only the partial-corner samples at the top and left
+    border.  One channel: at least 32 outputs of the smallest case, under 1.2e-2 max |ref| on the longest contraction."""
+    one, every, rel_one, rel_every = _defect_figures("keep_tap")
+    assert one >= 32 and every >= 64, (one, every)
+    assert 0.0 < rel_one <= VARIANTS_BF16_TOL, rel_one
+    assert rel_every > VARIANTS_BF16_TOL, rel_every
