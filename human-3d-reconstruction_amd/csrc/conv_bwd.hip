@@ -11,9 +11,10 @@
 //                              neither grad_res nor grad_b is wanted: gg is grad_y itself) and, in the same pass, the per-channel sums
 //                              of a chunk of pixels: thread = 4 channels x one pixel phase, chains of CB_CHAIN pixels, the phases meet in
 //                              a fixed tree through LDS; h3d_split_sum_kernel adds the chunks.
-//   2. grad_x, gather form     matrix cores (3x3 s1 p1, 3x3 s2 p1, 1x1 s1 p0; C, Cout % 16 == 0): heads_bwd_gy_kernel's design for any
-//                              Cout -> C.  Workgroup = 4 x 32 input pixels (stride 2: of ONE parity class of the input pixel, which has
-//                              1, 2, 2 or 4 live taps), wave = one row, 64 channels of grad_x; 64 channels of the gg halo at a time
+//   2. grad_x, gather form     matrix cores (3x3 s1 p1, 3x3 s2 p1, 1x1 s1 p0; C, Cout % 16 == 0): csrc/grad_tile.h's tile, halo and tap
+//                              contraction (the ones of heads_bwd_gy_kernel) for any Cout -> C.  Workgroup = 4 x 32 input pixels
+//                              (stride 2: of ONE parity class of the input pixel, which has 1, 2, 2 or 4 live taps), wave = one
+//                              row, 64 channels of grad_x; 64 channels of the gg halo at a time
 //                              through LDS.  The workgroup that owns a tile writes it.   General: one thread per element, fp32 FMA.
 //   3. grad_W, split-K         K = the B*Ho*Wo pixels in splits of at least CB_SPLIT_PIXELS.  Matrix cores: workgroup = 3 waves x 3
 //                              output tiles of 64 x 32 each (3x3: the nine taps of 32 input channels; 1x1: nine tiles of 32 input
@@ -21,17 +22,15 @@
 //                              Partials to the workspace, h3d_split_sum_kernel sums them in split order.   General: thread = one
 //                              filter element of one split.
 // Summation order: tap sums are chains of at most 64 terms added afterwards; the K = pixels contractions are chains of CB_CHAIN pixels,
-// the chain sums added in pixel order, then the splits.
+// the chain sums added in pixel order, then the splits.  The C/D layout, the K = pixels step and the split plan are csrc/grad_tile.h's too.
 #include "common.h"
+#include "grad_tile.h"
 #include "split_sum.h"
 #include <algorithm>
 
 constexpr int CB_SPLIT_PIXELS = 512;             // pixels per split of the K = pixels contractions, at least (tests/conv_grad_ref.py mirrors it)
 constexpr int CB_SPLIT_MAX = 256;                // splits, at most
 constexpr int CB_CHAIN = 32;                     // pixels per fmaf chain of the K = pixels contractions
-constexpr int CB_TH = 4, CB_TW = 32;             // grad_x: pixel tile of a workgroup (4 waves, one row each)
-constexpr int CB_IH = CB_TH + 2, CB_IW = CB_TW + 2;
-constexpr int CB_PS = 64 + 4;                    // floats per halo pixel (padded: the 16-byte B-fragment reads stay conflict-free)
 constexpr int CB_GP = 64 + 8, CB_XP = 32 + 8;    // grad_W: floats per staged gg / x pixel (4 * pitch = 32 mod 64: the two lane halves use disjoint banks)
 constexpr int CB_SLOTS = 9;                      // grad_W: output tiles of a workgroup
 constexpr int CB_BIAS_CHAINS = 4;                // grad_b: chains per thread and chunk
@@ -133,19 +132,13 @@ __global__ void conv_bwd_pack_kernel(const float *__restrict__ w, float *__restr
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int n = taps * Cout * Cpad;
     if (i >= n) return;
-    const int s = i & 3;
-    int r = i >> 2;
-    const int c = r % Cpad; r /= Cpad;
-    const int half = r & 1; r >>= 1;
-    const int kg = Cout / 8;
-    const int k8 = r % kg, t = r / kg;
-    wf[i] = c < C ? w[((size_t)(k8 * 8 + half * 4 + s) * C + c) * taps + t] : 0.f;
+    wf[i] = gt_filter_image(w, i, C, Cout, Cpad, taps, false);
 }
 
 // Matrix cores.  grid = (B * tiles, Cpad / 64, parity classes); block = 256.
 __global__ __launch_bounds__(256) void conv_bwd_gx_kernel(ConvBwdArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float s_halo[CB_IH * CB_IW * CB_PS];
+    __shared__ __attribute__((aligned(16))) float s_halo[GT_IH * GT_IW * GT_PS];
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, l32 = lane & 31, half = lane >> 5;
     const int s = a.sh, k = a.kh;
     const int py = s == 2 ? (int)(blockIdx.z >> 1) : 0, px = s == 2 ? (int)(blockIdx.z & 1) : 0;
@@ -153,39 +146,24 @@ __global__ __launch_bounds__(256) void conv_bwd_gx_kernel(ConvBwdArgs a)
     const int tiles = a.tiles_x * a.tiles_y;
     const int b = blockIdx.x / tiles, t_ = blockIdx.x - b * tiles;
     const int tyi = t_ / a.tiles_x, txi = t_ - tyi * a.tiles_x;
-    const int i0 = tyi * CB_TH, j0 = txi * CB_TW;
+    const int i0 = tyi * GT_TH, j0 = txi * GT_TW;
     if (i0 >= Hc || j0 >= Wc) return;
     // the gg halo of the tile: rows hy0 .. hy0 + ih - 1, columns hx0 .. hx0 + iw - 1
     const int org = (k == 3 && s == 1) ? 1 : 0;
-    const int ih = (k == 3) ? (s == 1 ? CB_IH : CB_TH + 1) : CB_TH, iw = (k == 3) ? (s == 1 ? CB_IW : CB_TW + 1) : CB_TW;
+    const int ih = (k == 3) ? (s == 1 ? GT_IH : GT_TH + 1) : GT_TH, iw = (k == 3) ? (s == 1 ? GT_IW : GT_TW + 1) : GT_TW;
     const int hy0 = i0 - org, hx0 = j0 - org;
     const int m0 = blockIdx.y * 64;
     const int kg_total = a.Cout / 8;
     f32x16 acc[2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
+    gt_zero(acc);
     const int nch = (a.Cout + 63) / 64;
     for (int ch = 0; ch < nch; ++ch) {
         const int ng = std::min(8, kg_total - ch * 8);            // groups of 8 gg channels in this chunk
         if (ch) __syncthreads();
-        const int nv = ng * 2;
-        for (int i = tid; i < ih * iw * nv; i += 256) {
-            const int v = i % nv, pix = i / nv;
-            const int iy = pix / iw, ix = pix - iy * iw;
-            const int gy = hy0 + iy, gx = hx0 + ix;
-            f32x4 val = {0.f, 0.f, 0.f, 0.f};
-            if (gy >= 0 && gy < a.Ho && gx >= 0 && gx < a.Wo)
-                val = *reinterpret_cast<const f32x4 *>(a.gg + ((size_t)(b * a.Ho + gy) * a.Wo + gx) * a.gg_cs + ch * 64 + v * 4);
-            *reinterpret_cast<f32x4 *>(s_halo + (iy * CB_IW + ix) * CB_PS + v * 4) = val;
-        }
+        gt_stage_halo(s_halo, a.gg, a.gg_cs, ch * 64, b, a.Ho, a.Wo, hy0, hx0, ih, iw, ng * 2, tid);
         __syncthreads();
         f32x16 part[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) part[m][e] = 0.f;
+        gt_zero(part);
 #pragma unroll 1
         for (int t = 0; t < k * k; ++t) {
             const int ty = t / k, tx = t - k * ty;
@@ -197,27 +175,9 @@ __global__ __launch_bounds__(256) void conv_bwd_gx_kernel(ConvBwdArgs a)
                     dyh = (py + 1 - ty) / 2; dxh = (px + 1 - tx) / 2;
                 }
             }
-            const float *bp = s_halo + ((wv + dyh) * CB_IW + l32 + dxh) * CB_PS + half * 4;
+            const float *bp = s_halo + ((wv + dyh) * GT_IW + l32 + dxh) * GT_PS + half * 4;
             const f32x4 *ap = reinterpret_cast<const f32x4 *>(a.wf) + ((size_t)(t * kg_total + ch * 8) * 2 + half) * a.Cpad + m0 + l32;
-            f32x16 tp[2];
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) tp[m][e] = 0.f;
-#pragma unroll
-            for (int k8 = 0; k8 < 8; ++k8) {
-                if (k8 < ng) {
-                    const f32x4 a0 = ap[(size_t)k8 * 2 * a.Cpad], a1 = ap[(size_t)k8 * 2 * a.Cpad + 32];
-                    const f32x4 bv = *reinterpret_cast<const f32x4 *>(bp + k8 * 8);
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        tp[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], bv[u], tp[0], 0, 0, 0);
-                        tp[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], bv[u], tp[1], 0, 0, 0);
-                    }
-                }
-            }
-            part[0] += tp[0];
-            part[1] += tp[1];
+            gt_tap_mfma(part, ap, a.Cpad, bp, ng);
         }
 #pragma unroll
         for (int m = 0; m < 2; ++m) acc[m] = ch ? acc[m] + part[m] : part[m];
@@ -229,7 +189,7 @@ __global__ __launch_bounds__(256) void conv_bwd_gx_kernel(ConvBwdArgs a)
         for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int c = m0 + m * 32 + 8 * g + 4 * half;     // rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) of the C/D layout
+                const int c = m0 + m * 32 + gt_row4(g, half);
                 if (c < a.C) {
                     const f32x4 v = {acc[m][4 * g], acc[m][4 * g + 1], acc[m][4 * g + 2], acc[m][4 * g + 3]};
                     *reinterpret_cast<f32x4 *>(dst + c) = v;
@@ -285,18 +245,13 @@ __global__ __launch_bounds__(192) void conv_bwd_gw_kernel(ConvBwdArgs a)
     const bool k3 = a.kh == 3;
     const int o0 = blockIdx.y * 64, sp = blockIdx.z;
     const int HWo = a.Ho * a.Wo;
-    const int q_begin = sp * a.L, q_end = std::min(a.NPX, q_begin + a.L);
+    const auto [q_begin, q_end] = gt_split_range(sp, a.L, a.NPX);
     const int cbase = k3 ? blockIdx.x * 32 : blockIdx.x * 32 * CB_SLOTS;      // first input channel of slot 0
     f32x16 acc[2][3], part[2][3];
     bool live[3];
 #pragma unroll
     for (int j = 0; j < 3; ++j) live[j] = k3 || cbase + (3 * wv + j) * 32 < a.C;
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][j][e] = 0.f;
+    gt_zero(acc);
     for (int Q = q_begin; Q < q_end; Q += CB_CHAIN) {
         if (Q > q_begin) __syncthreads();
         for (int i = tid; i < CB_CHAIN * 16; i += 192) {
@@ -322,12 +277,7 @@ __global__ __launch_bounds__(192) void conv_bwd_gw_kernel(ConvBwdArgs a)
             *reinterpret_cast<f32x4 *>(s_x + (j * CB_CHAIN + p) * CB_XP + v * 4) = val;
         }
         __syncthreads();
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) part[m][j][e] = 0.f;
+        gt_zero(part);
 #pragma unroll
         for (int g = 0; g < CB_CHAIN / 8; ++g) {
             float av[2][4], bv[3][4];
@@ -339,35 +289,18 @@ __global__ __launch_bounds__(192) void conv_bwd_gw_kernel(ConvBwdArgs a)
 #pragma unroll
                 for (int j = 0; j < 3; ++j) bv[j][u] = s_x[((3 * wv + j) * CB_CHAIN + p) * CB_XP + l32];
             }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-                    if (live[j]) {
-                        part[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0][u], bv[j][u], part[0][j], 0, 0, 0);
-                        part[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1][u], bv[j][u], part[1][j], 0, 0, 0);
-                    }
+            gt_gw_step(part, av, bv, [&](int, int j) { return live[j]; });
         }
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) acc[m][j] += part[m][j];
+        gt_add(acc, part);
     }
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
         const int slot = 3 * wv + j;
         const int c = cbase + (k3 ? 0 : slot * 32) + l32;
         if (c >= a.C) continue;
+        const size_t tile = k3 ? (size_t)sp * 9 + slot : sp;          // [split][tap][Cout][C] or [split][Cout][C]
 #pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int o = o0 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-                if (o < a.Cout) {
-                    if (k3) a.p_w[(((size_t)sp * 9 + slot) * a.Cout + o) * a.C + c] = acc[m][j][e];
-                    else a.p_w[((size_t)sp * a.Cout + o) * a.C + c] = acc[m][j][e];
-                }
-            }
+        for (int m = 0; m < 2; ++m) gt_store_column<true>(a.p_w, tile * a.Cout, acc[m][j], o0 + m * 32, a.Cout, a.C, c, half);
     }
 }
 
@@ -382,7 +315,7 @@ __global__ __launch_bounds__(256) void conv_bwd_gw_general_kernel(ConvBwdArgs a)
     const int ty = t / a.kw, tx = t - ty * a.kw;
     const int sp = blockIdx.y;
     const int HWo = a.Ho * a.Wo;
-    const int q_begin = sp * a.L, q_end = std::min(a.NPX, q_begin + a.L);
+    const auto [q_begin, q_end] = gt_split_range(sp, a.L, a.NPX);
     float acc = 0.f;
     for (int q0 = q_begin; q0 < q_end; q0 += CB_CHAIN) {
         float part = 0.f;
@@ -431,9 +364,7 @@ static int cb_plan(CbPlan &pl, const char *what, int B, int C, int H, int W, int
     if (flags & ~H3D_CONV_BWD_RELU) H3D_FAIL(H3D_ERR_ARG, "%s: unknown flags %#x", what, flags);
     pl.NPX = B * pl.Ho * pl.Wo;
     pl.taps = kh * kw;
-    const int S = std::min(CB_SPLIT_MAX, cdiv(pl.NPX, CB_SPLIT_PIXELS));
-    pl.L = cdiv(cdiv(pl.NPX, S), 8) * 8;
-    pl.S = cdiv(pl.NPX, pl.L);
+    h3d_split_plan(pl.NPX, CB_SPLIT_PIXELS, CB_SPLIT_MAX, &pl.S, &pl.L);
     pl.mfma = cb_mfma_takes(C, Cout, kh, kw, sh, sw, ph, pw, dh, dw);
     pl.Cpad = cdiv(C, 64) * 64;
     pl.V = Cout % 4 ? 1 : 4;
@@ -509,8 +440,8 @@ static int cb_run(bool general, const float *x, int x_cs, const float *weight, c
         if (mfma) {
             const int n = pl.taps * Cout * pl.Cpad;
             H3D_TRY(h3d_launch({"conv_bwd_pack_kernel"}, conv_bwd_pack_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, weight, a.wf, C, Cout, pl.Cpad, pl.taps));
-            a.tiles_y = cdiv(cdiv(H, sh), CB_TH);
-            a.tiles_x = cdiv(cdiv(W, sh), CB_TW);
+            a.tiles_y = cdiv(cdiv(H, sh), GT_TH);
+            a.tiles_x = cdiv(cdiv(W, sh), GT_TW);
             const dim3 grid(B * a.tiles_x * a.tiles_y, pl.Cpad / 64, sh == 2 ? 4 : 1);
             H3D_TRY(h3d_launch({"conv_bwd_gx_kernel"}, conv_bwd_gx_kernel, grid, dim3(256), 0, st, a));
         } else {

@@ -13,12 +13,14 @@
 //
 // Two levels.  GENERAL (any kernel size / stride / pad / dilation / deformable_group / channel count): fp32 FMA, LDS-tiled.
 // MODEL CONFIGURATION (3x3 s1 p1 d1 dg1, C % 16 == 0): both contractions on v_mfma_f32_32x32x2_f32 (exact fmaf chains, the
-// arithmetic H3D_DCN_F32_MFMA selects in the forward), sampling in the same kernel.
+// arithmetic H3D_DCN_F32_MFMA selects in the forward), sampling in the same kernel.  The K = pixels contraction of grad_weight, its
+// partial stores and the C/D layout are csrc/grad_tile.h's, shared with csrc/heads_bwd.hip and csrc/conv_bwd.hip.
 //
 // Reproducibility: grad_offset, grad_mask, grad_weight and grad_bias are sums in a fixed order (bit-identical from run to run);
 // grad_input is a scatter by float atomic adds to global memory (the order of the adds, hence the last bits, varies).
 #include "common.h"
 #include "dcn_sample.h"
+#include "grad_tile.h"
 #include "split_sum.h"
 #include <algorithm>
 
@@ -316,7 +318,7 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_mfma_kernel(DcnBwdArgs a)
             if (live) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int c = ct * 32 + 8 * r + 4 * half;          // rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) of the C/D layout
+                    const int c = ct * 32 + gt_row4(r, half);
                     if (c >= a.C) continue;                            // (C % 16 == 0: a run of 4 is inside or outside as a whole)
                     f32x4 v[4];
 #pragma unroll
@@ -374,8 +376,8 @@ __global__ __launch_bounds__(256) void dcn_bwd_data_mfma_kernel(DcnBwdArgs a)
 // MODEL CONFIGURATION, grad_weight on the matrix cores: D[co][c] += G[co][pixel] col[pixel][c] per tap, K = pixels.  Workgroup = 3 waves
 // = the 3 kernel rows (3 taps each) x one tile of 32 input channels x up to 64 output channels x one split of the pixels of one image.
 // A lane IS an input channel (column of the B operand) for the two pixel slots of a step: it samples col itself from the NHWC copy of the
-// input (32 lanes = 128 contiguous bytes per corner), so nothing is staged.  A group of 8 pixels is 4 steps; slot `half` of step s holds
-// pixel P + 4 half + s for both operands.  Partials [split][tap][Cout][C] go to the workspace.
+// input (32 lanes = 128 contiguous bytes per corner), so nothing is staged: gt_gw_pixels as a single chain with the sampling as its B
+// fetch.  Partials [split][tap][Cout][C] go to the workspace.
 __global__ __launch_bounds__(192) void dcn_bwd_weight_mfma_kernel(DcnBwdArgs a)
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l32 = lane & 31, half = lane >> 5;
@@ -384,67 +386,42 @@ __global__ __launch_bounds__(192) void dcn_bwd_weight_mfma_kernel(DcnBwdArgs a)
     const int cot0 = blockIdx.y * 2, COT = (a.Cout + 31) >> 5;
     const bool two = cot0 + 1 < COT;
     const int b = blockIdx.z / SP, chunk = blockIdx.z - b * SP;
-    const int p_begin = chunk * a.L, p_end = std::min(HW, p_begin + a.L);
+    const auto [p_begin, p_end] = gt_split_range(chunk, a.L, HW);
     const bool c_ok = c < a.C;
     f32x16 acc[2][3];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][j][e] = 0.f;
     const int co_a0 = cot0 * 32 + l32, co_a1 = co_a0 + 32;
-    for (int P = p_begin; P < p_end; P += 8) {
-        float av[2][4], bv[3][4];
+    gt_gw_pixels<0>(acc, p_begin, p_end, half, two, [&](int px, bool ok, int s, float (&av)[2][4], float (&bv)[3][4]) {
+        av[0][s] = (ok && co_a0 < a.Cout) ? a.go[((size_t)b * a.Cout + co_a0) * HW + px] : 0.f;
+        av[1][s] = (ok && two && co_a1 < a.Cout) ? a.go[((size_t)b * a.Cout + co_a1) * HW + px] : 0.f;
+        const int oh = ok ? px / a.W : 0, ow = ok ? px - oh * a.W : 0;
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int px = P + 4 * half + s;
-            const bool ok = px < p_end;
-            av[0][s] = (ok && co_a0 < a.Cout) ? a.go[((size_t)b * a.Cout + co_a0) * HW + px] : 0.f;
-            av[1][s] = (ok && two && co_a1 < a.Cout) ? a.go[((size_t)b * a.Cout + co_a1) * HW + px] : 0.f;
-            const int oh = ok ? px / a.W : 0, ow = ok ? px - oh * a.W : 0;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int t = 3 * wv + j;
-                float val = 0.f;
-                if (ok) {
-                    const float d_h = a.off[((size_t)b * 18 + 2 * t) * HW + px];
-                    const float d_w = a.off[((size_t)b * 18 + 2 * t + 1) * HW + px];
-                    const float m = a.mask[((size_t)b * 9 + t) * HW + px];
-                    const Sample sm = make_sample((float)(oh - 1 + wv) + d_h, (float)(ow - 1 + j) + d_w, m, a.H, a.W);
-                    if (sm.inside && c_ok) {
-                        const float *xb = a.xn + (size_t)b * HW * a.C + c;
-                        const float v1 = sm.off[0] >= 0 ? xb[(size_t)sm.off[0] * a.C] : 0.f;
-                        const float v2 = sm.off[1] >= 0 ? xb[(size_t)sm.off[1] * a.C] : 0.f;
-                        const float v3 = sm.off[2] >= 0 ? xb[(size_t)sm.off[2] * a.C] : 0.f;
-                        const float v4 = sm.off[3] >= 0 ? xb[(size_t)sm.off[3] * a.C] : 0.f;
-                        val = (sm.w[0] * v1 + sm.w[1] * v2 + sm.w[2] * v3 + sm.w[3] * v4) * m;
-                    }
+        for (int j = 0; j < 3; ++j) {
+            const int t = 3 * wv + j;
+            float val = 0.f;
+            if (ok) {
+                const float d_h = a.off[((size_t)b * 18 + 2 * t) * HW + px];
+                const float d_w = a.off[((size_t)b * 18 + 2 * t + 1) * HW + px];
+                const float m = a.mask[((size_t)b * 9 + t) * HW + px];
+                const Sample sm = make_sample((float)(oh - 1 + wv) + d_h, (float)(ow - 1 + j) + d_w, m, a.H, a.W);
+                if (sm.inside && c_ok) {
+                    const float *xb = a.xn + (size_t)b * HW * a.C + c;
+                    const float v1 = sm.off[0] >= 0 ? xb[(size_t)sm.off[0] * a.C] : 0.f;
+                    const float v2 = sm.off[1] >= 0 ? xb[(size_t)sm.off[1] * a.C] : 0.f;
+                    const float v3 = sm.off[2] >= 0 ? xb[(size_t)sm.off[2] * a.C] : 0.f;
+                    const float v4 = sm.off[3] >= 0 ? xb[(size_t)sm.off[3] * a.C] : 0.f;
+                    val = (sm.w[0] * v1 + sm.w[1] * v2 + sm.w[2] * v3 + sm.w[3] * v4) * m;
                 }
-                bv[j][s] = val;
             }
+            bv[j][s] = val;
         }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0][s], bv[j][s], acc[0][j], 0, 0, 0);
-                if (two) acc[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1][s], bv[j][s], acc[1][j], 0, 0, 0);
-            }
-    }
+    });
     if (!c_ok) return;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
         if (m == 1 && !two) break;
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int t = 3 * wv + j;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int co = (cot0 + m) * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-                if (co < a.Cout) a.part[(((size_t)blockIdx.z * 9 + t) * a.Cout + co) * a.C + c] = acc[m][j][e];
-            }
-        }
+        for (int j = 0; j < 3; ++j)
+            gt_store_column<true>(a.part, ((size_t)blockIdx.z * 9 + 3 * wv + j) * a.Cout, acc[m][j], (cot0 + m) * 32, a.Cout, a.C, c, half);
     }
 }
 

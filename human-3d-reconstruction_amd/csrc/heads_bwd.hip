@@ -16,18 +16,18 @@
 //                              forward's tile); per slab of 64 intermediate channels: pre on the matrix cores, W2^T gz on the matrix
 //                              cores into a second accumulator set of the SAME C/D layout (lane = pixel), gate, and gh / h leave as
 //                              16-byte NHWC stores to the workspace.
-//   3. heads_bwd_gy_kernel     the same tile and the same contraction routine, 3x3 over gh with the flipped filters, head_conv -> 64,
+//   3. heads_bwd_gy_kernel     the same tile and the same contraction (heads_bwd_conv), 3x3 over gh with the flipped filters, head_conv -> 64,
 //                              64 channels of gh halo at a time through LDS.  The one workgroup that owns a pixel tile writes (first
 //                              live head) or load-add-stores (later heads) grad_feat.
 //   4. heads_bwd_w1_kernel / heads_bwd_w2_kernel / heads_bwd_bias_kernel   K = pixels: one split of the B*H*W pixels per workgroup,
 //                              partials to the workspace, then h3d_split_sum_kernel (csrc/split_sum.h) sums them in split order.
+// The tile, its halo, the tap and K = pixels contractions, the C/D layout and the split plan are csrc/grad_tile.h's, shared with
+// csrc/conv_bwd.hip and csrc/dcn_bwd.hip.
 #include "common.h"
+#include "grad_tile.h"
 #include "split_sum.h"
 #include <algorithm>
 
-constexpr int HB_TH = 4, HB_TW = 32;              // pixel tile of a workgroup (4 waves, one row each)
-constexpr int HB_IH = HB_TH + 2, HB_IW = HB_TW + 2;
-constexpr int HB_PS = 64 + 4;                     // floats per halo pixel (padded: the 16-byte B-fragment reads stay conflict-free)
 constexpr int HB_SPLIT_PIXELS = 512;              // pixels per split of the K = pixels contractions, at least
 constexpr int HB_SPLIT_MAX = 64;                  // splits, at most
 constexpr int HB_CMAX = 96;
@@ -53,25 +53,16 @@ __global__ void heads_bwd_pack_kernel(const float *__restrict__ w1, float *__res
     const int n = 576 * hc;
     if (i >= n) return;
     const int s = i & 3;
-    {
-        int r = i >> 2;
-        const int o = r % hc; r /= hc;
-        const int half = r & 1; r >>= 1;
-        const int k8 = r & 7, t = r >> 3;
-        w1p[i] = w1[((size_t)o * 64 + k8 * 8 + half * 4 + s) * 9 + t];
-    }
-    {
-        int r = i >> 2;
-        const int c = r & 63; r >>= 6;
-        const int half = r & 1; r >>= 1;
-        const int o8 = r % (hc / 8), t = r / (hc / 8);
-        w1f[i] = w1[((size_t)(o8 * 8 + half * 4 + s) * 64 + c) * 9 + (8 - t)];
-    }
+    int r = i >> 2;
+    const int o = r % hc; r /= hc;
+    const int half = r & 1; r >>= 1;
+    const int k8 = r & 7, t = r >> 3;
+    w1p[i] = w1[((size_t)o * 64 + k8 * 8 + half * 4 + s) * 9 + t];
+    w1f[i] = gt_filter_image(w1, i, 64, hc, 64, 9, true);
 }
 
 // acc[m] += sum over the 9 taps and 64 K channels of  A[m*32 + row][k, tap] . halo[pixel + tap][k]   (two 32-row tiles, 32 pixels).
-// A operand: 16-byte loads of a packed image wp[tap][k8][half][M][4] (a lane's operand of four consecutive K steps; slot `half` of step
-// s of group k8 is K channel k8*8 + half*4 + s) at rows m0 + {0, 32} + l32.  B operand: 16 bytes of the lane's halo pixel.
+// A operand: a packed image wp[tap][k8][half][M][4] at rows m0 + {0, 32} + l32 (gt_tap_mfma).  B operand: the lane's halo pixel.
 // Summation order: one fmaf chain of 64 terms per tap, the nine tap sums added in tap order -- a single chain of 576 terms carries about
 // twice the rounding error of the blocked sums a CPU convolution makes, which is what the gradients are measured against.
 __device__ __forceinline__ void heads_bwd_conv(f32x16 (&acc)[2], const float *__restrict__ wp, int M, int m0, int kg_total, int kg0,
@@ -80,52 +71,21 @@ __device__ __forceinline__ void heads_bwd_conv(f32x16 (&acc)[2], const float *__
 #pragma unroll 1
     for (int t = 0; t < 9; ++t) {
         const int dy = t / 3, dx = t - 3 * dy;
-        const float *bp = s_halo + ((row + dy) * HB_IW + l32 + dx) * HB_PS + half * 4;
+        const float *bp = s_halo + ((row + dy) * GT_IW + l32 + dx) * GT_PS + half * 4;
         const f32x4 *ap = reinterpret_cast<const f32x4 *>(wp) + ((size_t)(t * kg_total + kg0) * 2 + half) * M + m0 + l32;
-        f32x16 part[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) part[m][e] = 0.f;
-#pragma unroll
-        for (int k8 = 0; k8 < 8; ++k8) {
-            const f32x4 a0 = ap[(size_t)k8 * 2 * M], a1 = ap[(size_t)k8 * 2 * M + 32];
-            const f32x4 bv = *reinterpret_cast<const f32x4 *>(bp + k8 * 8);
-#pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                part[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[s], bv[s], part[0], 0, 0, 0);
-                part[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[s], bv[s], part[1], 0, 0, 0);
-            }
-        }
-        acc[0] += part[0];
-        acc[1] += part[1];
-    }
-}
-
-// 64 channels [c0, c0 + 64) of the halo of a pixel tile -> LDS, zero outside the image.  src is NHWC with channel stride cs.
-__device__ __forceinline__ void heads_bwd_stage_halo(float *s_halo, const float *__restrict__ src, int cs, int c0, int b, int H, int W,
-                                                     int oy0, int ox0, int tid)
-{
-    for (int i = tid; i < HB_IH * HB_IW * 16; i += 256) {
-        const int v = i & 15, pix = i >> 4;
-        const int iy = pix / HB_IW, ix = pix - iy * HB_IW;
-        const int gy = oy0 - 1 + iy, gx = ox0 - 1 + ix;
-        f32x4 val = {0.f, 0.f, 0.f, 0.f};
-        if (gy >= 0 && gy < H && gx >= 0 && gx < W)
-            val = *reinterpret_cast<const f32x4 *>(src + ((size_t)(b * H + gy) * W + gx) * cs + c0 + v * 4);
-        *reinterpret_cast<f32x4 *>(s_halo + pix * HB_PS + v * 4) = val;
+        gt_tap_mfma(acc, ap, M, bp, 8);
     }
 }
 
 __global__ __launch_bounds__(256) void heads_bwd_gh_kernel(HeadsBwdArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float s_halo[HB_IH * HB_IW * HB_PS];
+    __shared__ __attribute__((aligned(16))) float s_halo[GT_IH * GT_IW * GT_PS];
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, l32 = lane & 31, half = lane >> 5;
     const int tiles = a.tiles_x * a.tiles_y;
     const int b = blockIdx.x / tiles, t = blockIdx.x - b * tiles;
     const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
-    const int oy0 = ty * HB_TH, ox0 = tx * HB_TW;
-    heads_bwd_stage_halo(s_halo, a.feat, a.in_cs, 0, b, a.H, a.W, oy0, ox0, tid);
+    const int oy0 = ty * GT_TH, ox0 = tx * GT_TW;
+    gt_stage_halo(s_halo, a.feat, a.in_cs, 0, b, a.H, a.W, oy0 - 1, ox0 - 1, GT_IH, GT_IW, 16, tid);
     __syncthreads();
     const int oy = oy0 + wv, ox = ox0 + l32;
     const bool valid = oy < a.H && ox < a.W;
@@ -135,10 +95,8 @@ __global__ __launch_bounds__(256) void heads_bwd_gh_kernel(HeadsBwdArgs a)
     const int k2n = (a.C + 1) >> 1;
     for (int sl = 0; sl < a.hc / 64; ++sl) {
         f32x16 acc[2], acc2[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) { acc[m][e] = 0.f; acc2[m][e] = 0.f; }
+        gt_zero(acc);
+        gt_zero(acc2);
         heads_bwd_conv(acc, a.w1p, a.hc, sl * 64, 8, 0, s_halo, wv, l32, half);
         // W2^T gz: rows = o, K = the head's channels (slot `half` of step k2 is channel 2 k2 + half), columns = pixels
         const float *w2p = a.w2 + sl * 64 + l32;
@@ -155,7 +113,7 @@ __global__ __launch_bounds__(256) void heads_bwd_gh_kernel(HeadsBwdArgs a)
             for (int m = 0; m < 2; ++m)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
-                    const int o = sl * 64 + m * 32 + 8 * g + 4 * half;     // rows (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) of the C/D layout
+                    const int o = sl * 64 + m * 32 + gt_row4(g, half);
                     const f32x4 b1v = *reinterpret_cast<const f32x4 *>(a.b1 + o);
                     f32x4 gv, hv;
 #pragma unroll
@@ -174,27 +132,21 @@ __global__ __launch_bounds__(256) void heads_bwd_gh_kernel(HeadsBwdArgs a)
 
 __global__ __launch_bounds__(256) void heads_bwd_gy_kernel(HeadsBwdArgs a)
 {
-    __shared__ __attribute__((aligned(16))) float s_halo[HB_IH * HB_IW * HB_PS];
+    __shared__ __attribute__((aligned(16))) float s_halo[GT_IH * GT_IW * GT_PS];
     const int tid = threadIdx.x, wv = tid >> 6, lane = tid & 63, l32 = lane & 31, half = lane >> 5;
     const int tiles = a.tiles_x * a.tiles_y;
     const int b = blockIdx.x / tiles, t = blockIdx.x - b * tiles;
     const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
-    const int oy0 = ty * HB_TH, ox0 = tx * HB_TW;
+    const int oy0 = ty * GT_TH, ox0 = tx * GT_TW;
     // per 64-channel chunk of gh its own sum (nine tap sums, see heads_bwd_conv), the chunk sums added in chunk order
     f32x16 acc[2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
+    gt_zero(acc);
     for (int ch = 0; ch < a.hc / 64; ++ch) {
         if (ch) __syncthreads();
-        heads_bwd_stage_halo(s_halo, a.gh, a.hc, ch * 64, b, a.H, a.W, oy0, ox0, tid);
+        gt_stage_halo(s_halo, a.gh, a.hc, ch * 64, b, a.H, a.W, oy0 - 1, ox0 - 1, GT_IH, GT_IW, 16, tid);
         __syncthreads();
         f32x16 part[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) part[m][e] = 0.f;
+        gt_zero(part);
         heads_bwd_conv(part, a.w1f, 64, 0, a.hc / 8, ch * 8, s_halo, wv, l32, half);
 #pragma unroll
         for (int m = 0; m < 2; ++m) acc[m] = ch ? acc[m] + part[m] : part[m];
@@ -206,7 +158,7 @@ __global__ __launch_bounds__(256) void heads_bwd_gy_kernel(HeadsBwdArgs a)
         for (int m = 0; m < 2; ++m)
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                f32x4 *p = reinterpret_cast<f32x4 *>(dst + m * 32 + 8 * g + 4 * half);
+                f32x4 *p = reinterpret_cast<f32x4 *>(dst + m * 32 + gt_row4(g, half));
                 f32x4 v = {acc[m][4 * g], acc[m][4 * g + 1], acc[m][4 * g + 2], acc[m][4 * g + 3]};
                 if (a.gy_add) { const f32x4 old = *p; v = old + v; }
                 *p = v;
@@ -215,74 +167,33 @@ __global__ __launch_bounds__(256) void heads_bwd_gy_kernel(HeadsBwdArgs a)
 }
 
 // gW1 partials: D[o][c] += gh[px][o] y[px + tap][c] per tap, K = pixels.  Workgroup = 3 waves = the 3 kernel rows (3 taps each) x one
-// tile of 32 input channels x 64 intermediate channels x one split of the pixels.  A group of 8 pixels is 4 steps; slot `half` of step s
-// holds pixel P + 4 half + s for both operands.
+// tile of 32 input channels x 64 intermediate channels x one split of the pixels: gt_gw_pixels with both operands from global memory.
 __global__ __launch_bounds__(192) void heads_bwd_w1_kernel(HeadsBwdArgs a)
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, l32 = lane & 31, half = lane >> 5;
     const int c = blockIdx.x * 32 + l32, o0 = blockIdx.y * 64, sp = blockIdx.z;
     const int HW = a.H * a.W;
-    const int q_begin = sp * a.L, q_end = std::min(a.NPX, q_begin + a.L);
+    const auto [q_begin, q_end] = gt_split_range(sp, a.L, a.NPX);
     f32x16 acc[2][3];
+    // (summation order: chains of HB_CHAIN pixels, the chain sums added in pixel order)
+    gt_gw_pixels<HB_CHAIN>(acc, q_begin, q_end, half, true, [&](int q, bool ok, int s, float (&av)[2][4], float (&bv)[3][4]) {
+        const float *gp = a.gh + (size_t)q * a.hc + o0 + l32;
+        av[0][s] = ok ? gp[0] : 0.f;
+        av[1][s] = ok ? gp[32] : 0.f;
+        const int b = ok ? q / HW : 0, n = ok ? q - b * HW : 0;
+        const int y = n / a.W, x = n - y * a.W;
+        const int yy = y + wv - 1;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int xx = x + j - 1;
+            bv[j][s] = (ok && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) ? a.feat[((size_t)(b * a.H + yy) * a.W + xx) * a.in_cs + c] : 0.f;
+        }
+    });
 #pragma unroll
     for (int m = 0; m < 2; ++m)
 #pragma unroll
         for (int j = 0; j < 3; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[m][j][e] = 0.f;
-    // (summation order: chains of HB_CHAIN pixels, the chain sums added in pixel order)
-    f32x16 part[2][3];
-    for (int P = q_begin; P < q_end; P += 8) {
-        if ((P - q_begin) % HB_CHAIN == 0) {
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) {
-                    if (P > q_begin) acc[m][j] += part[m][j];
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) part[m][j][e] = 0.f;
-                }
-        }
-        float av[2][4], bv[3][4];
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const int q = P + 4 * half + s;
-            const bool ok = q < q_end;
-            const float *gp = a.gh + (size_t)q * a.hc + o0 + l32;
-            av[0][s] = ok ? gp[0] : 0.f;
-            av[1][s] = ok ? gp[32] : 0.f;
-            const int b = ok ? q / HW : 0, n = ok ? q - b * HW : 0;
-            const int y = n / a.W, x = n - y * a.W;
-            const int yy = y + wv - 1;
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const int xx = x + j - 1;
-                bv[j][s] = (ok && yy >= 0 && yy < a.H && xx >= 0 && xx < a.W) ? a.feat[((size_t)(b * a.H + yy) * a.W + xx) * a.in_cs + c] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                part[0][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0][s], bv[j][s], part[0][j], 0, 0, 0);
-                part[1][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1][s], bv[j][s], part[1][j], 0, 0, 0);
-            }
-    }
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) acc[m][j] += part[m][j];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int t = 3 * wv + j;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int o = o0 + m * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-                a.p_w1[(((size_t)sp * 9 + t) * a.hc + o) * 64 + c] = acc[m][j][e];
-            }
-        }
+            gt_store_column<false>(a.p_w1, ((size_t)sp * 9 + (3 * wv + j)) * a.hc, acc[m][j], o0 + m * 32, a.hc, 64, c, half);
 }
 
 // gW2 partials: D[k][o] += gz[k][px] h[px][o], K = pixels.  One wave = all (up to 96) channels k x 32 intermediate channels x one split.
@@ -291,23 +202,12 @@ __global__ __launch_bounds__(64) void heads_bwd_w2_kernel(HeadsBwdArgs a)
     const int lane = threadIdx.x, l32 = lane & 31, half = lane >> 5;
     const int o = blockIdx.x * 32 + l32, sp = blockIdx.y;
     const int HW = a.H * a.W;
-    const int q_begin = sp * a.L, q_end = std::min(a.NPX, q_begin + a.L);
+    const auto [q_begin, q_end] = gt_split_range(sp, a.L, a.NPX);
     const int mt = (a.C + 31) >> 5;
-    f32x16 acc[3];
-#pragma unroll
-    for (int m = 0; m < 3; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[m][e] = 0.f;
-    f32x16 part[3];
+    f32x16 acc[3], part[3];
+    gt_zero(acc);
     for (int P = q_begin; P < q_end; P += 8) {
-        if ((P - q_begin) % HB_CHAIN == 0) {
-#pragma unroll
-            for (int m = 0; m < 3; ++m) {
-                if (P > q_begin) acc[m] += part[m];
-#pragma unroll
-                for (int e = 0; e < 16; ++e) part[m][e] = 0.f;
-            }
-        }
+        if ((P - q_begin) % HB_CHAIN == 0) gt_chain_next(acc, part, P > q_begin);
         float av[3][4], bv[4];
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -328,15 +228,9 @@ __global__ __launch_bounds__(64) void heads_bwd_w2_kernel(HeadsBwdArgs a)
             if (mt > 2) part[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[2][s], bv[s], part[2], 0, 0, 0);
         }
     }
+    gt_add(acc, part);
 #pragma unroll
-    for (int m = 0; m < 3; ++m) acc[m] += part[m];
-#pragma unroll
-    for (int m = 0; m < 3; ++m)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int k = m * 32 + (e & 3) + 8 * (e >> 2) + 4 * half;
-            if (k < a.C) a.p_w2[((size_t)sp * a.C + k) * a.hc + o] = acc[m][e];
-        }
+    for (int m = 0; m < 3; ++m) gt_store_column<true>(a.p_w2, (size_t)sp * a.C, acc[m], m * 32, a.C, a.hc, o, half);
 }
 
 // gb1 / gb2 partials of one split: gb1 thread = intermediate channel, pixels in order (chains of HB_CHAIN); gb2 wave = channel, lanes stride over the
@@ -345,7 +239,7 @@ __global__ __launch_bounds__(256) void heads_bwd_bias_kernel(HeadsBwdArgs a, int
 {
     const int tid = threadIdx.x, sp = blockIdx.x;
     const int HW = a.H * a.W;
-    const int q_begin = sp * a.L, q_end = std::min(a.NPX, q_begin + a.L);
+    const auto [q_begin, q_end] = gt_split_range(sp, a.L, a.NPX);
     if (want_b1 && tid < a.hc) {
         float v = 0.f;
         for (int q0 = q_begin; q0 < q_end; q0 += HB_CHAIN) {
@@ -390,9 +284,7 @@ static int hb_check(const char *what, int B, int H, int W, int head_conv, int nh
 static void hb_plan(HbPlan &pl, int B, int H, int W, int hc)
 {
     pl.NPX = B * H * W;
-    int S = std::min(HB_SPLIT_MAX, cdiv(pl.NPX, HB_SPLIT_PIXELS));
-    pl.L = cdiv(cdiv(pl.NPX, S), 8) * 8;
-    pl.S = cdiv(pl.NPX, pl.L);
+    h3d_split_plan(pl.NPX, HB_SPLIT_PIXELS, HB_SPLIT_MAX, &pl.S, &pl.L);
     h3d_ws_layout ws;
     pl.w1p = ws.take((size_t)576 * hc * 4);
     pl.w1f = ws.take((size_t)576 * hc * 4);
@@ -454,7 +346,7 @@ extern "C" int h3d_heads_backward(const float *feat, int in_cs, int B, int H, in
     a.p_w1 = (float *)(ws + pl.p_w1); a.p_w2 = (float *)(ws + pl.p_w2);
     a.p_b1 = (float *)(ws + pl.p_b1); a.p_b2 = (float *)(ws + pl.p_b2);
     a.feat = feat; a.in_cs = in_cs; a.B = B; a.H = H; a.W = W; a.hc = head_conv;
-    a.tiles_x = cdiv(W, HB_TW); a.tiles_y = cdiv(H, HB_TH);
+    a.tiles_x = cdiv(W, GT_TW); a.tiles_y = cdiv(H, GT_TH);
     a.NPX = pl.NPX; a.S = pl.S; a.L = pl.L;
     a.gy = grad_feat;
     const int hc = head_conv;
