@@ -35,9 +35,13 @@ constexpr int HEADS_LISTS_MAX = 4;   // position lists of one sparse launch (h3d
 #endif
 
 #ifndef HEADS_SPARSE_NW
+// (the LDS-patch path only, heads_kernel<SPARSE> behind H3D_TUNE_HEADS_SPARSE_LDS_PATCH; in the default heads_sparse_kernel every wave computes)
 #define HEADS_SPARSE_NW 8 // waves of a sparse workgroup, two of which compute: the 24 LDS-DMA instructions of a filter stage are spread over all of them.
 #endif                    // Measured (batch 64, K = 100: 100 six-head + 1700 one-head workgroups in one launch): 4: 217.7, 8: 171.0 us
 static_assert(HEADS_SPARSE_NW == 4 || HEADS_SPARSE_NW == 8, "sparse heads: 24 wave-instructions per stage in whole numbers per wave, at most 512 threads");
+#ifndef HEADS_SPARSE_PF
+#define HEADS_SPARSE_PF 2 // heads_sparse_kernel: steps of filter fragments requested ahead of the MFMAs (HEADS_PF of the dense narrow heads)
+#endif
 
 struct HeadsArgs {
     const char *in;      // NHWC T feature map
@@ -60,6 +64,7 @@ struct HeadsArgs {
     int nlists;
     const long long *l_inds[HEADS_LISTS_MAX];   // [B*K] flat output positions y*W + x, image = entry / K
     int l_K[HEADS_LISTS_MAX], l_wg0[HEADS_LISTS_MAX], l_nh[HEADS_LISTS_MAX];
+    int l_ng[HEADS_LISTS_MAX];   // heads_sparse_kernel: workgroups (groups of positions) per head of the list, see there
     int l_head[HEADS_LISTS_MAX][HEADS_MAX];
 };
 
@@ -650,6 +655,225 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
 #endif
 }
 
+// Sparse launches, the default path: a position's 3x3 x 64-channel neighbourhood lives in the REGISTERS of its lane as the 36 B
+// fragments of the 3x3 contraction (9 taps x 4 K-groups of 16 channels; lane (r, h) holds the 16-byte half h of position r), loaded
+// once from the feature map by range-checked buffer loads: a tap outside the image, and every tap of an entry that stores nothing,
+// carries an offset outside the buffer and reads zeros, as the LDS patch of heads_kernel<SPARSE> holds zeros there.  No patch area
+// in LDS, so EVERY wave computes (32 positions each) and a filter stage that streams through the ring serves 32 * NW positions
+// instead of 64.  A workgroup is ONE work item = (list, one head of it, one group of 32 * NW positions): l_wg0[] counts items, the
+// items of a head are l_ng[list] consecutive workgroups.  The filter ring, the swizzle, the buffer-form DMA, the software-pipelined
+// A-fragment reads, gemm2 and the epilogue are heads_kernel's; the three tap-row stages of a slab are unrolled so that every
+// fragment index is a compile-time constant (a run-time index would put the fragments in scratch).  Per position the chain of every
+// accumulator is the dense kernel's -- only where the B operand comes from differs -- so the value is the dense launch's bit for bit.
+template <typename T, int NW>
+struct HeadsSparseRegCfg {
+    using D = HeadsCfg<T, 16>;
+    static_assert(sizeof(T) == 2, "sparse heads: 2-byte plans");
+    static constexpr int ES = D::ES;
+    static constexpr int NPOS = 32 * NW;              // positions per workgroup: every wave computes
+    static constexpr int RBW = D::RBW, CPR = D::CPR, SWZ_SHIFT = D::SWZ_SHIFT, TAPS = D::TAPS, TRS = D::TRS, SLOT = D::SLOT;
+    static_assert(TAPS == 3 && TRS == 3, "a stage is one tap row");
+    static constexpr int NFRAG = 9 * (HC_IN / 16);    // B fragments of a position: 144 VGPRs
+    static constexpr int LDS_W2 = D::LDS_W2, LDS_BIAS = D::LDS_BIAS;
+    static constexpr int LDS_PARK = NW * HC_MT2 * 16 * 256;    // per wave: the 32-row output tiles of a wide head (16 registers each), see the kernel
+    static constexpr int LDS = 2 * SLOT + LDS_W2 + LDS_BIAS + LDS_PARK;   // one head per workgroup: one bias pair
+    static_assert(LDS <= 160 * 1024, "LDS of a CU");
+    static constexpr unsigned OUTSIDE = 0x80000000u;  // a buffer offset beyond any map this path takes (HEADS_SPARSE_REG_MAX_BYTES)
+};
+constexpr size_t HEADS_SPARSE_REG_MAX_BYTES = (size_t)1 << 31;   // the fragment loads address the feature map by 32-bit buffer offsets
+
+template <typename T, int NW>
+__global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void heads_sparse_kernel(HeadsArgs a)   // (4 waves: one per SIMD, up to 512 registers)
+{
+    using C = HeadsSparseRegCfg<T, NW>;
+    using E = ET<T>;
+    constexpr int ES = C::ES;
+    __shared__ __attribute__((aligned(16))) char smem[C::LDS];
+    char *s_ring = smem;
+    char *s_w2 = s_ring + 2 * C::SLOT;
+    char *s_bias = s_w2 + C::LDS_W2;
+    char *s_park = s_bias + C::LDS_BIAS;
+
+    const int tid = threadIdx.x;
+    const int wv = tid >> 6, l = tid & 63, r = l & 31, h = l >> 5;
+    const int wvs = __builtin_amdgcn_readfirstlane(wv);
+    // this workgroup's list (they start on workgroup boundaries), its head and its group of positions
+    const int bid = blockIdx.x;
+    int li = 0;
+#pragma unroll
+    for (int i = 1; i < HEADS_LISTS_MAX; ++i)
+        if (i < a.nlists && bid >= a.l_wg0[i]) li = i;
+    const int lb = bid - a.l_wg0[li], ng = a.l_ng[li];
+    const int hi = lb / ng, grp = lb - hi * ng;
+    const int head = a.l_head[li][hi];
+    const int sp_K = a.l_K[li];
+    const long long *sp_inds = a.l_inds[li];
+    const int slabs = a.head_conv / HC_SLAB;
+    const int nstages = slabs * C::TRS;
+    const int sw = (r >> C::SWZ_SHIFT) & (C::CPR - 1);
+
+    const int w1_bytes = a.nheads * a.head_conv * 9 * HC_IN * ES;
+    auto issue_w1 = [&](int s) {
+        const int slab = s / C::TRS, tr = s - slab * C::TRS;
+        heads_dma_w1<T, 16, NW>(a.w1, w1_bytes, s_ring + (s & 1) * C::SLOT, wvs, l, (((head * slabs + slab) * HC_SLAB * 9 + tr * C::TAPS) * HC_IN) * ES);
+    };
+    issue_w1(0);
+    heads_issue_bias(a.b1 + head * a.head_conv, a.head_conv, a.b2[head], s_bias, wvs, l);
+
+    // this lane's position (an entry past the list or outside the map stores nothing) and its 36 fragments
+    int sp_b = 0, sp_y = 0, sp_x = 0;
+    bool sp_ok = false;
+    const int p = grp * C::NPOS + wv * 32 + r;
+    if (p < a.B * sp_K) {
+        const long long ind = sp_inds[p];
+        if (ind >= 0 && ind < (long long)a.H * a.W) { sp_ok = true; sp_b = p / sp_K; sp_y = (int)ind / a.W; sp_x = (int)ind - sp_y * a.W; }
+    }
+    u32x4 bf[C::NFRAG];
+    {
+        const size_t in_bytes = (((size_t)a.B * a.H * a.W - 1) * a.in_cs + HC_IN) * ES;      // <= HEADS_SPARSE_REG_MAX_BYTES (the launcher)
+        const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)a.in, 0, (int)in_bytes, 0x00020000);
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            const int gy = sp_y - 1 + tap / 3, gx = sp_x - 1 + tap % 3;
+            const bool inside = sp_ok && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+            const unsigned off = inside ? (unsigned)((((sp_b * a.H + gy) * a.W + gx) * a.in_cs + 8 * h) * ES) : C::OUTSIDE;
+#pragma unroll
+            for (int kk = 0; kk < HC_IN / 16; ++kk)
+                bf[tap * (HC_IN / 16) + kk] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off + kk * 16 * ES, 0, 0));
+        }
+    }
+    // The barrier waits for what writes LDS -- the LDS-DMA of stage 0 and the biases, issued BEFORE the 36 fragment loads -- and
+    // not for the fragments: hipcc emits s_waitcnt vmcnt(36) here and waits for each fragment in front of the first MFMA that
+    // reads it (vmcnt(38) ... vmcnt(27) through the first stage, whose own DMA pieces are younger still).
+    __syncthreads();
+
+    auto body = [&](auto m2_tag) {
+        constexpr int M2H = decltype(m2_tag)::value;
+        // 144 fragment registers + 32 of the slab + the filter fragments in flight leave room for ONE 32-row output tile under the 256
+        // registers of two waves per SIMD.  A wide head (M2H > 1) parks its output tiles in LDS between the slabs' second
+        // contractions, a wave-private 1 KiB per register (lane-contiguous 16-byte pieces: conflict-free), and runs gemm2 tile by
+        // tile: plain fp32 copies, and the chain of every tile is still slab -> m -> sb.  The price: gemm2<..., 1> is called M2H times
+        // per slab, so the ReLU + pack of the slab accumulators into B fragments (it does not change acc under BIASC) is redone
+        // for every tile, 2 - 3 times the vector work of a gemm2 that builds them once, plus the LDS round trip of the tile.  A
+        // gemm2 variant that takes prepared fragments would remove the repeat; not built.
+        constexpr bool PARK = M2H > 1;
+        char *park = s_park + (wv * HC_MT2 * 16 * 64 + l * 4) * 4;
+        auto park_tile = [&](int m2, const f32x16 &t) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) *reinterpret_cast<f32x4 *>(park + (m2 * 4 + q) * 1024) = f32x4{t[4 * q], t[4 * q + 1], t[4 * q + 2], t[4 * q + 3]};
+        };
+        auto parked_tile = [&](int m2, f32x16 &t) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const f32x4 v = *reinterpret_cast<const f32x4 *>(park + (m2 * 4 + q) * 1024);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) t[4 * q + i] = v[i];
+            }
+        };
+        f32x16 acc[2][1], acc2[1][1];
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc[m][0][i] = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc2[0][0][i] = 0.f;
+        int s = 0;
+        for (int slab = 0; slab < slabs; ++slab) {
+            // one tap-row stage TR (heads_kernel's pipelined stage at NT = 1 with the B operand in registers); TR == 0 starts
+            // every accumulator tile at the bias tile (C operand of the slab's first MFMA)
+            auto stage = [&](auto tr_tag) {
+                constexpr int TR = decltype(tr_tag)::value;
+                if (s + 1 < nstages) issue_w1(s + 1);          // slot (s+1)&1 was last read in stage s-1
+                if (TR == 1) heads_dma_w2<T, 16, NW>(a.w2[head], a.head_conv, s_w2, wvs, l, slab * HC_SLAB * ES);   // after the barrier that follows the previous gemm2
+                const char *slot = s_ring + (s & 1) * C::SLOT;
+                auto load_bias = [&](f32x16 &dst, int m) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const f32x4 bv = *reinterpret_cast<const f32x4 *>(s_bias + (slab * HC_SLAB + m * 32 + 8 * g + 4 * h) * 4);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) dst[4 * g + i] = bv[i];
+                    }
+                };
+                constexpr int NSTEP = C::TAPS * (HC_IN / 16);  // a step = one tap x 16 channels: 2 filter fragments feeding 2 MFMAs
+                const uint32_t ring = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)slot + r * C::RBW;
+                uint32_t fa_base[HC_IN / 16];
+#pragma unroll
+                for (int kk = 0; kk < HC_IN / 16; ++kk) fa_base[kk] = ring + (((2 * kk + h) ^ sw) << 4);
+                constexpr int PF = HEADS_SPARSE_PF, NBUF = PF + 1;
+                static_assert(PF * 2 <= 15, "lgkmcnt field");
+                u32x4 fa[NBUF][2];
+                auto fetch = [&](auto step_tag) {
+                    constexpr int STEP = decltype(step_tag)::value, BUF = STEP % NBUF;
+                    constexpr int tp = STEP / (HC_IN / 16), kk = STEP - tp * (HC_IN / 16);
+                    lds_read16_async<(tp * HC_SLAB) * C::RBW>(fa[BUF][0], fa_base[kk]);
+                    lds_read16_async<(tp * HC_SLAB + 32) * C::RBW>(fa[BUF][1], fa_base[kk]);
+                };
+                static_for<PF>([&](auto step_tag) { fetch(step_tag); });
+                static_for<NSTEP>([&](auto step_tag) {
+                    constexpr int STEP = decltype(step_tag)::value, BUF = STEP % NBUF;
+                    if constexpr (STEP + PF < NSTEP) fetch(std::integral_constant<int, STEP + PF>{});
+                    constexpr int NEWER = (STEP + PF < NSTEP ? PF : NSTEP - 1 - STEP) * 2;          // reads issued after step STEP's
+                    __builtin_amdgcn_s_waitcnt(0xc07f | (NEWER << 8));                              // lgkmcnt(NEWER)
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) {
+                        if (TR == 0 && STEP == 0) { load_bias(acc[m][0], m); }
+                        typename E::frag a_, b_;
+                        a_.v = fa[BUF][m]; b_.v = bf[TR * NSTEP + STEP];
+                        E::mma(acc[m][0], a_, b_);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                });
+                __syncthreads();   // vmcnt(0) + barrier: next stage's weights (and the 1x1 slice) have landed
+                ++s;
+            };
+            stage(std::integral_constant<int, 0>{});
+            stage(std::integral_constant<int, 1>{});
+            stage(std::integral_constant<int, 2>{});
+            if constexpr (!PARK) {
+                gemm2<T, 16, 1, 1, true>(acc, acc2, s_bias + slab * HC_SLAB * 4, s_w2, r, h, sw, a.s1);
+            } else {
+#pragma unroll
+                for (int m2 = 0; m2 < M2H; ++m2) {
+                    if (slab == 0) {
+#pragma unroll
+                        for (int i = 0; i < 16; ++i) acc2[0][0][i] = 0.f;
+                    } else {
+                        parked_tile(m2, acc2[0][0]);
+                    }
+                    gemm2<T, 16, 1, 1, true>(acc, acc2, s_bias + slab * HC_SLAB * 4, s_w2 + m2 * 32 * C::RBW, r, h, sw, a.s1);
+                    park_tile(m2, acc2[0][0]);
+                }
+            }
+        }
+        // ---- z = acc2 + b2 -> NCHW fp32 at the lane's position ------------------------------------------
+        if (sp_ok) {
+            const int C_head = a.C[head];
+            const size_t cstride = (size_t)a.H * a.W;
+            float *op = a.out[head] + (((size_t)sp_b * C_head + 4 * h) * a.H + sp_y) * a.W + sp_x;
+#pragma unroll
+            for (int m2 = 0; m2 < M2H; ++m2) {
+                if (PARK) parked_tile(m2, acc2[0][0]);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const int c = m2 * 32 + 8 * g + 4 * h;
+                    float *q = op + (size_t)(m2 * 32 + 8 * g) * cstride;
+                    const f32x4 b2v = *reinterpret_cast<const f32x4 *>(s_bias + 1024 + c * 4);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+                        if (c + i < C_head) q[i * cstride] = acc2[0][0][4 * g + i] + b2v[i];
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+    };
+    // the 1 / 2 / 3-tile body of this workgroup's head, as the MIXED dense launch picks it per head
+    const int m2h = __builtin_amdgcn_readfirstlane((a.C[head] + 31) >> 5);
+    if (m2h <= 1) body(std::integral_constant<int, 1>{});
+    else if (m2h == 2) body(std::integral_constant<int, 2>{});
+    else body(std::integral_constant<int, 3>{});
+}
+
 static_assert(HEADS_MAX == H3D_HEADS_MAX, "header/kernel mismatch");
 
 // checks of an H3D_OP_HEADS op and its kernel arguments (the dense and the sparse launch)
@@ -674,7 +898,7 @@ static int heads_args(const h3d_op &op, HeadsArgs &a)
 #endif
     a.nlists = 0;
     memset(a.l_inds, 0, sizeof a.l_inds); memset(a.l_K, 0, sizeof a.l_K); memset(a.l_wg0, 0, sizeof a.l_wg0);
-    memset(a.l_nh, 0, sizeof a.l_nh); memset(a.l_head, 0, sizeof a.l_head);
+    memset(a.l_nh, 0, sizeof a.l_nh); memset(a.l_head, 0, sizeof a.l_head); memset(a.l_ng, 0, sizeof a.l_ng);
     a.nheads = d->nheads; a.head_conv = op.Cout; a.B = op.B; a.H = op.H; a.W = op.W; a.in_cs = op.in_cs;
     for (int i = 0; i < d->nheads; ++i) {
         if (!d->head[i].w2 || !d->head[i].b2 || !d->head[i].out) H3D_FAIL(H3D_ERR_ARG, "heads: head %d null pointer", i);
@@ -724,9 +948,10 @@ int h3d_launch_heads(const h3d_op &op, hipStream_t st)
 static_assert(HEADS_LISTS_MAX == H3D_HEADS_LISTS_MAX, "header/kernel mismatch");
 
 // The heads of an H3D_OP_HEADS op at listed positions, written into the heads' dense maps there: bit for bit what the op's dense
-// launch writes at those positions.  ONE launch for all lists: a list's workgroups (32 * CW positions each) form one run of the grid
-// and loop over that list's heads only; the lists with the most heads -- the longest chain of filter stages -- come first, so that
-// the short workgroups fill the CUs behind them instead of the other way round.
+// launch writes at those positions.  ONE launch for all lists, the lists with the most heads first.  Default: heads_sparse_kernel,
+// one workgroup per (list, head, 256 positions).  H3D_TUNE_HEADS_SPARSE_LDS_PATCH (A/B, and maps beyond 2 GiB): heads_kernel<SPARSE>,
+// where a list's workgroups (32 * CW positions each) form one run of the grid and loop over that list's heads -- there the order puts
+// the longest chains of filter stages first, so that the short workgroups fill the CUs behind them instead of the other way round.
 extern "C" int h3d_heads_sparse_lists(const h3d_op *op, int nlists, const h3d_heads_list *lists, void *stream)
 {
     if (!op || !lists) H3D_FAIL(H3D_ERR_ARG, "heads_sparse: null pointer");
@@ -740,7 +965,8 @@ extern "C" int h3d_heads_sparse_lists(const h3d_op *op, int nlists, const h3d_he
     }
     if (op->dtype != H3D_BF16 && op->dtype != H3D_F16)
         H3D_FAIL(H3D_ERR_UNSUPPORTED, "heads_sparse: dtype %d (the 2-byte plans)", op->dtype);
-    if (op->reserved) H3D_FAIL(H3D_ERR_UNSUPPORTED, "heads_sparse: tuning word %#x", (unsigned)op->reserved);
+    if (op->reserved & ~(H3D_TUNE_HEADS_SPARSE_LDS_PATCH | H3D_TUNE_HEADS_SPARSE_WAVES4))
+        H3D_FAIL(H3D_ERR_UNSUPPORTED, "heads_sparse: tuning word %#x", (unsigned)op->reserved);
     HeadsArgs a;
     if (const int rc = heads_args(*op, a)) return rc;
     uint32_t seen = 0;
@@ -758,11 +984,38 @@ extern "C" int h3d_heads_sparse_lists(const h3d_op *op, int nlists, const h3d_he
         for (int j = i; j > 0 && __builtin_popcount(lists[order[j]].head_mask) > __builtin_popcount(lists[order[j - 1]].head_mask); --j)
             std::swap(order[j], order[j - 1]);
     a.tiles_x = a.tiles_y = 1;
+    a.nlists = nlists;
+    // The neighbourhoods in registers (heads_sparse_kernel) unless the tuning word asks for the LDS-patch path below or the map is
+    // beyond the 32-bit buffer offsets of the fragment loads.  One work item (workgroup) per (list, head, group of positions): no
+    // workgroup runs more than one head's filter stages.  Grid order: the lists as below, in a list the widest heads first (their
+    // second contraction and epilogue are the longest), all groups of a head in a row.
+    const size_t in_bytes = (((size_t)op->B * op->H * op->W - 1) * op->in_cs + HC_IN) * h3d_dtype_bytes(op->dtype);
+    if (!(op->reserved & H3D_TUNE_HEADS_SPARSE_LDS_PATCH) && in_bytes < HEADS_SPARSE_REG_MAX_BYTES) {
+        const bool waves8 = !(op->reserved & H3D_TUNE_HEADS_SPARSE_WAVES4);
+        const int npos = 32 * (waves8 ? 8 : 4);
+        int wgs = 0;
+        for (int i = 0; i < nlists; ++i) {
+            const h3d_heads_list &ls = lists[order[i]];
+            a.l_inds[i] = (const long long *)ls.inds; a.l_K[i] = ls.K; a.l_wg0[i] = wgs; a.l_nh[i] = 0;
+            for (int tiles = HC_MT2; tiles >= 1; --tiles)
+                for (int h = 0; h < a.nheads; ++h)
+                    if ((ls.head_mask >> h & 1) && (a.C[h] + 31) / 32 == tiles) a.l_head[i][a.l_nh[i]++] = h;
+            a.l_ng[i] = cdiv(op->B * ls.K, npos);
+            wgs += a.l_nh[i] * a.l_ng[i];
+        }
+        return h3d_by_dtype<bf16_t, f16_t>(op->dtype, "heads_sparse: dtype %d", [&](auto t) {
+            using T = typename decltype(t)::type;
+            return h3d_by_values([&](auto nw) {
+                constexpr int NW = decltype(nw)::value;
+                const h3d_kname name{"heads_sparse_kernel", t, NW};
+                return h3d_launch(name, heads_sparse_kernel<T, NW>, dim3(wgs), dim3(64 * NW), 0, (hipStream_t)stream, a);
+            }, h3d_vals<4, 8>{}, waves8 ? 8 : 4);
+        });
+    }
     return h3d_by_dtype<bf16_t, f16_t>(op->dtype, "heads_sparse: dtype %d", [&](auto t) {
         using T = typename decltype(t)::type;
         using C = HeadsSparseCfg<T>;
         int wgs = 0;
-        a.nlists = nlists;
         for (int i = 0; i < nlists; ++i) {
             const h3d_heads_list &ls = lists[order[i]];
             a.l_inds[i] = (const long long *)ls.inds; a.l_K[i] = ls.K; a.l_wg0[i] = wgs; a.l_nh[i] = 0;

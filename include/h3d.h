@@ -446,6 +446,9 @@ enum {
 /* H3D_OP_HEADS (csrc/heads.hip) */
 enum {
     H3D_TUNE_HEADS_SEPARATE_BIAS = 0x200,      /* separate bias / zeroing pass (launches of equal-width heads only)                              */
+    H3D_TUNE_HEADS_SPARSE_LDS_PATCH = 0x400,   /* h3d_heads_sparse*: the neighbourhoods as LDS patches, 64 positions per workgroup, a list's heads in
+                                                  series (default: as register fragments, one head per workgroup); the same bits either way        */
+    H3D_TUNE_HEADS_SPARSE_WAVES4 = 0x800,      /* h3d_heads_sparse*, register path: 4 waves = 128 positions per workgroup (default: 8 waves = 256)   */
     H3D_TUNE_HEADS_ABLATE_MASK = 0xff          /* 1 no weight loads after the prologue, 2 no stage barrier, 4 / 8 one wave per SIMD, 64 per-wave stamps */
 };
 /* ---- end of the flag catalogue ---- */
@@ -473,7 +476,7 @@ int h3d_run_ops_timed(const h3d_op *ops, int n, void *stream, float *ms);
  * (e.g. "conv_kernel<unsigned short, 3, 1, 2, 32, 16>"); nothing is launched. */
 int h3d_op_kernel_name(const h3d_op *op, char *buf, int buflen);
 
-/* The heads of ONE H3D_OP_HEADS op (H3D_BF16 / H3D_F16, reserved = 0) at listed positions only (csrc/heads.hip): inds = [B][K]
+/* The heads of ONE H3D_OP_HEADS op (H3D_BF16 / H3D_F16; reserved = 0 or H3D_TUNE_HEADS_SPARSE_*) at listed positions only (csrc/heads.hip): inds = [B][K]
  * flat output positions y*W + x (multi_pose_decode's top-K centres).  Every head of the op's descriptor is evaluated at each
  * listed position and written into the head's dense NCHW fp32 map there; no other element is written.  The value is bit for bit
  * what h3d_run_ops writes at that position (same operands, same order of every accumulation).  An entry outside [0, H*W) is
@@ -483,12 +486,15 @@ int h3d_heads_sparse(const h3d_op *op, const int64_t *inds, int K, void *stream)
 /* The same in ONE launch over several position lists, each with its own heads: list i evaluates the heads whose descriptor slot is
  * set in head_mask at inds [B][K] (h3d_heads_sparse is the one-list, all-heads case).  multi_pose_decode reads `hp_offset` at the
  * 17 x K key-point peaks and every other gathered head at the K centres: two lists, one launch in the serial tail of the step.
- * A workgroup takes its positions from one list and runs that list's heads only; the lists with the most heads are scheduled
- * first.  A position may appear in several lists and more than once in a list (the same bits are stored again); an entry outside
- * [0, H*W) stores nothing.  A head that no list names is not computed.
+ * A workgroup takes its positions from one list and runs ONE head of that list (with H3D_TUNE_HEADS_SPARSE_LDS_PATCH: all of them
+ * in series); the lists with the most heads are scheduled first, in a list the widest heads.  A position may appear in several
+ * lists and more than once in a list (the same bits are stored again); an entry outside [0, H*W) stores nothing.  A head that no
+ * list names is not computed.  A feature map of 2 GiB or more (((B*H*W - 1) * in_cs + 64) elements) takes the
+ * H3D_TUNE_HEADS_SPARSE_LDS_PATCH kernel whatever op.reserved says: the default kernel addresses the map by 32-bit buffer offsets.
+ * The values are the same on either path.
  *    H3D_ERR_ARG: nlists outside 1..H3D_HEADS_LISTS_MAX, a NULL list, an empty mask, a mask bit at or beyond the descriptor's
  *    nheads, a head named by two lists.  Per list, as h3d_heads_sparse: K <= 0 or B*K > 2^24 is H3D_ERR_SHAPE; a dtype other than
- *    H3D_BF16 / H3D_F16 or a tuning word in op.reserved is H3D_ERR_UNSUPPORTED. */
+ *    H3D_BF16 / H3D_F16 or a bit of op.reserved other than H3D_TUNE_HEADS_SPARSE_LDS_PATCH / _WAVES4 is H3D_ERR_UNSUPPORTED. */
 #define H3D_HEADS_LISTS_MAX 4
 typedef struct h3d_heads_list {
     const int64_t *inds;    /* device, [B][K] */
