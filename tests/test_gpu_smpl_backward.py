@@ -3,7 +3,13 @@
 The rule of every comparison (tests/smpl_grad_ref.py, which takes it from smpl_ref.check; per case, per gradient tensor): e32 = max |float32
 autograd of the torch restatement - its float64 autograd| on the same inputs, and max |gpu - f64| <= 4 * e32 + 2^-23 * max |f64|.  Bodies are
 `jointed_model`s, poses `special_thetas` (the 12 pose edges wherever P >= 12), upstream gradients N(0,1) fp32.  The observed ratios are
-printed (`pytest -s`) and the largest per tensor recorded in DESIGN.md."""
+printed (`pytest -s`) and the largest per tensor recorded in DESIGN.md.
+
+The same rule person by person (G.check_per_person: e32[p] over person p's row, floored at the median over the persons) runs beside it
+wherever a test names it: one near-singular pose sets the whole tensor's e32 several hundred times above an ordinary person's, and the
+whole-tensor rule then checks the ordinary persons' grad_thetas to 1e-4 relative only.  The cases from V = 256 up give the kernels more
+than one partial of everything: tile groups of the vertex kernel, contraction splits of the coefficient kernel, the pose kernel's loops
+over both (counts: G.groups / G.splits, pinned to the sources in tests/test_oracle_smpl_backward.py)."""
 import numpy as np
 import pytest
 import torch
@@ -38,13 +44,25 @@ class Case:
         self.name = "V%d P%d" % (V, P)
         self._ref = {}
 
-    def ref(self, use_v, use_j):
+    def ref_pp(self, use_v, use_j):
+        """(target, e32 per person) of G.bounds_per_person, computed once."""
         if (use_v, use_j) not in self._ref:
-            self._ref[(use_v, use_j)] = G.bounds(self.betas, self.thetas, self.m.numpy_dict(), self.gv if use_v else None, self.gj if use_j else None)
+            self._ref[(use_v, use_j)] = G.bounds_per_person(self.betas, self.thetas, self.m.numpy_dict(), self.gv if use_v else None,
+                                                            self.gj if use_j else None)
         return self._ref[(use_v, use_j)]
+
+    def ref(self, use_v, use_j):
+        """(target, e32) of G.bounds: the whole tensor's e32 is the largest person's."""
+        target, e32 = self.ref_pp(use_v, use_j)
+        return target, [float(e.max()) for e in e32]
 
     def run(self, use_v=True, use_j=True):
         return smpl.lbs_backward(self.m, self.bt, self.tt, self.gvt if use_v else None, self.gjt if use_j else None)
+
+    def check_both(self, what, got, use_v=True, use_j=True):
+        """Both rules against this case's references; -> (whole-tensor ratios err / e32, per-person ratios err / limit)."""
+        return (G.check("%s %s" % (self.name, what), got, *self.ref(use_v, use_j)),
+                G.check_per_person("%s %s" % (self.name, what), got, *self.ref_pp(use_v, use_j)))
 
 
 def case(V, P, seed=1):
@@ -62,6 +80,7 @@ def test_parity_by_the_rule(V, P):
     assert all(bool(torch.isfinite(g).all()) for g in got)
     c_ref, e32 = c.ref(True, True)
     G.check(c.name + " both", got, c_ref, e32)
+    G.check_per_person(c.name + " both", got, *c.ref_pp(True, True))
 
 
 def test_the_three_upstream_combinations():
@@ -69,9 +88,83 @@ def test_the_three_upstream_combinations():
     only_v, only_j, both = c.run(True, False), c.run(False, True), c.run(True, True)
     G.check(c.name + " grad_verts only", only_v, *c.ref(True, False))
     G.check(c.name + " grad_joints only", only_j, *c.ref(False, True))
+    G.check_per_person(c.name + " grad_verts only", only_v, *c.ref_pp(True, False))
+    G.check_per_person(c.name + " grad_joints only", only_j, *c.ref_pp(False, True))
     _, e32 = c.ref(True, True)
     summed = [(a.double() + b.double()).cpu().numpy() for a, b in zip(only_v, only_j)]
     G.check(c.name + " both against the sum of the singles", both, summed, e32)
+    G.check_per_person(c.name + " both against the sum of the singles", both, summed, c.ref_pp(True, True)[1])
+
+
+# ---- several partials of everything: NG tile groups, NS contraction splits (G.groups / G.splits; the table is pinned in
+# tests/test_oracle_smpl_backward.py).  V = 256: one full group; 257: a second group of one tile holding one real vertex; 512: 3 Vpad = exactly
+# one split; 513: a last group of one tile and a last split of 192 elements; 1024: both exact; 6890: the real mesh, 27 groups and 14 splits
+# with a last split of 768.  P = 3 everywhere; (257, 257): two person blocks of the vertex kernel x two groups; (513, 130): two workgroups
+# of the coefficient kernel x two splits, the last wave holding 2 persons; (6890, 13): every pose edge.
+PARTIAL_CASES = [(V, 3) for V in (256, 257, 512, 513, 1024, 6890)] + [(257, 257), (513, 130), (6890, 13)]
+
+
+@pytest.mark.parametrize("V,P", PARTIAL_CASES)
+def test_vertex_counts_with_several_groups_and_splits(V, P):
+    c = case(V, P)
+    print("%s: Vpad %d, %d tile groups, %d splits" % (c.name, G.vpad(V), G.groups(V), G.splits(V)))
+    got = c.run()
+    assert all(bool(torch.isfinite(g).all()) for g in got)
+    c.check_both("both", got)
+    again = c.run()
+    assert torch.equal(got[0], again[0]) and torch.equal(got[1], again[1])
+
+
+class GroupCase(Case):
+    """Case(V, 3) whose grad_verts is non-zero only on the real vertices of tile group `g`, without a grad_joints: every other group's
+    partial slot holds zeros, so a contribution that lands in, or is read from, another slot is lost or doubled."""
+
+    def __init__(self, V, g, seed=1):
+        Case.__init__(self, V, 3, seed)
+        lo, hi = g * G.GROUP_TILES * G.TILE, min((g + 1) * G.GROUP_TILES * G.TILE, V)
+        assert 0 <= lo < hi
+        self.gv[:, :lo] = 0.0
+        self.gv[:, hi:] = 0.0
+        self.gvt = torch.from_numpy(self.gv).to(DEV)
+        self.name = "V%d P3 group %d [%d,%d)" % (V, g, lo, hi)
+
+
+def group_case(V, g):
+    if (V, "group", g) not in _CASES:
+        _CASES[(V, "group", g)] = GroupCase(V, g)
+    return _CASES[(V, "group", g)]
+
+
+@pytest.mark.parametrize("V,gs", [(513, (0, 1, 2)), (6890, (0, 13, 26))])
+def test_each_tile_group_alone(V, gs):
+    assert max(gs) == G.groups(V) - 1
+    got = {}
+    for g in gs:
+        c = group_case(V, g)
+        got[g] = c.run(True, False)
+        target, _ = c.ref(True, False)
+        print("%s: max |f64| grad_betas %.3g grad_thetas %.3g" % (c.name, np.abs(target[0]).max(), np.abs(target[1]).max()))
+        assert np.abs(target[0]).max() > 0.01 and np.abs(target[1]).max() > 0.1            # a single group's gradient is not nothing
+        c.check_both("grad_verts only", got[g], True, False)
+    if len(gs) == G.groups(V):
+        # the three groups cover the mesh and the upstream is the full case's, cut up: the gradients add up (fp64 sum of the device's
+        # three results) to the full upstream's, within the full upstream's own limits
+        full = case(V, 3)
+        assert np.array_equal(sum(group_case(V, g).gv for g in gs), full.gv)
+        summed = [sum(got[g][i].double().cpu().numpy() for g in gs) for i in range(2)]
+        full.check_both("the sum of the single groups against the full upstream", summed, True, False)
+
+
+def test_a_dirty_workspace_changes_nothing():
+    """The partial slots, g_vp and the forward intermediates live in a workspace the allocator hands back unchanged: a call at another
+    mesh size and person count in between leaves its values where the next call's slots are."""
+    small, large = case(513, 130), case(6890, 13)
+    first = small.run()
+    mid = large.run()
+    third = small.run()
+    assert torch.equal(first[0], third[0]) and torch.equal(first[1], third[1])
+    small.check_both("after a larger call", third)
+    large.check_both("between two smaller calls", mid)
 
 
 def test_closed_form_rest_pose_vertex_gradient():
@@ -147,7 +240,18 @@ def test_no_graph_without_requires_grad_or_under_no_grad():
 
 
 def test_lbs_from_heads_delivers_the_gradients_at_the_maps():
-    m, B, K, n, H, W, V = body(100), 2, 5, 3, 8, 8, 100
+    heads_maps_scheme(100, per_person=False)
+
+
+def test_heads_entry_with_several_partials():
+    """The heads entry point (h3d_smpl_heads_backward shares sb_run) at V = 577: 3 tile groups, the last of two tiles, and 2 splits, the last of
+    192 elements.  The per-person rule runs over the gathered pixels: a row is one pixel's 10 / 72 map values."""
+    assert (G.groups(577), G.splits(577)) == (3, 2)
+    heads_maps_scheme(577, per_person=True)
+
+
+def heads_maps_scheme(V, per_person):
+    m, B, K, n, H, W = body(V), 2, 5, 3, 8, 8
     rs = np.random.RandomState(11)
     pose = (rs.randn(B, 72, H, W) * 0.5).astype(np.float32)
     shape = rs.randn(B, 10, H, W).astype(np.float32)
@@ -183,7 +287,13 @@ def test_lbs_from_heads_delivers_the_gradients_at_the_maps():
         return ws, wp
     want, m32 = maps(torch.float64), maps(torch.float32)
     e32 = [float(np.abs(a - r).max()) for a, r in zip(m32, want)]          # the rule's e32, of the map tensors themselves
-    G.check("heads maps", (gs, gp), want, e32)
+    G.check("V%d heads maps" % V, (gs, gp), want, e32)
+    if per_person:                                     # the rule row by row, a row = one gathered pixel (the shared one holds two persons' sum)
+        at = sorted({(b, int(q)) for b in range(B) for q in pix[b]})
+        rows = lambda t: np.stack([t[b, :, q] for b, q in at])
+        e32_rows = [np.abs(rows(a) - rows(r)).max(1) for a, r in zip(m32, want)]
+        assert len(at) == P - 1
+        G.check_per_person("V%d heads maps" % V, [rows(gs), rows(gp)], [rows(w) for w in want], e32_rows)
     # the same against the device's own lbs_backward of the gathered parameters
     db, dt = smpl.lbs_backward(m, torch.from_numpy(betas).to(DEV), torch.from_numpy(thetas).to(DEV), torch.from_numpy(gv).to(DEV),
                                torch.from_numpy(gj).to(DEV))

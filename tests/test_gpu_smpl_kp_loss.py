@@ -154,6 +154,47 @@ def test_shared_vertex_zero_row_and_padding_entry_with_sentinels_on_both_sides()
     assert float(got[1][:, 16].abs().max()) == 0.0                # the all-zero row's keypoint
 
 
+# kp_bwd_fill_kernel: at most KP_FILL_MAX_BLOCKS = 2048 workgroups of KP_THREADS = 256 threads, each storing four floats per trip of the
+# grid-stride loop (both pinned in tests/test_oracle_smpl_backward.py): the loop takes a second trip past 2048 * 256 * 4 floats
+FILL_FLOATS_PER_TRIP = 2048 * 256 * 4
+BIG_V = 6890
+
+
+@pytest.mark.parametrize("n", [50, 51])
+def test_grad_verts_fill_past_the_grid_cap(n):
+    """The real mesh: P = 100 stays below the capped grid's reach (2 068 536 floats of grad_cam_map + grad_verts), P = 102 is past it
+    (2 109 876), so the zero fill of grad_verts wraps.  Into sentinel-filled buffers, 16-byte aligned and 4 bytes off."""
+    B, NV = 2, 5
+    P, floats = B * n, B * 3 * 256 + B * n * BIG_V * 3
+    assert (floats > FILL_FLOATS_PER_TRIP) == (n == 51) and floats == {50: 2068536, 51: 2109876}[n]
+    assert (P * BIG_V * 3 // 4 > FILL_FLOATS_PER_TRIP // 4) == (n == 51)          # grad_verts' own vector count against the thread count
+    if BIG_V not in _REG:
+        _REG[BIG_V] = smpl_loss.KeypointRegressor.synthetic(K, BIG_V, NV, seed=0)
+    r = _REG[BIG_V]
+    key = ("big", n)
+    if key not in _CASES:
+        _CASES[key] = KR.Case(r, B, n, n, 16, 16, seed=900 + n)
+    c = _CASES[key]
+    touched = np.zeros(BIG_V, bool)
+    touched[r.inv_vertex] = True
+    assert 0 < touched.sum() <= K * NV
+    sizes = {"gj": (P, 24, 3), "gv": (P, BIG_V, 3), "gc": tuple(c.cam.shape)}
+    for pad, misalign in ((4, 0), (5, 4)):                         # floats in front of the view: on a 16-byte boundary, 4 bytes past one
+        bufs = {k: torch.full((int(np.prod(s)) + 2 * pad,), SENT, device=DEV) for k, s in sizes.items()}
+        views = {k: bufs[k][pad:pad + int(np.prod(s))].view(s) for k, s in sizes.items()}
+        assert all(v.data_ptr() % 16 == misalign and v.is_contiguous() for v in views.values())
+        got = dev_run(c, bwd_out=(views["gj"], views["gv"], views["gc"]))
+        assert got[4].data_ptr() == views["gv"].data_ptr()
+        check_against_refs("fill n%d +%dB" % (n, misalign), c, got)
+        for k, s in sizes.items():
+            size = int(np.prod(s))
+            assert bool((bufs[k][:pad] == SENT).all()) and bool((bufs[k][pad + size:] == SENT).all()), (k, misalign)
+            assert not bool((views[k] == SENT).any()), (k, misalign)
+        gv = got[4]
+        assert float(gv[:, torch.from_numpy(~touched).to(DEV)].abs().max()) == 0.0, misalign
+        assert float(gv[:, torch.from_numpy(touched).to(DEV)].abs().max()) > 0.0
+
+
 def test_all_zero_mask_gives_exactly_zero():
     c = case("NV5", mask="none")
     got = dev_run(c)

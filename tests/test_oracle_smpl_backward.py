@@ -6,8 +6,10 @@ Bounds (fixed, derived from fp64): restatement against smpl_ref.lbs 1e-12 relati
 differences with h = 1e-6: truncation h^2 f''' ~ 1e-12 and rounding 1.1e-16 |f| / h ~ 1e-8 of the gradient's scale, bound 1e-6 of the
 gradient's largest entry; closed forms 1e-12 relative."""
 import ctypes
+import os
 
 import numpy as np
+import pytest
 import torch
 
 import smpl_grad_ref as G
@@ -82,6 +84,94 @@ def test_closed_form_root_joint_gradient():
     jsd = np.einsum("v,vck->ck", MODEL["J_regressor"][0].astype(np.float64), MODEL["shapedirs"].astype(np.float64))
     assert _rel(gb.numpy(), gj[:, 0] @ jsd) <= 1e-12
     assert float(gt.abs().max()) == 0.0
+
+
+# ---- the kernels' partials: the mirrored constants, the shape table, and what the per-person rule sees that the whole-tensor rule does not
+CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "human-3d-reconstruction_amd", "csrc")
+
+
+def _source(name):
+    with open(os.path.join(CSRC, name)) as f:
+        return f.read()
+
+
+def test_the_mirrored_constants_are_the_kernels():
+    bwd, tile, loss = _source("smpl_bwd.hip"), _source("smpl_tile.h"), _source("smpl_loss.hip")
+    assert "SB_NVT = %d" % G.GROUP_TILES in bwd and "SB_KC = %d" % G.SPLIT_K in bwd and "S3_VT = %d" % G.TILE in tile
+    assert (G.GROUP_TILES, G.SPLIT_K, G.TILE) == (4, 1536, 64)
+    # the zero fill of the keypoint loss's backward (tests/test_gpu_smpl_kp_loss.py derives its wrap point from these two)
+    assert "KP_FILL_MAX_BLOCKS = 2048" in loss and "KP_THREADS = 256" in loss
+
+
+# V -> (Vpad, NG, NS, elements of the last split): the cases of test_vertex_counts_with_several_groups_and_splits
+SHAPE_TABLE = {256: (256, 1, 1, 768), 257: (320, 2, 1, 960), 512: (512, 2, 1, 1536), 513: (576, 3, 2, 192), 1024: (1024, 4, 2, 1536),
+               6890: (6912, 27, 14, 768)}
+
+
+def test_the_shape_table_of_groups_and_splits():
+    for V, (Vpad, NG, NS, last) in SHAPE_TABLE.items():
+        assert (G.vpad(V), G.groups(V), G.splits(V)) == (Vpad, NG, NS), V
+        assert 3 * Vpad - (NS - 1) * G.SPLIT_K == last, V
+        tiles = Vpad // G.TILE
+        assert (NG - 1) * G.GROUP_TILES < tiles <= NG * G.GROUP_TILES and V > Vpad - G.TILE
+    assert G.vpad(257) // G.TILE - G.GROUP_TILES == 1 and 257 - G.GROUP_TILES * G.TILE == 1      # a second group of one tile, one real vertex
+    assert G.vpad(513) // G.TILE - 2 * G.GROUP_TILES == 1                                        # 513: the last group is one tile
+    # the library's workspace at the real mesh holds exactly these counts of partials
+    L, n = _lib.lib(), ctypes.c_size_t(0)
+    a256 = lambda x: (x + 255) // 256 * 256
+    for V, (Vpad, NG, NS, _) in SHAPE_TABLE.items():
+        P, Ppad = 13, 128
+        assert L.h3d_smpl_backward_workspace_bytes(P, V, Vpad, 4, 1, ctypes.byref(n)) == 0
+        assert n.value == (a256(4 * P * 207) + a256(4 * P * 288) + a256(4 * P * 72) + a256(1344 * Ppad) + a256(4 * P * 3 * Vpad)
+                           + a256(4 * NG * P * 288) + a256(4 * NS * P * 224)), V
+
+
+@pytest.mark.parametrize("V", [193, 577])
+def test_per_person_rule_sees_a_mutant_the_whole_tensor_rule_passes(V):
+    """The pose-corrective block of joint 23 scaled by 1 - 1e-3, in fp64: inside the whole-tensor limit, which one near-singular person sets,
+    and outside the per-person limit for at least 9 persons in 10.  The fp32 autograd itself passes the per-person rule (err = e32[p])."""
+    P = 130
+    model = R.jointed_model(V)
+    betas, thetas = R.make_case(P, 1)
+    rs = np.random.RandomState(501)
+    gv, gj = rs.randn(P, V, 3).astype(np.float32), rs.randn(P, 24, 3).astype(np.float32)
+    target, e32 = G.bounds_per_person(betas, thetas, model, gv, gj)
+    whole = [float(e.max()) for e in e32]
+    _, e_whole = G.bounds(betas, thetas, model, gv, gj)
+    assert whole == e_whole                                            # the per-person vectors are the whole-tensor rule's e32, row by row
+    mutant = dict(model, posedirs=model["posedirs"].astype(np.float64).copy())
+    mutant["posedirs"][:, :, 198:207] *= 1 - 1e-3
+    got = [g.numpy() for g in G.grads(betas, thetas, mutant, gv, gj, torch.float64)]
+    G.check("V%d mutant, whole tensor" % V, got, target, whole)
+    err, limit = G.person_errors(got, target, e32)["grad_thetas"]
+    over = int((err > limit).sum())
+    print("V%d mutant: %d of %d persons over their own grad_thetas limit; whole-tensor limit / median person's %.3g"
+          % (V, over, P, (G.FACTOR * whole[1]) / (G.FACTOR * float(np.median(e32[1])))))
+    assert over >= 0.9 * P
+    with pytest.raises(AssertionError):
+        G.check_per_person("V%d mutant" % V, got, target, e32)
+    g32 = G.grads(betas, thetas, model, gv, gj, torch.float32)
+    worst = G.check_per_person("V%d fp32 autograd" % V, g32, target, e32)
+    assert all(w <= 1.0 for w in worst.values())
+
+
+def test_per_person_rule_prints_and_flags_the_worst_person(capsys):
+    target = [np.ones((3, 10)), np.ones((3, 72))]
+    e32 = [np.array([1e-6, 1e-6, 1e-3]), np.array([1e-6, 2e-6, 1e-3])]
+    got = [t.copy() for t in target]
+    got[1][2, 5] += 3e-3                                               # the edge person, inside its own limit of 4e-3 + 2^-23
+    got[1][0, 7] += 7e-6                                               # an ordinary person inside 4 * median = 8e-6
+    worst = G.check_per_person("toy", got, target, e32)
+    assert worst["grad_betas"] == 0.0 and 0.7 < worst["grad_thetas"] < 1.0
+    got[1][1, 0] += 1e-5                                               # an ordinary person past 4 * max(e32[p], median) = 8e-6 + 2^-23
+    G.check("toy", got, target, [1e-3, 1e-3])
+    with pytest.raises(AssertionError) as ex:
+        G.check_per_person("toy", got, target, e32)
+    assert "'person': 1" in str(ex.value) and "grad_thetas" in str(ex.value)
+    assert "toy grad_thetas per person: worst person 1 of 3" in capsys.readouterr().out
+    got[0][0, 0] = np.nan
+    with pytest.raises(AssertionError):
+        G.check_per_person("toy", got, target, e32)
 
 
 # ---- the C ABI ---------------------------------------------------------------------------------------------------------------------
