@@ -720,24 +720,12 @@ __global__ __launch_bounds__(256) void upadd_kernel(const T *__restrict__ in, co
             }
         }
         sv = *reinterpret_cast<const u32x4 *>(skip + pix * skip_cs + v * N);
-        float acc[N], x[N];
-#pragma unroll
-        for (int n = 0; n < N; ++n) acc[n] = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (!ok[q]) continue;                // same association order as before: taps (a, c2) ascending
-            unpack16<T>(xv[q], x);
-            const float *wp;
-            if constexpr (WLDS) wp = s_w + tap[q] * wrow + v * N;
-            else wp = w + tap[q] * C + v * N;
-#pragma unroll
-            for (int n = 0; n < N; ++n) acc[n] = fmaf(wp[n], x[n], acc[n]);
-        }
-        unpack16<T>(sv, x);
-#pragma unroll
-        for (int n = 0; n < N; ++n) acc[n] += x[n];
-        if constexpr (F16OUT) *reinterpret_cast<u32x4 *>(out + pix * out_cs + v * N) = pack16_f16(acc);
-        else *reinterpret_cast<u32x4 *>(out + pix * out_cs + v * N) = pack16<T>(acc);
+        // the arithmetic itself is csrc/epilogue.h's upadd_vec (taps (a, c2) ascending, invalid ones skipped), shared with the DeformConv
+        // epilogue that folds this op in
+        u32x4 o;
+        if constexpr (WLDS) o = upadd_vec<T>([&](int q, int n) { return s_w[tap[q] * wrow + v * N + n]; }, ok, xv, sv, F16OUT);
+        else o = upadd_vec<T>([&](int q, int n) { return w[tap[q] * C + v * N + n]; }, ok, xv, sv, F16OUT);
+        *reinterpret_cast<u32x4 *>(out + pix * out_cs + v * N) = o;
     }
 }
 
@@ -774,7 +762,8 @@ int h3d_launch_elementwise(const h3d_op &op, hipStream_t st)
     // 8 KiB (128 ch) 0.057 -> 0.043; 16 KiB with 64 channels (f = 4) 0.102 -> 0.075; 16 KiB with 256 channels (8-pixel
     // segments) 0.029 -> 0.041: stays in global memory.  Tuning override: H3D_TUNE_UPADD_TAPS_GLOBAL = never, H3D_TUNE_UPADD_TAPS_LDS = whenever it fits 64 KiB
     const size_t up_wbytes = (size_t)op.ksize * op.ksize * op.Cin * sizeof(float);
-    const bool up_wlds = op.reserved == H3D_TUNE_UPADD_TAPS_GLOBAL ? false : op.reserved == H3D_TUNE_UPADD_TAPS_LDS ? up_wbytes <= 64 * 1024 : (up_wbytes <= 8192 || (up_wbytes <= 16384 && op.Cin <= 64));
+    const int up_tune = op.reserved & ~H3D_OPF_UPADD_FOLDED;      // (the fold flag is the run loop's: a launch of this op is the unfolded pair)
+    const bool up_wlds = up_tune == H3D_TUNE_UPADD_TAPS_GLOBAL ? false : up_tune == H3D_TUNE_UPADD_TAPS_LDS ? up_wbytes <= 64 * 1024 : (up_wbytes <= 8192 || (up_wbytes <= 16384 && op.Cin <= 64));
     // (measured and dropped in round 3: f = 2 tap weights in registers, rows in pairs with ten loads in flight -- 0.341 vs 0.325 ms
     //  over the six f = 2 launches of the batch-64 plan: the kernel sits at the 4.4-4.9 TB/s these mixed read / write streams reach)
     return h3d_by_store_dtype<bf16_t, f16_t, float, x3_t>(op.dtype, "elementwise: dtype %d", [&](auto t) {

@@ -43,6 +43,7 @@ struct Dcn3Args {
     int xscaled;   // with wmax: the input was scaled by 2^dcn_act_exp(wmax[2]) (H3D_OPF_DCN_FUSED_SCALED_INPUT, the `DCN` module's f16x3 launch)
     int xcd;   // h3d_tile_id mode
     unsigned long long *stamps;   // profiling builds: in-kernel phase stamps (common.h H3D_STAMP)
+    UpFoldArgs up;     // FOLD instantiations: the H3D_OP_UPADD folded into the epilogue (host: up.out != nullptr = a fold is requested)
 };
 
 // profiling builds with -DDCN3_STAMP_B: the six phase stamps are replaced by sub-step stamps of phase B's second stage
@@ -109,12 +110,15 @@ struct Dcn3Cfg {
 // bits instead of 8).  Selected by H3D_OPF_DCN_STREAM_F16_INPUT.
 // STATS: the statistics launch of h3d_dcn_far_samples -- its own instantiation (phase A + geometry only; everything behind the
 // slot count is compiled out), so that a profiler lists it under its own name and the production kernel carries no switch for it.
-template <typename T, int MT, int CK, int MARGIN, int EPI = 0, bool WDMA = false, int NP = 0, bool PK = false, bool F16IN = false, bool STATS = false>   // EPI: 0 general, 1 lean NHWC, 2 LDS-transposed (bf16)
+// FOLD: the up-sample + skip add that follows this layer (an H3D_OP_UPADD with H3D_OPF_UPADD_FOLDED whose skip is this output) runs in the
+// final stores of the LDS-transposed epilogue (csrc/epilogue.h tile_epilogue_lds_fold): the layer's own output never reaches HBM.
+template <typename T, int MT, int CK, int MARGIN, int EPI = 0, bool WDMA = false, int NP = 0, bool PK = false, bool F16IN = false, bool STATS = false, bool FOLD = false>   // EPI: 0 general, 1 lean NHWC, 2 LDS-transposed (bf16)
 __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) void dcn3_kernel(Dcn3Args a)
 {
     using C = Dcn3Cfg<T, MT, CK, MARGIN, WDMA, NP, PK>;
     using X = SE<std::conditional_t<F16IN, f16_t, T>>;
     static_assert(!F16IN || (std::is_same<T, bf16_t>::value && WDMA && NP > 0), "fp16 input: an option of the bf16 patch-slot variants");
+    static_assert(!FOLD || (sizeof(T) == 2 && WDMA && NP > 0 && EPI == 2 && !STATS), "folded up-sample + add: the 2-byte patch-slot variants with the LDS-transposed epilogue");
     constexpr int ES = C::ES, SS = C::SS;
     constexpr bool ONEBUF = WDMA || C::SINGLE;     // one apron (and, register-staged, one filter) buffer: a barrier before it is rewritten
     __shared__ __attribute__((aligned(256))) char smem[C::LDS];
@@ -958,7 +962,8 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
     const EpiArgs e = dcn_epi_args(a);
     if constexpr (EPI == 2) {
         __syncthreads();                          // the apron and the filters are no longer read
-        tile_epilogue_lds<T, MT>(acc, e, b, oy0, ox0, cout0, wv, l, smem + wv * epi_lds_stride<MT>());
+        if constexpr (FOLD) tile_epilogue_lds_fold<T, MT>(acc, e, a.up, b, oy0, ox0, cout0, wv, l, smem + wv * epi_lds_stride<MT>());
+        else tile_epilogue_lds<T, MT>(acc, e, b, oy0, ox0, cout0, wv, l, smem + wv * epi_lds_stride<MT>());
     } else {
         tile_epilogue<typename StoreT<T>::type, MT, 1, EPI == 1>(acc, e, b, oy0, ox0, cout0, wv, r, h);
     }
@@ -976,7 +981,7 @@ __global__ __launch_bounds__(512, (WDMA && MT <= 2 && sizeof(T) == 2) ? 4 : 2) v
 }
 
 template <typename T, int MT, int CK, int MARGIN, bool WDMA = false, int NP = 0, bool PK = false, bool F16IN = false>
-static int launch_dcn3_cfg(const Dcn3Args &a0, hipStream_t st, bool stats = false)
+static int launch_dcn3_cfg(const Dcn3Args &a0, hipStream_t st, bool stats = false, bool *folded = nullptr)
 {
     using C = Dcn3Cfg<T, MT, CK, MARGIN, WDMA, NP, PK>;
     static_assert(!(WDMA && MT <= 2 && sizeof(T) == 2) || C::LDS * 2 <= 160 * 1024, "two workgroups per CU");
@@ -997,6 +1002,16 @@ static int launch_dcn3_cfg(const Dcn3Args &a0, hipStream_t st, bool stats = fals
             if (stats) {                            // h3d_dcn_far_samples: named as the kernel it counts for
                 if (name.dry()) return H3D_OK;
                 return h3d_bind({"dcn3_kernel<stats>"}, dcn3_kernel<T, MT, CK, MARGIN, 1, WDMA, NP, PK, F16IN, true>).launch(dim3(grid.x), dim3(C::THREADS), 0, st, a);
+            }
+        }
+        // a requested fold (a.up.out) is taken by the 64-channel patch-slot tiles with the LDS-transposed epilogue; every other launch
+        // ignores the request and leaves *folded as it was: the caller then launches the H3D_OP_UPADD itself
+        if constexpr (WDMA && NP > 0 && sizeof(T) == 2 && MT == 2 && e == 2) {
+            if (a.up.out && !stats) {
+                const h3d_kname fname{"dcn3_kernel", h3d_tag<T>{}, MT, CK, MARGIN, e, WDMA, NP, h3d_opt(PK), h3d_opt(F16IN), h3d_opt(false), h3d_opt(true)};
+                if (fname.dry()) return H3D_OK;
+                if (folded) *folded = true;
+                return h3d_bind(fname, dcn3_kernel<T, MT, CK, MARGIN, 2, WDMA, NP, PK, F16IN, false, true>).launch(grid, dim3(C::THREADS), 0, st, a);
             }
         }
         if constexpr (F16IN && e != 2) {
@@ -1022,6 +1037,7 @@ struct Dcn3Flags {
     bool narrow_wg;                         // > 64 output channels on 64-channel workgroups (h3d_dcn_narrow_wg: the grid, or forced either way)
     bool stats;                             // h3d_dcn_far_samples
     bool dcn5;                              // fp16 stream ops: the LDS-DMA apron kernel of csrc/dcn5.hip
+    bool *folded;                           // h3d_launch_dcn3_fold: set when the launch took the H3D_OP_UPADD with it
     // f16x3 plans
     int margin;                             // forced apron margin, 0 = the launcher's rule
     bool raw_pack, scaled_input;            // fused op of the stand-alone `DCN` module: fp32 packs + maxima behind the bias | input pre-scaled
@@ -1074,20 +1090,20 @@ static int launch_dcn3_lowp(const h3d_op &op, const Dcn3Flags &f, const Dcn3Args
         if (f.wide_margin)
             return dcn_by_mt(op.Cout, mt2, [&](auto mt) {
                 constexpr int MT = decltype(mt)::value;
-                return launch_dcn3_cfg<T, MT, 16, 4, true, 256, MT < 4, MT >= 2 && F16IN>(a, st, f.stats);
+                return launch_dcn3_cfg<T, MT, 16, 4, true, 256, MT < 4, MT >= 2 && F16IN>(a, st, f.stats, f.folded);
             });
         // experiment / candidate default: margin 2 on the PACKED apron (15 KB instead of 28) with 512 patch slots per tile, the second
         // 256 filled in a second round per stage
         if (f.slots512)
             return dcn_by_mt(op.Cout, mt2, [&](auto mt) {
                 constexpr int MT = decltype(mt)::value;
-                return launch_dcn3_cfg<T, MT, 16, MT < 4 ? 2 : 4, true, 512, MT < 4, MT >= 2 && F16IN>(a, st, f.stats);
+                return launch_dcn3_cfg<T, MT, 16, MT < 4 ? 2 : 4, true, 512, MT < 4, MT >= 2 && F16IN>(a, st, f.stats, f.folded);
             });
         // <= 64 output channels: margin-2 apron, 16-channel stages, <= 128 VGPRs and 78 KB of LDS -> two workgroups
         // (16 waves) per CU, one computing while the other waits at its stage barriers; 256 patch slots per tile
         return dcn_by_mt(op.Cout, mt2, [&](auto mt) {
             constexpr int MT = decltype(mt)::value;
-            return launch_dcn3_cfg<T, MT, 16, MT < 4 ? 2 : 4, true, 256, false, MT >= 2 && F16IN>(a, st, f.stats);
+            return launch_dcn3_cfg<T, MT, 16, MT < 4 ? 2 : 4, true, 256, false, MT >= 2 && F16IN>(a, st, f.stats, f.folded);
         });
     }
     // register-staged filters: 32-channel stages where Cin allows and the workgroup has <= 64 channels (the small-grid rule as above)
@@ -1098,7 +1114,37 @@ static int launch_dcn3_lowp(const h3d_op &op, const Dcn3Flags &f, const Dcn3Args
 
 int h3d_launch_dcn5(const h3d_op &op, hipStream_t st);      // csrc/dcn5.hip: fp16 plans, every operand by LDS-DMA
 
-int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
+static int launch_dcn3(const h3d_op &op, hipStream_t st, const UpFoldArgs &up, bool *folded);
+int h3d_launch_dcn3(const h3d_op &op, hipStream_t st) { return launch_dcn3(op, st, UpFoldArgs{}, nullptr); }
+
+// The pair (H3D_OP_DCN_FUSED_STREAM `op`, H3D_OP_UPADD `up` with up.in2 == op.out) as one launch where `up` is what the folding epilogue
+// covers and the tile the launcher picks has it: *folded says whether `up` is done.  Whatever `up` asks beyond that (another dtype, an
+// odd factor, misaligned maps) is left to its own launcher, which also owns its error messages.
+int h3d_launch_dcn3_fold(const h3d_op &op, const h3d_op &up, hipStream_t st, bool *folded)
+{
+    *folded = false;
+    UpFoldArgs u = {};
+    const int f = up.stride;
+    const bool f16out = up.out_mode == H3D_OUT_NHWC_F16;
+    const bool ok = (op.dtype == H3D_BF16 || op.dtype == H3D_F16) && up.dtype == op.dtype && up.in && up.w && up.out && up.in2 == op.out &&
+                    (up.out_mode == H3D_OUT_NHWC || (f16out && op.dtype == H3D_BF16)) && op.out_mode == H3D_OUT_NHWC &&
+                    up.B == op.B && up.Ho == op.H && up.Wo == op.W && up.Cin == op.Cout && up.Cout == op.Cout && up.in2_cs == op.out_cs &&
+                    (f == 2 || f == 4 || f == 8) && up.ksize == 2 * f && up.Ho == up.H * f && up.Wo == up.W * f &&
+                    op.Cout % 8 == 0 && up.in_cs % 8 == 0 && up.out_cs % 8 == 0 && up.in_cs >= up.Cin && up.out_cs >= up.Cout &&
+                    ((uintptr_t)up.in & 15) == 0 && ((uintptr_t)up.out & 15) == 0 && ((uintptr_t)up.w & 15) == 0 &&
+                    // the tail's 32-bit offsets and 24-bit multiplies (csrc/epilogue.h)
+                    (size_t)up.H * up.W * up.in_cs * 2 < 0x7fffffffull && (size_t)up.Ho * up.Wo * up.out_cs * 2 < 0x7fffffffull &&
+                    (size_t)up.W * up.in_cs * 2 < (1u << 24) && (size_t)up.Wo * up.out_cs * 2 < (1u << 24) && up.ksize * up.ksize * up.Cin < (1 << 24);
+    if (ok) {
+        u.x = (const char *)up.in; u.w = (const float *)up.w; u.out = (char *)up.out;
+        u.H = up.H; u.W = up.W; u.x_cs = up.in_cs; u.out_cs = up.out_cs; u.C = up.Cin;
+        u.fs = f == 2 ? 1 : f == 4 ? 2 : 3;
+        u.f16out = f16out;
+    }
+    return launch_dcn3(op, st, u, folded);
+}
+
+static int launch_dcn3(const h3d_op &op, hipStream_t st, const UpFoldArgs &up, bool *folded)
 {
     const bool wdma = op.kind == H3D_OP_DCN_FUSED_STREAM;
     if (wdma && op.dtype != H3D_BF16 && op.dtype != H3D_F16 && op.dtype != H3D_F16X3) H3D_FAIL(H3D_ERR_DTYPE, "dcn_fused_stream: bf16 / fp16 / f16x3 plans only");
@@ -1115,8 +1161,10 @@ int h3d_launch_dcn3(const h3d_op &op, hipStream_t st)
     a.oscale = ldexpf(1.f, -op.wexp2);
     a.wmax = nullptr;
     a.xscaled = 0;
+    a.up = up;
     if (wdma && (size_t)op.H * op.W * op.in_cs * es >= 0x7ffffff0ull) H3D_FAIL(H3D_ERR_SHAPE, "dcn_fused_stream: image of 2 GiB or more");
-    const Dcn3Flags f = dcn3_decode(op, wdma);
+    Dcn3Flags f = dcn3_decode(op, wdma);
+    f.folded = folded;
     if (f.f16_input) return launch_dcn3_lowp<bf16_t, true>(op, f, a, wdma, st);      // (a flag of bf16 plans: dcn3_decode)
     // fp16 plans: the apron needs no conversion while it is staged.  csrc/dcn5.hip also moves it by LDS-DMA (double buffered, one
     // barrier per phase-A stage): measured 5.7 % SLOWER on the ten <= 64-channel launches of the batch-64 plan (1.519 vs 1.437 ms,

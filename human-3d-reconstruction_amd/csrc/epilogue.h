@@ -115,9 +115,48 @@ __device__ __forceinline__ void tile_epilogue(f32x16 (&acc)[MT][NT], const EpiAr
 // no longer be read by anyone else).  Residual images must be smaller than 2 GiB (buffer offsets).
 template <int MT, int NT = 1> constexpr int epi_lds_stride() { return (NT * 32 * (64 * MT + 16) + 1023) / 1024 * 1024; }
 
-template <typename T, int MT, int NT, bool HASRES>
+// The per-vector arithmetic of the up-sample + skip add (depthwise ConvTranspose2d(k = 2f, stride f, padding f/2) + skip): ONE copy, called
+// by upadd_kernel (csrc/conv.hip) and by the folding tail of tile_epilogue_lds_impl below, so that both give the same bits.  acc = 0,
+// then the valid taps q = (a, c2) ascending as fmaf(w, x, acc) -- an invalid tap is skipped, not added as zero --, then acc += skip,
+// then the store format (f16out: IEEE fp16 from a bf16 plan, H3D_OUT_NHWC_F16).  w(q, n): the weight of tap q for channel n of this vector --
+// the callers differ in where they keep the tap table (LDS or global memory read at the use; registers loaded ahead), not in the arithmetic.
+template <typename T, typename WS>
+__device__ __forceinline__ u32x4 upadd_vec(WS w, const bool (&ok)[4], const u32x4 (&xv)[4], const u32x4 &sv, bool f16out)
+{
+    constexpr int N = 16 / sizeof(T);
+    float acc[N], x[N];
+#pragma unroll
+    for (int n = 0; n < N; ++n) acc[n] = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (!ok[q]) continue;
+        unpack16<T>(xv[q], x);
+#pragma unroll
+        for (int n = 0; n < N; ++n) acc[n] = fmaf(w(q, n), x[n], acc[n]);
+    }
+    unpack16<T>(sv, x);
+#pragma unroll
+    for (int n = 0; n < N; ++n) acc[n] += x[n];
+    if constexpr (sizeof(T) == 2) {
+        if (f16out) return pack16_f16(acc);
+    }
+    return pack16<T>(acc);
+}
+
+// FOLD: the H3D_OP_UPADD that follows the producer (its skip is this tile's result and nothing else reads it) is applied to every
+// 16-byte vector on its way out: out = up(x) + result, written to the UPADD's output; the result itself is never stored.
+struct UpFoldArgs {
+    const char *x;      // the UPADD's `in`: [B][H][W][x_cs] of the producer's type, H = Ho >> fs
+    const float *w;     // fp32 [k*k][C] tap table (k = 2f), read through L2
+    char *out;          // the UPADD's `out`: [B][Ho][Wo][out_cs]
+    int H, W, x_cs, out_cs, C;      // (an image of `x` and of `out` is smaller than 2 GiB, a row of either smaller than 16 MiB)
+    int fs;             // log2 of the up-sampling factor f
+    int f16out;         // H3D_OUT_NHWC_F16
+};
+
+template <typename T, int MT, int NT, bool HASRES, bool FOLD = false>
 __device__ __forceinline__ void tile_epilogue_lds_impl(f32x16 (&acc)[MT][NT], const EpiArgs &a, int b, int oy0, int ox0,
-                                                       int cout0, int wv, int l, char *lw)
+                                                       int cout0, int wv, int l, char *lw, const UpFoldArgs &u = UpFoldArgs{})
 {
     constexpr int ROWB = 64 * MT + 16;
     constexpr int SPP = 4 * MT;                  // 16-byte slots per pixel
@@ -142,6 +181,46 @@ __device__ __forceinline__ void tile_epilogue_lds_impl(f32x16 (&acc)[MT][NT], co
         __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0)
         __builtin_amdgcn_wave_barrier();
     }
+    // FOLD: the geometry of store iteration `it` as upadd_kernel computes it (two contributing rows and columns; f = 1 << fs, so the
+    // divisions are shifts), and its up-to-four 16-byte loads of the low-resolution map.  Iteration 0's are issued here, in front of
+    // the bias / pack pass, iteration it + 1's in front of the arithmetic of iteration it.  The 32-byte tap rows are read through L2
+    // where they are used.  (Measured and dropped: all four tap rows of an iteration loaded into registers together with the map
+    // vectors, one iteration ahead -- the batch-64 step went from 1.2 % faster than the unfolded plan to 1.0 % slower: the tail is
+    // bound by vector instructions, and the 32 extra registers per set cost more of them than the round trips they hide.)
+    // Offsets are 32-bit byte offsets inside one image (the launcher checks: images below 2 GiB, rows below 16 MiB), built from
+    // 24-bit multiplies and the per-image bases, which are scalar: with 64-bit pixel indices the four taps of a vector cost more vector
+    // issue than its arithmetic, in a tail that is bound by it.
+    [[maybe_unused]] u32x4 fxv[2][4];
+    [[maybe_unused]] bool fok[2][4];
+    [[maybe_unused]] int fwo[2][4];             // float offset of a tap's row in the table
+    [[maybe_unused]] const char *fxb = nullptr;
+    [[maybe_unused]] int fxrow = 0, fxpx = 0, fch = 0;
+    if constexpr (FOLD) {
+        static_assert(64 % SPP == 0, "a lane keeps its 16-byte slot through the store iterations");
+        fxb = u.x + (size_t)b * u.H * u.W * u.x_cs * 2;
+        fxrow = u.W * u.x_cs * 2;
+        fxpx = u.x_cs * 2;
+        fch = cout0 + (l % SPP) * 8;
+    }
+    [[maybe_unused]] auto fold_fetch = [&](int it) {
+        const int p = it * (64 / SPP) + l / SPP;
+        const int oy = oy0 + 2 * NT * wv + (p >> 4), ox = ox0 + (p & 15);
+        const bool live = oy < a.Ho && ox < a.Wo && fch < a.Cout;
+        const int f = 1 << u.fs;
+        const int ry = (oy + (f >> 1)) & (f - 1), rx = (ox + (f >> 1)) & (f - 1);
+        const int iy0 = (oy + (f >> 1)) >> u.fs, ix0 = (ox + (f >> 1)) >> u.fs;
+        const int off00 = (int)(__umul24(iy0, fxrow) + __umul24(ix0, fxpx)) + fch * 2;
+        const int w00 = (int)__umul24((ry << (u.fs + 1)) + rx, u.C);             // tap (ry, rx) of the k = 2f wide table
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int iy = iy0 - (t >> 1), ix = ix0 - (t & 1);
+            const bool ok = live && (unsigned)iy < (unsigned)u.H && (unsigned)ix < (unsigned)u.W;
+            fok[it & 1][t] = ok;
+            fwo[it & 1][t] = w00 + (((t >> 1) << (2 * u.fs + 1)) + ((t & 1) << u.fs)) * u.C;      // + (a f k + c2 f) rows
+            if (ok) fxv[it & 1][t] = *reinterpret_cast<const u32x4 *>(fxb + (off00 - (t >> 1) * fxrow - (t & 1) * fxpx));
+        }
+    };
+    if constexpr (FOLD) fold_fetch(0);
     {
         const float *bp = a.bias + cout0 + 4 * h;
         const float lo = a.relu ? 0.f : -__builtin_inff();
@@ -173,6 +252,24 @@ __device__ __forceinline__ void tile_epilogue_lds_impl(f32x16 (&acc)[MT][NT], co
     }
     __builtin_amdgcn_s_waitcnt(0xc07f);          // lgkmcnt(0): my wave's LDS writes are done
     __builtin_amdgcn_wave_barrier();
+    if constexpr (FOLD) {
+        char *ob = u.out + (size_t)b * a.Ho * a.Wo * u.out_cs * 2;
+        const int orow = a.Wo * u.out_cs * 2, opx = u.out_cs * 2;
+        const float *wb = u.w + fch;
+#pragma unroll
+        for (int it = 0; it < NT * SPP / 2; ++it) {
+            if (it + 1 < NT * SPP / 2) fold_fetch(it + 1);
+            const int p = it * (64 / SPP) + l / SPP;
+            const int oy = oy0 + 2 * NT * wv + (p >> 4), ox = ox0 + (p & 15);
+            if (oy < a.Ho && ox < a.Wo && fch < a.Cout) {
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(lw + p * ROWB + (l % SPP) * 16);      // the producer's value, rounded to T: the skip
+                const auto &wo = fwo[it & 1];
+                *reinterpret_cast<u32x4 *>(ob + (int)(__umul24(oy, orow) + __umul24(ox, opx)) + fch * 2) =
+                    upadd_vec<T>([&](int q, int n) { return wb[wo[q] + n]; }, fok[it & 1], fxv[it & 1], v, u.f16out != 0);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int it = 0; it < NT * SPP / 2; ++it) {
         const int q = it * 64 + l;
@@ -193,4 +290,13 @@ __device__ __forceinline__ void tile_epilogue_lds(f32x16 (&acc)[MT][NT], const E
     static_assert(sizeof(T) == 2, "2-byte NHWC outputs");
     if (a.res) tile_epilogue_lds_impl<T, MT, NT, true>(acc, a, b, oy0, ox0, cout0, wv, l, lw);     // wave-uniform
     else tile_epilogue_lds_impl<T, MT, NT, false>(acc, a, b, oy0, ox0, cout0, wv, l, lw);
+}
+
+// ... with the following up-sample + skip add folded into the final stores (producers without a residual)
+template <typename T, int MT, int NT = 1>
+__device__ __forceinline__ void tile_epilogue_lds_fold(f32x16 (&acc)[MT][NT], const EpiArgs &a, const UpFoldArgs &u, int b, int oy0, int ox0,
+                                                       int cout0, int wv, int l, char *lw)
+{
+    static_assert(sizeof(T) == 2, "2-byte NHWC outputs");
+    tile_epilogue_lds_impl<T, MT, NT, false, true>(acc, a, b, oy0, ox0, cout0, wv, l, lw, u);
 }

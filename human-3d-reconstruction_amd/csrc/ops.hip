@@ -64,13 +64,26 @@ int h3d_launch_dcn(const h3d_op &op, hipStream_t st);
 int h3d_launch_heads(const h3d_op &op, hipStream_t st);
 int h3d_launch_dcn2(const h3d_op &op, hipStream_t st);
 int h3d_launch_dcn3(const h3d_op &op, hipStream_t st);
+int h3d_launch_dcn3_fold(const h3d_op &op, const h3d_op &up, hipStream_t st, bool *folded);
 int h3d_launch_conv_stream(const h3d_op &op, hipStream_t st);
 int h3d_launch_dcn4(const h3d_op &op, hipStream_t st);
 int h3d_launch_updcn(const h3d_op &op, hipStream_t st);
 int h3d_launch_stem3(const h3d_op &op, hipStream_t st);
 int h3d_launch_extra(const h3d_op &op, hipStream_t st);
 
-static int run_one(const h3d_op &op, int i, hipStream_t st);
+static int run_one(const h3d_op &op, int i, hipStream_t st, const h3d_op *up = nullptr, bool *folded = nullptr);
+
+// ops[i], or ops[i] and ops[i + 1] as one launch (*folded): a fused DeformConv stream op directly followed by an H3D_OP_UPADD that carries
+// H3D_OPF_UPADD_FOLDED and whose skip (`in2`) is the DeformConv's `out`, where the DeformConv launcher has a folding tile for the pair
+// (csrc/dcn3.hip h3d_launch_dcn3_fold).  Everywhere else the flag is ignored: the result never depends on the plan's claim being used.
+static int run_at(const h3d_op *ops, int i, int n, hipStream_t st, bool *folded)
+{
+    *folded = false;
+    if (i + 1 < n && ops[i].kind == H3D_OP_DCN_FUSED_STREAM && ops[i + 1].kind == H3D_OP_UPADD && (ops[i + 1].reserved & H3D_OPF_UPADD_FOLDED) &&
+        ops[i].out && ops[i + 1].in2 == ops[i].out)
+        return run_one(ops[i], i, st, &ops[i + 1], folded);
+    return run_one(ops[i], i, st);
+}
 
 extern "C" int h3d_op_kernel_name(const h3d_op *op, char *buf, int buflen)
 {
@@ -92,13 +105,23 @@ extern "C" int h3d_run_ops_timed(const h3d_op *ops, int n, void *stream, float *
     for (int i = 0; i <= n; ++i) (void)hipEventCreate(&ev[i]);
     int rc = H3D_OK;
     (void)hipEventRecord(ev[0], st);
+    for (int i = 0; i < n; ++i) ms[i] = 0.f;
     for (int i = 0; i < n && rc == H3D_OK; ++i) {
-        rc = run_one(ops[i], i, st);
+        bool folded = false;
+        rc = run_at(ops, i, n, st, &folded);
         (void)hipEventRecord(ev[i + 1], st);
+        if (folded) {                            // the pair's time stands under the DeformConv op; the folded op reports 0 ms
+            ++i;
+            ms[i] = -1.f;
+            (void)hipEventRecord(ev[i + 1], st);
+        }
     }
     if (rc == H3D_OK) {
         (void)hipEventSynchronize(ev[n]);
-        for (int i = 0; i < n; ++i) (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+        for (int i = 0; i < n; ++i) {
+            if (ms[i] < 0.f) ms[i] = 0.f;
+            else (void)hipEventElapsedTime(&ms[i], ev[i], ev[i + 1]);
+        }
     }
     for (int i = 0; i <= n; ++i) (void)hipEventDestroy(ev[i]);
     free(ev);
@@ -110,13 +133,15 @@ extern "C" int h3d_run_ops(const h3d_op *ops, int n, void *stream)
     if (!ops || n < 0) H3D_FAIL(H3D_ERR_ARG, "run_ops: null plan");
     hipStream_t st = (hipStream_t)stream;
     for (int i = 0; i < n; ++i) {
-        const int rc = run_one(ops[i], i, st);
+        bool folded = false;
+        const int rc = run_at(ops, i, n, st, &folded);
         if (rc != H3D_OK) return rc;
+        if (folded) ++i;
     }
     return H3D_OK;
 }
 
-static int run_one(const h3d_op &op, int i, hipStream_t st)
+static int run_one(const h3d_op &op, int i, hipStream_t st, const h3d_op *up, bool *folded)
 {
     int rc;
     if (op.B <= 0 || op.H <= 0 || op.W <= 0 || op.Ho <= 0 || op.Wo <= 0 || op.Cin <= 0 || op.Cout <= 0) {
@@ -141,7 +166,7 @@ static int run_one(const h3d_op &op, int i, hipStream_t st)
         return H3D_ERR_UNSUPPORTED;
 #endif
     case H3D_OP_DCN_FUSED:
-    case H3D_OP_DCN_FUSED_STREAM: rc = h3d_launch_dcn3(op, st); break;
+    case H3D_OP_DCN_FUSED_STREAM: rc = up ? h3d_launch_dcn3_fold(op, *up, st, folded) : h3d_launch_dcn3(op, st); break;
     case H3D_OP_HEADS: rc = h3d_launch_heads(op, st); break;
     case H3D_OP_MAXPOOL:
     case H3D_OP_UPADD:

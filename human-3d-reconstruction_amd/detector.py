@@ -159,6 +159,8 @@ class MultiPoseDetector:
             self.model.engine_flags["split_heads"] = tuple(h for h in opt.heads if h in WHOLE_MAP_HEADS)   # (the plan's lowering; `run` decides per call)
             # (without `hm_hp` there are no peaks and the assemble step does not read `hp_offset`: the run computes it nowhere)
             self.model.engine_flags["peak_heads"] = tuple(h for h in opt.heads if h in PEAK_HEADS)
+            # four of IDAUp's up-sample + add passes run in the epilogue of the DeformConv that writes their skip (Plan.FLAGS fold_upadd): same bits
+            self.model.engine_flags["fold_upadd"] = True
         if opt.smpl and smpl_model is None:
             self.smpl_model = _smpl.SMPLModel.synthetic()
 

@@ -82,6 +82,12 @@ class Plan:
                                   # the other heads in the default groups, follows it (`run_deferred`).  `run_sparse` evaluates the
                                   # deferred heads (without the peak_heads) at listed positions only (h3d_heads_sparse).  `run` still runs everything:
                                   # same instantiations, same per-head arithmetic, the default lowering's maps bit for bit
+        fold_upadd=False,         # True (MultiPoseDetector sets it for DLA-34 bf16 / f16): every IDAUp lowers its proj DeformConvs first, and where the
+                                  # skip of an up-sample + add is the output of the node DeformConv lowered just before it, read by nothing else
+                                  # (dla_up.ida_2 steps 2 and 3, ida_up steps 1 and 2: 64 channels at a quarter of the input size), the op
+                                  # carries H3D_OPF_UPADD_FOLDED: h3d_run_ops launches the pair as one kernel whose epilogue adds the up-sampled
+                                  # map to each vector before it is stored (csrc/epilogue.h tile_epilogue_lds_fold).  The node's own output
+                                  # buffer is then never written; same bits downstream.  Off by default: the default lowering is pinned
         peak_heads=(),            # with split_heads: heads (of split_heads or not) that are NOT read whole either, but at a second, longer position
                                   # list (multi_pose_decode reads `hp_offset` at the 17 x K key-point peaks).  They leave the eager launch
                                   # for the deferred groups, in their default place, and join the sparse op, where `run_sparse_lists`
@@ -209,14 +215,19 @@ class Plan:
         self._op(_lib.OP_MAXPOOL, x, out, ksize=2, stride=2)
         return out
 
-    def upadd(self, x, skip, wkey, f16=False):
+    def upadd(self, x, skip, wkey, f16=False, private_skip=False):
         """f16: the sum is written as fp16 (same 2-byte NHWC buffer) for a DeformConv that reads fp16: the F16IN variants of
-        csrc/dcn3.hip (H3D_OPF_DCN_STREAM_F16_INPUT, the default) or csrc/dcn4.hip (stream_dcn, `make EXTRA=1`)."""
+        csrc/dcn3.hip (H3D_OPF_DCN_STREAM_F16_INPUT, the default) or csrc/dcn4.hip (stream_dcn, `make EXTRA=1`).
+        private_skip: the caller knows that no other op reads `skip`.  When the op just lowered is the fused DeformConv that writes it,
+        the op carries H3D_OPF_UPADD_FOLDED and the run loop launches the pair as one kernel (include/h3d.h)."""
         w, k = self.pw.up(wkey)
         f = k // 2
         out = self._alloc(x.H * f, x.W * f, x.C)
         assert (skip.H, skip.W, skip.C) == (out.H, out.W, out.C), wkey
-        self._op(_lib.OP_UPADD, x, out, skip, w=w.data_ptr(), ksize=k, stride=f, out_mode=_lib.OUT_NHWC_F16 if f16 else _lib.OUT_NHWC)
+        fold = (private_skip and self.ops and self.ops[-1].kind == _lib.OP_DCN_FUSED_STREAM and self.ops[-1].out == skip.ptr
+                and (skip.coff, skip.cs) == (0, skip.C))          # the whole buffer: no sibling slice that somebody else could read
+        self._op(_lib.OP_UPADD, x, out, skip, w=w.data_ptr(), ksize=k, stride=f, out_mode=_lib.OUT_NHWC_F16 if f16 else _lib.OUT_NHWC,
+                 reserved=_lib.OPF_UPADD_FOLDED if fold else 0)
         return out
 
     # -- network ---------------------------------------------------------------------------------
@@ -321,17 +332,27 @@ class Plan:
             self.dcn_layers.append((p, i))
         return out
 
-    def _ida(self, layers, p, startp, endp):
-        """IDAUp.forward (model.py:384-390) on the python list `layers` (mutated like the reference)."""
+    def _ida_projs(self, layers, p, startp, endp):
+        """The proj_k DeformConvs of an IDAUp, all in front of its first step (fold_upadd): proj_k reads layers[i] before step i replaces
+        it, so lowering them early changes no value."""
+        return [self._deform(layers[i], "%s.proj_%d" % (p, i - startp)) for i in range(startp + 1, endp)]
+
+    def _ida(self, layers, p, startp, endp, private=(), projs=None):
+        """IDAUp.forward (model.py:384-390) on the python list `layers` (mutated like the reference).
+        fold_upadd: `private` = the steps k whose skip layers[i - 1] no op outside this step reads; `projs` = the proj outputs when the
+        caller has lowered them already (else they are lowered here, in front of the first step).  The up-sample + add of a private step
+        then directly follows the node DeformConv that writes its skip, and `upadd` marks it for the run loop's fold."""
+        if self.fold_upadd and projs is None:
+            projs = self._ida_projs(layers, p, startp, endp)
         for i in range(startp + 1, endp):
             k = i - startp
-            y = self._deform(layers[i], "%s.proj_%d" % (p, k))
+            y = projs[k - 1] if projs is not None else self._deform(layers[i], "%s.proj_%d" % (p, k))
             f16 = self._dcn_f16_ok("%s.node_%d" % (p, k))
             if f16 and self.fuse_upnode and self.pw.up("%s.up_%d.weight" % (p, k))[1] // 2 >= self.fuse_upnode_min_f:
                 layers[i] = self._updcn(y, layers[i - 1], "%s.up_%d.weight" % (p, k), "%s.node_%d" % (p, k))
                 continue
             nf16 = not f16 and self._node_f16_ok("%s.node_%d" % (p, k))
-            y = self.upadd(y, layers[i - 1], "%s.up_%d.weight" % (p, k), f16=f16 or nf16)
+            y = self.upadd(y, layers[i - 1], "%s.up_%d.weight" % (p, k), f16=f16 or nf16, private_skip=self.fold_upadd and k in private)
             layers[i] = self._deform(y, "%s.node_%d" % (p, k), x_is_f16=f16, in_f16=nf16)
 
     def _updcn(self, x, skip, wkey, p):
@@ -380,12 +401,21 @@ class Plan:
         layers = [y0, y1, y2, y3, y4, y5]
         # DLAUp.forward (model.py:409-415)
         outs = [layers[-1]]
+        pre = None
         for i in range(3):
-            self._ida(layers, "dla_up.ida_%d" % i, len(layers) - i - 2, len(layers))
+            startp, private = len(layers) - i - 2, ()
+            if self.fold_upadd and i == 2:
+                # The last IDA of DLAUp: only its final map is read again, so from step 2 on every skip (the node output of the step
+                # before) is private.  That final map, outs[0] below, is read by ida_up's first step alone, as its skip: ida_up's
+                # proj DeformConvs (they read what are outs[0] and outs[1] NOW) are lowered first, so that ida_up's first up-sample +
+                # add directly follows the node that writes its skip.
+                pre = self._ida_projs([None, outs[0], outs[1]], "ida_up", 0, 3)
+                private = tuple(range(2, len(layers) - startp))
+            self._ida(layers, "dla_up.ida_%d" % i, startp, len(layers), private=private)
             outs.insert(0, layers[-1])
-        # DLASeg.forward (model.py:480-483): ida_up over the three finest maps
+        # DLASeg.forward (model.py:480-483): ida_up over the three finest maps; only ys[-1] is used, so both skips are private
         ys = [outs[0], outs[1], outs[2]]
-        self._ida(ys, "ida_up", 0, 3)
+        self._ida(ys, "ida_up", 0, 3, private=(1, 2), projs=pre)
         self.feat = ys[-1]
         if self.lower_heads:
             self._lower_heads(self.feat)

@@ -437,10 +437,17 @@ enum {
     H3D_TUNE_CONV_X3_MT2 = 0x4000              /* 1x1 stride 1: 64-channel tiles above 64 output channels too                                    */
 };
 
-/* H3D_OP_UPADD (csrc/conv.hip): the whole word, compared for equality */
+/* H3D_OP_UPADD (csrc/conv.hip): the word without H3D_OPF_UPADD_FOLDED, compared for equality */
 enum {
     H3D_TUNE_UPADD_TAPS_GLOBAL = 1,            /* tap table read from global memory                                                              */
-    H3D_TUNE_UPADD_TAPS_LDS = 2                /* tap table in LDS whenever it fits 64 KiB                                                       */
+    H3D_TUNE_UPADD_TAPS_LDS = 2,               /* tap table in LDS whenever it fits 64 KiB                                                       */
+    H3D_OPF_UPADD_FOLDED = 0x100               /* the plan's claim that nothing but this op reads `in2`.  h3d_run_ops / h3d_run_ops_timed then launch an
+                                                  H3D_OP_DCN_FUSED_STREAM op that stands directly in front of this one, and whose `out` is this op's
+                                                  `in2`, together with it as ONE kernel where the DeformConv's tile can (2-byte plans, the patch-slot
+                                                  tiles of 64-channel workgroups with the LDS-transposed epilogue, f a power of two): that kernel adds
+                                                  the up-sampled `in` to every vector it would have stored and writes the sum to this op's `out`; `in2`
+                                                  is then NOT written.  The same bits in `out` as the two launches.  Anywhere else the flag is
+                                                  ignored, and the timed run reports the pair's time under the DeformConv op and 0 under this one    */
 };
 
 /* H3D_OP_HEADS (csrc/heads.hip) */
