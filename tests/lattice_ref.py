@@ -9,6 +9,10 @@ pixel or a channel read from its neighbour changes most of the pixels it touches
 
 tests/test_oracle_lattice.py pins the conditions above for every case tests/test_gpu_lattice.py runs.
 
+The up-sample + add FOLDED into the DeformConv that writes its skip has its reference here too (`fold_operands`, `exact_fold`, the
+loop-form `fold_restated` with four defects of the folding tail): tests/test_gpu_upadd_fold.py runs it, tests/test_oracle_upadd_fold.py
+pins its conditions.
+
 The DeformConv also runs on a QUARTER-PIXEL lattice (the last two sections): sampling positions on k/4 and dyadic masks keep the bilinear
 blend exact, for the fused plan kernels (`dcn_frac_operands`) and for the fp32 operator and its backward (`dcn_grid_case`,
 tests/test_gpu_dcn_lattice.py; conditions in tests/test_oracle_dcn_backward.py)."""
@@ -34,6 +38,13 @@ def lowp_round(t, dtype):
     """One round-to-nearest-even into the plan's storage type (f32 / f16x3 store fp32: unchanged)."""
     t = t.float()
     return t if dtype in ("f32", "f16x3") else t.to(TD[dtype]).float()
+
+
+def round_to(t, store):
+    """One round-to-nearest-even of an fp64 (or fp32) tensor into the torch dtype `store`, back as fp32: for ops whose stored type is not
+    the plan's (H3D_OUT_NHWC_F16 in a bf16 plan).  The lattice values are exact in fp32, so the conversion rounds once whichever way torch
+    takes from fp64."""
+    return t.to(store).float()
 
 
 def _ints(key, shape, lo, hi):
@@ -230,6 +241,95 @@ def upadd_operands(B, C, h, w, f):
 def exact_upadd(x, skip, w, f, dtype):
     y = F.conv_transpose2d(x.double(), w.double(), None, stride=f, padding=f // 2, groups=x.shape[1]) + skip.double()
     return lowp_round(y, dtype)
+
+
+# ---- up-sample + add folded into the DeformConv that writes its skip (H3D_OPF_UPADD_FOLDED) ---------------------------------------------
+# out = round_out( up(x_lo) + round_node( relu(dcn_pre) ) ): the node value is rounded to the plan's type where the kernel packs it into
+# LDS, the sum once more to the stored type (bf16 -> bf16, bf16 -> fp16 with H3D_OUT_NHWC_F16, fp16 -> fp16).  x_lo in -3..3, taps on k/8,
+# node values integers: every product and every partial sum is a multiple of 1/8 below 2^10, exact in fp32 in any order.
+FOLD_DEFECTS = ("swap_rx_ry", "clamp_border", "group0_taps", "image0_map")
+FOLD_UNIT = 1.0 / 8.0
+
+
+def fold_operands(B, Ci, Co, H, W, f):
+    """(x, w, b, wo, bo, x_lo, w_up): the producer operands of `dcn_operands(B, Ci, Co, H, W)`, then the low-resolution map [B, Co, H/f, W/f]
+    and the depthwise taps [Co, 1, 2f, 2f] of `upadd_operands(B, Co, H // f, W // f, f)` (whose `skip` is not used: the skip is the producer's
+    result)."""
+    x_lo, _, w_up = upadd_operands(B, Co, H // f, W // f, f)
+    return dcn_operands(B, Ci, Co, H, W) + (x_lo, w_up)
+
+
+@functools.lru_cache(maxsize=None)
+def fold_pre(B, Ci, Co, H, W):
+    """fp64 DeformConv output before ReLU of `dcn_operands(B, Ci, Co, H, W)`; computed once per producer shape."""
+    return dcn_pre(*dcn_operands(B, Ci, Co, H, W))
+
+
+def fold_node(pre, node_dtype):
+    """The producer's own result as the kernel holds it before the add: ReLU, rounded once to the plan's type."""
+    return round_to(F.relu(pre.double()), node_dtype)
+
+
+def exact_fold(x_lo, w_up, pre, f, node_dtype, out_dtype):
+    """The folded pair's output: fp64 depthwise transposed conv of the low-resolution map + the rounded node value, rounded once to the
+    stored type.  node_dtype / out_dtype: torch dtypes."""
+    up = F.conv_transpose2d(x_lo.double(), w_up.double(), None, stride=f, padding=f // 2, groups=x_lo.shape[1])
+    return round_to(up + fold_node(pre, node_dtype).double(), out_dtype)
+
+
+def fold_restated(x_lo, w_up, pre, f, node_dtype, out_dtype, defect=None, acc_dtype=torch.float64, rounded=True):
+    """`exact_fold` restated the way the kernels walk it (csrc/epilogue.h upadd_vec): per output pixel the two contributing rows and columns
+    iy0 - a, ix0 - c2 with iy0 = (oy + f/2) / f, their table rows (ry + a f) * 2f + rx + c2 f with ry = (oy + f/2) % f, acc = 0, the valid taps
+    (a, c2) ascending as acc += w * x (an invalid tap is skipped), then + node -- equal to `exact_fold` bit for bit (in fp32 too:
+    acc_dtype=torch.float32; a lattice product is exact, so a fused multiply-add gives the same) -- with one defect on request:
+      swap_rx_ry    ry and rx exchanged in the tap-table index;
+      clamp_border  an invalid border tap is read from the clamped pixel instead of being skipped;
+      group0_taps   channels >= 64 use the tap rows of channel c - 64 (a workgroup's cout0 left out of the table offset);
+      image0_map    images b > 0 read image 0 of the low-resolution map (the per-image base left out).
+    rounded=False: the sum before the final rounding, in acc_dtype."""
+    assert defect is None or defect in FOLD_DEFECTS, defect
+    B, C, h, w = x_lo.shape
+    k, p = 2 * f, f // 2
+    oy, ox = torch.arange(h * f), torch.arange(w * f)
+    ry, iy0, rx, ix0 = (oy + p) % f, (oy + p) // f, (ox + p) % f, (ox + p) // f
+    table = w_up.to(acc_dtype).reshape(C, k, k)
+    if defect == "group0_taps":
+        table = torch.cat([table[:64]] + [table[c0 - 64:c0 - 64 + min(64, C - c0)] for c0 in range(64, C, 64)])
+    xs = x_lo.to(acc_dtype)
+    if defect == "image0_map":
+        xs = xs[:1].expand(B, C, h, w)
+    acc = torch.zeros(B, C, h * f, w * f, dtype=acc_dtype)
+    for a in range(2):
+        for c2 in range(2):
+            iy, ix, ki, kj = iy0 - a, ix0 - c2, ry + a * f, rx + c2 * f
+            ok = ((iy >= 0) & (iy < h)).view(-1, 1) & ((ix >= 0) & (ix < w)).view(1, -1)
+            if defect == "clamp_border":
+                ok = torch.ones_like(ok)
+            xv = xs[:, :, iy.clamp(0, h - 1)][:, :, :, ix.clamp(0, w - 1)]
+            if defect == "swap_rx_ry":
+                wt = table[:, rx + a * f][:, :, ry + c2 * f].transpose(1, 2)         # row index from the column's phase and the reverse
+            else:
+                wt = table[:, ki][:, :, kj]
+            acc = torch.where(ok.view(1, 1, h * f, w * f), acc + wt.unsqueeze(0) * xv, acc)
+    acc = acc + fold_node(pre, node_dtype).to(acc_dtype)
+    return round_to(acc, out_dtype) if rounded else acc
+
+
+@functools.lru_cache(maxsize=None)
+def fold_chain_operands(Ci, Co):
+    """(w, b, wo, bo) of a DeformConv that READS a folded pair's output (multiples of 1/8, no integers): zero offset filters and integer
+    offset biases in -2..2, so every pixel of a tap samples at the same integer displacement whatever the input holds, bilinear weights 0
+    or 1, masks as in `dcn_operands`.  A sample is then an input value itself (exact in the fp16 blend), and the contraction with w in
+    {-1, 0, 1} sums multiples of 1/8 below 2^18: exact in fp32 in any order."""
+    w = lattice_w((Co, Ci, 3, 3), "lcw")
+    b = lattice_bias(Co, "lcb")
+    wo = torch.zeros(27, Ci, 3, 3)
+    bo = torch.zeros(27)
+    bo[:18] = _ints("lco", (18,), -2, 2)
+    on = _ints("lcm", (9,), 0, 3)
+    bo[18:] = torch.where(on > 0, torch.tensor(DCN_MASK_ON), torch.tensor(DCN_MASK_OFF))
+    bo[18 + 4] = DCN_MASK_ON
+    return w, b, wo, bo
 
 
 # ---- fused DeformConv with integer offsets ------------------------------------------------------------------------------------------

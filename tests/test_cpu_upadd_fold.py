@@ -1,6 +1,6 @@
 """Plan.FLAGS fold_upadd on the CPU (the lowering is host code): which H3D_OP_UPADD ops carry H3D_OPF_UPADD_FOLDED, that each stands where
-the run loop can take it together with the DeformConv that writes its skip, that nothing else reads that skip, and that the flag off is
-the default plan."""
+the run loop can take it together with the DeformConv that writes its skip, that nothing else reads that skip, that the flag off is
+the default plan, and that every folded pair of the plans the product runs has an exact lattice case in tests/test_gpu_upadd_fold.py."""
 import ctypes
 import importlib.util
 import os
@@ -81,6 +81,24 @@ def test_f16_plan_folds_the_same_four(builder):
     folded = [i for i, op in enumerate(ops) if op.kind == _lib.OP_UPADD and op.reserved & _lib.OPF_UPADD_FOLDED]
     assert len(folded) == 4 and all(ops[i - 1].kind == _lib.OP_DCN_FUSED_STREAM and ops[i - 1].out == ops[i].in2 and ops[i].out_mode == _lib.OUT_NHWC
                                     for i in folded)
+
+
+@pytest.mark.parametrize("dtype", ["bf16", "f16"])
+@pytest.mark.parametrize("B,H,W", [(64, 512, 512), (32, 512, 512), (16, 512, 512), (8, 512, 512), (2, 64, 96)])
+def test_every_folded_pair_of_the_plans_has_a_lattice_case(builder, dtype, B, H, W):
+    """What decides the code a folded pair runs -- the producer's kernel, the plan's dtype, f, Cout, the UPADD's out_mode and whether the
+    low-resolution map is exactly C wide -- is among the tuples tests/test_gpu_upadd_fold.py's FOLD_CASES dispatch to (the folding twins
+    have no name of their own in h3d_op_kernel_name, so the kernel-name coverage tests cannot see them)."""
+    import test_gpu_upadd_fold as G
+    tested = G.folded_dispatches()
+    pw, _ = builder.packer("dla34", dtype)
+    ops = list(Plan(pw, B, H, W, fold_upadd=True).op_array)
+    folded = [i for i, op in enumerate(ops) if op.kind == _lib.OP_UPADD and op.reserved & _lib.OPF_UPADD_FOLDED]
+    assert len(folded) == 4
+    for i in folded:
+        up = ops[i]
+        key = (dump_plans.kernel_name(ops[i - 1]), dtype, up.stride, up.Cout, up.out_mode, up.in_cs == up.Cin)
+        assert key in tested, "no lattice case dispatches to the folded pair %s" % (key,)
 
 
 @pytest.mark.parametrize("B,H,W", SHAPES)
