@@ -68,27 +68,33 @@ struct HeadsArgs {
     int l_head[HEADS_LISTS_MAX][HEADS_MAX];
 };
 
-template <typename T, int TH>
-struct HeadsCfg {
-    static constexpr int TW = 32;
+// What the dense tile (HeadsCfg) and both sparse layouts (HeadsSparseCfg, HeadsSparseRegCfg) share: filter ring, 1x1 slice, bias pairs, pixel stride
+template <typename T>
+struct HeadsRingCfg {
     static constexpr int ES = sizeof(T);
-    static constexpr int NT = TH / 8;                 // N-tiles (rows of 32 pixels) per wave, 8 waves
-    static constexpr int NW = 8;                      // waves of the workgroup
-    static constexpr int IN_H = TH + 2, IN_W = TW + 2;
     static constexpr int SB = HC_IN * ES + 16;        // halo pixel stride (padded: register-staged once)
-    static constexpr int RB = IN_W * SB;              // halo row stride
     static constexpr int RBW = HC_IN * ES;            // weight row bytes (64 K elements), UNPADDED: LDS-DMA image
     static constexpr int CPR = RBW / 16;              // 16-byte chunks per weight row (8 bf16 / 16 f32)
     static constexpr int SWZ_SHIFT = ES == 2 ? 1 : 0; // chunk' = chunk ^ ((row >> SWZ_SHIFT) & (CPR-1))
     static constexpr int TAPS = ES == 2 ? 3 : 1;      // taps per stage (f32: LDS only fits one)
     static constexpr int TRS = 9 / TAPS;              // stages per slab
     static constexpr int SLOT = TAPS * HC_SLAB * RBW; // ring slot bytes
-    static constexpr int LDS_IN = IN_H * RB;
     static constexpr int LDS_W2 = 32 * HC_MT2 * RBW;  // 96 rows
     static constexpr int LDS_BIAS = 1024 + 1024;      // per head: b1 (<= 256 floats) + b2 (96 floats; its DMA piece writes a whole KiB), two heads in flight
-    static constexpr int LDS = LDS_IN + 2 * SLOT + LDS_W2 + 2 * LDS_BIAS;
     static constexpr int RPI = 1024 / RBW;            // weight rows per LDS-DMA wave-instruction
     static constexpr int VPR = HC_IN * ES / 16;       // 16-byte vectors per halo pixel
+};
+
+template <typename T, int TH>
+struct HeadsCfg : HeadsRingCfg<T> {
+    using R = HeadsRingCfg<T>;
+    static constexpr int TW = 32;
+    static constexpr int NT = TH / 8;                 // N-tiles (rows of 32 pixels) per wave, 8 waves
+    static constexpr int NW = 8;                      // waves of the workgroup
+    static constexpr int IN_H = TH + 2, IN_W = TW + 2;
+    static constexpr int RB = IN_W * R::SB;           // halo row stride
+    static constexpr int LDS_IN = IN_H * RB;
+    static constexpr int LDS = LDS_IN + 2 * R::SLOT + R::LDS_W2 + 2 * R::LDS_BIAS;
 };
 
 // Sparse launches (h3d_heads_sparse_lists): the heads at LISTS of output positions instead of a tile; a workgroup's positions come from
@@ -99,22 +105,19 @@ struct HeadsCfg {
 // stage code, gemm2 and the epilogue are the dense kernel's at NT = 1.  The other waves only help with the LDS-DMA of the
 // filters (an LDS-DMA instruction costs its wave 100-185 issue cycles; a stage is 24 MFMAs per computing wave here).
 template <typename T>
-struct HeadsSparseCfg {
-    using D = HeadsCfg<T, 16>;
+struct HeadsSparseCfg : HeadsRingCfg<T> {
+    using D = HeadsRingCfg<T>;
     static_assert(sizeof(T) == 2, "sparse heads: 2-byte plans");
-    static constexpr int ES = D::ES, NT = 1, TW = D::TW;
+    static constexpr int NT = 1, TW = 32;
     static constexpr int CW = 2, NW = HEADS_SPARSE_NW;   // computing waves | waves of the workgroup
     static constexpr int NPOS = 32 * CW;              // positions per workgroup
-    static constexpr int SB = D::SB, RB = 3 * SB, PB = 3 * RB;   // pixel | patch row | patch (position) stride
-    static constexpr int RBW = D::RBW, CPR = D::CPR, SWZ_SHIFT = D::SWZ_SHIFT, TAPS = D::TAPS, TRS = D::TRS, SLOT = D::SLOT;
+    static constexpr int RB = 3 * D::SB, PB = 3 * RB; // patch row | patch (position) stride
     static constexpr int LDS_IN = NPOS * PB;
-    static constexpr int LDS_W2 = D::LDS_W2, LDS_BIAS = D::LDS_BIAS;
-    static constexpr int LDS = LDS_IN + 2 * SLOT + LDS_W2 + 2 * LDS_BIAS;
-    static constexpr int RPI = D::RPI, VPR = D::VPR;
+    static constexpr int LDS = LDS_IN + 2 * D::SLOT + D::LDS_W2 + 2 * D::LDS_BIAS;
     static_assert(LDS <= 160 * 1024, "LDS of a CU");
 };
 
-// 16-byte LDS read the compiler's wait-count pass does not see (see heads_kernel's stage): the caller waits.
+// 16-byte LDS read the compiler's wait-count pass does not see (see stage_pipelined): the caller waits.
 template <int OFF>
 __device__ __forceinline__ void lds_read16_async(u32x4 &dst, uint32_t addr)
 {
@@ -125,6 +128,36 @@ template <class F, int... I>
 __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, class F>
 __device__ __forceinline__ void static_for(F &&f) { static_for_impl(f, std::make_integer_sequence<int, N>{}); }
+
+// (one tile: with the loops over a kernel's tiles in here too, hipcc allocates the dense kernels' registers differently)
+__device__ __forceinline__ void zero_tile(f32x16 &t)
+{
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t[i] = 0.f;
+}
+
+// Sparse launches: the list that owns workgroup `bid` (the lists start on workgroup boundaries, HeadsArgs::l_wg0) and the
+// workgroup's index among that list's workgroups ...
+struct HeadsList { int li, lb, ng, K; const long long *inds; };   // (ng: heads_sparse_kernel's workgroups per head, HeadsArgs::l_ng)
+__device__ __forceinline__ HeadsList heads_list_of(const HeadsArgs &a, int bid)
+{
+    int li = 0;
+#pragma unroll
+    for (int i = 1; i < HEADS_LISTS_MAX; ++i)
+        if (i < a.nlists && bid >= a.l_wg0[i]) li = i;
+    return {li, bid - a.l_wg0[li], a.l_ng[li], a.l_K[li], a.l_inds[li]};
+}
+// ... and entry p of the list as a position of the maps; an entry past the list or outside the map is not `ok`: it stores nothing
+struct HeadsPos { bool ok; int b, y, x; };
+__device__ __forceinline__ HeadsPos heads_position(const HeadsArgs &a, const HeadsList &ls, int p)
+{
+    HeadsPos q = {false, 0, 0, 0};
+    if (p < a.B * ls.K) {
+        const long long ind = ls.inds[p];
+        if (ind >= 0 && ind < (long long)a.H * a.W) { q.ok = true; q.b = p / ls.K; q.y = (int)ind / a.W; q.x = (int)ind - q.y * a.W; }
+    }
+    return q;
+}
 
 // Biases of one head -> LDS by LDS-DMA (wave 0: b1[head_conv] <= 1 KiB, wave 1: b2[96]); lanes past the end of either
 // array carry offsets outside the buffer and write zeros.  Reading them from global memory where they are used put
@@ -222,6 +255,78 @@ __device__ __forceinline__ void gemm2(f32x16 (&acc)[2][NT], f32x16 (&acc2)[M2][N
     }
 }
 
+// The bias tile of accumulator tile m of a slab goes from LDS (s_b1: the head's b1) straight INTO the accumulators (accumulator
+// row = channel).  Round 3 built it in 32 registers first and copied it into each N-tile: those 32 registers were live together
+// with the fragment pipeline and pushed the 3-tile body into scratch (256 VGPRs + 24-36 bytes spilled)
+__device__ __forceinline__ void load_bias(f32x16 &dst, const char *s_b1, int slab, int m, int h)
+{
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 bv = *reinterpret_cast<const f32x4 *>(s_b1 + (slab * HC_SLAB + m * 32 + 8 * g + 4 * h) * 4);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dst[4 * g + i] = bv[i];
+    }
+}
+
+// One tap-row stage of the 2-byte kernels as an explicit software pipeline (bf16, narrow heads: the 3-tile instantiation spills
+// with it, in the 2-tile one it measures the same as the compiler's schedule: 0.279 / 0.287 vs 0.280 ms at depth 2 / 1).  The
+// fragments of step i+1 (a step = one tap x 16 channels: 2 filter + NT pixel fragments feeding 2*NT MFMAs) are requested BEFORE
+// the MFMAs of step i and waited for with a counted s_waitcnt.  Left to itself hipcc issues every ds_read right in front of its
+// MFMA behind lgkmcnt(0) -- and does so even when the loads are hoisted in the source -- so the reads are inline asm (invisible
+// to its wait-count pass) and the waits are ours: LDS returns in order, the NT + 2 reads (2 with B in registers) of each of the
+// PF newer steps may stay in flight.  sched_barrier pins the MFMAs behind their wait.
+// B: where the pixel fragments come from.  A uint32_t is the LDS address of this lane's fragment of tap 0, K-group 0, N-tile 0 in
+// an image of row stride C::RB and pixel stride C::SB (the halo tile, the patches of heads_kernel<SPARSE>): NT more reads per
+// step.  Otherwise b is an array of fragments in registers (heads_sparse_kernel, NT = 1) and step i multiplies b[BOFF + i].
+// FIRST: the slab's first MFMA of every accumulator tile takes its C operand from the bias tile.
+template <typename T, class C, int NT, int PF, bool FIRST, int BOFF = 0, class B>
+__device__ __forceinline__ void stage_pipelined(f32x16 (&acc)[2][NT], const char *slot, const B &b, const char *s_b1, int slab, int r, int h, int sw)
+{
+    using E = ET<T>;
+    constexpr bool B_LDS = std::is_same_v<B, uint32_t>;
+    static_assert(B_LDS || NT == 1, "fragments in registers: one N-tile");
+    constexpr int NSTEP = C::TAPS * (HC_IN / 16), NBUF = PF + 1;   // steps of the stage | fragment sets: PF steps in flight ahead of the MFMAs
+    constexpr int NRD = 2 + (B_LDS ? NT : 0);                      // LDS reads of a step
+    static_assert(PF * NRD <= 15, "lgkmcnt field");
+    const uint32_t ring = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)slot + r * C::RBW;
+    uint32_t fa_base[HC_IN / 16];
+#pragma unroll
+    for (int kk = 0; kk < HC_IN / 16; ++kk) fa_base[kk] = ring + (((2 * kk + h) ^ sw) << 4);
+    u32x4 fa[NBUF][2], fb[B_LDS ? NBUF : 1][NT];
+    auto fetch = [&](auto step_tag) {
+        constexpr int STEP = decltype(step_tag)::value, BUF = STEP % NBUF;
+        constexpr int tp = STEP / (HC_IN / 16), kk = STEP - tp * (HC_IN / 16);
+        lds_read16_async<(tp * HC_SLAB) * C::RBW>(fa[BUF][0], fa_base[kk]);
+        lds_read16_async<(tp * HC_SLAB + 32) * C::RBW>(fa[BUF][1], fa_base[kk]);
+        if constexpr (B_LDS) {
+            static_for<NT>([&](auto n_tag) {
+                constexpr int n = decltype(n_tag)::value;
+                lds_read16_async<n * C::RB + tp * C::SB + kk * 32>(fb[BUF][n], b);
+            });
+        }
+    };
+    static_for<PF>([&](auto step_tag) { fetch(step_tag); });
+    static_for<NSTEP>([&](auto step_tag) {
+        constexpr int STEP = decltype(step_tag)::value, BUF = STEP % NBUF;
+        if constexpr (STEP + PF < NSTEP) fetch(std::integral_constant<int, STEP + PF>{});
+        constexpr int NEWER = (STEP + PF < NSTEP ? PF : NSTEP - 1 - STEP) * NRD;        // reads issued after step STEP's
+        __builtin_amdgcn_s_waitcnt(0xc07f | (NEWER << 8));                              // lgkmcnt(NEWER)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int n = 0; n < NT; ++n) {
+                if (FIRST && STEP == 0) { load_bias(acc[m][n], s_b1, slab, m, h); }
+                typename E::frag a_, b_;
+                a_.v = fa[BUF][m];
+                if constexpr (B_LDS) b_.v = fb[BUF][n];
+                else b_.v = b[BOFF + STEP];
+                E::mma(acc[m][n], a_, b_);
+            }
+        __builtin_amdgcn_sched_barrier(0);
+    });
+}
+
 // LDS-DMA of one weight stage / one 1x1 slice in the BUFFER form: per-lane 32-bit offsets that do not depend on the stage
 // (row, tap and swizzled chunk of the lane's 16 bytes) + a scalar stage offset, instead of a 64-bit per-lane address rebuilt
 // for every piece (global_load_lds): an LDS-DMA instruction costs its wave 100-185 issue cycles as it is, and the address
@@ -264,6 +369,45 @@ __device__ __forceinline__ void heads_dma_w2(const char *w2, int head_conv, char
     }
 }
 
+// Profiling build (make ABLATE=1, tools/stamp_heads.py): where heads_kernel's cycles go, per workgroup.  begin() ... end_x() brackets
+// one phase of the stage loop; every member is empty in the production build.
+struct HeadsTimers {
+#ifdef H3D_ABLATE
+    static __device__ __forceinline__ unsigned long long now() { return __builtin_readcyclecounter(); }
+    unsigned long long t_bar = 0, t_g2 = 0, t_dma = 0, t_stage = 0, t0 = 0;
+    const unsigned long long t_start = now();
+    __device__ __forceinline__ void begin() { t0 = now(); }
+    __device__ __forceinline__ void end_stage()   // + the wave's own DMA pieces of the next stage, to tell DMA wait from barrier wait
+    {
+        t_stage += now() - t0;
+        t0 = now();
+        __builtin_amdgcn_s_waitcnt(0x0f70);
+        const unsigned long long t1 = now();
+        t_dma += t1 - t0;
+        t0 = t1;
+    }
+    __device__ __forceinline__ void end_barrier() { t_bar += now() - t0; }
+    __device__ __forceinline__ void end_gemm2() { t_g2 += now() - t0; }
+    // stamps of the workgroup: {kernel start, end, cycles wave 0 spent in the stage barriers, in gemm2, waiting for its own DMA pieces, in the stages}
+    __device__ __forceinline__ void store(const HeadsArgs &a, int tid, int wv, int l) const
+    {
+        if (!a.stamps || blockIdx.x >= 65536) return;
+        unsigned long long *st = a.stamps + blockIdx.x * H3D_NSTAMP;
+        if (a.dbg & 64) {                       // per-wave barrier time instead (tools/stamp_heads.py --waves)
+            if (l == 0) st[wv] = t_bar;
+        } else if (tid == 0) {
+            st[0] = t_start; st[1] = now(); st[2] = t_bar; st[3] = t_g2; st[4] = t_dma; st[5] = t_stage;
+        }
+    }
+#else
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ void end_stage() {}
+    __device__ __forceinline__ void end_barrier() {}
+    __device__ __forceinline__ void end_gemm2() {}
+    __device__ __forceinline__ void store(const HeadsArgs &, int, int, int) const {}
+#endif
+};
+
 // SPARSE: the workgroup's "tile" is 32 * CW entries of ONE of the position lists (HeadsSparseCfg); everything per position -- operands,
 // the order of every accumulator's MFMA chain, the epilogue -- is the dense code, so the value is the dense launch's bit for bit.
 template <typename T, int TH, int M2, bool BIASC, bool MIXED = false, bool SPARSE = false>
@@ -289,15 +433,16 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
     const int oy0 = ty * TH, ox0 = tx * C::TW;
     const int slabs = a.head_conv / HC_SLAB;
     // sparse: this workgroup's list (they start on workgroup boundaries), its index among the list's workgroups, the list's heads
+    // (heads_list_of and, below, heads_position of this lane, written out: called here they move the register allocation of this
+    // instantiation by one or two VGPRs; the patch staging and heads_sparse_kernel call them)
     [[maybe_unused]] int li = 0;
     if constexpr (SPARSE) {
 #pragma unroll
         for (int i = 1; i < HEADS_LISTS_MAX; ++i)
             if (i < a.nlists && bid >= a.l_wg0[i]) li = i;
     }
-    [[maybe_unused]] const int lb = SPARSE ? bid - a.l_wg0[li] : 0, sp_K = SPARSE ? a.l_K[li] : 0;
-    [[maybe_unused]] const long long *sp_inds = SPARSE ? a.l_inds[li] : nullptr;
-    const int nh = SPARSE ? a.l_nh[li] : a.nheads;       // heads this workgroup runs: the hi-th one is head_at(hi) of the descriptor
+    [[maybe_unused]] const HeadsList ls = {li, SPARSE ? bid - a.l_wg0[li] : 0, 0, SPARSE ? a.l_K[li] : 0, SPARSE ? a.l_inds[li] : nullptr};
+    const int nh = SPARSE ? a.l_nh[li] : a.nheads;      // heads this workgroup runs: the hi-th one is head_at(hi) of the descriptor
     auto head_at = [&](int hi) -> int {
         if constexpr (SPARSE) return a.l_head[li][hi];
         else return hi;
@@ -327,27 +472,26 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
     issue_w1(0);
     heads_issue_bias(a.b1 + head_at(0) * a.head_conv, a.head_conv, a.b2[head_at(0)], s_bias, __builtin_amdgcn_readfirstlane(wv), l);
     // sparse: this lane's position (computing waves; an entry past the list or outside the map stores nothing) and whether the wave computes
-    [[maybe_unused]] int sp_b = 0, sp_y = 0, sp_x = 0;
-    [[maybe_unused]] bool sp_ok = false, idle = false;
+    [[maybe_unused]] HeadsPos sp = {false, 0, 0, 0};
+    [[maybe_unused]] bool idle = false;
     if constexpr (SPARSE) {
         idle = wvs >= C::CW;
-        const int p = lb * C::NPOS + wv * 32 + r;
-        if (!idle && p < a.B * sp_K) {
-            const long long ind = sp_inds[p];
-            if (ind >= 0 && ind < (long long)a.H * a.W) { sp_ok = true; sp_b = p / sp_K; sp_y = (int)ind / a.W; sp_x = (int)ind - sp_y * a.W; }
+        const int p = ls.lb * C::NPOS + wv * 32 + r;
+        if (!idle && p < a.B * ls.K) {
+            const long long ind = ls.inds[p];
+            if (ind >= 0 && ind < (long long)a.H * a.W) { sp.ok = true; sp.b = p / ls.K; sp.y = (int)ind / a.W; sp.x = (int)ind - sp.y * a.W; }
         }
         // the 3x3 neighbourhood of every position (all 64 channels, zero outside the image, as the dense halo)
         constexpr int NPV = C::NPOS * 9 * C::VPR;
         stage_vectors<NPV, 64 * C::NW>(
             tid,
             [&](int i) -> u32x4 {
-                const int v = i % C::VPR, q = i / C::VPR, pix = q % 9, p = lb * C::NPOS + q / 9;
-                if (p >= a.B * sp_K) return u32x4{0u, 0u, 0u, 0u};
-                const long long ind = sp_inds[p];
-                if (ind < 0 || ind >= (long long)a.H * a.W) return u32x4{0u, 0u, 0u, 0u};
-                const int y = (int)ind / a.W, gy = y - 1 + pix / 3, gx = (int)ind - y * a.W - 1 + pix % 3;
+                const int v = i % C::VPR, q = i / C::VPR, pix = q % 9;
+                const HeadsPos c = heads_position(a, ls, ls.lb * C::NPOS + q / 9);
+                if (!c.ok) return u32x4{0u, 0u, 0u, 0u};
+                const int gy = c.y - 1 + pix / 3, gx = c.x - 1 + pix % 3;
                 if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W)
-                    return *reinterpret_cast<const u32x4 *>(a.in + (((size_t)(p / sp_K) * a.H * a.W + (size_t)gy * a.W + gx) * a.in_cs) * ES + v * 16);
+                    return *reinterpret_cast<const u32x4 *>(a.in + (((size_t)c.b * a.H * a.W + (size_t)gy * a.W + gx) * a.in_cs) * ES + v * 16);
                 return u32x4{0u, 0u, 0u, 0u};
             },
             [&](int i, u32x4 val) {
@@ -392,10 +536,7 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
         else boff[n] = (wv * NT + n) * C::RB + r * C::SB + 8 * h * ES;
     }
 
-#ifdef H3D_ABLATE
-    unsigned long long t_bar = 0, t_g2 = 0, t_dma = 0, t_stage = 0;
-    const unsigned long long t_start = __builtin_readcyclecounter();
-#endif
+    HeadsTimers tm;
     int s = 0;
     // one head: M2H = 32-row tiles of ITS 1x1 output.  MIXED launches (all heads of the model in one launch, so that the halo
     // tile is staged once per workgroup for all of them) instantiate the body for every width up to M2 and pick per head
@@ -405,34 +546,17 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
         const char *s_b = s_bias + (hi & 1) * C::LDS_BIAS;
         f32x16 acc[2][NT], acc2[M2H][NT];
 #pragma unroll
-        for (int m = 0; m < 2; ++m)
+        for (int n = 0; n < NT; ++n) {
 #pragma unroll
-            for (int n = 0; n < NT; ++n)
+            for (int m = 0; m < 2; ++m) zero_tile(acc[m][n]);
 #pragma unroll
-                for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.f;
-#pragma unroll
-        for (int m = 0; m < M2H; ++m)
-#pragma unroll
-            for (int n = 0; n < NT; ++n)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc2[m][n][i] = 0.f;
+            for (int m = 0; m < M2H; ++m) zero_tile(acc2[m][n]);
+        }
         for (int slab = 0; slab < slabs; ++slab) {
             // one tap-row stage; FIRST: the slab's first MFMA of every accumulator tile takes its C operand from the
             // bias tile (accumulator row = channel), so neither a zeroing pass nor a bias pass exists
             auto stage = [&](auto first_tag, const char *slot, int tr) {
                 constexpr bool FIRST = decltype(first_tag)::value;
-                // the bias tile goes from LDS straight INTO the accumulators (accumulator row = channel).  Round 3 built it in 32
-                // registers first and copied it into each N-tile: those 32 registers were live together with the fragment
-                // pipeline and pushed the 3-tile body into scratch (256 VGPRs + 24-36 bytes spilled)
-                auto load_bias = [&](f32x16 &dst, int m) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x4 bv = *reinterpret_cast<const f32x4 *>(s_b + (slab * HC_SLAB + m * 32 + 8 * g + 4 * h) * 4);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) dst[4 * g + i] = bv[i];
-                    }
-                };
-                constexpr int NSTEP = C::TAPS * (HC_IN / 16);
                 auto plain = [&]() {
 #pragma unroll
                     for (int tp = 0; tp < C::TAPS; ++tp) {
@@ -454,59 +578,18 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
                             for (int m = 0; m < 2; ++m)
 #pragma unroll
                                 for (int n = 0; n < NT; ++n) {
-                                    if (FIRST && tp == 0 && kk == 0) { load_bias(acc[m][n], m); }
+                                    if (FIRST && tp == 0 && kk == 0) { load_bias(acc[m][n], s_b, slab, m, h); }
                                     E::mma(acc[m][n], fa[m], fb[n]);
                                 }
                         }
                     }
-                                };
+                };
                 // (two levels: inside this generic lambda only a condition that does not depend on M2H keeps the fp32
                 // instantiation from type-checking the 2-byte fragment code)
                 if constexpr (ES == 2) {
                 if constexpr ((M2H == 1 && HEADS_PF > 0) || (M2H > 1 && HEADS_PF_WIDE > 0)) {
-                    // bf16, narrow heads (the 3-tile instantiation spills with it, in the 2-tile one it measures the same as the
-                    // compiler's schedule: 0.279 / 0.287 vs 0.280 ms at depth 2 / 1): explicit software pipeline.  The fragments of step i+1 (a step = one tap x 16 channels: 2 filter
-                    // + NT pixel fragments feeding 2*NT MFMAs) are requested BEFORE the MFMAs of step i and waited for with a
-                    // counted s_waitcnt.  Left to itself hipcc issues every ds_read right in front of its MFMA behind
-                    // lgkmcnt(0) -- and does so even when the loads are hoisted in the source -- so the reads are inline asm
-                    // (invisible to its wait-count pass) and the waits are ours: LDS returns in order, NT + 2 newer reads
-                    // may stay in flight.  sched_barrier pins the MFMAs behind their wait.
-                    const uint32_t ring = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)slot + r * C::RBW;
-                    uint32_t fa_base[HC_IN / 16];
-#pragma unroll
-                    for (int kk = 0; kk < HC_IN / 16; ++kk) fa_base[kk] = ring + (((2 * kk + h) ^ sw) << 4);
                     const uint32_t fb_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)s_in + boff[0] + tr * C::RB;
-                    constexpr int PF = M2H == 1 ? HEADS_PF : HEADS_PF_WIDE, NBUF = PF + 1;          // steps in flight ahead of the MFMAs
-                    static_assert(PF * (NT + 2) <= 15, "lgkmcnt field");
-                    u32x4 fa[NBUF][2], fb[NBUF][NT];
-                    auto fetch = [&](auto step_tag) {
-                        constexpr int STEP = decltype(step_tag)::value, BUF = STEP % NBUF;
-                        constexpr int tp = STEP / (HC_IN / 16), kk = STEP - tp * (HC_IN / 16);
-                        lds_read16_async<(tp * HC_SLAB) * C::RBW>(fa[BUF][0], fa_base[kk]);
-                        lds_read16_async<(tp * HC_SLAB + 32) * C::RBW>(fa[BUF][1], fa_base[kk]);
-                        static_for<NT>([&](auto n_tag) {
-                            constexpr int n = decltype(n_tag)::value;
-                            lds_read16_async<n * C::RB + tp * C::SB + kk * 32>(fb[BUF][n], fb_base);
-                        });
-                    };
-                    static_for<PF>([&](auto step_tag) { fetch(step_tag); });
-                    static_for<NSTEP>([&](auto step_tag) {
-                        constexpr int STEP = decltype(step_tag)::value, BUF = STEP % NBUF;
-                        if constexpr (STEP + PF < NSTEP) fetch(std::integral_constant<int, STEP + PF>{});
-                        constexpr int NEWER = (STEP + PF < NSTEP ? PF : NSTEP - 1 - STEP) * (NT + 2);   // reads issued after step STEP's
-                        __builtin_amdgcn_s_waitcnt(0xc07f | (NEWER << 8));                              // lgkmcnt(NEWER)
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int m = 0; m < 2; ++m)
-#pragma unroll
-                            for (int n = 0; n < NT; ++n) {
-                                if (FIRST && STEP == 0) { load_bias(acc[m][n], m); }
-                                typename E::frag a_, b_;
-                                a_.v = fa[BUF][m]; b_.v = fb[BUF][n];
-                                E::mma(acc[m][n], a_, b_);
-                            }
-                        __builtin_amdgcn_sched_barrier(0);
-                    });
+                    stage_pipelined<T, C, NT, (M2H == 1 ? HEADS_PF : HEADS_PF_WIDE), FIRST>(acc, slot, fb_base, s_b, slab, r, h, sw);
                 } else {
                     plain();
                 }
@@ -539,7 +622,7 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
                         for (int m = 0; m < 2; ++m)
 #pragma unroll
                             for (int n = 0; n < NT; ++n) {
-                                if (FIRST && kk == 0) { load_bias(acc[m][n], m); }
+                                if (FIRST && kk == 0) { load_bias(acc[m][n], s_b, slab, m, h); }
                                 E::mma(acc[m][n], fa[kk & 1][m], fb[kk & 1][n]);
                             }
                         if (kk + 1 < HC_IN / 16) {
@@ -565,49 +648,33 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
                     heads_issue_bias(a.b1 + head_at(hi + 1) * a.head_conv, a.head_conv, a.b2[head_at(hi + 1)],   // previous head's epilogue, at least one barrier ago
                                      s_bias + ((hi + 1) & 1) * C::LDS_BIAS, __builtin_amdgcn_readfirstlane(wv), l);
                 const char *slot = s_ring + (s & 1) * C::SLOT;
-#ifdef H3D_ABLATE
-                const unsigned long long ts0 = __builtin_readcyclecounter();
-#endif
+                tm.begin();
                 if (SPARSE && idle) { /* a wave that only moves filters */ }
                 else if ((H3D_DBG(a) & 4) && wv >= 4) { /* profiling: only the older wave of each SIMD computes (timing only) */ }
                 else if ((H3D_DBG(a) & 8) && wv < 4) { /* profiling: only the younger wave computes */ }
                 else if (BIASC && tr == 0) stage(std::true_type{}, slot, tr);
                 else stage(std::false_type{}, slot, tr);
-#ifdef H3D_ABLATE
-                t_stage += __builtin_readcyclecounter() - ts0;
-#endif
-#ifdef H3D_ABLATE
-                const unsigned long long tb0 = __builtin_readcyclecounter();
-                __builtin_amdgcn_s_waitcnt(0x0f70);          // my own DMA pieces of the next stage
-                const unsigned long long tb1 = __builtin_readcyclecounter();
-                t_dma += tb1 - tb0;
-#endif
+                tm.end_stage();
                 if (!(H3D_DBG(a) & 2))   // (profiling: 2 = no stage barrier -- wrong results, timing only)
                 __syncthreads();   // vmcnt(0) + barrier: next stage's weights (and the 1x1 slice) have landed
-#ifdef H3D_ABLATE
-                t_bar += __builtin_readcyclecounter() - tb1;
-#endif
+                tm.end_barrier();
             }
             // ---- slab done: X = ReLU(acc [+ b1]) -> B operand; acc2 += W2[:, slab] . X ----------------------
-#ifdef H3D_ABLATE
-            const unsigned long long tg0 = __builtin_readcyclecounter();
-#endif
+            tm.begin();
             if (!(SPARSE && idle))
             gemm2<T, TH, NT, M2H, BIASC>(acc, acc2, s_b + slab * HC_SLAB * 4, s_w2, r, h, sw, a.s1);
-#ifdef H3D_ABLATE
-            t_g2 += __builtin_readcyclecounter() - tg0;
-#endif
+            tm.end_gemm2();
             if (C::TRS == 1) __syncthreads();   // (f32 path) s_w2 is rewritten in the very next stage
         }
-        // ---- head done: z = acc2 + b2 -> NCHW fp32 (lane = pixel: coalesced rows) ------------------------
+        // ---- head done: z = acc2 [* s2] + b2 -> NCHW fp32 (lane = pixel: coalesced rows) -----------------
         const int C_head = a.C[head];
         float *out = a.out[head];
         const size_t cstride = (size_t)a.H * a.W;
-        [[maybe_unused]] const float s2 = a.s2[head];
+        const float s2 = a.s2[head];
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
-            const int oy = SPARSE ? sp_y : oy0 + wv * NT + n, ox = SPARSE ? sp_x : ox0 + r, ob = SPARSE ? sp_b : b;
-            if (SPARSE ? sp_ok : oy < a.H && ox < a.W) {
+            const int oy = SPARSE ? sp.y : oy0 + wv * NT + n, ox = SPARSE ? sp.x : ox0 + r, ob = SPARSE ? sp.b : b;
+            if (SPARSE ? sp.ok : oy < a.H && ox < a.W) {
                 float *op = out + (((size_t)ob * C_head + 4 * h) * a.H + oy) * a.W + ox;
 #pragma unroll
                 for (int m2 = 0; m2 < M2H; ++m2) {
@@ -639,20 +706,7 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
             else head_body(std::integral_constant<int, M2>{}, hi, head);
         }
     }
-#ifdef H3D_ABLATE
-    if (a.stamps && blockIdx.x < 65536) {
-        if (a.dbg & 64) {                       // per-wave barrier time instead (tools/stamp_heads.py --waves)
-            if (l == 0) a.stamps[blockIdx.x * H3D_NSTAMP + wv] = t_bar;
-        } else if (tid == 0) {
-            a.stamps[blockIdx.x * H3D_NSTAMP + 0] = t_start;
-            a.stamps[blockIdx.x * H3D_NSTAMP + 1] = __builtin_readcyclecounter();
-            a.stamps[blockIdx.x * H3D_NSTAMP + 2] = t_bar;
-            a.stamps[blockIdx.x * H3D_NSTAMP + 3] = t_g2;
-            a.stamps[blockIdx.x * H3D_NSTAMP + 4] = t_dma;
-            a.stamps[blockIdx.x * H3D_NSTAMP + 5] = t_stage;
-        }
-    }
-#endif
+    tm.store(a, tid, wv, l);
 }
 
 // Sparse launches, the default path: a position's 3x3 x 64-channel neighbourhood lives in the REGISTERS of its lane as the 36 B
@@ -661,22 +715,22 @@ __global__ __launch_bounds__(512) void heads_kernel(HeadsArgs a)
 // carries an offset outside the buffer and reads zeros, as the LDS patch of heads_kernel<SPARSE> holds zeros there.  No patch area
 // in LDS, so EVERY wave computes (32 positions each) and a filter stage that streams through the ring serves 32 * NW positions
 // instead of 64.  A workgroup is ONE work item = (list, one head of it, one group of 32 * NW positions): l_wg0[] counts items, the
-// items of a head are l_ng[list] consecutive workgroups.  The filter ring, the swizzle, the buffer-form DMA, the software-pipelined
-// A-fragment reads, gemm2 and the epilogue are heads_kernel's; the three tap-row stages of a slab are unrolled so that every
-// fragment index is a compile-time constant (a run-time index would put the fragments in scratch).  Per position the chain of every
-// accumulator is the dense kernel's -- only where the B operand comes from differs -- so the value is the dense launch's bit for bit.
+// items of a head are l_ng[list] consecutive workgroups.  The code is heads_kernel's, the same functions: heads_dma_w1 /
+// heads_dma_w2 / heads_issue_bias (the filter ring, the swizzle, the buffer-form DMA), stage_pipelined (the software-pipelined
+// A-fragment reads; B from the register array), load_bias, zero_tile and gemm2; heads_list_of and heads_position (the workgroup's
+// list, the lane's position) are shared with the patch staging of heads_kernel<SPARSE>.  Only the epilogue is a copy (see there).
+// The three tap-row stages of a slab are unrolled so that every fragment index is a compile-time constant (a run-time index would
+// put the fragments in scratch).  Per position the chain of every accumulator is the dense kernel's -- only where the B operand
+// comes from differs -- so the value is the dense launch's bit for bit.
 template <typename T, int NW>
-struct HeadsSparseRegCfg {
-    using D = HeadsCfg<T, 16>;
+struct HeadsSparseRegCfg : HeadsRingCfg<T> {
+    using D = HeadsRingCfg<T>;
     static_assert(sizeof(T) == 2, "sparse heads: 2-byte plans");
-    static constexpr int ES = D::ES;
     static constexpr int NPOS = 32 * NW;              // positions per workgroup: every wave computes
-    static constexpr int RBW = D::RBW, CPR = D::CPR, SWZ_SHIFT = D::SWZ_SHIFT, TAPS = D::TAPS, TRS = D::TRS, SLOT = D::SLOT;
-    static_assert(TAPS == 3 && TRS == 3, "a stage is one tap row");
+    static_assert(D::TAPS == 3 && D::TRS == 3, "a stage is one tap row");
     static constexpr int NFRAG = 9 * (HC_IN / 16);    // B fragments of a position: 144 VGPRs
-    static constexpr int LDS_W2 = D::LDS_W2, LDS_BIAS = D::LDS_BIAS;
     static constexpr int LDS_PARK = NW * HC_MT2 * 16 * 256;    // per wave: the 32-row output tiles of a wide head (16 registers each), see the kernel
-    static constexpr int LDS = 2 * SLOT + LDS_W2 + LDS_BIAS + LDS_PARK;   // one head per workgroup: one bias pair
+    static constexpr int LDS = 2 * D::SLOT + D::LDS_W2 + D::LDS_BIAS + LDS_PARK;   // one head per workgroup: one bias pair
     static_assert(LDS <= 160 * 1024, "LDS of a CU");
     static constexpr unsigned OUTSIDE = 0x80000000u;  // a buffer offset beyond any map this path takes (HEADS_SPARSE_REG_MAX_BYTES)
 };
@@ -686,7 +740,6 @@ template <typename T, int NW>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void heads_sparse_kernel(HeadsArgs a)   // (4 waves: one per SIMD, up to 512 registers)
 {
     using C = HeadsSparseRegCfg<T, NW>;
-    using E = ET<T>;
     constexpr int ES = C::ES;
     __shared__ __attribute__((aligned(16))) char smem[C::LDS];
     char *s_ring = smem;
@@ -698,16 +751,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void heads_sparse_kernel(
     const int wv = tid >> 6, l = tid & 63, r = l & 31, h = l >> 5;
     const int wvs = __builtin_amdgcn_readfirstlane(wv);
     // this workgroup's list (they start on workgroup boundaries), its head and its group of positions
-    const int bid = blockIdx.x;
-    int li = 0;
-#pragma unroll
-    for (int i = 1; i < HEADS_LISTS_MAX; ++i)
-        if (i < a.nlists && bid >= a.l_wg0[i]) li = i;
-    const int lb = bid - a.l_wg0[li], ng = a.l_ng[li];
-    const int hi = lb / ng, grp = lb - hi * ng;
-    const int head = a.l_head[li][hi];
-    const int sp_K = a.l_K[li];
-    const long long *sp_inds = a.l_inds[li];
+    const HeadsList ls = heads_list_of(a, blockIdx.x);
+    const int hi = ls.lb / ls.ng, grp = ls.lb - hi * ls.ng;
+    const int head = a.l_head[ls.li][hi];
     const int slabs = a.head_conv / HC_SLAB;
     const int nstages = slabs * C::TRS;
     const int sw = (r >> C::SWZ_SHIFT) & (C::CPR - 1);
@@ -721,22 +767,16 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void heads_sparse_kernel(
     heads_issue_bias(a.b1 + head * a.head_conv, a.head_conv, a.b2[head], s_bias, wvs, l);
 
     // this lane's position (an entry past the list or outside the map stores nothing) and its 36 fragments
-    int sp_b = 0, sp_y = 0, sp_x = 0;
-    bool sp_ok = false;
-    const int p = grp * C::NPOS + wv * 32 + r;
-    if (p < a.B * sp_K) {
-        const long long ind = sp_inds[p];
-        if (ind >= 0 && ind < (long long)a.H * a.W) { sp_ok = true; sp_b = p / sp_K; sp_y = (int)ind / a.W; sp_x = (int)ind - sp_y * a.W; }
-    }
+    const HeadsPos sp = heads_position(a, ls, grp * C::NPOS + wv * 32 + r);
     u32x4 bf[C::NFRAG];
     {
         const size_t in_bytes = (((size_t)a.B * a.H * a.W - 1) * a.in_cs + HC_IN) * ES;      // <= HEADS_SPARSE_REG_MAX_BYTES (the launcher)
         const auto rs = __builtin_amdgcn_make_buffer_rsrc((void *)a.in, 0, (int)in_bytes, 0x00020000);
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
-            const int gy = sp_y - 1 + tap / 3, gx = sp_x - 1 + tap % 3;
-            const bool inside = sp_ok && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
-            const unsigned off = inside ? (unsigned)((((sp_b * a.H + gy) * a.W + gx) * a.in_cs + 8 * h) * ES) : C::OUTSIDE;
+            const int gy = sp.y - 1 + tap / 3, gx = sp.x - 1 + tap % 3;
+            const bool inside = sp.ok && gy >= 0 && gy < a.H && gx >= 0 && gx < a.W;
+            const unsigned off = inside ? (unsigned)((((sp.b * a.H + gy) * a.W + gx) * a.in_cs + 8 * h) * ES) : C::OUTSIDE;
 #pragma unroll
             for (int kk = 0; kk < HC_IN / 16; ++kk)
                 bf[tap * (HC_IN / 16) + kk] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off + kk * 16 * ES, 0, 0));
@@ -772,58 +812,17 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void heads_sparse_kernel(
         };
         f32x16 acc[2][1], acc2[1][1];
 #pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[m][0][i] = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc2[0][0][i] = 0.f;
+        for (int m = 0; m < 2; ++m) zero_tile(acc[m][0]);
+        zero_tile(acc2[0][0]);
         int s = 0;
         for (int slab = 0; slab < slabs; ++slab) {
-            // one tap-row stage TR (heads_kernel's pipelined stage at NT = 1 with the B operand in registers); TR == 0 starts
-            // every accumulator tile at the bias tile (C operand of the slab's first MFMA)
+            // one tap-row stage TR: its 12 steps multiply the fragments bf[12 TR ...]; TR == 0 starts every accumulator tile at
+            // the bias tile (C operand of the slab's first MFMA)
             auto stage = [&](auto tr_tag) {
                 constexpr int TR = decltype(tr_tag)::value;
                 if (s + 1 < nstages) issue_w1(s + 1);          // slot (s+1)&1 was last read in stage s-1
                 if (TR == 1) heads_dma_w2<T, 16, NW>(a.w2[head], a.head_conv, s_w2, wvs, l, slab * HC_SLAB * ES);   // after the barrier that follows the previous gemm2
-                const char *slot = s_ring + (s & 1) * C::SLOT;
-                auto load_bias = [&](f32x16 &dst, int m) {
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const f32x4 bv = *reinterpret_cast<const f32x4 *>(s_bias + (slab * HC_SLAB + m * 32 + 8 * g + 4 * h) * 4);
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) dst[4 * g + i] = bv[i];
-                    }
-                };
-                constexpr int NSTEP = C::TAPS * (HC_IN / 16);  // a step = one tap x 16 channels: 2 filter fragments feeding 2 MFMAs
-                const uint32_t ring = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)slot + r * C::RBW;
-                uint32_t fa_base[HC_IN / 16];
-#pragma unroll
-                for (int kk = 0; kk < HC_IN / 16; ++kk) fa_base[kk] = ring + (((2 * kk + h) ^ sw) << 4);
-                constexpr int PF = HEADS_SPARSE_PF, NBUF = PF + 1;
-                static_assert(PF * 2 <= 15, "lgkmcnt field");
-                u32x4 fa[NBUF][2];
-                auto fetch = [&](auto step_tag) {
-                    constexpr int STEP = decltype(step_tag)::value, BUF = STEP % NBUF;
-                    constexpr int tp = STEP / (HC_IN / 16), kk = STEP - tp * (HC_IN / 16);
-                    lds_read16_async<(tp * HC_SLAB) * C::RBW>(fa[BUF][0], fa_base[kk]);
-                    lds_read16_async<(tp * HC_SLAB + 32) * C::RBW>(fa[BUF][1], fa_base[kk]);
-                };
-                static_for<PF>([&](auto step_tag) { fetch(step_tag); });
-                static_for<NSTEP>([&](auto step_tag) {
-                    constexpr int STEP = decltype(step_tag)::value, BUF = STEP % NBUF;
-                    if constexpr (STEP + PF < NSTEP) fetch(std::integral_constant<int, STEP + PF>{});
-                    constexpr int NEWER = (STEP + PF < NSTEP ? PF : NSTEP - 1 - STEP) * 2;          // reads issued after step STEP's
-                    __builtin_amdgcn_s_waitcnt(0xc07f | (NEWER << 8));                              // lgkmcnt(NEWER)
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int m = 0; m < 2; ++m) {
-                        if (TR == 0 && STEP == 0) { load_bias(acc[m][0], m); }
-                        typename E::frag a_, b_;
-                        a_.v = fa[BUF][m]; b_.v = bf[TR * NSTEP + STEP];
-                        E::mma(acc[m][0], a_, b_);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                });
+                stage_pipelined<T, C, 1, HEADS_SPARSE_PF, TR == 0, TR * C::TAPS * (HC_IN / 16)>(acc, s_ring + (s & 1) * C::SLOT, bf, s_bias, slab, r, h, sw);
                 __syncthreads();   // vmcnt(0) + barrier: next stage's weights (and the 1x1 slice) have landed
                 ++s;
             };
@@ -835,25 +834,23 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void heads_sparse_kernel(
             } else {
 #pragma unroll
                 for (int m2 = 0; m2 < M2H; ++m2) {
-                    if (slab == 0) {
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) acc2[0][0][i] = 0.f;
-                    } else {
-                        parked_tile(m2, acc2[0][0]);
-                    }
+                    if (slab == 0) zero_tile(acc2[0][0]);
+                    else parked_tile(m2, acc2[0][0]);
                     gemm2<T, 16, 1, 1, true>(acc, acc2, s_bias + slab * HC_SLAB * 4, s_w2 + m2 * 32 * C::RBW, r, h, sw, a.s1);
                     park_tile(m2, acc2[0][0]);
                 }
             }
         }
         // ---- z = acc2 + b2 -> NCHW fp32 at the lane's position ------------------------------------------
-        if (sp_ok) {
+        if (sp.ok) {
             const int C_head = a.C[head];
             const size_t cstride = (size_t)a.H * a.W;
-            float *op = a.out[head] + (((size_t)sp_b * C_head + 4 * h) * a.H + sp_y) * a.W + sp_x;
+            float *op = a.out[head] + (((size_t)sp.b * C_head + 4 * h) * a.H + sp.y) * a.W + sp.x;
 #pragma unroll
             for (int m2 = 0; m2 < M2H; ++m2) {
                 if (PARK) parked_tile(m2, acc2[0][0]);
+                // (heads_kernel's epilogue at NT = 1 without the f16x3 scale, a copy: as one function of a tile both kernels could call it
+                // changed the s_waitcnt count of a dense instantiation)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const int c = m2 * 32 + 8 * g + 4 * h;
@@ -947,6 +944,25 @@ int h3d_launch_heads(const h3d_op &op, hipStream_t st)
 
 static_assert(HEADS_LISTS_MAX == H3D_HEADS_LISTS_MAX, "header/kernel mismatch");
 
+// The per-list kernel arguments of a sparse launch from the lists in launch order (order[]), npos positions per workgroup; returns
+// the grid.  per_head: a workgroup is (head, group of positions), in a list the widest heads first and all groups of a head in a row
+// (heads_sparse_kernel); otherwise it is a group of positions that loops over the list's heads in descriptor order (heads_kernel<SPARSE>).
+static int heads_fill_lists(HeadsArgs &a, const h3d_heads_list *lists, const int *order, bool per_head, int npos)
+{
+    int wgs = 0;
+    for (int i = 0; i < a.nlists; ++i) {
+        const h3d_heads_list &ls = lists[order[i]];
+        a.l_inds[i] = (const long long *)ls.inds; a.l_K[i] = ls.K; a.l_wg0[i] = wgs; a.l_nh[i] = 0;
+        for (int tiles = per_head ? HC_MT2 : 1; tiles >= 1; --tiles)
+            for (int h = 0; h < a.nheads; ++h)
+                if ((ls.head_mask >> h & 1) && (!per_head || (a.C[h] + 31) / 32 == tiles)) a.l_head[i][a.l_nh[i]++] = h;
+        const int ng = cdiv(a.B * ls.K, npos);
+        if (per_head) a.l_ng[i] = ng;
+        wgs += per_head ? a.l_nh[i] * ng : ng;
+    }
+    return wgs;
+}
+
 // The heads of an H3D_OP_HEADS op at listed positions, written into the heads' dense maps there: bit for bit what the op's dense
 // launch writes at those positions.  ONE launch for all lists, the lists with the most heads first.  Default: heads_sparse_kernel,
 // one workgroup per (list, head, 256 positions).  H3D_TUNE_HEADS_SPARSE_LDS_PATCH (A/B, and maps beyond 2 GiB): heads_kernel<SPARSE>,
@@ -992,17 +1008,7 @@ extern "C" int h3d_heads_sparse_lists(const h3d_op *op, int nlists, const h3d_he
     const size_t in_bytes = (((size_t)op->B * op->H * op->W - 1) * op->in_cs + HC_IN) * h3d_dtype_bytes(op->dtype);
     if (!(op->reserved & H3D_TUNE_HEADS_SPARSE_LDS_PATCH) && in_bytes < HEADS_SPARSE_REG_MAX_BYTES) {
         const bool waves8 = !(op->reserved & H3D_TUNE_HEADS_SPARSE_WAVES4);
-        const int npos = 32 * (waves8 ? 8 : 4);
-        int wgs = 0;
-        for (int i = 0; i < nlists; ++i) {
-            const h3d_heads_list &ls = lists[order[i]];
-            a.l_inds[i] = (const long long *)ls.inds; a.l_K[i] = ls.K; a.l_wg0[i] = wgs; a.l_nh[i] = 0;
-            for (int tiles = HC_MT2; tiles >= 1; --tiles)
-                for (int h = 0; h < a.nheads; ++h)
-                    if ((ls.head_mask >> h & 1) && (a.C[h] + 31) / 32 == tiles) a.l_head[i][a.l_nh[i]++] = h;
-            a.l_ng[i] = cdiv(op->B * ls.K, npos);
-            wgs += a.l_nh[i] * a.l_ng[i];
-        }
+        const int wgs = heads_fill_lists(a, lists, order, true, 32 * (waves8 ? 8 : 4));
         return h3d_by_dtype<bf16_t, f16_t>(op->dtype, "heads_sparse: dtype %d", [&](auto t) {
             using T = typename decltype(t)::type;
             return h3d_by_values([&](auto nw) {
@@ -1015,15 +1021,7 @@ extern "C" int h3d_heads_sparse_lists(const h3d_op *op, int nlists, const h3d_he
     return h3d_by_dtype<bf16_t, f16_t>(op->dtype, "heads_sparse: dtype %d", [&](auto t) {
         using T = typename decltype(t)::type;
         using C = HeadsSparseCfg<T>;
-        int wgs = 0;
-        for (int i = 0; i < nlists; ++i) {
-            const h3d_heads_list &ls = lists[order[i]];
-            a.l_inds[i] = (const long long *)ls.inds; a.l_K[i] = ls.K; a.l_wg0[i] = wgs; a.l_nh[i] = 0;
-            for (int h = 0; h < a.nheads; ++h)
-                if (ls.head_mask >> h & 1) a.l_head[i][a.l_nh[i]++] = h;
-            wgs += cdiv(op->B * ls.K, C::NPOS);
-        }
-        const dim3 grid(wgs), blk(64 * C::NW);
+        const dim3 grid(heads_fill_lists(a, lists, order, false, C::NPOS)), blk(64 * C::NW);
         // one instantiation: the body picks the 1 / 2 / 3-tile epilogue width per head
         const h3d_kname name{"heads_kernel", t, 16, 3, true, h3d_opt(true), h3d_opt(true)};
         return h3d_launch(name, heads_kernel<T, 16, 3, true, true, true>, grid, blk, 0, (hipStream_t)stream, a);

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Per-kernel register / scratch / LDS usage of one csrc source, as hipcc's resource-usage remarks report it:
 #   tools/kernel_resources.sh dcn3.hip [extra hipcc flags]
+#   tools/kernel_resources.sh heads.hip [-DH3D_ABLATE]   (the 34 heads kernels: DESIGN.md section 2.3, profiles/heads_refactor_resources_*.txt)
 #   tools/kernel_resources.sh smpl_bwd.hip          (the three SMPL backward kernels: DESIGN.md section 16 holds their table)
 #   tools/kernel_resources.sh heads_bwd.hip         (the heads backward kernels: DESIGN.md section 18 holds their table)
 #   tools/kernel_resources.sh optim.hip -ffp-contract=off   (the Adam step: DESIGN.md section 21)
