@@ -36,6 +36,7 @@ TUNE_CONV_STREAM_TILE_MASK, TUNE_CONV_STREAM_AUTO, TUNE_CONV_STREAM_ROUND4_RULE,
 TUNE_CONV_TILE, TUNE_CONV_HALO_TILE, TUNE_CONV_FORCE_GEMM, TUNE_CONV_GEMM_TILE_MASK = 0x1000, 0x2000, 0x4000, 0xf00
 TUNE_CONV_X3_TILED, TUNE_CONV_X3_TILE_MASK, TUNE_CONV_X3_CK16, TUNE_CONV_X3_MT2 = 0x1000, 0x1fff, 0x2000, 0x4000
 TUNE_UPADD_TAPS_GLOBAL, TUNE_UPADD_TAPS_LDS, OPF_UPADD_FOLDED = 1, 2, 0x100
+OPF_TREE_ENTRY, OPF_TREE_ENTRY_PRIVATE_POOL = 0x20000000, 0x40000000
 TUNE_HEADS_SEPARATE_BIAS, TUNE_HEADS_ABLATE_MASK = 0x200, 0xff
 TUNE_HEADS_SPARSE_LDS_PATCH, TUNE_HEADS_SPARSE_WAVES4 = 0x400, 0x800
 

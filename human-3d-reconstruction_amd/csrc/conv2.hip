@@ -15,6 +15,14 @@
 //           (engine.PackedWeights.conv_stream), so the DMA is a linear copy of MT*9728 bytes.
 // Both strides make every 16-lane ds_read_b128 group hit 16 distinct 16-byte bank slots.
 // Two ring slots: stage s+1 is in flight while stage s feeds 9*MT MFMAs per wave; one barrier a stage.
+//
+// ENTRY (stride 2): the entry of a DLA Tree in one launch -- this conv, the 2x2 max-pool of the same input and the 1x1 `project`
+// conv of the pooled map (H3D_OPF_TREE_ENTRY, include/h3d.h).  Taps (1,1), (1,2), (2,1), (2,2) of output pixel (oy, ox) are input pixels
+// (2oy, 2ox) .. (2oy+1, 2ox+1): the pool's window in the order maxpool_kernel (csrc/conv.hip) reads it, so the running maximum of those four
+// B fragments is the pooled pixel's 16 channels of the stage and the B operand of one more MFMA chain per stage, the project conv's (K in
+// 16-channel steps ascending, as csrc/gemm1.hip and the 1x1 tiles of csrc/conv.hip walk it).  Its filters come from the project op's own
+// [wrows][Cin] pack, 1 KiB per 32 rows and stage behind the slot's 3x3 filter image; the pooled map is stored by the workgroups of channel
+// block 0; a second epilogue pass writes the project result.  Same bits as the three launches.
 #include "common.h"
 #include "epilogue.h"
 
@@ -30,10 +38,16 @@ struct Conv2Args {
     int dbg;   // ABLATE builds only (H3D_TUNE_CONV_STREAM_ABLATE_OF(op.reserved)): 1 = no DMA after stage 0, 2 = no fragment reads / MFMA
     int xcd;   // h3d_tile_id mode
     int f16;   // host side only: fp16 plan (the launcher picks the f16_t instantiation)
+    // ENTRY: the project conv (filters [pwrows][Cin], bias, NHWC output of Cout channels) and the pooled map (null: not stored)
+    const char *pw;
+    const float *pbias;
+    char *pout;
+    char *pool_out;
+    int pwrows, pout_cs, pool_cs;
     unsigned long long *stamps;   // profiling builds: per workgroup and wave (0-7) the cycles spent at the stage barrier; slot 7: wave 0's {DMA issue} (tools/stamp_conv2.py)
 };
 
-template <int MT, int WAVES, int S = 1, int SLOTS = 2, int NT = 1>
+template <int MT, int WAVES, int S = 1, int SLOTS = 2, int NT = 1, bool ENTRY = false>
 struct Conv2Cfg {
     static constexpr int TH = 2 * WAVES * NT;           // a wave owns NT N-tiles (2 rows x 16 px each): filter fragments are reused NT times
     static constexpr int HROWS = (TH - 1) * S + 3;      // halo rows
@@ -46,7 +60,8 @@ struct Conv2Cfg {
     static constexpr int WGRP = 32 * WROW;              // one 32-row group: 9728 B
     static constexpr int WPIECES = (MT * WGRP + 1023) / 1024;
     static constexpr int WALLOC = WPIECES * 1024;
-    static constexpr int SLOT = HALO + WALLOC;
+    static constexpr int PALLOC = ENTRY ? MT * 1024 : 0;   // ENTRY: the project filters of the stage, [32 rows][32 B] per M-tile
+    static constexpr int SLOT = HALO + WALLOC + PALLOC;
     static constexpr int LDS_EPI = WAVES * ((NT * 32 * (64 * MT + 16) + 1023) / 1024 * 1024);   // tile_epilogue_lds regions
     static constexpr int LDS_RING = SLOTS * SLOT;   // SLOTS = 1: single-stage layers (Cin = 16) keep more workgroups per CU
     static constexpr int LDS = LDS_RING > LDS_EPI ? LDS_RING : LDS_EPI;
@@ -80,12 +95,24 @@ __device__ __forceinline__ void conv2_issue(const char *in_b, int in_bytes, cons
     }
 }
 
-template <typename T, int MT, int WAVES, int EPI, int S = 1, int SLOTS = 2, int NT = 1, bool PIPE = false>   // T: bf16_t | f16_t; EPI: 0 general, 1 lean NHWC, 2 LDS-transposed NHWC (epilogue.h); S: stride
-__global__ __launch_bounds__(64 * WAVES) void conv2_kernel(Conv2Args a)
+// ENTRY: LDS-DMA of the stage's project filters to `base` (behind the 3x3 filter image): M-tile m is one piece, lane = (row, 16-byte half);
+// `poff` = the lane's byte offset in the [rows][Cin] pack at stage 0 of M-tile 0, the M-tile and the stage go through soffset
+template <int MT, int WAVES>
+__device__ __forceinline__ void conv2_issue_proj(const char *pw, int pw_bytes, char *base, int poff, int wv, int s, int mstep)
 {
-    using C = Conv2Cfg<MT, WAVES, S, SLOTS, NT>;
+    const auto r_p = __builtin_amdgcn_make_buffer_rsrc((void *)pw, 0, pw_bytes, 0x00020000);
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+        if (m % WAVES == wv) __builtin_amdgcn_raw_ptr_buffer_load_lds(r_p, (lds_void *)(base + m * 1024), 16, poff, m * mstep + s * 32, 0, 0);
+}
+
+template <typename T, int MT, int WAVES, int EPI, int S = 1, int SLOTS = 2, int NT = 1, bool PIPE = false, bool ENTRY = false>   // T: bf16_t | f16_t; EPI: 0 general, 1 lean NHWC, 2 LDS-transposed NHWC (epilogue.h); S: stride
+__global__ __launch_bounds__(64 * WAVES, ENTRY ? 2 : 1) void conv2_kernel(Conv2Args a)   // ENTRY: two waves per SIMD (two workgroups per CU), as the one-slot tiles have without the project chain
+{
+    using C = Conv2Cfg<MT, WAVES, S, SLOTS, NT, ENTRY>;
     using E = ET<T>;
     static_assert(sizeof(T) == 2, "2-byte element types");
+    static_assert(!ENTRY || (S == 2 && NT == 1 && EPI == 2 && !PIPE && SLOTS == 1 && MT <= WAVES), "ENTRY: the one-slot stride-2 tiles with the LDS-transposed epilogue");
     __shared__ __attribute__((aligned(1024))) char smem[C::LDS];
 
     const int tid = threadIdx.x;
@@ -131,6 +158,21 @@ __global__ __launch_bounds__(64 * WAVES) void conv2_kernel(Conv2Args a)
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc[m][n][i] = 0.f;
 
+    // ENTRY: the project conv's accumulators and this lane's offset in its filter pack (row cout0 + l / 2, half l & 1)
+    [[maybe_unused]] f32x16 acc2[ENTRY ? MT : 1][1];
+    [[maybe_unused]] const int poff = ((cout0 + (l >> 1)) * a.Cin + (l & 1) * 8) * 2;
+    [[maybe_unused]] const int pw_bytes = a.pwrows * a.Cin * 2;
+    if constexpr (ENTRY) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) acc2[m][0][i] = 0.f;
+    }
+    auto issue = [&](char *base, int s) {
+        conv2_issue<MT, WAVES, S, NT>(in_b, (int)img_bytes, a.wimg, w_bytes, base, hoff, woff, wv, s, (s * a.G + g0) * C::WGRP, H3D_DBG(a));
+        if constexpr (ENTRY) conv2_issue_proj<MT, WAVES>(a.pw, pw_bytes, base + C::HALO + C::WALLOC, poff, wv, s, 32 * a.Cin * 2);
+    };
+
     // ring of SLOTS stages: stage s + SLOTS - 1 is issued when stage s starts, so a stage has SLOTS - 1 stages of
     // MFMA time to land (with 2 slots the SQ counters showed the waves parked ~48 % of the time)
     constexpr int AHEAD = SLOTS > 1 ? SLOTS - 1 : 1;
@@ -140,7 +182,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv2_kernel(Conv2Args a)
 #pragma unroll
     for (int j = 0; j < AHEAD; ++j)
         if (j < nst && (SLOTS > 1 || j == 0))
-            conv2_issue<MT, WAVES, S, NT>(in_b, (int)img_bytes, a.wimg, w_bytes, smem + j * C::SLOT, hoff, woff, wv, j, (j * a.G + g0) * C::WGRP, H3D_DBG(a));
+            issue(smem + j * C::SLOT, j);
     int cslot = 0, pslot = AHEAD % SLOTS;          // slot consumed by stage s / filled with stage s + AHEAD
 #ifdef H3D_ABLATE
     unsigned long long t_bar = 0, t_iss = 0;
@@ -152,7 +194,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv2_kernel(Conv2Args a)
             // covered by the CU's other workgroups (the slot is small enough for two or three of them)
             if (s > 0) {
                 __syncthreads();
-                conv2_issue<MT, WAVES, S, NT>(in_b, (int)img_bytes, a.wimg, w_bytes, smem, hoff, woff, wv, s, (s * a.G + g0) * C::WGRP, H3D_DBG(a));
+                issue(smem, s);
             }
         }
         // my pieces of stage s have landed once only stage s+1's may be outstanding (vmcnt retires in order)
@@ -168,7 +210,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv2_kernel(Conv2Args a)
         t_bar += tb1 - tb0;
 #endif
         if (SLOTS > 1 && s + AHEAD < nst && !(H3D_DBG(a) & 1))
-            conv2_issue<MT, WAVES, S, NT>(in_b, (int)img_bytes, a.wimg, w_bytes, smem + pslot * C::SLOT, hoff, woff, wv, s + AHEAD, ((s + AHEAD) * a.G + g0) * C::WGRP, H3D_DBG(a));
+            issue(smem + pslot * C::SLOT, s + AHEAD);
 #ifdef H3D_ABLATE
         t_iss += __builtin_readcyclecounter() - tb1;
 #endif
@@ -201,6 +243,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv2_kernel(Conv2Args a)
                 __builtin_amdgcn_sched_group_barrier(0x008, MT * NT, 0);
             }
         } else {
+        [[maybe_unused]] float pm[8];             // ENTRY: running maximum over taps 4, 5, 7, 8 = the 2x2 pool window, as maxpool_kernel takes it
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
             const int dy = tap / 3, dx = tap - 3 * dy;
@@ -214,6 +257,25 @@ __global__ __launch_bounds__(64 * WAVES) void conv2_kernel(Conv2Args a)
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int n = 0; n < NT; ++n) E::mma(acc[m][n], fa[m], fb[n]);
+            if constexpr (ENTRY) {
+                if (tap == 4) {
+                    unpack16<T>(fb[0].v, pm);
+                } else if (tap == 5 || tap == 7 || tap == 8) {
+                    float x[8];
+                    unpack16<T>(fb[0].v, x);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) pm[k] = fmaxf(pm[k], x[k]);
+                }
+            }
+        }
+        if constexpr (ENTRY) {
+            typename E::frag pb;
+            pb.v = pack16<T>(pm);
+#pragma unroll
+            for (int m = 0; m < MT; ++m) E::mma(acc2[m][0], E::lds_frag(sl + C::HALO + C::WALLOC + m * 1024 + r * 32 + h * 16), pb);
+            const int oy = oy0 + py, ox = ox0 + px;
+            if (a.pool_out && blockIdx.y == 0 && oy < a.Ho && ox < a.Wo)
+                *reinterpret_cast<u32x4 *>(a.pool_out + ((((size_t)b * a.Ho + oy) * a.Wo + ox) * a.pool_cs + 16 * s + 8 * h) * 2) = pb.v;
         }
         }
     }
@@ -232,6 +294,10 @@ __global__ __launch_bounds__(64 * WAVES) void conv2_kernel(Conv2Args a)
     if constexpr (EPI == 2) {
         __syncthreads();                          // nobody reads the ring any more
         tile_epilogue_lds<T, MT, NT>(acc, e, b, oy0, ox0, cout0, wv, l, smem + wv * epi_lds_stride<MT, NT>());
+        if constexpr (ENTRY) {                    // the project result through the same region of this wave: bias, no residual, no ReLU
+            e.bias = a.pbias; e.res = nullptr; e.out = a.pout; e.out_cs = a.pout_cs; e.res_cs = 0; e.relu = 0;
+            tile_epilogue_lds<T, MT, 1>(acc2, e, b, oy0, ox0, cout0, wv, l, smem + wv * epi_lds_stride<MT, NT>());
+        }
     } else {
         tile_epilogue<T, MT, NT, EPI == 1>(acc, e, b, oy0, ox0, cout0, wv, r, h);
     }
@@ -262,7 +328,28 @@ static int launch_conv2_cfg(const Conv2Args &a0, hipStream_t st)
     }, h3d_vals<false, true>{}, a.f16 != 0, h3d_vals<0, 1, 2>{}, epi);
 }
 
-int h3d_launch_conv_stream(const h3d_op &op, hipStream_t st)
+// ENTRY: the one-slot stride-2 tile of MT x 32 channels, one instantiation per element type (the LDS-transposed epilogue;
+// h3d_conv_stream_entry_takes admits nothing else)
+template <int MT>
+static int launch_conv2_entry(const Conv2Args &a0, hipStream_t st)
+{
+    constexpr int WAVES = 4, S = 2, SLOTS = 1;
+    using C = Conv2Cfg<MT, WAVES, S, SLOTS, 1, true>;
+    static_assert(2 * C::LDS <= 160 * 1024, "LDS budget: two workgroups per CU, as without the project filters");
+    Conv2Args a = a0;
+    a.tiles_x = cdiv(a.Wo, 16);
+    a.tiles_y = cdiv(a.Ho, C::TH);
+    a.xcd = h3d_xcd_mode();
+    a.stamps = nullptr;
+    dim3 grid(a.B * a.tiles_x * a.tiles_y, cdiv(cdiv(a.Cout, 32), MT));
+    return h3d_by_values([&](auto f16) {
+        using T = std::conditional_t<f16, f16_t, bf16_t>;
+        return h3d_launch({"conv2_kernel", h3d_tag<T>{}, MT, WAVES, 2, S, SLOTS, 1, false, true},
+                          conv2_kernel<T, MT, WAVES, 2, S, SLOTS, 1, false, true>, grid, dim3(C::THREADS), 0, st, a);
+    }, h3d_vals<false, true>{}, a.f16 != 0);
+}
+
+static int conv_stream_check(const h3d_op &op)
 {
     if (!op.in || !op.w || !op.bias || !op.out) H3D_FAIL(H3D_ERR_ARG, "conv_stream: null pointer");
     if (op.dtype != H3D_BF16 && op.dtype != H3D_F16) H3D_FAIL(H3D_ERR_DTYPE, "conv_stream: bf16 / fp16 plans only (dtype %d)", op.dtype);
@@ -277,6 +364,11 @@ int h3d_launch_conv_stream(const h3d_op &op, hipStream_t st)
     if (op.out_mode != H3D_OUT_NCHW_F32 && (op.out_cs % 4 || op.Cout > op.out_cs))
         H3D_FAIL(H3D_ERR_SHAPE, "conv_stream: out channel stride %d", op.out_cs);
     if (op.in2 && (op.in2_cs % 4 || op.Cout > op.in2_cs)) H3D_FAIL(H3D_ERR_SHAPE, "conv_stream: residual stride %d", op.in2_cs);
+    return H3D_OK;
+}
+
+static Conv2Args conv_stream_args(const h3d_op &op)
+{
     Conv2Args a;
     a.in = (const char *)op.in; a.wimg = (const char *)op.w; a.bias = op.bias; a.res = (const char *)op.in2;
     a.out = (char *)op.out; a.B = op.B; a.H = op.H; a.W = op.W; a.Cin = op.Cin; a.in_cs = op.in_cs;
@@ -284,6 +376,59 @@ int h3d_launch_conv_stream(const h3d_op &op, hipStream_t st)
     a.G = op.wrows / 32; a.tiles_x = a.tiles_y = 0;
     a.f16 = op.dtype == H3D_F16;
     a.dbg = H3D_TUNE_CONV_STREAM_ABLATE_OF(op.reserved);
+    a.pw = nullptr; a.pbias = nullptr; a.pout = nullptr; a.pool_out = nullptr; a.pwrows = a.pout_cs = a.pool_cs = 0;
+    return a;
+}
+
+// Can [pool, proj, conv] = [H3D_OP_MAXPOOL, 1x1 H3D_OP_CONV, 3x3 stride-2 H3D_OP_CONV_STREAM] run as the ONE launch of the ENTRY tile?  All
+// three carry H3D_OPF_TREE_ENTRY, the 1x1 conv reads exactly what the pool writes and the 3x3 conv what the pool reads, and every condition of
+// the tile holds: 2-byte plan, even H and W, the same output size and channel count, no residual and no ReLU on the 1x1 conv, a one-slot
+// tile of 128 or 64 channels with the LDS-transposed epilogue for both results (what the separate launches use for these shapes too: same bits).
+// Whatever fails here goes to the three launchers, which own the error messages.
+bool h3d_conv_stream_entry_takes(const h3d_op &pool, const h3d_op &proj, const h3d_op &conv)
+{
+    if (pool.kind != H3D_OP_MAXPOOL || proj.kind != H3D_OP_CONV || conv.kind != H3D_OP_CONV_STREAM) return false;
+    if (!(pool.reserved & H3D_OPF_TREE_ENTRY) || !(proj.reserved & H3D_OPF_TREE_ENTRY) || !(conv.reserved & H3D_OPF_TREE_ENTRY)) return false;
+    // the conv alone runs on the tile that has the twin: the launcher's own choice from 128 channels on, below that (64 .. 127) the one-slot
+    // 64-channel tile by its tuning code (the launcher's choice there has two slots)
+    const int gq = cdiv(conv.Cout, 32);
+    if ((conv.reserved & ~H3D_OPF_TREE_ENTRY) != (gq >= 4 ? 0 : H3D_TUNE_CONV_STREAM_TILE(4, 2, 4))) return false;
+    if ((proj.reserved & ~H3D_OPF_TREE_ENTRY) || (pool.reserved & ~(H3D_OPF_TREE_ENTRY | H3D_OPF_TREE_ENTRY_PRIVATE_POOL))) return false;
+    if ((conv.dtype != H3D_BF16 && conv.dtype != H3D_F16) || pool.dtype != conv.dtype || proj.dtype != conv.dtype) return false;
+    if (!pool.in || !pool.out || !proj.w || !proj.bias || !proj.out || proj.in2) return false;
+    // the pointer identities, and the geometry all three agree on
+    if (proj.in != pool.out || proj.in_cs != pool.out_cs || conv.in != pool.in || conv.in_cs != pool.in_cs) return false;
+    const int B = conv.B, H = conv.H, W = conv.W, C = conv.Cin;
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || conv.Cout <= 0) return false;
+    if (pool.B != B || proj.B != B || pool.H != H || pool.W != W || (H & 1) || (W & 1)) return false;
+    if (pool.Cin != C || pool.Cout != C || proj.Cin != C || C > pool.out_cs) return false;
+    const int Ho = H / 2, Wo = W / 2;
+    if (conv.ksize != 3 || conv.stride != 2 || conv.Ho != Ho || conv.Wo != Wo || pool.Ho != Ho || pool.Wo != Wo) return false;
+    if (proj.ksize != 1 || proj.stride != 1 || proj.H != Ho || proj.W != Wo || proj.Ho != Ho || proj.Wo != Wo) return false;
+    if (proj.Cout != conv.Cout || proj.relu || proj.wexp || proj.out_mode != H3D_OUT_NHWC || conv.out_mode != H3D_OUT_NHWC) return false;
+    // the tile: channel blocks whose filter and bias rows all exist, 16-byte vectors everywhere
+    if (conv.Cout % 8 || gq < 2 || proj.wrows < cdiv(conv.Cout, 128) * 128 || (long long)proj.wrows * C * 2 >= 0x7ffffff0ll) return false;
+    if (conv.out_cs % 8 || proj.out_cs % 8 || proj.Cout > proj.out_cs || pool.out_cs % 8) return false;
+    if (((uintptr_t)conv.out & 15) || ((uintptr_t)conv.bias & 15) || ((uintptr_t)proj.out & 15) || ((uintptr_t)proj.bias & 15) || ((uintptr_t)proj.w & 15) ||
+        ((uintptr_t)pool.out & 15))
+        return false;
+    return conv_stream_check(conv) == H3D_OK;
+}
+
+// ... as one launch (the caller has asked h3d_conv_stream_entry_takes)
+int h3d_launch_conv_stream_entry(const h3d_op &pool, const h3d_op &proj, const h3d_op &conv, hipStream_t st)
+{
+    Conv2Args a = conv_stream_args(conv);
+    a.pw = (const char *)proj.w; a.pbias = proj.bias; a.pout = (char *)proj.out; a.pwrows = proj.wrows; a.pout_cs = proj.out_cs;
+    a.pool_out = (pool.reserved & H3D_OPF_TREE_ENTRY_PRIVATE_POOL) ? nullptr : (char *)pool.out;      // private: nothing else reads the pooled map
+    a.pool_cs = pool.out_cs;
+    return cdiv(conv.Cout, 32) >= 4 ? launch_conv2_entry<4>(a, st) : launch_conv2_entry<2>(a, st);
+}
+
+int h3d_launch_conv_stream(const h3d_op &op, hipStream_t st)
+{
+    H3D_TRY(conv_stream_check(op));
+    const Conv2Args a = conv_stream_args(op);
     const int tile = op.reserved & H3D_TUNE_CONV_STREAM_TILE_MASK;       // tuning override: H3D_TUNE_CONV_STREAM_TILE(variant, MT, WAVES)
     // workgroups a (th rows x 16 px) x (32*mt channels) tiling produces
     const int gq = cdiv(op.Cout, 32);

@@ -66,22 +66,36 @@ int h3d_launch_dcn2(const h3d_op &op, hipStream_t st);
 int h3d_launch_dcn3(const h3d_op &op, hipStream_t st);
 int h3d_launch_dcn3_fold(const h3d_op &op, const h3d_op &up, hipStream_t st, bool *folded);
 int h3d_launch_conv_stream(const h3d_op &op, hipStream_t st);
+bool h3d_conv_stream_entry_takes(const h3d_op &pool, const h3d_op &proj, const h3d_op &conv);
+int h3d_launch_conv_stream_entry(const h3d_op &pool, const h3d_op &proj, const h3d_op &conv, hipStream_t st);
 int h3d_launch_dcn4(const h3d_op &op, hipStream_t st);
 int h3d_launch_updcn(const h3d_op &op, hipStream_t st);
 int h3d_launch_stem3(const h3d_op &op, hipStream_t st);
 int h3d_launch_extra(const h3d_op &op, hipStream_t st);
 
 static int run_one(const h3d_op &op, int i, hipStream_t st, const h3d_op *up = nullptr, bool *folded = nullptr);
+static int fail_at(int rc, const h3d_op &op, int i);
 
-// ops[i], or ops[i] and ops[i + 1] as one launch (*folded): a fused DeformConv stream op directly followed by an H3D_OP_UPADD that carries
+// ops[i], or ops[i] and the *folded ops behind it as one launch.  One op more: a fused DeformConv stream op directly followed by an H3D_OP_UPADD that carries
 // H3D_OPF_UPADD_FOLDED and whose skip (`in2`) is the DeformConv's `out`, where the DeformConv launcher has a folding tile for the pair
-// (csrc/dcn3.hip h3d_launch_dcn3_fold).  Everywhere else the flag is ignored: the result never depends on the plan's claim being used.
-static int run_at(const h3d_op *ops, int i, int n, hipStream_t st, bool *folded)
+// (csrc/dcn3.hip h3d_launch_dcn3_fold).  Two ops more: the entry of a Tree, [H3D_OP_MAXPOOL, 1x1 H3D_OP_CONV, stride-2 H3D_OP_CONV_STREAM] that all
+// carry H3D_OPF_TREE_ENTRY, where csrc/conv2.hip has the tile for the triple (h3d_conv_stream_entry_takes: the structure and the shapes).
+// Everywhere else the flags are ignored: the result never depends on the plan's claim being used.
+static int run_at(const h3d_op *ops, int i, int n, hipStream_t st, int *folded)
 {
-    *folded = false;
+    *folded = 0;
     if (i + 1 < n && ops[i].kind == H3D_OP_DCN_FUSED_STREAM && ops[i + 1].kind == H3D_OP_UPADD && (ops[i + 1].reserved & H3D_OPF_UPADD_FOLDED) &&
-        ops[i].out && ops[i + 1].in2 == ops[i].out)
-        return run_one(ops[i], i, st, &ops[i + 1], folded);
+        ops[i].out && ops[i + 1].in2 == ops[i].out) {
+        bool pair = false;
+        const int rc = run_one(ops[i], i, st, &ops[i + 1], &pair);
+        *folded = pair;
+        return rc;
+    }
+    if (i + 2 < n && ops[i].kind == H3D_OP_MAXPOOL && (ops[i].reserved & H3D_OPF_TREE_ENTRY) &&
+        h3d_conv_stream_entry_takes(ops[i], ops[i + 1], ops[i + 2])) {
+        *folded = 2;
+        return fail_at(h3d_launch_conv_stream_entry(ops[i], ops[i + 1], ops[i + 2], st), ops[i], i);
+    }
     return run_one(ops[i], i, st);
 }
 
@@ -107,10 +121,10 @@ extern "C" int h3d_run_ops_timed(const h3d_op *ops, int n, void *stream, float *
     (void)hipEventRecord(ev[0], st);
     for (int i = 0; i < n; ++i) ms[i] = 0.f;
     for (int i = 0; i < n && rc == H3D_OK; ++i) {
-        bool folded = false;
+        int folded = 0;
         rc = run_at(ops, i, n, st, &folded);
         (void)hipEventRecord(ev[i + 1], st);
-        if (folded) {                            // the pair's time stands under the DeformConv op; the folded op reports 0 ms
+        for (; folded > 0; --folded) {           // the launch's time stands under its first op; the ops folded into it report 0 ms
             ++i;
             ms[i] = -1.f;
             (void)hipEventRecord(ev[i + 1], st);
@@ -133,10 +147,10 @@ extern "C" int h3d_run_ops(const h3d_op *ops, int n, void *stream)
     if (!ops || n < 0) H3D_FAIL(H3D_ERR_ARG, "run_ops: null plan");
     hipStream_t st = (hipStream_t)stream;
     for (int i = 0; i < n; ++i) {
-        bool folded = false;
+        int folded = 0;
         const int rc = run_at(ops, i, n, st, &folded);
         if (rc != H3D_OK) return rc;
-        if (folded) ++i;
+        i += folded;
     }
     return H3D_OK;
 }
@@ -176,6 +190,11 @@ static int run_one(const h3d_op &op, int i, hipStream_t st, const h3d_op *up, bo
     case H3D_OP_DEPTH2SPACE: rc = h3d_launch_extra(op, st); break;
     default: h3d_set_error("op %d: unknown kind %d", i, op.kind); return H3D_ERR_ARG;
     }
+    return fail_at(rc, op, i);
+}
+
+static int fail_at(int rc, const h3d_op &op, int i)
+{
     if (rc != H3D_OK) {
         char tmp[400];
         snprintf(tmp, sizeof(tmp), "%s", h3d_last_error());

@@ -161,6 +161,8 @@ class MultiPoseDetector:
             self.model.engine_flags["peak_heads"] = tuple(h for h in opt.heads if h in PEAK_HEADS)
             # four of IDAUp's up-sample + add passes run in the epilogue of the DeformConv that writes their skip (Plan.FLAGS fold_upadd): same bits
             self.model.engine_flags["fold_upadd"] = True
+            # the max-pool and the `project` conv at the entry of levels 2 to 5 run inside the stride-2 conv of the same input (Plan.FLAGS fold_tree_entry): same bits
+            self.model.engine_flags["fold_tree_entry"] = True
         if opt.smpl and smpl_model is None:
             self.smpl_model = _smpl.SMPLModel.synthetic()
 

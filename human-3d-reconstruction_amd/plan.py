@@ -2,7 +2,9 @@
 pre-allocated NHWC buffers (`View`s) and the packed weights of `weights.PackedWeights`.
 
 Every op is emitted by `Plan._op` from the Views it reads and writes: the pointers, sizes and channel strides of an op are never
-spelled out at a lowering site, which states only what is particular to it (kind, filters, kernel size, stride, epilogue, flags)."""
+spelled out at a lowering site, which states only what is particular to it (kind, filters, kernel size, stride, epilogue, flags).
+The lowering decisions are the switches of `Plan.FLAGS`; two of them mark ops the run loop launches together with their neighbours
+(fold_upadd: up-sample + add into its skip's DeformConv; fold_tree_entry: a Tree's max-pool and project conv into its stride-2 conv)."""
 import ctypes
 
 import torch
@@ -88,6 +90,13 @@ class Plan:
                                   # carries H3D_OPF_UPADD_FOLDED: h3d_run_ops launches the pair as one kernel whose epilogue adds the up-sampled
                                   # map to each vector before it is stored (csrc/epilogue.h tile_epilogue_lds_fold).  The node's own output
                                   # buffer is then never written; same bits downstream.  Off by default: the default lowering is pinned
+        fold_tree_entry=False,    # True (MultiPoseDetector sets it for DLA-34 bf16 / f16; needs share_pool): the entry of a Tree -- the max-pool of x,
+                                  # `project` of the pooled map and the stride-2 conv1 of x, lowered next to each other in this order -- carries
+                                  # H3D_OPF_TREE_ENTRY on all three ops (levels 2 to 5): h3d_run_ops launches the triple as one kernel (the pool is
+                                  # the maximum of four taps conv1 holds, project one more MFMA chain per stage); same bits in all three maps.
+                                  # Level 2's conv1 (32 -> 64) then runs on csrc/conv2.hip's one-slot 64-channel tile instead of csrc/conv.hip
+                                  # (same accumulation order, same bits), and its pooled map, which nothing else reads, is not written.
+                                  # Off by default: the default lowering is pinned
         peak_heads=(),            # with split_heads: heads (of split_heads or not) that are NOT read whole either, but at a second, longer position
                                   # list (multi_pose_decode reads `hp_offset` at the 17 x K key-point peaks).  They leave the eager launch
                                   # for the deferred groups, in their default place, and join the sparse op, where `run_sparse_lists`
@@ -164,13 +173,17 @@ class Plan:
         return len(self.ops) - 1
 
     def conv(self, x, wkey, out=None, bkey=None, bn=None, stride=1, relu=True, res=None, out_mode=_lib.OUT_NHWC,
-             pad_cout_to=None):
-        """out_mode OUT_NCHW_F32: `out` is the View of a head output (`_new_output`)."""
+             pad_cout_to=None, entry=False):
+        """out_mode OUT_NCHW_F32: `out` is the View of a head output (`_new_output`).
+        entry: the stride-2 conv1 of a Tree entry under fold_tree_entry.  It goes through csrc/conv2.hip below stream_s2_min_cin channels
+        too, and with fewer than 128 output channels on that kernel's one-slot 64-channel tile: the tile that has the fused twin (alone it
+        takes what csrc/conv.hip takes for level 2: 0.114 against 0.111 ms at batch 64)."""
         wshape = self.pw.sd[wkey].shape
         if (self.stream_convs and self.pw.dtype in LOWP and wshape[2] == 3 and wshape[1] % 16 == 0
-                and (stride == 1 or (stride == 2 and wshape[1] >= self.stream_s2_min_cin and self.stream_s2))
+                and (stride == 1 or (stride == 2 and (wshape[1] >= self.stream_s2_min_cin or entry) and self.stream_s2))
                 and out_mode == _lib.OUT_NHWC and pad_cout_to is None):
-            return self._conv_stream(x, wkey, out, bkey, bn, relu, res, stride)
+            tile = _lib.TUNE_CONV_STREAM_TILE(4, 2, 4) if entry and stride == 2 and 64 <= wshape[0] < 128 else 0
+            return self._conv_stream(x, wkey, out, bkey, bn, relu, res, stride, reserved=tile)
         wp, bp, cout, cin, k, rows = self.pw.conv(wkey, bkey, bn, pad_cout_to)
         assert cin == x.C, (wkey, cin, x.C)
         Ho = (x.H + 2 * (k // 2) - k) // stride + 1
@@ -188,7 +201,7 @@ class Plan:
                  out_mode=out_mode, wrows=rows, reserved=tune, wexp=self.pw.wexp.get(wp.data_ptr(), 0))
         return out
 
-    def _conv_stream(self, x, wkey, out, bkey, bn, relu, res, stride=1):
+    def _conv_stream(self, x, wkey, out, bkey, bn, relu, res, stride=1, reserved=0):
         """3x3 conv (stride 1 or 2) through the LDS-DMA kernel (csrc/conv2.hip)."""
         wimg, bp, cout, cin, rows = self.pw.conv_stream(wkey, bkey, bn)
         assert cin == x.C, (wkey, cin, x.C)
@@ -197,7 +210,7 @@ class Plan:
             out = self._alloc(Ho, Wo, cout)
         assert (out.H, out.W, out.C) == (Ho, Wo, cout), (wkey, out.H, out.W, out.C)
         self._op(_lib.OP_CONV_STREAM, x, out, res, w=wimg.data_ptr(), bias=bp.data_ptr(), ksize=3, stride=stride, relu=int(relu),
-                 out_mode=_lib.OUT_NHWC, wrows=rows)
+                 out_mode=_lib.OUT_NHWC, wrows=rows, reserved=reserved)
         return out
 
     def dcn(self, x, om, wkey, bkey, bn):
@@ -231,9 +244,9 @@ class Plan:
         return out
 
     # -- network ---------------------------------------------------------------------------------
-    def _block(self, x, p, stride, residual, out):
-        """BasicBlock (model.py:46-60): conv-bn-relu, conv-bn, +residual, relu."""
-        t = self.conv(x, p + ".conv1.weight", bn=p + ".bn1", stride=stride)
+    def _block(self, x, p, stride, residual, out, entry=False):
+        """BasicBlock (model.py:46-60): conv-bn-relu, conv-bn, +residual, relu.  entry: see `conv`."""
+        t = self.conv(x, p + ".conv1.weight", bn=p + ".bn1", stride=stride, entry=entry)
         return self.conv(t, p + ".conv2.weight", bn=p + ".bn2", res=residual, out=out)
 
     def _tree1(self, x, p, cin, cout, stride, level_root, out, cat=None, bottom=None, residual=None):
@@ -245,6 +258,9 @@ class Plan:
         if cat is None:
             cat = self._alloc(Ho, Wo, 2 * cout + (cin if level_root else 0))
         s_x2, s_x1 = cat.slice(0, cout), cat.slice(cout, cout)
+        # fold_tree_entry: pool, project and conv1 are lowered next to each other below (the pool by the caller when it passes `bottom`)
+        entry = self.fold_tree_entry and self.share_pool and stride == 2 and residual is None and cin != cout
+        private = bottom is None and not level_root         # ... and the pooled map is a buffer of its own that `project` alone reads
         if residual is not None:                             # (the caller already has project(pool(x)): csrc/stem3.hip PROJ)
             assert stride > 1 and not level_root and cin != cout and (residual.H, residual.W, residual.C) == (Ho, Wo, cout)
         elif bottom is not None:
@@ -253,15 +269,35 @@ class Plan:
             bottom = self.pool(x, cat.slice(2 * cout, cin) if level_root else None)
         else:
             bottom = x
+        n_proj = len(self.ops)
         if residual is not None:
             pass
         elif cin != cout:
             residual = self.conv(bottom, p + ".project.0.weight", bn=p + ".project.1", relu=False)
         else:
             residual = bottom
-        self._block(x, p + ".tree1", stride, residual, s_x1)
+        self._block(x, p + ".tree1", stride, residual, s_x1, entry=entry)
+        if entry:
+            self._flag_tree_entry(n_proj - 1, private)
         self._block(s_x1, p + ".tree2", 1, s_x1, s_x2)
         return self.conv(cat, p + ".root.conv.weight", bn=p + ".root.bn", out=out)
+
+    def _flag_tree_entry(self, i, private):
+        """fold_tree_entry: ops[i : i + 3] = the max-pool of x, `project` of the pooled map, conv1 of x.  Flagged where conv1 is a stride-2 op of
+        csrc/conv2.hip on a one-slot tile (the tiles with the fused twin: the launcher's own choice from 128 output channels on, the tile
+        `conv` asked for below that; every level measured faster fused than as three launches: DESIGN.md); the run loop checks the structure
+        again and ignores the flag wherever its tile cannot take the triple.  private: nothing else reads the pooled map (level 2)."""
+        if i < 0 or i + 3 > len(self.ops):
+            return
+        pool, proj, conv1 = self.ops[i:i + 3]
+        tile = 0 if conv1.Cout >= 128 else _lib.TUNE_CONV_STREAM_TILE(4, 2, 4)
+        if (pool.kind == _lib.OP_MAXPOOL and proj.kind == _lib.OP_CONV and conv1.kind == _lib.OP_CONV_STREAM and proj.ksize == 1 and conv1.stride == 2
+                and (proj.in_, proj.in_cs) == (pool.out, pool.out_cs) and (conv1.in_, conv1.in_cs) == (pool.in_, pool.in_cs)
+                and proj.Cout == conv1.Cout >= 64 and pool.H % 2 == 0 and pool.W % 2 == 0 and conv1.reserved == tile
+                and not (proj.reserved or pool.reserved)):
+            pool.reserved = _lib.OPF_TREE_ENTRY | (_lib.OPF_TREE_ENTRY_PRIVATE_POOL if private else 0)
+            proj.reserved = _lib.OPF_TREE_ENTRY
+            conv1.reserved = tile | _lib.OPF_TREE_ENTRY
 
     def _tree2(self, x, p, cin, cout, out):
         """Two-level Tree with level_root (level3/level4; model.py:209-222): Root input of the inner

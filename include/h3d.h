@@ -450,6 +450,20 @@ enum {
                                                   ignored, and the timed run reports the pair's time under the DeformConv op and 0 under this one    */
 };
 
+/* H3D_OP_MAXPOOL, H3D_OP_CONV and H3D_OP_CONV_STREAM, the 2-byte dtypes: the entry of a DLA Tree (Tree.forward, model.py:209-218) as one launch */
+enum {
+    H3D_OPF_TREE_ENTRY = 0x20000000,           /* on three ops in a row -- the 2x2 H3D_OP_MAXPOOL of x, the 1x1 H3D_OP_CONV (`project`: no residual, no ReLU)
+                                                  that reads exactly the pool's `out`, and the 3x3 stride-2 H3D_OP_CONV_STREAM that reads exactly the pool's
+                                                  `in`, H and W even, both convs with the same Cout >= 64, the 3x3 conv on a one-slot tile (its launcher's
+                                                  choice from 128 channels on; below that the op also carries H3D_TUNE_CONV_STREAM_TILE(4, 2, 4)) --:
+                                                  h3d_run_ops / h3d_run_ops_timed launch them as ONE kernel (csrc/conv2.hip ENTRY: the pool is the maximum of
+                                                  four taps the conv holds anyway, `project` one more MFMA chain per stage).  The same bits in all three outputs as the three launches.  Where the
+                                                  structure or the tile's conditions do not hold the flag is ignored, on a single op always; the timed run
+                                                  reports the launch under the pool op and 0 under the two convs                                      */
+    H3D_OPF_TREE_ENTRY_PRIVATE_POOL = 0x40000000 /* on the H3D_OP_MAXPOOL of such a triple: the plan's claim that nothing but the 1x1 conv reads the pooled
+                                                  map.  The one launch then does NOT write the pool's `out`                                          */
+};
+
 /* H3D_OP_HEADS (csrc/heads.hip) */
 enum {
     H3D_TUNE_HEADS_SEPARATE_BIAS = 0x200,      /* separate bias / zeroing pass (launches of equal-width heads only)                              */
