@@ -24,9 +24,12 @@ Training the heads `Conv3x3 + ReLU + Conv1x1` (models.model.DLASeg.__init__ / fo
         with the optimiser state -> h3d_amd.optim.Adam, h3d_amd.trainer.HeadsTrainer, h3d_amd.checkpoint.{save_model,load_model}
 Training plain convolutions (nn.Conv2d, models.model.BasicBlock / Root with folded BatchNorm) -> h3d_amd.conv.{conv2d_backward,
         conv2d_autograd,TrainableConv2d,TrainableBasicBlock}
+Training the whole DLA-34 (models.model.DLASeg with frozen BatchNorm statistics): nn.MaxPool2d(2, 2) and IDAUp's depthwise
+        ConvTranspose2d + skip add -> h3d_amd.pool_up.{max_pool2_backward,upsample_backward,max_pool2_autograd,up_add_autograd};
+        the network under autograd -> h3d_amd.train_model.TrainableDLASeg, h3d_amd.trainer.NetworkTrainer
 Without a counterpart in the reference: the 3D evaluation of the SMPL output, MPJPE / PA-MPJPE / PVE / PA-PVE on the device
         -> h3d_amd.mesh_eval.{GroundTruth3D,pointset_errors,metric_means,evaluate_pairs,MeshEvaluator}, HeadsTrainer.val(loader, gt, gt3d, smpl_model)
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth", "arch", "model", "engine", "weights", "plan", "dcn_calibrate", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets", "heads", "train_input", "optim", "trainer", "checkpoint", "mesh_eval", "conv"]
+__all__ = ["synth", "arch", "model", "engine", "weights", "plan", "dcn_calibrate", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets", "heads", "train_input", "optim", "trainer", "checkpoint", "mesh_eval", "conv", "pool_up", "train_model"]

@@ -218,6 +218,10 @@ SIGNATURES = {
     "h3d_conv2d_backward_workspace_bytes": [c_i] * 14 + [ctypes.POINTER(ctypes.c_size_t)],
     "h3d_conv2d_backward": [c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_i] + [c_vp] * 4 + [c_i] * 14 + [c_vp, ctypes.c_size_t, c_vp],
     "h3d_conv2d_backward_general": [c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_i] + [c_vp] * 4 + [c_i] * 14 + [c_vp, ctypes.c_size_t, c_vp],
+    # max-pool and up-sample + add backward (include/h3d.h section 2d; h3d_amd/pool_up.py)
+    "h3d_maxpool2_backward": [c_vp, c_i, c_vp, c_i, c_vp, c_i] + [c_i] * 4 + [c_vp],
+    "h3d_upsample_backward_workspace_bytes": [c_i] * 5 + [ctypes.POINTER(ctypes.c_size_t)],
+    "h3d_upsample_backward": [c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_i, c_vp] + [c_i] * 5 + [c_vp, ctypes.c_size_t, c_vp],
     # training targets (include/h3d.h section 6; h3d_amd/targets.py)
     "h3d_targets_workspace_bytes": [c_i] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
     "h3d_multi_pose_targets": [c_vp] * 8 + [c_i] * 7 + [c_vp] * 13 + [c_i, c_vp, ctypes.c_size_t, c_vp],

@@ -1,12 +1,14 @@
 """The training side of the reference's HMRTrainer (trains/trainer.py:140-323) for what trains here: the output heads on the frozen
 backbone (heads.TrainableHeads), the fused losses (losses.loss_multi_pose / loss_obj_detection) and the one-launch Adam step
-(optim.Adam).  Printing, `debug`, the logger and the data loaders are the caller's."""
+(optim.Adam).  NetworkTrainer (below) is the same loop over the whole network under autograd (train_model.TrainableDLASeg, BatchNorm
+folded).  Printing, `debug`, the logger and the data loaders are the caller's."""
 import time
 
 import torch
 
 from . import checkpoint, losses, optim
 from .heads import TrainableHeads
+from .train_model import TrainableDLASeg
 
 
 def _opt(opt, name, default):
@@ -48,11 +50,13 @@ class HeadsTrainer:
     the loss is smpl_loss.loss_multi_pose_smpl, which adds the keypoint reprojection loss on the SMPL output and so trains the `pose`,
     `shape` and `cam` (3 channels) heads the model must then have; otherwise nothing changes."""
 
+    MODULE = TrainableHeads         # what trains: the module type behind `self.heads`
+
     def __init__(self, opt, model, smpl_model=None, kp_regressor=None):
         self.opt = opt
         self.model = model
         self.smpl_model = smpl_model
-        self.heads = TrainableHeads(model)
+        self.heads = self.MODULE(model)
         task = _opt(opt, "task", "multi_pose")
         if task == "multi_pose" and smpl_model is not None and kp_regressor is not None and _opt(opt, "smpl_kp_weight", 0) > 0:
             from . import smpl_loss
@@ -124,6 +128,7 @@ class HeadsTrainer:
         from . import coco_eval, decode
         from .detector import multi_pose_post_process
         opt = self.opt
+        self._before_val()
         if _opt(opt, "task", "multi_pose") != "multi_pose":
             raise ValueError("HeadsTrainer.val: task %r not defined" % (_opt(opt, "task", None),))
         model = self.model
@@ -168,6 +173,9 @@ class HeadsTrainer:
             self.last_val["mesh"] = meshes.compute()
         return self.last_val["keypoints"].stats, self.last_val["bbox"].stats
 
+    def _before_val(self):
+        """What val() does before it runs `self.model` (nothing here: the heads are the model's own parameters)."""
+
     def end_epoch(self, epoch):
         """The learning-rate drop of trainer.py:316-320; -> the new rate, or None when `epoch` is no step."""
         if epoch not in self.lr_step:
@@ -184,3 +192,14 @@ class HeadsTrainer:
         """-> start_epoch (trainer.py:167-169)."""
         _, _, start_epoch = checkpoint.load_model(self.heads, model_path, self.optimizer, resume, self.lr, self.lr_step)
         return start_epoch
+
+
+class NetworkTrainer(HeadsTrainer):
+    """HeadsTrainer with the whole network under autograd: `self.heads` is a train_model.TrainableDLASeg (the reference's graph on the
+    trainable operators, BatchNorm folded: frozen statistics), Adam runs over all of its parameters (optim.Adam launches them in blocks
+    of H3D_ADAM_CAPACITY tensors), and val() first loads the trained weights back into `model` (TrainableDLASeg.sync)."""
+
+    MODULE = TrainableDLASeg
+
+    def _before_val(self):
+        self.heads.sync()

@@ -598,6 +598,33 @@ int h3d_conv2d_backward_general(const float *x, int x_cs, const float *weight, c
                                 size_t workspace_bytes, void *stream);
 
 /* =====================================================================================
+ * 2d. Max-pool and up-sample + add backward (csrc/pool_up_bwd.hip): the gradients of H3D_OP_MAXPOOL (2x2, stride 2, floor) and of
+ *     H3D_OP_UPADD, y = skip + ConvTranspose2d(x; w, k = 2f, stride f, padding p = f/2, groups = C).
+ *    Common: fp32 NHWC with a channel stride (*_cs >= C, a multiple of 4), 16-byte aligned; C % 4 == 0; every output pointer may be NULL
+ *    (all NULL: nothing is launched); no float atomics: every output element is written exactly once, as a sum in a fixed order, so the
+ *    results are bit-identical from run to run whichever other outputs are requested; outputs are overwritten, never accumulated into.
+ *    Non-positive or inconsistent sizes (C % 4, a channel stride below C or no multiple of 4, f outside {2, 4, 8}, more than 2^31 / 4
+ *    pixels): H3D_ERR_SHAPE.  NULL operands, a misaligned pointer, a NULL / misaligned / short workspace ("workspace" in the message):
+ *    H3D_ERR_ARG.  Every check runs before the first HIP call.
+ *    - h3d_maxpool2_backward: x [B,H,W,C], grad_y [B,H/2,W/2,C] (floor; not read when H < 2 or W < 2), grad_x [B,H,W,C at gx_cs].  The
+ *      gradient of an output pixel goes to the FIRST element of its window, in the order (0,0), (0,1), (1,0), (1,1), that equals the
+ *      window's maximum (the scan of torch's CPU max_pool2d: from -inf, move on `v > max || isnan(v)`); the other three elements and the
+ *      last row / column of an odd H / W get 0.  The argmax is recomputed from x.
+ *    - h3d_upsample_backward: x [B,H,W,C], w = H3D_OP_UPADD's tap-major [k*k][C] image (k = 2f), grad_y [B,H f,W f,C];
+ *          grad_x[c,iy,ix] = sum_{ki,kj} w[ki,kj,c] gy[c, iy f - p + ki, ix f - p + kj]              (grad_x [B,H,W,C at gx_cs])
+ *          grad_w[ki,kj,c] = sum_{b,iy,ix} x[b,c,iy,ix] gy[b,c, iy f - p + ki, ix f - p + kj]         (grad_w [k*k][C], contiguous)
+ *      over the in-range positions (an out-of-range position enters as an exact zero).  The skip's gradient is grad_y itself.
+ *      Order: grad_x is the sum of R = 1, 2, 16 (f = 2, 4, 8) fmaf chains over 2f / R kernel rows each, taps in (ki, kj) order, the
+ *      chains added in order.  grad_w: one fmaf chain per tile of 8x8, 4x4, 2x2 input pixels (row-major), then with S = B * tiles,
+ *      G = ceil(S / 64): chain g adds the tiles g, g + G, ... in order (at most 64 terms), and the G chain sums are added in order.
+ *      workspace (256-byte aligned; read only with grad_w): ceil(S / G) G k k C floats + (G > 1 ? G k k C : 0), each rounded up to 256 bytes. */
+int h3d_maxpool2_backward(const float *x, int x_cs, const float *grad_y, int gy_cs, float *grad_x, int gx_cs, int B, int C, int H, int W,
+                          void *stream);
+int h3d_upsample_backward_workspace_bytes(int B, int C, int H, int W, int f, size_t *bytes);
+int h3d_upsample_backward(const float *x, int x_cs, const float *w, const float *grad_y, int gy_cs, float *grad_x, int gx_cs, float *grad_w,
+                          int B, int C, int H, int W, int f, void *workspace, size_t workspace_bytes, void *stream);
+
+/* =====================================================================================
  * 3. Heat-map decode (decode.py, utils.py).  All tensors contiguous NCHW fp32 as the
  *    reference's heads (model.py:485-489).  Index outputs are int64 like torch.topk's.
  *    Tie rule: equal scores -> lowest flat index first (torch leaves it unspecified).
