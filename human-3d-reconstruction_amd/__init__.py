@@ -32,4 +32,4 @@ Without a counterpart in the reference: the 3D evaluation of the SMPL output, MP
 """
 from . import synth  # noqa: F401
 
-__all__ = ["synth", "arch", "model", "engine", "weights", "plan", "dcn_calibrate", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets", "heads", "train_input", "optim", "trainer", "checkpoint", "mesh_eval", "conv", "pool_up", "train_model"]
+__all__ = ["synth", "arch", "model", "engine", "weights", "plan", "dcn_calibrate", "decode", "utils", "dcn_v2", "smpl", "detector", "losses", "targets", "heads", "train_input", "optim", "trainer", "checkpoint", "mesh_eval", "conv", "pool_up", "bn", "train_model"]

@@ -222,6 +222,13 @@ SIGNATURES = {
     "h3d_maxpool2_backward": [c_vp, c_i, c_vp, c_i, c_vp, c_i] + [c_i] * 4 + [c_vp],
     "h3d_upsample_backward_workspace_bytes": [c_i] * 5 + [ctypes.POINTER(ctypes.c_size_t)],
     "h3d_upsample_backward": [c_vp, c_i, c_vp, c_vp, c_i, c_vp, c_i, c_vp] + [c_i] * 5 + [c_vp, ctypes.c_size_t, c_vp],
+    # BatchNorm with batch statistics (include/h3d.h section 2e; h3d_amd/bn.py)
+    "h3d_batch_norm_workspace_bytes": [c_i] * 4 + [ctypes.POINTER(ctypes.c_size_t)],
+    "h3d_batch_norm_plan": [c_i] * 4 + [ctypes.POINTER(c_i), ctypes.POINTER(c_i)],
+    "h3d_batch_norm_forward": [c_vp, c_i, c_vp, c_vp, c_vp, c_i, c_vp, c_i] + [c_vp] * 5 + [c_i] * 6 + [ctypes.c_float, ctypes.c_float, c_vp,
+                               ctypes.c_size_t, c_vp],
+    "h3d_batch_norm_backward": [c_vp, c_i, c_vp, c_i, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_i, c_vp, c_vp] + [c_i] * 6 +
+                               [c_vp, ctypes.c_size_t, c_vp],
     # training targets (include/h3d.h section 6; h3d_amd/targets.py)
     "h3d_targets_workspace_bytes": [c_i] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
     "h3d_multi_pose_targets": [c_vp] * 8 + [c_i] * 7 + [c_vp] * 13 + [c_i, c_vp, ctypes.c_size_t, c_vp],

@@ -10,6 +10,7 @@ with the reference's state_dict names on it so reference checkpoints load unchan
 LEVELS = (1, 1, 1, 2, 2, 1)              # dla34 (model.py:309-312)
 CHANNELS = (16, 32, 64, 128, 256, 512)
 BN_EPS = 1e-5
+BN_MOMENTUM = 0.1     # models/model.py:18
 
 
 def _bn(shapes, p, c):

@@ -3,10 +3,17 @@ the trainable operators: `conv.conv2d_autograd` (stem, level0 / level1, BasicBlo
 `pool_up.max_pool2_autograd` (Tree.downsample), `TrainableDCN`'s route (the DeformConvs; `conv2d_autograd` with `not_use_dcn`),
 `pool_up.up_add_autograd` (IDAUp's up-sampling + skip add) and `heads.heads_autograd`.
 
-Every BatchNorm is folded into the convolution in front of it (weights.PackedWeights._fold, the engine's folding): training the folded
-filters and biases is fine-tuning with FROZEN statistics.  Batch statistics (training-mode BatchNorm) are not implemented.
+bn="frozen" (the default): every BatchNorm is folded into the convolution in front of it (weights.PackedWeights._fold, the engine's
+folding): training the folded filters and biases is fine-tuning with FROZEN statistics.
+bn="batch": the reference's own training (HMRTrainer.run_epoch: model.train()): the parameters are the reference's tensors (conv.weight,
+each BatchNorm's weight / bias, the DeformConvs' conv.bias and conv_offset_mask.*, up_k.weight, the heads), the running statistics and
+num_batches_tracked are buffers, nothing is folded: a convolution without bias, residual or ReLU, then `bn.batch_norm_autograd`
+(+ residual) (+ ReLU) where the reference has its BatchNorm.  .train(): batch statistics, the running ones move; .eval(): the running
+ones, through the same operator.  The state_dict is the reference's keys and nothing else.  One deviation: the reference's two-level
+Trees also run their unused `project` in train() and so move base.level3/4.project.1's running statistics, which no output reads;
+here they stay as stored.
 
-    TrainableDLASeg(model)      model: a model.dla_net(...) in 'f32' or 'f16x3' with head_conv > 0, with or without DCN
+    TrainableDLASeg(model, bn="frozen")    model: a model.dla_net(...) in 'f32' or 'f16x3' with head_conv > 0, with or without DCN
       .forward(x)               [ {head: [B,C,H/4,W/4]} ], differentiable at every parameter
       .export_state_dict()      the reference's keys, every fold undone (conv.weight = W' / scale, the shift in the BatchNorm's bias)
       .state_dict() / .load_state_dict()    the export (plus the folded tensors themselves, below) and its inverse
@@ -16,6 +23,7 @@ import torch
 from torch import nn
 
 from . import arch
+from . import bn as bn_ops
 from .conv import conv2d_autograd
 from .dcn_v2 import dcn_v2_conv_autograd
 from .heads import heads_autograd
@@ -38,15 +46,31 @@ def _conv_of_bn(bn):
     raise ValueError("TrainableDLASeg: no convolution known in front of BatchNorm %r" % bn)
 
 
+def _bn_of_conv(conv):
+    """The inverse of `_conv_of_bn` for the plain convolutions (not the DeformConvs)."""
+    head, leaf = conv.rsplit(".", 1)
+    if leaf in ("conv1", "conv2"):
+        return head + ".bn" + leaf[4]
+    if leaf == "conv":
+        return head + ".bn"
+    if leaf == "0":
+        return head + ".1"
+    raise ValueError("TrainableDLASeg: no BatchNorm known behind convolution %r" % conv)
+
+
 def _name(key):
     return key.replace(".", "__")       # (parameter names may not hold a dot; no reference key holds two underscores in a row)
 
 
 class TrainableDLASeg(nn.Module):
     DTYPES = ("f32", "f16x3")
+    BN_MODES = ("frozen", "batch")
 
-    def __init__(self, model):
+    def __init__(self, model, bn="frozen"):
         super().__init__()
+        if bn not in self.BN_MODES:
+            raise ValueError("TrainableDLASeg: bn must be one of %s, not %r" % (self.BN_MODES, bn))
+        self.bn = bn
         if model.compute_dtype not in self.DTYPES:
             raise ValueError("TrainableDLASeg: the model must run in 'f32' or 'f16x3' (fp32 maps), not %r" % (model.compute_dtype,))
         if getattr(model, "arch_name", "") != "dla34" or model.head_conv <= 0:
@@ -59,10 +83,22 @@ class TrainableDLASeg(nn.Module):
         self._bns = [k[:-len(".running_mean")] for k in sd if k.endswith(".running_mean")
                      and not any(k.startswith(u + ".") for u in self._unused)]
         self._plain = [k for k in sd if ".conv_offset_mask." in k or ".up_" in k]
-        self.folded = nn.ParameterDict()
         dev = next(model.parameters()).device
-        for key, t in self._fold_all(sd).items():
-            self.folded[_name(key)] = nn.Parameter(t.to(dev))
+        if bn == "batch":
+            # the reference's own tensors: parameters under `ref`, the running statistics and counters as buffers
+            convs = [_conv_of_bn(b) for b in self._bns]
+            self._ref_params = [c + ".weight" for c in convs] + [c + ".bias" for c in convs if c + ".bias" in sd] + \
+                               [b + leaf for b in self._bns for leaf in (".weight", ".bias")] + list(self._plain)
+            self._ref_buffers = [b + leaf for b in self._bns for leaf in (".running_mean", ".running_var", ".num_batches_tracked") if b + leaf in sd]
+            self.ref = nn.ParameterDict()
+            for key in self._ref_params:
+                self.ref[_name(key)] = nn.Parameter(sd[key].detach().clone().to(dev))
+            for key in self._ref_buffers:
+                self.register_buffer(_name(key), sd[key].detach().clone().to(dev))
+        else:
+            self.folded = nn.ParameterDict()
+            for key, t in self._fold_all(sd).items():
+                self.folded[_name(key)] = nn.Parameter(t.to(dev))
         for head in model.heads:
             self.add_module(head, model._modules[head])
 
@@ -93,7 +129,10 @@ class TrainableDLASeg(nn.Module):
         return out
 
     def _p(self, key):
-        return self.folded[_name(key)]
+        return self.ref[_name(key)] if self.bn == "batch" else self.folded[_name(key)]
+
+    def _b(self, key):
+        return self._buffers[_name(key)]
 
     @staticmethod
     def _unfold(w, b, s, b0, mean):
@@ -119,6 +158,10 @@ class TrainableDLASeg(nn.Module):
         shift b' - (conv.bias - running_mean) * scale in the BatchNorm's bias (conv.bias of a DeformConv stays as stored); running
         statistics and the BatchNorm weights untouched.  Tensors on the model's device."""
         sd = {k: v.detach().clone() for k, v in self._model.state_dict().items()}
+        if self.bn == "batch":
+            for k in self._ref_params + self._ref_buffers:
+                sd[k] = (self._p(k) if k in self._ref_params else self._b(k)).detach().clone().to(sd[k].device)
+            return sd
         for k, v in self._export_of(sd, self._p).items():
             sd[k] = v.to(sd[k].device)
         return sd
@@ -128,6 +171,8 @@ class TrainableDLASeg(nn.Module):
         fp32 (for |scale| > 1 not every W' is the rounded product of an fp32 filter), so a resumed run could not continue with the bits
         of the uninterrupted one from the reference's keys alone.  A reader that only knows the reference's keys ignores the rest."""
         sd = self.export_state_dict()
+        if self.bn == "batch":
+            return sd
         for name, p in self.folded.items():
             sd[FOLDED_PREFIX + name.replace("__", ".")] = p.detach().clone()
         return sd
@@ -139,6 +184,12 @@ class TrainableDLASeg(nn.Module):
         ref = {k: v for k, v in state_dict.items() if not k.startswith(FOLDED_PREFIX)}
         ret = self._model.load_state_dict(ref, strict=strict)
         loaded = self._model.state_dict()
+        if self.bn == "batch":
+            with torch.no_grad():
+                for k in self._ref_params + self._ref_buffers:
+                    dst = self._p(k) if k in self._ref_params else self._b(k)
+                    dst.copy_(loaded[k].to(dst.device))
+            return ret
         folded = self._fold_all(loaded)
         kept = {k: state_dict.get(FOLDED_PREFIX + k) for k in folded}
         if all(v is not None and tuple(v.shape) == tuple(folded[k].shape) for k, v in kept.items()):
@@ -160,7 +211,17 @@ class TrainableDLASeg(nn.Module):
         return self._model
 
     # ---- the graph (oracle/dla.py follows the same reference lines) ----------------------------------------------------------------------
+    def _bn(self, x, key, res=None, relu=False):
+        """BatchNorm `key` (+ res) (+ ReLU) on the batch's statistics in train(), the running ones in eval()."""
+        if self.training and key + ".num_batches_tracked" in self._ref_buffers:
+            self._b(key + ".num_batches_tracked").add_(1)
+        return bn_ops.batch_norm_autograd(x, self._p(key + ".weight"), self._p(key + ".bias"), self._b(key + ".running_mean"),
+                                          self._b(key + ".running_var"), self.training, arch.BN_MOMENTUM, arch.BN_EPS, res, relu)
+
     def _cb(self, x, conv, stride=1, padding=0, res=None, relu=False):
+        if self.bn == "batch":
+            y = conv2d_autograd(x, self._p(conv + ".weight"), None, stride, padding, 1, None, False)
+            return self._bn(y, _bn_of_conv(conv), res, relu)
         return conv2d_autograd(x, self._p(conv + ".weight"), self._p(conv + ".bias"), stride, padding, 1, res, relu)
 
     def _block(self, x, p, stride, residual=None):
@@ -187,7 +248,10 @@ class TrainableDLASeg(nn.Module):
 
     def _deform_conv(self, x, p):
         w, b = self._p(p + ".conv.weight"), self._p(p + ".conv.bias")
+        batch = self.bn == "batch"
         if not self.use_dcn:
+            if batch:
+                return self._bn(conv2d_autograd(x, w, b, 1, 1, 1, None, False), p + ".actf.0", None, True)
             return conv2d_autograd(x, w, b, 1, 1, 1, None, True)
         B, _, H, W = x.shape
         x = x.contiguous()                                   # (the DeformConv operator and its backward are NCHW)
@@ -198,7 +262,7 @@ class TrainableDLASeg(nn.Module):
                                    (1, 1), (1, 1), (1, 1), 1)
         o1, o2, mask = torch.chunk(out, 3, dim=1)
         y = dcn_v2_conv_autograd(x, torch.cat((o1, o2), dim=1), torch.sigmoid(mask), w, b, (1, 1), (1, 1), (1, 1), 1)
-        return torch.relu(y)
+        return self._bn(y, p + ".actf.0", None, True) if batch else torch.relu(y)
 
     def _ida_up(self, layers, p, startp, endp):
         for i in range(startp + 1, endp):

@@ -56,7 +56,7 @@ class HeadsTrainer:
         self.opt = opt
         self.model = model
         self.smpl_model = smpl_model
-        self.heads = self.MODULE(model)
+        self.heads = self._build_module(model)
         task = _opt(opt, "task", "multi_pose")
         if task == "multi_pose" and smpl_model is not None and kp_regressor is not None and _opt(opt, "smpl_kp_weight", 0) > 0:
             from . import smpl_loss
@@ -75,6 +75,9 @@ class HeadsTrainer:
         self.lr = _opt(opt, "lr", 1.25e-4)
         self.lr_step = list(_opt(opt, "lr_step", [90, 120]))
         self.optimizer = optim.Adam(self.heads.parameters(), self.lr)
+
+    def _build_module(self, model):
+        return self.MODULE(model)
 
     def train_step(self, batch):
         """forward, loss.mean(), zero_grad(), backward(), step() (trainer.py:262-267) -> (output, loss, loss_stats)."""
@@ -196,10 +199,19 @@ class HeadsTrainer:
 
 class NetworkTrainer(HeadsTrainer):
     """HeadsTrainer with the whole network under autograd: `self.heads` is a train_model.TrainableDLASeg (the reference's graph on the
-    trainable operators, BatchNorm folded: frozen statistics), Adam runs over all of its parameters (optim.Adam launches them in blocks
-    of H3D_ADAM_CAPACITY tensors), and val() first loads the trained weights back into `model` (TrainableDLASeg.sync)."""
+    trainable operators), Adam runs over all of its parameters (optim.Adam launches them in blocks of H3D_ADAM_CAPACITY tensors), and
+    val() first loads the trained weights back into `model` (TrainableDLASeg.sync).
+    bn: "frozen" (BatchNorm folded: frozen statistics) or "batch" (the reference's training-mode BatchNorm: run_epoch's
+    model_with_loss.train(train) switches between batch and running statistics); None takes opt.bn if present, else "frozen"."""
 
     MODULE = TrainableDLASeg
+
+    def __init__(self, opt, model, smpl_model=None, kp_regressor=None, bn=None):
+        self.bn = _opt(opt, "bn", "frozen") if bn is None else bn
+        super().__init__(opt, model, smpl_model, kp_regressor)
+
+    def _build_module(self, model):
+        return self.MODULE(model, bn=self.bn)
 
     def _before_val(self):
         self.heads.sync()

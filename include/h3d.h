@@ -625,6 +625,40 @@ int h3d_upsample_backward(const float *x, int x_cs, const float *w, const float 
                           int B, int C, int H, int W, int f, void *workspace, size_t workspace_bytes, void *stream);
 
 /* =====================================================================================
+ * 2e. BatchNorm2d with batch statistics (csrc/bn.hip): nn.BatchNorm2d (+ residual) (+ ReLU) in training and evaluation mode, and its
+ *     gradients.  2d's common contract: fp32 NHWC with a channel stride (*_cs >= C, a multiple of 4), every operand 16-byte aligned,
+ *     C % 4 == 0, every output pointer may be NULL, no float atomics, every output element written once as a sum in a fixed order that
+ *     depends on the shape alone, outputs overwritten.  Errors as in 2d; N = B H W = 1 in training: H3D_ERR_SHAPE (torch refuses it too);
+ *     eps < 0 or momentum outside [0, 1]: H3D_ERR_ARG.  Every check runs before the first HIP call.
+ *       mean = sum x / N, var = sum (x - mean)^2 / N (biased, two passes), invstd = 1 / sqrt(var + eps)
+ *       y = act((x - mean) (gamma invstd) + beta + res)          res optional; act = ReLU (relu != 0) or the identity
+ *    - h3d_batch_norm_forward, training != 0: the statistics are the batch's.  Writes y, mean (= save_mean), var (biased), save_invstd and,
+ *      in place, running_mean <- (1 - momentum) running_mean + momentum mean, running_var <- (1 - momentum) running_var + momentum var N / (N - 1).
+ *      training == 0: `mean` / `var` are inputs (the running statistics); writes y and save_invstd.
+ *      Launches: 1 in evaluation; in training 1 when the plan has one slot, else 3.
+ *    - h3d_batch_norm_backward: gg = grad_y [y > 0] under ReLU (the mask from the saved output y; y is not read otherwise), else grad_y.
+ *          grad_res = gg     grad_beta = sum gg     grad_gamma = sum gg xhat,  xhat = (x - save_mean) save_invstd
+ *          training:   grad_x = gamma invstd (gg - grad_beta / N - xhat grad_gamma / N)
+ *          evaluation: grad_x = gg gamma invstd
+ *      gamma is read only with grad_x.  At most 2 launches.
+ *    - Order of the sums (h3d_batch_norm_plan): a workgroup is V x PPP threads (V = 1, 2, 4, 8 = the smallest with 4 V >= min(C, 32),
+ *      PPP = 256 / V) and owns `chunk` consecutive pixels of 4 V channels: thread p adds the pixels p, p + PPP, ... of the chunk in order (at
+ *      most 64 terms), the PPP sums meet in a halving tree (h = PPP / 2 ... 1: p += p + h).  The `slots` = ceil(N / chunk) workgroup sums are
+ *      added as h3d_upsample_backward adds its tiles: G = ceil(slots / 64) chains over the slots g, g + G, ..., then the chain sums in order.
+ *      The per-channel scalars (the divisions by N, invstd, the running update) are formed in double and rounded once.
+ *    - workspace (256-byte aligned): 2 slots C floats + 2 C floats, each rounded up to 256 bytes; needed by backward, and by the training
+ *      forward when slots > 1. */
+int h3d_batch_norm_workspace_bytes(int B, int C, int H, int W, size_t *bytes);
+int h3d_batch_norm_plan(int B, int C, int H, int W, int *chunk, int *slots);
+int h3d_batch_norm_forward(const float *x, int x_cs, const float *gamma, const float *beta, const float *res, int res_cs, float *y, int y_cs,
+                           float *mean, float *var, float *save_invstd, float *running_mean, float *running_var, int B, int C, int H, int W,
+                           int training, int relu, float momentum, float eps, void *workspace, size_t workspace_bytes, void *stream);
+int h3d_batch_norm_backward(const float *x, int x_cs, const float *y, int y_cs, const float *grad_y, int gy_cs, const float *gamma,
+                            const float *save_mean, const float *save_invstd, float *grad_x, int gx_cs, float *grad_res, int gr_cs,
+                            float *grad_gamma, float *grad_beta, int B, int C, int H, int W, int training, int relu, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
+/* =====================================================================================
  * 3. Heat-map decode (decode.py, utils.py).  All tensors contiguous NCHW fp32 as the
  *    reference's heads (model.py:485-489).  Index outputs are int64 like torch.topk's.
  *    Tie rule: equal scores -> lowest flat index first (torch leaves it unspecified).

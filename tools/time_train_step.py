@@ -2,7 +2,10 @@
 (the heads on the frozen backbone) on a synthetic multi_pose batch at 512x512, B = 8: wall time (HIP events around `--reps` steps after
 `--warmup` steps, median of `--rounds` rounds) and the peak of torch's device allocator over a step.
 
-    python tools/time_train_step.py [--out profiles/train_step.json]
+    python tools/time_train_step.py [--bn batch] [--out profiles/train_step.json]
+
+--bn batch adds the same step with training-mode BatchNorm (NetworkTrainer(bn="batch"), h3d_amd/bn.py) under "NetworkTrainer_bn_batch",
+measured in the same process right after the frozen step.
 """
 import argparse, json, os, random, sys
 from types import SimpleNamespace as NS
@@ -18,6 +21,7 @@ ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--plain", action="store_true", help="not_use_dcn")
+ap.add_argument("--bn", choices=("frozen", "batch"), default="frozen", help="batch: also time NetworkTrainer(bn='batch')")
 ap.add_argument("--out", default="profiles/train_step.json")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -57,8 +61,8 @@ batch = train_input.multi_pose_train_batch(imgs, np.stack([s[0] for s in scenes]
                                            data_rng=np.random.RandomState(123))
 
 
-def measure(cls):
-    tr = cls(opt, make_net())
+def measure(cls, **kw):
+    tr = cls(opt, make_net(), **kw)
     for _ in range(args.warmup):
         tr.train_step(dict(batch))
     torch.cuda.synchronize()
@@ -84,6 +88,11 @@ for name, cls in (("HeadsTrainer", trainer.HeadsTrainer), ("NetworkTrainer", tra
     res[name] = measure(cls)
     print(name, json.dumps(res[name]), flush=True)
     torch.cuda.empty_cache()
+if args.bn == "batch":
+    res["NetworkTrainer_bn_batch"] = measure(trainer.NetworkTrainer, bn="batch")
+    print("NetworkTrainer_bn_batch", json.dumps(res["NetworkTrainer_bn_batch"]), flush=True)
+    torch.cuda.empty_cache()
+    res["ratio_ms_batch_over_frozen"] = res["NetworkTrainer_bn_batch"]["ms"] / res["NetworkTrainer"]["ms"]
 # what the graph of one image keeps for its backward: distinct storages handed to save_for_backward during one forward
 seen = {}
 
