@@ -9,6 +9,9 @@ Reference-named entry points (same names / argument meaning as the reference's s
     models.model.dla_net                      -> h3d_amd.model.dla_net
     models.DCNv2.dcn_v2.{dcn_v2_conv,DCNv2,DCN,dcn_v2_pooling,DCNv2Pooling,DCNPooling},
         _ext.{dcn_v2_forward,dcn_v2_psroi_pooling_forward} -> h3d_amd.dcn_v2.*
+    training (opt-in; the names above stay inference-only): _ext.{dcn_v2_backward,dcn_v2_psroi_pooling_backward} -> h3d_amd.dcn_v2.*,
+        _DCNv2.apply / _DCNv2Pooling.apply -> h3d_amd.dcn_v2.{dcn_v2_conv_autograd,dcn_v2_pooling_autograd}, DCNv2 / DCN / DCNv2Pooling /
+        DCNPooling under autograd -> h3d_amd.dcn_v2.{TrainableDCNv2,TrainableDCN,TrainableDCNv2Pooling,TrainableDCNPooling}
     models.decode.{_nms,_topk,_topk_channel,multi_pose_decode,ctdet_decode} -> h3d_amd.decode.*
     models.utils.{_sigmoid,_gather_feat,_transpose_and_gather_feat} -> h3d_amd.utils.*
     utils.post_process.multi_pose_post_process -> h3d_amd.detector.multi_pose_post_process

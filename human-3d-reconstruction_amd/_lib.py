@@ -164,6 +164,9 @@ SIGNATURES = {
     "h3d_dcn_offset_mask": [c_vp] * 5 + [c_i] * 11 + [c_vp],
     "h3d_dcn_v2_psroi_pooling_forward": [c_vp] * 5 + [c_i] * 7 + [ctypes.c_float] + [c_i] * 5 + [ctypes.c_float, c_vp],
     "h3d_dcn_pooling_modulated": [c_vp] * 4 + [c_i] * 5 + [ctypes.c_float] + [c_i] * 5 + [ctypes.c_float, c_vp],
+    "h3d_dcn_v2_psroi_pooling_backward": [c_vp] * 7 + [c_i] * 8 + [ctypes.c_float] + [c_i] * 5 + [ctypes.c_float, c_i, c_vp],
+    "h3d_dcn_pooling_modulated_backward": [c_vp] * 6 + [c_i] * 5 + [ctypes.c_float] + [c_i] * 5 + [ctypes.c_float, c_i, c_vp],
+    "h3d_psroi_backward_path": [c_vp, c_vp] + [c_i] * 6 + [ctypes.c_float] + [c_i] * 3 + [ctypes.c_float, c_i, c_i, ctypes.POINTER(c_i)],
     "h3d_build_flags": [],
     "h3d_dcn_fused_ck": [c_i, c_i],
     "h3d_dcn_far_samples": [ctypes.POINTER(H3dOp), c_vp, c_vp],

@@ -16,11 +16,14 @@
 //   masked mode    the DCNPooling second pass: offsets are channels 0/1 of the fully-connected output [R,3,P,P] (roi stride
 //                  3*P*P), and the result is multiplied by sigmoid(channel 2) -- chunk + cat + sigmoid + pool + mul in one launch.
 //
-// Compiled with -ffp-contract=off: every geometry operation is one IEEE fp32 operation in the reference's order, so sample
-// positions and counts match an fp32 restatement exactly.  Guards come before any address is formed: a roi whose batch index is
-// not finite or truncates outside [0, B) yields 0 / count 0; non-finite coordinates follow the reference's arithmetic (infinite
-// samples fail the gate, NaN ones are clamped to 0 by fmaxf / fminf), so every corner address is inside its channel plane.
+// The sample geometry is csrc/psroi_geom.h's (shared with the backward, csrc/psroi_bwd.hip).  Compiled with -ffp-contract=off: every
+// geometry operation is one IEEE fp32 operation in the reference's order, so sample positions and counts match an fp32 restatement
+// exactly.  Guards come before any address is formed: a roi whose batch index is not finite or truncates outside [0, B) yields
+// 0 / count 0; non-finite coordinates follow the reference's arithmetic (infinite samples fail the gate, NaN ones are clamped to 0
+// by fmaxf / fminf), so every corner address is inside its channel plane.
 #include "common.h"
+#include "psroi_geom.h"
+#include "psroi_check.h"
 
 constexpr int PSROI_THREADS = 256;
 constexpr int PSROI_LDS_SAMPLES = 2048;   // 32 KiB of sample table per workgroup at most
@@ -52,19 +55,10 @@ __global__ __launch_bounds__(PSROI_THREADS) void psroi_kernel(PsroiArgs a)
         const int k = (int)(nk % a.ncls);
         const long long n = nk / a.ncls;
 
-        // ---- roi geometry (uniform over the workgroup), the reference's operations in its order
-        const float *roi = a.bbox + n * 5;
-        const float bf = roi[0];
-        const bool bvalid = bf > -1.f && bf < (float)a.B;                // NaN fails both; (int) truncates toward zero
-        const int b = bvalid ? (int)bf : 0;
-        const float roi_start_w = roundf(roi[1]) * a.scale - 0.5f;
-        const float roi_start_h = roundf(roi[2]) * a.scale - 0.5f;
-        const float roi_end_w = (roundf(roi[3]) + 1.f) * a.scale - 0.5f;
-        const float roi_end_h = (roundf(roi[4]) + 1.f) * a.scale - 0.5f;
-        const float roi_w = fmaxf(roi_end_w - roi_start_w, 0.1f);
-        const float roi_h = fmaxf(roi_end_h - roi_start_h, 0.1f);
-        const float bin_w = roi_w / (float)P, bin_h = roi_h / (float)P;
-        const float sub_w = bin_w / (float)a.spp, sub_h = bin_h / (float)a.spp;
+        // ---- roi geometry (uniform over the workgroup): csrc/psroi_geom.h
+        const PsroiRoi geo = psroi_roi(a.bbox + n * 5, a.B, a.scale, P, a.spp);
+        const bool bvalid = geo.valid;
+        const int b = geo.b;
         const float *tr = a.trans + n * a.trans_stride;
 
         // ---- this thread's four output elements
@@ -97,31 +91,15 @@ __global__ __launch_bounds__(PSROI_THREADS) void psroi_kernel(PsroiArgs a)
                     if (s < S2) {
                         const int ih = s / a.spp, iw = s - ih * a.spp;
                         const int ph = bi / P, pw = bi - ph * P;
-                        int part_h = (int)floorf((float)ph / (float)P * (float)a.part);
-                        int part_w = (int)floorf((float)pw / (float)P * (float)a.part);
-                        part_h = min(max(part_h, 0), a.part - 1);
-                        part_w = min(max(part_w, 0), a.part - 1);
+                        const int part_h = psroi_part(ph, P, a.part), part_w = psroi_part(pw, P, a.part);
                         float trans_x = 0.f, trans_y = 0.f;
                         if (!a.no_trans) {
                             const float *tk = tr + (long long)(2 * k) * a.part * a.part + part_h * a.part + part_w;
                             trans_x = tk[0] * a.trans_std;
                             trans_y = tk[a.part * a.part] * a.trans_std;
                         }
-                        float wstart = (float)pw * bin_w + roi_start_w;
-                        wstart += trans_x * roi_w;
-                        float hstart = (float)ph * bin_h + roi_start_h;
-                        hstart += trans_y * roi_h;
-                        float w = wstart + (float)iw * sub_w;
-                        float h = hstart + (float)ih * sub_h;
-                        if (!(w < -0.5f || w > (float)a.W - 0.5f || h < -0.5f || h > (float)a.H - 0.5f)) {
-                            w = fminf(fmaxf(w, 0.f), (float)(a.W - 1));
-                            h = fminf(fmaxf(h, 0.f), (float)(a.H - 1));
-                            const int x1 = (int)floorf(w), y1 = (int)floorf(h);
-                            const float fx = w - (float)x1, fy = h - (float)y1;
-                            // ceil == floor + (fraction > 0): the far corners are inside the plane whenever they are used
-                            ent = make_int4(y1 * a.W + x1, __float_as_int(fx), __float_as_int(fy),
-                                            1 | (fx > 0.f ? 2 : 0) | (fy > 0.f ? 4 : 0));
-                        }
+                        const PsroiSample sm = psroi_sample(geo, ph, pw, ih, iw, trans_x, trans_y, a.H, a.W);
+                        if (sm.flags) ent = make_int4(sm.y * a.W + sm.x, __float_as_int(sm.fx), __float_as_int(sm.fy), sm.flags);
                     }
                     tab[i] = ent;
                     if (MASKED && s0 == 0 && i - bi * a.S2c == 0) {
@@ -174,13 +152,19 @@ __global__ __launch_bounds__(PSROI_THREADS) void psroi_kernel(PsroiArgs a)
     }
 }
 
+int psroi_check_limits(const char *what, int P, int part, int spp)
+{
+    if (P > 45) H3D_FAIL(H3D_ERR_UNSUPPORTED, "%s: pooled_size %d > 45 (P*P bins must fit the LDS sample table)", what, P);
+    if (spp > 4096 || part > 65535) H3D_FAIL(H3D_ERR_UNSUPPORTED, "%s: sample_per_part / part_size out of range", what);
+    return H3D_OK;
+}
+
 static int psroi_launch(const char *what, const float *input, const float *bbox, const float *trans, float *output, float *count,
                         int B, int C, int H, int W, int R, long long trans_stride, int ncls, int no_trans, float spatial_scale,
                         int P, int part, int spp, float trans_std, void *stream)
 {
     if (R == 0) return H3D_OK;                                          // empty output, no launch (reference :308-312)
-    if (P > 45) H3D_FAIL(H3D_ERR_UNSUPPORTED, "%s: pooled_size %d > 45 (P*P bins must fit the LDS sample table)", what, P);
-    if (spp > 4096 || part > 65535) H3D_FAIL(H3D_ERR_UNSUPPORTED, "%s: sample_per_part / part_size out of range", what);
+    H3D_TRY(psroi_check_limits(what, P, part, spp));
     const int P2 = P * P, S2 = spp * spp;
     PsroiArgs a;
     a.input = input; a.bbox = bbox; a.trans = trans; a.out = output; a.count = count;
@@ -200,8 +184,8 @@ static int psroi_launch(const char *what, const float *input, const float *bbox,
     return h3d_launch({"psroi_kernel", true}, psroi_kernel<true>, dim3(grid), dim3(PSROI_THREADS), lds, (hipStream_t)stream, a);
 }
 
-static int psroi_check_common(const char *what, int B, int C, int H, int W, int R, int output_dim, int group_size, int P, int part,
-                              int spp)
+// the argument checks and their texts, shared with the backward's entry points (csrc/psroi_bwd.hip)
+int psroi_check_common(const char *what, int B, int C, int H, int W, int R, int output_dim, int group_size, int P, int part, int spp)
 {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || R < 0) H3D_FAIL(H3D_ERR_SHAPE, "%s: bad shape B=%d C=%d H=%d W=%d R=%d", what, B, C, H, W, R);
     if (H > (1 << 23) || W > (1 << 23) || (long long)H * W > 0x7fffffffLL || B >= (1 << 24))
@@ -211,6 +195,16 @@ static int psroi_check_common(const char *what, int B, int C, int H, int W, int 
         H3D_FAIL(H3D_ERR_UNSUPPORTED, "%s: group_size %d: only group_size == 1 is supported (the reference indexes channel "
                  "(ctop*gs+gh)*gs+gw past the input for any other value)", what, group_size);
     if (P <= 0 || part <= 0 || spp <= 0) H3D_FAIL(H3D_ERR_ARG, "%s: pooled_size, part_size and sample_per_part must be positive", what);
+    return H3D_OK;
+}
+
+int psroi_check_trans(const char *what, int channels_trans, int output_dim, int *ncls)
+{
+    if (channels_trans < 2 || channels_trans % 2)
+        H3D_FAIL(H3D_ERR_SHAPE, "%s: trans has %d channels, expected an even number >= 2 (2 * num_classes)", what, channels_trans);
+    *ncls = channels_trans / 2;
+    if (output_dim % *ncls)
+        H3D_FAIL(H3D_ERR_SHAPE, "%s: output_dim %d is not a multiple of num_classes %d", what, output_dim, *ncls);
     return H3D_OK;
 }
 
@@ -224,13 +218,7 @@ extern "C" int h3d_dcn_v2_psroi_pooling_forward(const float *input, const float 
     int rc = psroi_check_common(what, B, C, H, W, num_bbox, output_dim, group_size, pooled_size, part_size, sample_per_part);
     if (rc) return rc;
     int ncls = 1;
-    if (!no_trans) {
-        if (channels_trans < 2 || channels_trans % 2)
-            H3D_FAIL(H3D_ERR_SHAPE, "%s: trans has %d channels, expected an even number >= 2 (2 * num_classes)", what, channels_trans);
-        ncls = channels_trans / 2;
-        if (output_dim % ncls)
-            H3D_FAIL(H3D_ERR_SHAPE, "%s: output_dim %d is not a multiple of num_classes %d", what, output_dim, ncls);
-    }
+    if (!no_trans && (rc = psroi_check_trans(what, channels_trans, output_dim, &ncls))) return rc;
     return psroi_launch(what, input, bbox, no_trans ? nullptr : trans, output, output_count, B, C, H, W, num_bbox,
                         no_trans ? 0 : (long long)channels_trans * part_size * part_size, ncls, no_trans ? 1 : 0, spatial_scale,
                         pooled_size, part_size, sample_per_part, trans_std, stream);

@@ -10,7 +10,10 @@ raises; parameters may require grad (the nn.Parameter default), results are comp
 
 Training is opt-in: `dcn_v2_backward` (the `_ext` entry point, DCNv2/src/dcn_v2.h:41-74; kernels: csrc/dcn_bwd.hip), the autograd
 function `_DCNv2` / `dcn_v2_conv_autograd` (dcn_v2.py:16-51) and the modules `TrainableDCNv2` / `TrainableDCN` (same constructors and
-state_dict keys as `DCNv2` / `DCN`; their forward builds a graph).  dcn_v2_psroi_pooling_backward is not implemented."""
+state_dict keys as `DCNv2` / `DCN`; their forward builds a graph); and for the pooling `dcn_v2_psroi_pooling_backward` (the `_ext` entry
+point, DCNv2/src/dcn_v2.h:109-142; kernels: csrc/psroi_bwd.hip), the autograd function `_DCNv2Pooling` / `dcn_v2_pooling_autograd`
+(dcn_v2.py:132-187) and the modules `TrainableDCNv2Pooling` / `TrainableDCNPooling` (same constructors and state_dict keys as
+`DCNv2Pooling` / `DCNPooling`)."""
 import math
 
 import os
@@ -514,7 +517,7 @@ def dcn_v2_pooling(input, rois, offset, spatial_scale, pooled_size, output_dim, 
                    sample_per_part=4, trans_std=.0):
     """`_DCNv2Pooling.apply` argument order and defaults (dcn_v2.py:132-161), forward only: returns `output`."""
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (input, offset)):
-        raise RuntimeError("h3d_amd DCNv2 pooling is inference-only (dcn_v2_psroi_pooling_backward is out of scope): "
+        raise RuntimeError("h3d_amd DCNv2 pooling is inference-only (use dcn_v2_pooling_autograd / TrainableDCNv2Pooling to train): "
                            "an input tensor requires grad")
     part_size = pooled_size if part_size is None else part_size
     with torch.no_grad():
@@ -568,8 +571,7 @@ class DCNPooling(DCNv2Pooling):
 
     def forward(self, input, rois):
         if torch.is_grad_enabled() and input.requires_grad:
-            raise RuntimeError("h3d_amd DCNv2 pooling is inference-only (dcn_v2_psroi_pooling_backward is out of scope): "
-                               "the input requires grad")
+            raise RuntimeError("h3d_amd DCNv2 pooling is inference-only (use TrainableDCNPooling to train): the input requires grad")
         with torch.no_grad():
             out = self._forward(input, rois)
         if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
@@ -589,3 +591,203 @@ class DCNPooling(DCNv2Pooling):
         offset_mask = self.offset_mask_fc(roi.reshape(n, self.output_dim * self.pooled_size ** 2)).view(n, 3, self.pooled_size, self.pooled_size)
         return _dcn_pooling_modulated(input, rois, offset_mask, self.spatial_scale, self.pooled_size, self.output_dim,
                                       self.group_size, self.part_size, self.sample_per_part, self.trans_std)
+
+
+# ---- training: dcn_v2_psroi_pooling_backward, the autograd functions and the trainable modules (kernels: csrc/psroi_bwd.hip) -----
+
+def _check_trans(what, trans, input, R, output_dim, part_size):
+    """The forward's checks of `trans` ([>= R, 2*num_classes, part, part] fp32 on input's device) -> contiguous trans."""
+    _lib.require_cuda(trans)
+    if trans.dtype != torch.float32:
+        raise RuntimeError("%s: expected float32 tensors (reference uses .data<float>())" % what)
+    if trans.device != input.device:
+        raise RuntimeError("%s: trans is on %s, input on %s" % (what, trans.device, input.device))
+    if trans.dim() != 4 or tuple(trans.shape[2:]) != (part_size, part_size) or trans.shape[0] < R:
+        raise RuntimeError("%s: trans %s does not match [>= %d, 2*num_classes, %d, %d]"
+                           % (what, tuple(trans.shape), R, part_size, part_size))
+    ct = trans.shape[1]
+    if ct < 2 or ct % 2:
+        raise RuntimeError("%s: trans has %d channels, expected 2 * num_classes" % (what, ct))
+    if output_dim % (ct // 2):
+        raise RuntimeError("%s: output_dim %d is not a multiple of num_classes %d" % (what, output_dim, ct // 2))
+    return trans.contiguous()
+
+
+def _check_grad_output(what, grad_output, input, R, output_dim, pooled_size):
+    _lib.require_cuda(grad_output)
+    if grad_output.dtype != torch.float32:
+        raise RuntimeError("%s: expected float32 tensors (reference uses .data<float>())" % what)
+    if grad_output.device != input.device or tuple(grad_output.shape) != (R, output_dim, pooled_size, pooled_size):
+        raise RuntimeError("%s: grad_output %s on %s does not match [%d, %d, %d, %d] on %s"
+                           % (what, tuple(grad_output.shape), grad_output.device, R, output_dim, pooled_size, pooled_size, input.device))
+    return grad_output.contiguous()
+
+
+def _dcn_v2_psroi_pooling_backward(grad_output, input, bbox, trans, output_count, no_trans, spatial_scale, output_dim, group_size,
+                                   pooled_size, part_size, sample_per_part, trans_std, need=(True, True), direct=False):
+    """`dcn_v2_psroi_pooling_backward` with a choice of outputs (`need`: input, trans -- autograd's needs_input_grad; an output that is not
+    needed is None) and of the grad_input path (`direct`: one global atomic per sample corner, never combined in LDS)."""
+    what = "dcn_v2_psroi_pooling_backward"
+    input, bbox, (B, C, H, W, R) = _pool_common(what, input, bbox, output_dim, group_size, pooled_size, part_size, sample_per_part)
+    no_trans = int(bool(no_trans))
+    grad_output = _check_grad_output(what, grad_output, input, R, output_dim, pooled_size)
+    _lib.require_cuda(output_count)
+    if output_count.dtype != torch.float32 or output_count.device != input.device or output_count.shape != grad_output.shape:
+        raise RuntimeError("%s: output_count %s does not match grad_output %s (float32)" % (what, tuple(output_count.shape), tuple(grad_output.shape)))
+    output_count = output_count.contiguous()
+    ct = 0
+    if not no_trans:
+        trans = _check_trans(what, trans, input, R, output_dim, part_size)
+        ct = trans.shape[1]
+    with torch.cuda.device(input.device):
+        grad_input = torch.empty_like(input) if need[0] else None
+        # (the reference returns zeros_like(trans) in either mode: with no_trans that is whatever placeholder it was given)
+        grad_trans = (torch.zeros_like(trans) if no_trans else torch.empty_like(trans)) if need[1] and trans is not None else None
+        rc = _lib.lib().h3d_dcn_v2_psroi_pooling_backward(
+            _lib.ptr(grad_output), _lib.ptr(input), _lib.ptr(bbox), _lib.ptr(None if no_trans else trans), _lib.ptr(output_count),
+            _lib.ptr(grad_input), _lib.ptr(None if no_trans else grad_trans), B, C, H, W, R, 0 if no_trans else trans.shape[0], ct, no_trans,
+            float(spatial_scale), output_dim, group_size, pooled_size, part_size, sample_per_part, float(trans_std), int(bool(direct)),
+            _lib.stream_ptr())
+    _lib.check(rc, what)
+    return grad_input, grad_trans
+
+
+def dcn_v2_psroi_pooling_backward(grad_output, input, bbox, trans, output_count, no_trans, spatial_scale, output_dim, group_size,
+                                  pooled_size, part_size, sample_per_part, trans_std):
+    """Positional twin of `_ext.dcn_v2_psroi_pooling_backward` (dcn_v2.py:165-178 call site): returns (grad_input, grad_trans), new
+    tensors shaped like input and trans.  An element whose `output_count` is <= 0 is skipped, the others contribute grad_output /
+    output_count per valid sample.  grad_input is summed by float atomics; grad_trans in a fixed order (bit-identical from run to run),
+    rows of trans beyond the rois get zero.  Current stream, no host synchronisation; the forward's argument checks and error texts."""
+    return _dcn_v2_psroi_pooling_backward(grad_output, input, bbox, trans, output_count, no_trans, spatial_scale, output_dim, group_size,
+                                          pooled_size, part_size, sample_per_part, trans_std)
+
+
+def _dcn_pooling_modulated_backward(grad_output, input, rois, offset_mask, spatial_scale, pooled_size, output_dim, group_size, part_size,
+                                    sample_per_part, trans_std, need=(True, True), direct=False):
+    """Backward of `_dcn_pooling_modulated` (`h3d_dcn_pooling_modulated_backward`) -> (grad_input, grad_offset_mask [R,3,P,P]): channels 0/1 the
+    offset gradients, channel 2 the gradient of the mask logit; the chunk / cat / sigmoid / mul chain never appears as torch ops."""
+    what = "DCNPooling"
+    input, rois, (B, C, H, W, R) = _pool_common(what, input, rois, output_dim, group_size, pooled_size, part_size, sample_per_part)
+    if part_size != pooled_size:
+        raise RuntimeError("%s: part_size %d != pooled_size %d: the reference indexes its [R,2,P,P] offsets with part_size"
+                           % (what, part_size, pooled_size))
+    _lib.require_cuda(offset_mask)
+    if offset_mask.device != input.device:
+        raise RuntimeError("%s: offset/mask is on %s, input on %s" % (what, offset_mask.device, input.device))
+    offset_mask = offset_mask.contiguous()
+    if offset_mask.dtype != torch.float32 or tuple(offset_mask.shape) != (R, 3, pooled_size, pooled_size):
+        raise RuntimeError("%s: offset/mask %s is not float32 [%d, 3, %d, %d]" % (what, tuple(offset_mask.shape), R, pooled_size,
+                                                                                 pooled_size))
+    grad_output = _check_grad_output(what, grad_output, input, R, output_dim, pooled_size)
+    with torch.cuda.device(input.device):
+        grad_input = torch.empty_like(input) if need[0] else None
+        grad_om = torch.empty_like(offset_mask) if need[1] else None
+        rc = _lib.lib().h3d_dcn_pooling_modulated_backward(
+            _lib.ptr(grad_output), _lib.ptr(input), _lib.ptr(rois), _lib.ptr(offset_mask), _lib.ptr(grad_input), _lib.ptr(grad_om),
+            B, C, H, W, R, float(spatial_scale), output_dim, group_size, pooled_size, part_size, sample_per_part, float(trans_std),
+            int(bool(direct)), _lib.stream_ptr())
+    _lib.check(rc, what)
+    return grad_input, grad_om
+
+
+def psroi_backward_path(roi, trans_row, input_shape, no_trans, spatial_scale, pooled_size, part_size, sample_per_part, trans_std,
+                        class_id=0, direct=False):
+    """Which grad_input path the backward kernel takes for one (roi, class) -- a function of the geometry alone, computed on the host
+    by the code the kernel runs (`h3d_psroi_backward_path`): 0 = nothing to add, 1 = combined in LDS, 2 = added directly.  roi: 5
+    numbers; trans_row: the roi's [2*num_classes, part, part] translations (an offset_mask row [3,P,P] in modulated mode) or None."""
+    import ctypes
+    B, C, H, W = input_shape
+    r = (ctypes.c_float * 5)(*[float(v) for v in roi])
+    ct, t = 0, None
+    if not no_trans:
+        tr = torch.as_tensor(trans_row, dtype=torch.float32).cpu().contiguous()
+        ct = tr.shape[0] - tr.shape[0] % 2
+        t = ctypes.c_void_p(tr.data_ptr())
+    path = ctypes.c_int(-1)
+    _lib.check(_lib.lib().h3d_psroi_backward_path(ctypes.cast(r, ctypes.c_void_p), t, B, C, H, W, ct, int(bool(no_trans)), float(spatial_scale),
+                                                  pooled_size, part_size, sample_per_part, float(trans_std), class_id, int(bool(direct)),
+                                                  ctypes.byref(path)), "psroi_backward_path")
+    return path.value
+
+
+class _DCNv2Pooling(torch.autograd.Function):
+    """The reference's autograd function (dcn_v2.py:132-181), argument order and defaults included; rois get no gradient."""
+
+    @staticmethod
+    def forward(ctx, input, rois, offset, spatial_scale, pooled_size, output_dim, no_trans, group_size=1, part_size=None,
+                sample_per_part=4, trans_std=.0):
+        ctx.spatial_scale = spatial_scale
+        ctx.no_trans = int(no_trans)
+        ctx.output_dim = output_dim
+        ctx.group_size = group_size
+        ctx.pooled_size = pooled_size
+        ctx.part_size = pooled_size if part_size is None else part_size
+        ctx.sample_per_part = sample_per_part
+        ctx.trans_std = trans_std
+        output, output_count = dcn_v2_psroi_pooling_forward(input, rois, offset, ctx.no_trans, ctx.spatial_scale, ctx.output_dim,
+                                                            ctx.group_size, ctx.pooled_size, ctx.part_size, ctx.sample_per_part,
+                                                            ctx.trans_std)
+        ctx.save_for_backward(input, rois, offset, output_count)
+        return output
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        input, rois, offset, output_count = ctx.saved_tensors
+        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[2])
+        grad_input, grad_offset = _dcn_v2_psroi_pooling_backward(grad_output, input, rois, offset, output_count, ctx.no_trans,
+                                                                 ctx.spatial_scale, ctx.output_dim, ctx.group_size, ctx.pooled_size,
+                                                                 ctx.part_size, ctx.sample_per_part, ctx.trans_std, need=need)
+        return grad_input, None, grad_offset, None, None, None, None, None, None, None, None
+
+
+dcn_v2_pooling_autograd = _DCNv2Pooling.apply
+
+
+class _DCNPoolingModulated(torch.autograd.Function):
+    """DCNPooling's second pass with its backward: forward(input, rois, offset_mask [R,3,P,P], ...) = `_dcn_pooling_modulated`."""
+
+    @staticmethod
+    def forward(ctx, input, rois, offset_mask, spatial_scale, pooled_size, output_dim, group_size, part_size, sample_per_part, trans_std):
+        ctx.geo = (spatial_scale, pooled_size, output_dim, group_size, part_size, sample_per_part, trans_std)
+        ctx.save_for_backward(input, rois, offset_mask)
+        return _dcn_pooling_modulated(input, rois, offset_mask, *ctx.geo)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_output):
+        input, rois, offset_mask = ctx.saved_tensors
+        grad_input, grad_om = _dcn_pooling_modulated_backward(grad_output, input, rois, offset_mask, *ctx.geo,
+                                                              need=(ctx.needs_input_grad[0], ctx.needs_input_grad[2]))
+        return grad_input, None, grad_om, None, None, None, None, None, None, None
+
+
+class TrainableDCNv2Pooling(DCNv2Pooling):
+    """`DCNv2Pooling` whose forward builds a graph (the reference's behaviour): same constructor, no parameters."""
+
+    def forward(self, input, rois, offset):
+        assert input.shape[1] == self.output_dim
+        if self.no_trans:
+            offset = input.new()
+        return dcn_v2_pooling_autograd(input, rois, offset, self.spatial_scale, self.pooled_size, self.output_dim, self.no_trans,
+                                       self.group_size, self.part_size, self.sample_per_part, self.trans_std)
+
+
+class TrainableDCNPooling(DCNPooling):
+    """`DCNPooling` whose forward builds a graph: same constructor, same state_dict keys.  Pass 1 is `dcn_v2_pooling_autograd` without
+    translations, the MLP runs in torch, pass 2 is ONE launch forward (`h3d_dcn_pooling_modulated`) and one backward
+    (`h3d_dcn_pooling_modulated_backward`): the same launches as `DCNPooling`, so the forward results are bit-identical to its."""
+
+    def forward(self, input, rois):
+        if self.no_trans:
+            return dcn_v2_pooling_autograd(input, rois, input.new(), self.spatial_scale, self.pooled_size, self.output_dim, self.no_trans,
+                                           self.group_size, self.part_size, self.sample_per_part, self.trans_std)
+        if self.part_size != self.pooled_size:
+            raise RuntimeError("DCNPooling: part_size %d != pooled_size %d: the reference indexes its [R,2,P,P] offsets with "
+                               "part_size" % (self.part_size, self.pooled_size))
+        n = rois.shape[0]
+        roi = dcn_v2_pooling_autograd(input, rois, input.new(), self.spatial_scale, self.pooled_size, self.output_dim, True,
+                                      self.group_size, self.part_size, self.sample_per_part, self.trans_std)
+        offset_mask = self.offset_mask_fc(roi.reshape(n, self.output_dim * self.pooled_size ** 2)).view(n, 3, self.pooled_size, self.pooled_size)
+        return _DCNPoolingModulated.apply(input, rois, offset_mask, self.spatial_scale, self.pooled_size, self.output_dim, self.group_size,
+                                          self.part_size, self.sample_per_part, self.trans_std)

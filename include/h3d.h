@@ -208,6 +208,37 @@ int h3d_dcn_v2_psroi_pooling_forward(const float *input, const float *bbox, cons
 int h3d_dcn_pooling_modulated(const float *input, const float *bbox, const float *offset_mask, float *output, int B, int C, int H,
                               int W, int num_bbox, float spatial_scale, int output_dim, int group_size, int pooled_size, int part_size,
                               int sample_per_part, float trans_std, void *stream);
+/* Deformable PS-ROI pooling, backward: `_ext.dcn_v2_psroi_pooling_backward` (DCNv2/src/dcn_v2.h:109-142 ->
+ * dcn_v2_psroi_pooling_cuda.cu:148-269, 343-419), positional twin plus outputs, shapes and stream (csrc/psroi_bwd.hip).
+ *   grad_output, output_count [num_bbox, output_dim, P, P]: an element with output_count <= 0 is skipped, the others contribute
+ *   grad_output / output_count per valid sample; the sample geometry is the forward's (csrc/psroi_geom.h), exactly
+ *   grad_input  [B,C,H,W]: zeroed on `stream`, then a scatter by float atomics (the order of the adds is not fixed)
+ *   grad_trans  [num_trans >= num_bbox, channels_trans, part_size, part_size]: zeroed on `stream` (rows beyond num_bbox stay zero);
+ *               summed without atomics in an order that depends on the shapes and the geometry only (not on force_direct, nor on
+ *               whether grad_input is wanted): bit-identical from run to run
+ *   grad_input or grad_trans may be NULL: not computed (grad_trans is ignored when no_trans).  force_direct != 0: every grad_input
+ *   contribution is one global atomic (the reference's form) instead of being combined per workgroup in LDS first.
+ * Arguments are checked as in the forward, with its texts; a roi with an invalid batch index contributes nothing; num_bbox == 0: the
+ * outputs are zeroed and nothing is launched. */
+int h3d_dcn_v2_psroi_pooling_backward(const float *grad_output, const float *input, const float *bbox, const float *trans,
+                                      const float *output_count, float *grad_input, float *grad_trans, int B, int C, int H, int W,
+                                      int num_bbox, int num_trans, int channels_trans, int no_trans, float spatial_scale, int output_dim,
+                                      int group_size, int pooled_size, int part_size, int sample_per_part, float trans_std,
+                                      int force_direct, void *stream);
+/* Backward of h3d_dcn_pooling_modulated: grad_offset_mask [num_bbox,3,P,P] = the translation gradients (channels 0/1) and the
+ * gradient of the mask logit m (channel 2), s (1 - s) * sum_c grad_output * pooled with s = sigmoid(m) and pooled the unmasked mean;
+ * the upstream of a pooled element is grad_output * s and the count per bin is recomputed.  Same order rules as above. */
+int h3d_dcn_pooling_modulated_backward(const float *grad_output, const float *input, const float *bbox, const float *offset_mask,
+                                       float *grad_input, float *grad_offset_mask, int B, int C, int H, int W, int num_bbox,
+                                       float spatial_scale, int output_dim, int group_size, int pooled_size, int part_size,
+                                       int sample_per_part, float trans_std, int force_direct, void *stream);
+/* Which grad_input path the backward takes for ONE (roi, class): a function of the geometry alone, computed on the host by the code the
+ * kernel runs.  roi = 5 floats, trans_row = that roi's [channels_trans, part_size, part_size] translations (HOST pointers; an
+ * [3,P,P] offset_mask row with channels_trans = 2 in modulated mode).  *path = 0: nothing to add (invalid batch index, or no valid
+ * sample), 1: combined in LDS, one global atomic per touched pixel, 2: one global atomic per sample corner. */
+int h3d_psroi_backward_path(const float *roi, const float *trans_row, int B, int C, int H, int W, int channels_trans, int no_trans,
+                            float spatial_scale, int pooled_size, int part_size, int sample_per_part, float trans_std, int class_id,
+                            int force_direct, int *path);
 
 /* =====================================================================================
  * 2. Network ops (DLA-34 + DLAUp/IDAUp + heads, model.py:32-61,148-222,286-292,346-415,475-489)
