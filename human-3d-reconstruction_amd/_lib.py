@@ -210,6 +210,11 @@ SIGNATURES = {
     "h3d_smpl_kp_loss_workspace_bytes": [c_i, c_i, ctypes.POINTER(ctypes.c_size_t)],
     "h3d_smpl_kp_loss_forward": [c_vp] * 6 + [c_i] + [c_vp] * 3 + [c_i] * 7 + [c_vp] * 4 + [ctypes.c_size_t, c_vp],
     "h3d_smpl_kp_loss_backward": [c_vp] * 6 + [c_i] + [c_vp] * 7 + [c_i] * 7 + [c_vp] * 4,
+    # SMPL 3D supervision (include/h3d.h section 4e; h3d_amd/smpl_sup.py)
+    "h3d_smpl_sup_labels": [c_vp] * 10 + [c_i] * 3 + [c_vp] * 7,
+    "h3d_smpl_sup_loss_workspace_bytes": [c_i, c_i, ctypes.POINTER(ctypes.c_size_t)],
+    "h3d_smpl_sup_loss_forward": [c_vp] * 10 + [c_i] * 4 + [c_vp, c_vp, ctypes.c_size_t, c_vp],
+    "h3d_smpl_sup_loss_backward": [c_vp] * 10 + [c_i] * 4 + [c_vp] * 6,
     # mesh rendering (include/h3d.h section 4d; h3d_amd/render.py)
     "h3d_render_workspace_bytes": [c_i] * 3 + [ctypes.POINTER(ctypes.c_size_t)],
     "h3d_render_rasterize": [c_vp] * 6 + [c_i] * 9 + [c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],

@@ -211,11 +211,13 @@ def _input_res(opt):
     return (res, res) if res else (_opt(opt, "input_h", 512), _opt(opt, "input_w", 512))
 
 
-def multi_pose_train_batch(images, boxes, keypoints, num, opt, np_random=np.random, data_rng=None, py_random=random, params=None):
+def multi_pose_train_batch(images, boxes, keypoints, num, opt, np_random=np.random, data_rng=None, py_random=random, params=None, smpl_labels=None):
     """COCOHP.__getitem__ with split == 'train' for a batch: images as train_input takes them, boxes / keypoints / num as
     targets.multi_pose_targets takes them.  The parameters are drawn here (draw_params; or handed in through `params`), and the input and
     the labels are built from the same c, s, rot, flipped and image widths.  opt: input_res (or input_h / input_w), no_color_aug and
-    what draw_params and multi_pose_targets read.  -> multi_pose_targets' dict + 'input' [B,3,res_h,res_w]."""
+    what draw_params and multi_pose_targets read.  -> multi_pose_targets' dict + 'input' [B,3,res_h,res_w].
+    smpl_labels: a dict of pose [B,M,72], shape [B,M,10], valid [B,M] and optionally joints, joint_weight, pose_weight, smpl_model (what
+    smpl_sup.smpl_targets takes); the result then also carries the six SMPL label tensors, moved with the same rot and flipped."""
     sizes = _sizes(images)
     if params is None:
         params = draw_params(sizes, opt, "multi_pose", np_random, data_rng, py_random)
@@ -224,6 +226,12 @@ def multi_pose_train_batch(images, boxes, keypoints, num, opt, np_random=np.rand
     ret = targets.multi_pose_targets(boxes, keypoints, num, params["c"], params["s"], rot=params["rot"], flipped=params["flipped"],
                                      width=[w for _, w in sizes], opt=opt, device=dev)
     ret["input"] = inp
+    if smpl_labels is not None:
+        from . import smpl_sup
+        lab = smpl_labels
+        ret.update(smpl_sup.smpl_targets(lab["pose"], lab["shape"], lab["valid"], num, ret["reg_mask"], rot=params["rot"], flipped=params["flipped"],
+                                         c=params["c"], s=params["s"], joints=lab.get("joints"), joint_weight=lab.get("joint_weight"),
+                                         pose_weight=lab.get("pose_weight"), smpl_model=lab.get("smpl_model"), opt=opt))
     return ret
 
 

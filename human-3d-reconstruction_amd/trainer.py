@@ -48,7 +48,11 @@ class HeadsTrainer:
     whole loader), device, and what the task's loss reads.  model: a model.dla_net(...) in 'f32' or 'f16x3' on the device.
     smpl_model (smpl.SMPLModel) and kp_regressor (smpl_loss.KeypointRegressor), both given and opt.smpl_kp_weight > 0 (multi_pose only):
     the loss is smpl_loss.loss_multi_pose_smpl, which adds the keypoint reprojection loss on the SMPL output and so trains the `pose`,
-    `shape` and `cam` (3 channels) heads the model must then have; otherwise nothing changes."""
+    `shape` and `cam` (3 channels) heads the model must then have; otherwise nothing changes.
+    smpl_model given and any of opt.smpl_pose_weight / smpl_shape_weight / smpl_j3d_weight > 0 (multi_pose only): the loss is
+    smpl_sup.loss_multi_pose_smpl3d -- the rotation, shape and 3D-joint terms against the batch's six SMPL label tensors
+    (smpl_sup.smpl_targets), the keypoint term as well when it is switched on as above; the model must have `pose` and `shape` (and `cam`
+    with the keypoint term)."""
 
     MODULE = TrainableHeads         # what trains: the module type behind `self.heads`
 
@@ -58,7 +62,14 @@ class HeadsTrainer:
         self.smpl_model = smpl_model
         self.heads = self._build_module(model)
         task = _opt(opt, "task", "multi_pose")
-        if task == "multi_pose" and smpl_model is not None and kp_regressor is not None and _opt(opt, "smpl_kp_weight", 0) > 0:
+        kp_on = kp_regressor is not None and _opt(opt, "smpl_kp_weight", 0) > 0
+        if task == "multi_pose" and smpl_model is not None and any(_opt(opt, w, 0) > 0 for w in ("smpl_pose_weight", "smpl_shape_weight", "smpl_j3d_weight")):
+            from . import smpl_sup
+            want = dict({"pose": 72, "shape": 10}, **({"cam": 3} if kp_on else {}))
+            if any(model.heads.get(h) != c for h, c in want.items()):
+                raise ValueError("HeadsTrainer: the SMPL 3D supervision needs the heads %s, the model has %s" % (want, dict(model.heads)))
+            self.loss = smpl_sup.loss_multi_pose_smpl3d(opt, smpl_model, kp_regressor if kp_on else None)
+        elif task == "multi_pose" and smpl_model is not None and kp_on:
             from . import smpl_loss
             want = {"pose": 72, "shape": 10, "cam": 3}
             if any(model.heads.get(h) != c for h, c in want.items()):

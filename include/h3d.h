@@ -1007,6 +1007,67 @@ int h3d_render_shade(const void *keys, const float *verts, const int32_t *faces,
                      void *stream);
 
 /* =====================================================================================
+ * 4e. SMPL 3D supervision: the label transform and the rotation / shape / 3D-joint loss (csrc/smpl_sup.hip; h3d_amd/smpl_sup.py; no
+ *    reference code: the project's own definition).  Model x / y are the output map's x / y (y down), as in 4c.
+ *    pi = the mirror's joint permutation, the pairs (1,2) (4,5) (7,8) (10,11) (13,14) (16,17) (18,19) (20,21) (22,23); S = diag(-1, 1, 1).
+ *    LABEL TRANSFORM (h3d_smpl_sup_labels), image b, output row m < max_objs = annotation m of pose_lab [B,M,72], shape_lab [B,M,10],
+ *    joints_lab [B,M,24,3] or NULL, valid [B,M] f32, pose_w / joints_w [B,M,24] f32 or NULL, num [B] i32, reg_mask [B,max_objs] u8 (what
+ *    h3d_multi_pose_targets wrote), flipped [B] i32 or NULL, rot2 [B,2,2] f64 or NULL (= identity):
+ *      gate        = m < min(num[b], max_objs, M)  and  reg_mask[b,m] != 0  and  valid[b,m] != 0
+ *      R_lab[j]    = Rodrigues(pose_lab[b,m,j])        smpl_pose.h's convention (angle = ||theta + 1e-8||), in fp64
+ *      flipped:      R'[pi(j)] = S R_lab[j] S          J'[pi(j)] = S J_lab[j]         w'[pi(j)] = w[j]          (exact: sign changes only)
+ *      then rot2:    R''[0]    = Rz R'[0]              J''[j]    = Rz J'[j]           Rz = [[A2, 0], [0, 1]], A2 = rot2[b]; the other 23
+ *                                                                                     rotations are parent-relative: unchanged
+ *      weights:      smpl_pose_w = gate ? (pose_w or valid) : 0;  smpl_shape_w = gate ? valid : 0;  smpl_joints_w = gate and joints_lab ?
+ *                    (joints_w or valid) : 0
+ *    Outputs, fp32, every element written: smpl_rotmat [B,max_objs,24,9] (row-major as SmplRot::R), smpl_pose_w [B,max_objs,24], smpl_shape
+ *    [B,max_objs,10] (copied: a mirror does not change betas), smpl_shape_w [B,max_objs], smpl_joints [B,max_objs,24,3], smpl_joints_w
+ *    [B,max_objs,24].  Rows and entries whose weight is 0 hold zeros and their labels are never read into a result (NaN labels behind
+ *    valid == 0 are harmless).  The arithmetic is fp64, each product and sum rounded on its own, rounded once to fp32.  One launch.
+ *    LOSS (h3d_smpl_sup_loss_forward), slot p = b n + m (the first n <= max_objs rows), theta = pose_map[b, :, ind[b,m]] and beta =
+ *    shape_map[b, :, ind[b,m]] read in place from the NCHW fp32 head maps [B,72,HW] / [B,10,HW]:
+ *      R[j]    = smpl_rodrigues<float>(theta_j)                                                 the SMPL forward's own bits
+ *      l_pose  = sum_p sum_j wp[b,m,j] sum_{a<9} (R[j][a] - smpl_rotmat[b,m,j][a])^2            num_pose  = 9 sum wp
+ *      l_shape = sum_p ws[b,m] sum_{k<10} (beta_k - smpl_shape[b,m,k])^2                        num_shape = 10 sum ws
+ *      root(X) = 0.5 (X[1] + X[2])                                                              (section 8b's root = (1, 2))
+ *      d_j     = (joints[p,j] - root(joints[p])) - (smpl_joints[b,m,j] - root(smpl_joints[b,m]))
+ *      l_j3d   = sum_p sum_j wj[b,m,j] ||d_j||^2                                                num_j3d   = 3 sum wj
+ *      stats[9] = {loss_t, l_t, num_t} for t = pose, shape, j3d;  loss_t = l_t / (num_t + 1e-4)
+ *    joints [P,24,3] (P = B n) is what h3d_smpl_pose_heads wrote; NULL = the third term is absent (stats[6..8] = 0).
+ *    DECIDED HERE: a slot whose ind lies outside [0,HW) adds nothing to any l, num or gradient (as in sections 4c and 5); an entry whose
+ *    weight is 0 adds exactly 0 even when its label is NaN (a select, not a product); rows m >= n are never read; num_t == 0 gives loss 0
+ *    and zero gradients.
+ *    - Forward: two launches, asynchronous on `stream`, no allocation.  One wave per slot, four per workgroup; fp32 per lane -> wave
+ *      shuffles -> LDS -> six plain-stored partials per workgroup, summed in a fixed order in fp64 by the finish launch: no float atomics,
+ *      bit-identical from run to run.
+ *    - Backward (h3d_smpl_sup_loss_backward): coef_t = grad_out[t] / (num_t + 1e-4) formed in fp64 and rounded once (grad_out [3] and stats
+ *      in device memory).  grad_pose_map [B,72,HW] += 2 coef wp sum_a (R - R_lab)_a dR_a / dtheta_c at the slot's pixel -- Rodrigues, the
+ *      residual and the derivative recomputed in fp64 from the fp32 inputs and rounded once (an untrained head emits theta ~ 0, where the
+ *      fp32 derivative of sin a / a and (1 - cos a) / a^2 is lost to cancellation); grad_shape_map [B,10,HW] += 2 coef ws (beta - beta_lab);
+ *      grad_joints [P,24,3] = 2 coef wj[j] d_j, joints 1 and 2 each in addition -0.5 sum_j 2 coef wj[j] d_j (the sum by the wave's shuffle
+ *      tree: a fixed order); every element of grad_joints is stored.  Any of the three may be NULL (skipped; grad_joints needs joints).  Two
+ *      launches: a zero fill of the two maps, then the scatter; the map gradients are added with float atomic adds because two slots may
+ *      share a pixel -- the order of those adds varies (last bits of a shared pixel), everything else is bit-identical from run to run.
+ *    B, M, max_objs, n, HW <= 0, n > max_objs, more than 2^31 / 216 label rows: H3D_ERR_SHAPE.  NULL operands, joints_w without joints_lab,
+ *    joints without smpl_joints / smpl_joints_w, grad_joints without joints, a pointer that is not aligned to its element, a NULL, short or
+ *    not 8-byte aligned workspace ("workspace" in the message): H3D_ERR_ARG.  Every check runs before the first HIP call.
+ *    Workspace: a256(24 ceil(B n / 4)) bytes, six partials per workgroup of four slots.
+ * ===================================================================================== */
+int h3d_smpl_sup_labels(const float *pose_lab, const float *shape_lab, const float *joints_lab, const float *valid, const float *pose_w,
+                        const float *joints_w, const int32_t *num, const uint8_t *reg_mask, const int32_t *flipped, const double *rot2, int B,
+                        int M, int max_objs, float *smpl_rotmat, float *smpl_pose_w, float *smpl_shape, float *smpl_shape_w, float *smpl_joints,
+                        float *smpl_joints_w, void *stream);
+int h3d_smpl_sup_loss_workspace_bytes(int B, int n, size_t *bytes);
+int h3d_smpl_sup_loss_forward(const float *pose_map, const float *shape_map, const int64_t *ind, const float *joints, const float *smpl_rotmat,
+                              const float *smpl_pose_w, const float *smpl_shape, const float *smpl_shape_w, const float *smpl_joints,
+                              const float *smpl_joints_w, int B, int max_objs, int n, int HW, float *stats, void *workspace,
+                              size_t workspace_bytes, void *stream);
+int h3d_smpl_sup_loss_backward(const float *pose_map, const float *shape_map, const int64_t *ind, const float *joints, const float *smpl_rotmat,
+                               const float *smpl_pose_w, const float *smpl_shape, const float *smpl_shape_w, const float *smpl_joints,
+                               const float *smpl_joints_w, int B, int max_objs, int n, int HW, const float *stats, const float *grad_out,
+                               float *grad_pose_map, float *grad_shape_map, float *grad_joints, void *stream);
+
+/* =====================================================================================
  * 5. Losses (losses.py, trains/trainer.py:29-137): the focal term of `_neg_loss` (losses.py:42-67) and the four gathered regression
  *    terms, forward and backward, in descriptor form: one h3d_loss_term per term, ALL terms of a call in one partial-sum launch plus
  *    one finish launch (csrc/loss.hip).  No host synchronisation: where the reference branches on the host (`if num_pos == 0`) the

@@ -6,7 +6,8 @@
 #   tools/kernel_resources.sh heads_bwd.hip         (the heads backward kernels: DESIGN.md section 18 holds their table)
 #   tools/kernel_resources.sh optim.hip -ffp-contract=off   (the Adam step: DESIGN.md section 21)
 #   tools/kernel_resources.sh smpl_loss.hip -ffp-contract=off   (the keypoint reprojection loss: DESIGN.md section 22)
-#   tools/kernel_resources.sh render.hip -ffp-contract=off      (the mesh rasteriser: DESIGN.md section 23)
+#   tools/kernel_resources.sh smpl_sup.hip -ffp-contract=off    (the SMPL 3D supervision: DESIGN.md section 34)
+#   tools/kernel_resources.sh render.hip -ffp-contract=off     (the mesh rasteriser: DESIGN.md section 23)
 #   tools/kernel_resources.sh mesh_eval.hip -ffp-contract=off   (the 3D evaluation: DESIGN.md section 27)
 #   tools/kernel_resources.sh conv_bwd.hip          (the convolution backward kernels: DESIGN.md section 28 holds their table)
 # (device-only compile, nothing is written; use it to check that a change did not push a variant over its VGPR cap or into scratch)
